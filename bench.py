@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: Msamples/s (path-bounces per second) of the HIP path tracer on the north-star workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`roofline`, `cpu_baseline` and `parity` are null).
+`--full` adds, after the timed steps, everything listed at the end of this docstring.  `--dump-outputs DIR` writes what the
+last timed step computed -- the frame a caller of `pathtrace_scene` reads back -- as float32 / float64 .npy files (see
+dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json configs[4], the frame the north star is quoted on, on however many GPUs there are): the
 bistro-class scene (seeded procedural stand-in for bistroexterior, which is not in the container -- SURVEY 8d: 2.88 M
@@ -17,7 +22,7 @@ was built and tested against.  Launch with `python -m torch.distributed.run --np
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_PORT from the environment), or plain `python bench.py --gpus N`, which starts the
 N rank processes itself.
 
-The JSON line also carries (rank 0, N = 1)
+With --full the JSON line also carries (rank 0, N = 1)
   roofline      dominant kernel: bytes it requests per path-bounce in THIS build's layout after light culling (64 B per
                 node visit, 48 B per triangle test, 64 B per instance entry, 56 B of path state; counted on the device by
                 the kernel's work-counting instantiation) x units per launch / its hipEvent-measured launch time, against
@@ -315,6 +320,31 @@ def accuracy_1024spp(api, oracle, ctx, gpu_scene, host_scene, cam, size, bounces
     return out
 
 
+DUMP_SAMPLE_PIXELS = 1 << 20   # 16 MB of RGBA float32 + 8 MB of indices; frames up to 1024 x 1024 are written whole
+DUMP_BLOCK = 8
+
+
+def dump_outputs(frame, out_dir):
+    """The last timed frame ((H, W, 4) float16, as Texture.download returns it) as .npy files, 29 MB at 3840 x 2160:
+      frame_pixels.npy       (n, 4) float32   RGBA of n = min(H * W, 2^20) pixels, a fixed sample (seed 0), sorted
+      frame_pixel_index.npy  (n,) float64     their flat indices y * W + x
+      frame_block_mean.npy   (ceil(H / 8), ceil(W / 8), 4) float64   mean of every 8 x 8 block: every pixel counts somewhere."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    h, w, _ = frame.shape
+    flat = frame.reshape(h * w, 4)
+    if h * w <= DUMP_SAMPLE_PIXELS:
+        idx = np.arange(h * w)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "frame_pixels.npy"), flat[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+    ys, xs = np.arange(0, h, DUMP_BLOCK), np.arange(0, w, DUMP_BLOCK)
+    sums = np.add.reduceat(np.add.reduceat(frame.astype(np.float64), ys, axis=0), xs, axis=1)
+    counts = np.outer(np.diff(np.append(ys, h)), np.diff(np.append(xs, w)))[..., None]
+    np.save(os.path.join(out_dir, "frame_block_mean.npy"), sums / counts)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -328,9 +358,12 @@ def main():
     ap.add_argument("--integrator", default="Standard", choices=["Standard", "MIS", "Naive", "Direct"], help="pathtrace type (the headline is Standard)")
     ap.add_argument("--tile-size", type=int, default=8, help="tile edge in 4-px workgroups for multi-GPU sharding")
     ap.add_argument("--gather", default="root", choices=["root", "all"], help="N > 1 readback: tiles to rank 0 (ncclSend / ncclRecv) or to every rank (ncclAllGather)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle legs (cpu_baseline, parity, accuracy)")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="skip the per-kernel passes (roofline = null)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip BASELINE configs 2 and 3")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's frame to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the per-kernel roofline, CPU baseline, parity and "
+                                                        "the secondary BASELINE configs (rank 0, N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle legs (cpu_baseline, parity, accuracy)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel passes (roofline = null)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip BASELINE configs 2 and 3")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -431,8 +464,11 @@ def main():
         lo = hi = rank_units
         phases = None
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out.back().download(), args.dump_outputs)   # back = the last frame rendered (and gathered, N > 1)
+
     extras = {}
-    if rank == 0 and world == 1 and comm is None:
+    if args.full and rank == 0 and world == 1 and comm is None:
         extras = single_gpu_extras(args, api, ctx, scene, cam, cam_params, W, H, ptype)
 
     if rank == 0:

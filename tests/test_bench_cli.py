@@ -26,7 +26,7 @@ def run_bench(extra_env, *args, check=True):
 
 @pytest.mark.gpu
 def test_bench_line_contract(built):
-    d = run_bench({}, "--steps", "4", "--warmup", "2", *SMALL)
+    d = run_bench({}, "--steps", "4", "--warmup", "2", "--full", *SMALL)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline", "parity"):
         assert key in d, key
@@ -40,6 +40,26 @@ def test_bench_line_contract(built):
     assert d["config"]["frames_in_flight"] == 4 and d["config"]["traversal"] == "binary"   # reported by the library (LDS-resident scene: four lanes)
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert d["hip_runtime"]["num_hip_runtimes_mapped"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_line_and_dumped_outputs(built, tmp_path):
+    """Without --full the line holds the headline only; --dump-outputs writes the last timed frame, the same from run to run."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = run_bench({}, "--steps", "3", "--warmup", "1", "--dump-outputs", str(out), *SMALL)
+        assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and abs(d["ms_per_step"] - d["timed_seconds"] / 3 * 1e3) < 1e-6
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity"] is None and "configs" not in d
+        runs.append({n[:-len(".npy")]: np.load(out / n) for n in os.listdir(out)})
+    a, b = runs
+    assert sorted(a) == ["frame_block_mean", "frame_pixel_index", "frame_pixels"]
+    assert a["frame_pixels"].dtype == np.float32 and a["frame_pixels"].shape == (256 * 256, 4)   # a small frame is written whole
+    assert a["frame_block_mean"].dtype == np.float64 and a["frame_block_mean"].shape == (32, 32, 4)
+    assert np.array_equal(a["frame_pixel_index"], np.arange(256 * 256)) and a["frame_pixels"][:, :3].max() > 0
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
 
 
 @pytest.mark.gpu
@@ -74,6 +94,29 @@ def test_gpus_n_without_launcher_spawns_ranks_or_fails(built):
                        capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode != 0
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
+
+
+def test_options_are_listed():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+
+
+def test_dump_outputs_sample_and_block_means(tmp_path):
+    """The dump of a frame larger than the sample: at most 2^20 pixels, the same ones every time, every pixel in a block mean."""
+    from unittest import mock
+    import numpy as np
+    with mock.patch.dict(os.environ):   # bench.py sets its default GPU_MAX_HW_QUEUES on import: not for this process
+        import bench
+    frame = np.random.default_rng(3).random((1100, 1000, 4)).astype(np.float16)
+    for k in range(2):
+        bench.dump_outputs(frame, str(tmp_path / str(k)))
+    px, idx, mean = (np.load(tmp_path / "0" / f"frame_{n}.npy") for n in ("pixels", "pixel_index", "block_mean"))
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and mean.dtype == np.float64
+    assert px.shape == (1 << 20, 4) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(px, frame.reshape(-1, 4)[idx.astype(np.int64)].astype(np.float32))
+    assert mean.shape == (138, 125, 4) and np.allclose(mean[-1, -1], frame[1096:, 992:].astype(np.float64).mean(axis=(0, 1)))
+    assert sum(os.path.getsize(p) for p in (tmp_path / "0").iterdir()) <= 64 << 20
+    assert np.array_equal(idx, np.load(tmp_path / "1" / "frame_pixel_index.npy"))
 
 
 def test_world_size_mismatch_is_an_error(built):
