@@ -540,6 +540,39 @@ int lupin_hip_trace_rays_wide(LupinContext *ctx, const LupinScene *scene, uint32
  * result to be bit-identical to the host build of the same header. */
 int lupin_hip_detmath_probe(LupinContext *ctx, int fn, uint32_t n, const float *x, const float *y, float *out);
 
+/* Scattering-function probe: evaluates the device BSDF, delta-lobe, phase-function and homogeneous-medium functions
+ * (pathtracer.wgsl:1789-1949 sample_*, :1951-2095 eval_*, :2097-2229 *_pdf, :2231-2422 delta / scattering /
+ * transmittance) over n host records.  The tests require the result to be bit-identical to oracle_scatter_probe.
+ *
+ * Input record, LUPIN_SCATTER_IN_FLOATS floats:
+ *   [0] material type (LupinMatType, as a float)   [1] mode (LupinScatterMode, as a float)
+ *   [2..4] color  [5] roughness (as the material point stores it: already squared)  [6] metallic  [7] ior
+ *   [8..10] density  [11..13] scattering  [14] anisotropy
+ *   [15..17] normal  [18..20] outgoing  [21..23] incoming  [24] rnl  [25..26] rn  [27] max distance
+ * Output record, LUPIN_SCATTER_OUT_FLOATS floats: [0..2] direction  [3..5] eval  [6] pdf  [7] 0.
+ * Modes:
+ *   BSDF_SAMPLE   direction = sample_delta(rnl) when the material is delta, else sample_bsdfcos(rnl, rn); eval and pdf
+ *                 of the same family (eval_delta / sample_delta_pdf, eval_bsdfcos / sample_bsdfcos_pdf) at it
+ *   BSDF_EVAL     the same eval and pdf at the given incoming; direction = incoming
+ *   PHASE_SAMPLE  direction = sample_scattering(rn); eval = eval_scattering, pdf = sample_scattering_pdf at it
+ *   PHASE_EVAL    the same at the given incoming
+ *   MEDIUM_SAMPLE direction = (d, 0, 0) with d = sample_transmittance(density, max distance, rnl, rn[0]);
+ *                 eval = eval_transmittance(density, d), pdf = sample_transmittance_pdf(density, d, max distance)
+ *   MEDIUM_EVAL   the same with d = incoming[0]
+ * Any other mode writes zeros.  Types and modes must be small non-negative integers. */
+#define LUPIN_SCATTER_IN_FLOATS 28
+#define LUPIN_SCATTER_OUT_FLOATS 8
+typedef enum LupinScatterMode
+{
+    LUPIN_SCATTER_BSDF_SAMPLE = 0,
+    LUPIN_SCATTER_BSDF_EVAL = 1,
+    LUPIN_SCATTER_PHASE_SAMPLE = 2,
+    LUPIN_SCATTER_PHASE_EVAL = 3,
+    LUPIN_SCATTER_MEDIUM_SAMPLE = 4,
+    LUPIN_SCATTER_MEDIUM_EVAL = 5
+} LupinScatterMode;
+int lupin_hip_scatter_probe(LupinContext *ctx, uint32_t n, const float *records, float *out);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

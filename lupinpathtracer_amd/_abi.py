@@ -194,6 +194,7 @@ SYMBOLS = [
     ("lupin_hip_collapse_bvh4", C.c_int64, [_P, _U32, _P, _U32, _P, _U32, _P, C.c_uint64, C.POINTER(C.c_uint32), _P]),
     ("lupin_hip_trace_rays_wide", C.c_int, [_P, _P, _U32, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
     ("lupin_hip_detmath_probe", C.c_int, [_P, C.c_int, _U32, _P, _P, _P]),
+    ("lupin_hip_scatter_probe", C.c_int, [_P, _U32, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_lbvh_depth", _U32, [_U32]),
     ("lupin_hip_lbvh_node_count", C.c_uint64, [_U32]),

@@ -911,3 +911,26 @@ def trace_rays_wide(ctx, scene, ori, dir_, ray_epsilon=0.001):
     check(lib().lupin_hip_trace_rays_wide(ctx.handle, scene.handle, n, ptr(ori), ptr(dir_), ray_epsilon,
                                           ptr(hit), ptr(dst), ptr(uv), ptr(inst), ptr(tri), ptr(flag)))
     return hit, dst, uv, inst, tri, flag
+
+
+# lupin_hip_scatter_probe record layout (include/lupin_hip.h)
+SCATTER_IN_FLOATS = 28
+SCATTER_OUT_FLOATS = 8
+
+
+class ScatterMode(enum.IntEnum):
+    BSDF_SAMPLE = 0
+    BSDF_EVAL = 1
+    PHASE_SAMPLE = 2
+    PHASE_EVAL = 3
+    MEDIUM_SAMPLE = 4
+    MEDIUM_EVAL = 5
+
+
+def scatter_probe(ctx, records):
+    """BSDF / delta / phase / medium functions of the device over (n, SCATTER_IN_FLOATS) float32 records; returns the
+    (n, SCATTER_OUT_FLOATS) float32 outputs (direction, eval, pdf, 0)."""
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, SCATTER_IN_FLOATS)
+    out = np.zeros((len(rec), SCATTER_OUT_FLOATS), np.float32)
+    check(lib().lupin_hip_scatter_probe(ctx.handle, len(rec), ptr(rec), ptr(out)))
+    return out

@@ -2152,15 +2152,45 @@ int lupin_hip_detmath_probe(LupinContext *ctx, int fn, uint32_t n, const float *
     if (n == 0) return LUPIN_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     float *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc((void **)&dx, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&dy, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&dout, (size_t)n * 4));
-    HIP_TRY(hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dy, y, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_detmath, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, ctx->stream, fn, n, dx, dy, dout);
-    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    hipError_t e = hipMalloc((void **)&dx, (size_t)n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&dy, (size_t)n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&dout, (size_t)n * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+    {
+        hipLaunchKernelGGL(k_detmath, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, ctx->stream, fn, n, dx, dy, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    // freed on every path (hipFree(nullptr) is a no-op)
     hipFree(dx); hipFree(dy); hipFree(dout);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("lupin_hip_detmath_probe: ") + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+int lupin_hip_scatter_probe(LupinContext *ctx, uint32_t n, const float *records, float *out)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !records || !out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return LUPIN_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t in_bytes = (size_t)n * LUPIN_SCATTER_IN_FLOATS * 4, out_bytes = (size_t)n * LUPIN_SCATTER_OUT_FLOATS * 4;
+    float *din = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc((void **)&din, in_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&dout, out_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(din, records, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+    {
+        hipLaunchKernelGGL(k_scatter_probe, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, ctx->stream, n, din, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    // freed on every path (hipFree(nullptr) is a no-op)
+    hipFree(din); hipFree(dout);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("lupin_hip_scatter_probe: ") + hipGetErrorString(e));
     return LUPIN_OK;
 }
 

@@ -2033,6 +2033,71 @@ __global__ void __launch_bounds__(LP_BLOCK) k_detmath(int fn, uint32_t n, const 
     out[i] = r;
 }
 
+// The scattering functions of lupin_device.hpp over a batch of records (layout and modes: lupin_hip_scatter_probe in
+// include/lupin_hip.h).  Every call is the force-inlined function the shade kernels use.
+__global__ void __launch_bounds__(LP_BLOCK) k_scatter_probe(uint32_t n, const float *in, float *out)
+{
+    uint32_t i = blockIdx.x * LP_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float *r = in + (size_t)i * LUPIN_SCATTER_IN_FLOATS;
+    MatPoint m;
+    m.type = (uint32_t)r[0];
+    m.emission = splat(0.0f);
+    m.color = mk3(r[2], r[3], r[4]);
+    m.opacity = 1.0f;
+    m.roughness = r[5]; m.metallic = r[6]; m.ior = r[7];
+    m.density = mk3(r[8], r[9], r[10]);
+    m.scattering = mk3(r[11], r[12], r[13]);
+    m.anisotropy = r[14];
+    f3 normal = mk3(r[15], r[16], r[17]), outgoing = mk3(r[18], r[19], r[20]), incoming = mk3(r[21], r[22], r[23]);
+    float rnl = r[24], r0 = r[25], r1 = r[26], max_distance = r[27];
+    f3 ev = splat(0.0f);
+    float pdf = 0.0f;
+    switch ((uint32_t)r[1])
+    {
+    case LUPIN_SCATTER_BSDF_SAMPLE:
+    case LUPIN_SCATTER_BSDF_EVAL:
+        if (mat_is_delta(m))
+        {
+            if ((uint32_t)r[1] == LUPIN_SCATTER_BSDF_SAMPLE) incoming = delta_sample(m, normal, outgoing, rnl);
+            ev = delta_eval(m, normal, outgoing, incoming);
+            pdf = delta_pdf(m, normal, outgoing, incoming);
+        }
+        else
+        {
+            if ((uint32_t)r[1] == LUPIN_SCATTER_BSDF_SAMPLE) incoming = bsdf_sample(m, normal, outgoing, rnl, r0, r1);
+            ev = bsdf_eval(m, normal, outgoing, incoming);
+            pdf = bsdf_pdf(m, normal, outgoing, incoming);
+        }
+        break;
+    case LUPIN_SCATTER_PHASE_SAMPLE:
+    case LUPIN_SCATTER_PHASE_EVAL:
+    {
+        Medium md{m.density, m.scattering, m.anisotropy};
+        if ((uint32_t)r[1] == LUPIN_SCATTER_PHASE_SAMPLE) incoming = phase_sample(md, outgoing, r0, r1);
+        ev = phase_eval(md, outgoing, incoming);
+        pdf = phase_pdf(md, outgoing, incoming);
+        break;
+    }
+    case LUPIN_SCATTER_MEDIUM_SAMPLE:
+    case LUPIN_SCATTER_MEDIUM_EVAL:
+    {
+        float d = ((uint32_t)r[1] == LUPIN_SCATTER_MEDIUM_SAMPLE) ? medium_sample_distance(m.density, max_distance, rnl, r0) : incoming.x;
+        incoming = mk3(d, 0.0f, 0.0f);
+        ev = medium_transmittance(m.density, d);
+        pdf = medium_distance_pdf(m.density, d, max_distance);
+        break;
+    }
+    default:
+        incoming = splat(0.0f);
+        break;
+    }
+    float *o = out + (size_t)i * LUPIN_SCATTER_OUT_FLOATS;
+    o[0] = incoming.x; o[1] = incoming.y; o[2] = incoming.z;
+    o[3] = ev.x; o[4] = ev.y; o[5] = ev.z;
+    o[6] = pdf; o[7] = 0.0f;
+}
+
 // Tile pack / unpack for the multi-GPU gather.  Payload of a rank = its tiles in ascending order (include/lupin_tiles.h),
 // each tile row-major, 8 B per pixel.  One block per tile: the block first sums the pixel counts of the owner's earlier
 // tiles (a few hundred terms at most, strided over the threads), then copies the tile's rows.

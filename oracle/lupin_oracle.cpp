@@ -2434,6 +2434,70 @@ void oracle_bsdf_probe(uint32_t mat_type, const float color[3], float roughness,
     *out_pdf = pdf;
 }
 
+// Batched scattering-function probe: the record layout and modes of lupin_hip_scatter_probe (include/lupin_hip.h),
+// evaluated with the Inv:: functions (sample_bsdfcos / sample_delta / sample_scattering / sample_transmittance and
+// their eval / pdf twins).  The device probe must match it bit for bit.
+int oracle_scatter_probe(uint32_t n, const float *records, float *out)
+{
+    if (!records || !out) return -1;
+    #pragma omp parallel for schedule(static, 4096)
+    for (int64_t i = 0; i < (int64_t)n; i++)
+    {
+        const float *r = records + (size_t)i * LUPIN_SCATTER_IN_FLOATS;
+        MaterialPoint m;
+        m.mat_type = (uint32_t)r[0];
+        m.color = {r[2], r[3], r[4]};
+        m.roughness = r[5]; m.metallic = r[6]; m.ior = r[7];
+        m.density = {r[8], r[9], r[10]};
+        m.scattering = {r[11], r[12], r[13]};
+        m.sc_anisotropy = r[14];
+        const uint32_t mode = (uint32_t)r[1];
+        vec3f nrm = {r[15], r[16], r[17]}, o = {r[18], r[19], r[20]}, inc = {r[21], r[22], r[23]};
+        const float rnl = r[24], max_distance = r[27];
+        const vec2f rn = {r[25], r[26]};
+        vec3f ev = v3(0.0f);
+        float pdf = 0.0f;
+        switch (mode)
+        {
+            case LUPIN_SCATTER_BSDF_SAMPLE:
+            case LUPIN_SCATTER_BSDF_EVAL:
+                if (Inv::is_mat_delta(m)) {
+                    if (mode == LUPIN_SCATTER_BSDF_SAMPLE) inc = Inv::sample_delta(m, nrm, o, rnl);
+                    ev = Inv::eval_delta(m, nrm, o, inc);
+                    pdf = Inv::sample_delta_pdf(m, nrm, o, inc);
+                } else {
+                    if (mode == LUPIN_SCATTER_BSDF_SAMPLE) inc = Inv::sample_bsdfcos(m, nrm, o, rnl, rn);
+                    ev = Inv::eval_bsdfcos(m, nrm, o, inc);
+                    pdf = Inv::sample_bsdfcos_pdf(m, nrm, o, inc);
+                }
+                break;
+            case LUPIN_SCATTER_PHASE_SAMPLE:
+            case LUPIN_SCATTER_PHASE_EVAL:
+                if (mode == LUPIN_SCATTER_PHASE_SAMPLE) inc = Inv::sample_scattering(m, o, rn);
+                ev = Inv::eval_scattering(m, o, inc);
+                pdf = Inv::sample_scattering_pdf(m, o, inc);
+                break;
+            case LUPIN_SCATTER_MEDIUM_SAMPLE:
+            case LUPIN_SCATTER_MEDIUM_EVAL:
+            {
+                const float d = (mode == LUPIN_SCATTER_MEDIUM_SAMPLE) ? Inv::sample_transmittance(m.density, max_distance, rnl, rn.x) : inc.x;
+                inc = {d, 0.0f, 0.0f};
+                ev = Inv::eval_transmittance(m.density, d);
+                pdf = Inv::sample_transmittance_pdf(m.density, d, max_distance);
+                break;
+            }
+            default:
+                inc = v3(0.0f);
+                break;
+        }
+        float *w = out + (size_t)i * LUPIN_SCATTER_OUT_FLOATS;
+        w[0] = inc.x; w[1] = inc.y; w[2] = inc.z;
+        w[3] = ev.x; w[4] = ev.y; w[5] = ev.z;
+        w[6] = pdf; w[7] = 0.0f;
+    }
+    return 0;
+}
+
 // tonemap_and_fit_aspect (tonemapping.rs:155-224 + tonemapping.wgsl) evaluated at target pixel centres: viewport /
 // scissor (:163-167,:216-217), aspect-fit scale of the quad (:168-174), vertex positions pos * scale with tex coords
 // 0..1 (wgsl:24-48), fragment: clamp-to-edge linear sample, max(.,0), * exp2(exposure), tonemap_filmic,

@@ -50,6 +50,8 @@ def lib():
         h.oracle_bsdf_probe.restype = None
         h.oracle_bsdf_probe.argtypes = [C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        h.oracle_scatter_probe.restype = C.c_int
+        h.oracle_scatter_probe.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
         h.oracle_float_to_half.restype = C.c_uint16
         h.oracle_float_to_half.argtypes = [C.c_float]
         h.oracle_float_to_half_rtz.restype = C.c_uint16
@@ -177,6 +179,16 @@ def bsdf_probe(mat_type, color, roughness, metallic, ior, normal, outgoing, rnl,
     lib().oracle_bsdf_probe(int(mat_type), _abi.ptr(color), roughness, metallic, ior, _abi.ptr(normal), _abi.ptr(outgoing),
                             rnl, _abi.ptr(rn), _abi.ptr(inc), _abi.ptr(ev), C.byref(pdf))
     return inc, ev, float(pdf.value)
+
+
+def scatter_probe(records):
+    """oracle_scatter_probe over (n, 28) float32 records (layout of lupin_hip_scatter_probe, include/lupin_hip.h);
+    returns the (n, 8) float32 outputs: direction, eval, pdf, 0."""
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, 28)
+    out = np.zeros((len(rec), 8), np.float32)
+    if lib().oracle_scatter_probe(len(rec), _abi.ptr(rec), _abi.ptr(out)) != 0:
+        raise RuntimeError("oracle_scatter_probe failed")
+    return out
 
 
 def effective_cpus():
