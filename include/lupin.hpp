@@ -442,6 +442,36 @@ inline void tonemap_and_fit_aspect(const Device &d, TextureRef src, std::vector<
     check(lupin_hip_tonemap_and_fit_aspect(d.raw(), src.raw(), dst_rgba8.data(), dst_width, dst_height, &c));
 }
 
+// lp::DenoiseResources / build_denoise_resources / DenoiseQuality / DenoiseDesc / denoise (denoising.rs:56-306): the
+// filter is the library's own a-trous denoiser, not OIDN; the Device plays the role of the DenoiseDevice
+class DenoiseResources
+{
+  public:
+    DenoiseResources(const Device &d, uint32_t width, uint32_t height) { check(lupin_hip_build_denoise_resources(d.raw(), width, height, &res_)); }
+    DenoiseResources(DenoiseResources &&o) noexcept : res_(o.res_) { o.res_ = nullptr; }
+    DenoiseResources(const DenoiseResources &) = delete;
+    ~DenoiseResources() { if (res_) lupin_hip_destroy_denoise_resources(res_); }
+    LupinDenoiseResources *raw() const { return res_; }
+  private:
+    LupinDenoiseResources *res_ = nullptr;
+};
+inline DenoiseResources build_denoise_resources(const Device &d, uint32_t width, uint32_t height) { return DenoiseResources(d, width, height); }
+enum class DenoiseQuality : uint32_t { Low = LUPIN_DENOISE_LOW, Medium = LUPIN_DENOISE_MEDIUM, High = LUPIN_DENOISE_HIGH };
+struct DenoiseDesc
+{
+    TextureRef pathtrace_output;
+    std::optional<TextureRef> albedo;
+    std::optional<TextureRef> normals;
+    TextureRef denoise_output;   // may be pathtrace_output: in place
+    DenoiseQuality quality = DenoiseQuality::High;
+};
+inline void denoise(const Device &d, DenoiseResources &res, const DenoiseDesc &desc)
+{
+    const LupinDenoiseDesc c{desc.pathtrace_output.raw(), desc.albedo ? desc.albedo->raw() : nullptr, desc.normals ? desc.normals->raw() : nullptr,
+                             desc.denoise_output.raw(), (uint32_t)desc.quality};
+    check(lupin_hip_denoise(d.raw(), res.raw(), &c));
+}
+
 }  // namespace lp
 
 namespace lpl {

@@ -455,6 +455,37 @@ int lupin_hip_pathtrace_scene_tiles(LupinContext *ctx, const LupinPathtraceResou
                                     uint32_t pathtrace_type, const LupinPathtraceDesc *desc,
                                     uint32_t tile_size, uint32_t rank, uint32_t world);
 
+/* ---- denoising (denoising.rs:83-306; the context plays the role of the reference's DenoiseDevice) ----
+ * The reference runs OIDN; this library runs a G-buffer-guided edge-avoiding a-trous wavelet filter of its own, in HIP
+ * (DESIGN.md 9): albedo demodulation, normal / albedo / luminance-variance edge stopping, 3 / 4 / 5 passes. */
+
+/* denoising.rs:208-218 DenoiseQuality (default High) */
+enum LupinDenoiseQuality { LUPIN_DENOISE_LOW = 0, LUPIN_DENOISE_MEDIUM = 1, LUPIN_DENOISE_HIGH = 2 };
+
+/* denoising.rs:193-206 DenoiseDesc.  Every texture is Rgba16Float of the resources' size. */
+typedef struct LupinDenoiseDesc {
+    const LupinTexture *pathtrace_output;   /* linear colour (required) */
+    const LupinTexture *albedo;             /* NULL = None; FalsecolorType Albedo */
+    const LupinTexture *normals;            /* NULL = None; FalsecolorType Normals (signed; 0 = background) */
+    LupinTexture       *denoise_output;     /* required; may be pathtrace_output (in place, same bits as out of place) */
+    uint32_t            quality;            /* LupinDenoiseQuality */
+} LupinDenoiseDesc;
+
+typedef struct LupinDenoiseResources LupinDenoiseResources;
+
+/* lp::build_denoise_resources (denoising.rs:83-191): the ping-pong scratch and guides of one width x height
+ * (64 bytes per pixel), reusable for any number of denoise calls of that size. */
+int lupin_hip_build_denoise_resources(LupinContext *ctx, uint32_t width, uint32_t height, LupinDenoiseResources **out);
+/* Drop for DenoiseResources (denoising.rs:71-81): waits for the context's work, then frees the scratch. */
+void lupin_hip_destroy_denoise_resources(LupinDenoiseResources *res);
+/* lp::denoise (denoising.rs:220-306).  Checks what the reference asserts (:226-237: every given texture has the
+ * resources' size) plus NULL colour / output textures, quality > 2 and objects of another or a destroyed context:
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing written.  Recorded pathtrace calls run first (their targets may be the inputs); the
+ * filter is enqueued on the context's primary stream after every frame enqueued so far and the call returns without a
+ * host stall (the reference stalls, :258).  Output: f16 rounded to nearest even, alpha copied from pathtrace_output; the
+ * output's f32 accumulator becomes invalid (lupin_hip_texture_download_rgba32f of it fails). */
+int lupin_hip_denoise(LupinContext *ctx, LupinDenoiseResources *res, const LupinDenoiseDesc *desc);
+
 /* ---- measurement hooks (no reference counterpart; the reference exposes none) ---- */
 
 typedef struct LupinStats {

@@ -4,7 +4,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 macro_rules! opaque { ($($n:ident),*) => { $(#[repr(C)] pub struct $n { _p: [u8; 0] })* } }
-opaque!(LupinContext, LupinPathtraceResources, LupinScene, LupinTexture, LupinDoubleBufferedTexture, LupinComm);
+opaque!(LupinContext, LupinPathtraceResources, LupinScene, LupinTexture, LupinDoubleBufferedTexture, LupinComm, LupinDenoiseResources);
 
 pub const LUPIN_OK: c_int = 0;
 pub const LUPIN_SENTINEL_IDX: u32 = 0xFFFF_FFFF;
@@ -56,6 +56,14 @@ pub const LUPIN_SENTINEL_IDX: u32 = 0xFFFF_FFFF;
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinTonemapDesc {
     pub has_viewport: u32, pub viewport_x: f32, pub viewport_y: f32, pub viewport_w: f32, pub viewport_h: f32,
     pub exposure: f32, pub filmic: u32, pub srgb: u32, pub clear: u32,
+}
+// denoising.rs:193-218 (quality: 0 Low, 1 Medium, 2 High = the reference's default)
+pub const LUPIN_DENOISE_LOW: u32 = 0;
+pub const LUPIN_DENOISE_MEDIUM: u32 = 1;
+pub const LUPIN_DENOISE_HIGH: u32 = 2;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinDenoiseDesc {
+    pub pathtrace_output: *const LupinTexture, pub albedo: *const LupinTexture, pub normals: *const LupinTexture,
+    pub denoise_output: *mut LupinTexture, pub quality: u32,
 }
 
 extern "C" {
@@ -112,6 +120,10 @@ extern "C" {
     pub fn lupin_hip_texture_download_rgba32f(tex: *const LupinTexture, out_pixels: *mut f32) -> c_int;
     pub fn lupin_hip_tonemap_and_fit_aspect(ctx: *mut LupinContext, src: *const LupinTexture, dst_rgba8: *mut u8, w: u32, h: u32,
                                             desc: *const LupinTonemapDesc) -> c_int;
+    // lp::build_denoise_resources / denoise (denoising.rs:83-306), the library's own a-trous filter in place of OIDN
+    pub fn lupin_hip_build_denoise_resources(ctx: *mut LupinContext, width: u32, height: u32, out: *mut *mut LupinDenoiseResources) -> c_int;
+    pub fn lupin_hip_destroy_denoise_resources(res: *mut LupinDenoiseResources);
+    pub fn lupin_hip_denoise(ctx: *mut LupinContext, res: *mut LupinDenoiseResources, desc: *const LupinDenoiseDesc) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

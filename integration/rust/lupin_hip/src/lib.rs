@@ -12,6 +12,7 @@
 //! | `pathtrace_scene`, `PathtraceDesc`, `AccumulationParams`, `TileParams` | [`pathtrace_scene`]  |
 //! | `pathtrace_scene_falsecolor`, `pathtrace_scene_debug`| [`pathtrace_scene_falsecolor`], [`pathtrace_scene_debug`] |
 //! | `tonemap_and_fit_aspect`, `TonemapDesc`              | [`tonemap_and_fit_aspect`]             |
+//! | `build_denoise_resources`, `denoise`, `DenoiseDesc`, `DenoiseQuality` | [`build_denoise_resources`], [`denoise`] (own a-trous filter, not OIDN) |
 //!
 //! Like the reference, failures panic (the reference asserts / panics; the C ABI returns a status + message).
 pub mod ffi;
@@ -177,4 +178,23 @@ pub fn tonemap_and_fit_aspect(device: &Device, src: Texture, dst: &mut [u8], dst
     let c = LupinTonemapDesc { has_viewport: desc.viewport.is_some() as u32, viewport_x: v.x, viewport_y: v.y, viewport_w: v.w, viewport_h: v.h,
                                exposure: desc.exposure, filmic: desc.filmic as u32, srgb: desc.srgb as u32, clear: desc.clear as u32 };
     check(unsafe { lupin_hip_tonemap_and_fit_aspect(device.raw, src.raw, dst.as_mut_ptr(), dst_width, dst_height, &c) });
+}
+
+/// `lp::DenoiseResources` (denoising.rs:56): scratch of one width x height.
+pub struct DenoiseResources { raw: *mut LupinDenoiseResources }
+impl Drop for DenoiseResources { fn drop(&mut self) { unsafe { lupin_hip_destroy_denoise_resources(self.raw) } } }
+/// `lp::build_denoise_resources` (denoising.rs:83); the `Device` plays the role of the `DenoiseDevice`.
+pub fn build_denoise_resources(device: &Device, width: u32, height: u32) -> DenoiseResources {
+    let mut raw = ptr::null_mut();
+    check(unsafe { lupin_hip_build_denoise_resources(device.raw, width, height, &mut raw) });
+    DenoiseResources { raw }
+}
+#[derive(Copy, Clone, Debug, Default)] pub enum DenoiseQuality { Low = 0, Medium = 1, #[default] High = 2 }   // denoising.rs:208-218
+pub struct DenoiseDesc { pub pathtrace_output: Texture, pub albedo: Option<Texture>, pub normals: Option<Texture>, pub denoise_output: Texture, pub quality: DenoiseQuality }
+/// `lp::denoise` (denoising.rs:222): enqueued after every frame so far; returns without a host stall.
+pub fn denoise(device: &Device, resources: &mut DenoiseResources, desc: &DenoiseDesc) {
+    let c = LupinDenoiseDesc { pathtrace_output: desc.pathtrace_output.raw, albedo: desc.albedo.map_or(ptr::null(), |t| t.raw as *const _),
+                               normals: desc.normals.map_or(ptr::null(), |t| t.raw as *const _), denoise_output: desc.denoise_output.raw,
+                               quality: desc.quality as u32 };
+    check(unsafe { lupin_hip_denoise(device.raw, resources.raw, &c) });
 }

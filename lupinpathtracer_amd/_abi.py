@@ -132,6 +132,11 @@ class TonemapDescC(C.Structure):
                 ("viewport_h", C.c_float), ("exposure", C.c_float), ("filmic", C.c_uint32), ("srgb", C.c_uint32), ("clear", C.c_uint32)]
 
 
+class DenoiseDescC(C.Structure):   # LupinDenoiseDesc (denoising.rs:193-206)
+    _fields_ = [("pathtrace_output", C.c_void_p), ("albedo", C.c_void_p), ("normals", C.c_void_p), ("denoise_output", C.c_void_p),
+                ("quality", C.c_uint32)]
+
+
 class StatsC(C.Structure):
     _fields_ = [("path_bounces", C.c_uint64), ("paths", C.c_uint64), ("extend_launches", C.c_uint64),
                 ("extend_ms", C.c_double), ("shade_ms", C.c_double), ("total_ms", C.c_double),
@@ -196,6 +201,9 @@ SYMBOLS = [
     ("lupin_hip_detmath_probe", C.c_int, [_P, C.c_int, _U32, _P, _P, _P]),
     ("lupin_hip_scatter_probe", C.c_int, [_P, _U32, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
+    ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
+    ("lupin_hip_destroy_denoise_resources", None, [_P]),
+    ("lupin_hip_denoise", C.c_int, [_P, _P, C.POINTER(DenoiseDescC)]),
     ("lupin_hip_lbvh_depth", _U32, [_U32]),
     ("lupin_hip_lbvh_node_count", C.c_uint64, [_U32]),
     ("lupin_hip_build_bvh_device", C.c_int64, [_P, _P, _U32, _P, _U32, _P, C.c_uint64]),

@@ -9,6 +9,9 @@ data_structures.rs, on top of the C ABI in include/lupin_hip.h:
                                          renderer.rs:644-766  -> dataclasses below
     lp::get_num_tiles                    renderer.rs:675      -> get_num_tiles
     lp::DoubleBufferedTexture            wgpu_utils.rs:279    -> DoubleBufferedTexture
+    lp::build_denoise_resources / denoise / DenoiseDesc / DenoiseQuality
+                                         denoising.rs:83-306  -> build_denoise_resources, denoise (the library's own
+                                                                 a-trous filter in HIP, not OIDN: DESIGN.md 9)
     lp::SceneCPU / validate_scene / build_accel_structures_and_upload
                                          renderer.rs:62-76, data_structures.rs:696-928
 
@@ -780,6 +783,68 @@ def tonemap_and_fit_aspect(ctx, src, dst_width, dst_height, desc=None, dst=None)
                           float(desc.exposure), 1 if desc.filmic else 0, 1 if desc.srgb else 0, 1 if desc.clear else 0)
     check(lib().lupin_hip_tonemap_and_fit_aspect(ctx.handle, src.handle, ptr(out), dst_width, dst_height, C.byref(c)))
     return out
+
+
+class DenoiseQuality(enum.IntEnum):  # denoising.rs:208-218
+    Low = 0
+    Medium = 1
+    High = 2
+
+    @classmethod
+    def default(cls):
+        return cls.High   # #[default]
+
+
+@dataclass
+class DenoiseDesc:  # denoising.rs:193-206
+    pathtrace_output: "Texture"
+    denoise_output: "Texture"          # may be pathtrace_output: denoised in place
+    albedo: Optional["Texture"] = None   # FalsecolorType.Albedo
+    normals: Optional["Texture"] = None  # FalsecolorType.Normals
+    quality: DenoiseQuality = DenoiseQuality.High
+
+
+def _require_device(ctx, what):
+    if ctx is None or getattr(ctx, "handle", None) is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), f"{what} needs a device context; there is no CPU fallback")
+
+
+class DenoiseResources:
+    """lp::DenoiseResources (denoising.rs:56-81): the filter's scratch for one width x height."""
+
+    def __init__(self, ctx, width, height):
+        _require_device(ctx, "build_denoise_resources")
+        self.ctx = ctx
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        check(lib().lupin_hip_build_denoise_resources(ctx.handle, self.width, self.height, C.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        try:
+            if self.handle:   # after its context: only frees the scratch
+                lib().lupin_hip_destroy_denoise_resources(self.handle)
+            self.handle = None
+        except Exception:
+            pass
+
+
+def build_denoise_resources(ctx, width, height):
+    """lp::build_denoise_resources (denoising.rs:83): reusable for every denoise of that size."""
+    return DenoiseResources(ctx, width, height)
+
+
+def denoise(ctx, resources, desc: DenoiseDesc):
+    """lp::denoise (denoising.rs:222-306): enqueued after every frame so far, returns without a host stall.  The output is
+    f16 (nearest even) with the colour's alpha; its f32 accumulator is invalidated (Texture.download_f32 then fails)."""
+    _require_device(ctx, "denoise")
+    if resources is None or getattr(resources, "handle", None) is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "denoise resources were not built on a device")
+
+    def h(t):
+        return None if t is None else t.handle
+    c = _abi.DenoiseDescC(h(desc.pathtrace_output), h(desc.albedo), h(desc.normals), h(desc.denoise_output), int(desc.quality))
+    check(lib().lupin_hip_denoise(ctx.handle, resources.handle, C.byref(c)))
 
 
 def pathtrace_scene_tiles(ctx, resources, scene, render_target, pathtrace_type, desc, tile_size, rank, world):

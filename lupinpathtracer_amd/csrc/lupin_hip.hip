@@ -1,7 +1,7 @@
 // lupin_hip.hip -- host side of liblupin_hip.so: the C ABI of include/lupin_hip.h (contexts and their lanes, scene upload,
 // textures, the pathtrace_scene family, measurement hooks, probes).  The stage kernels live in lupin_stages.hpp, the
 // traversal / material / light device functions in lupin_device.hpp, the CPU builders in builders.cpp, the device BLAS
-// builder in lbvh.hip.
+// builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp.
 //
 // THERE IS NO CPU FALLBACK: without a HIP device every entry point that needs one fails with LUPIN_ERR_NO_DEVICE.
 
@@ -19,6 +19,7 @@
 #include <atomic>
 
 #include "lupin_stages.hpp"
+#include "lupin_denoise.hpp"
 #include "lupin_internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -2264,6 +2265,105 @@ int lupin_hip_tonemap_and_fit_aspect(LupinContext *ctx, const LupinTexture *src,
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     hipFree(d);
     if (e != hipSuccess) return fail(LUPIN_ERR_HIP, hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+
+// ---- denoising (denoising.rs:83-306; kernels and algorithm: lupin_denoise.hpp) ----
+
+}  // extern "C"
+
+struct LupinDenoiseResources
+{
+    LupinContext *ctx;
+    int device;
+    uint32_t width, height;
+    float4 *iv[2];          // (irradiance rgb, variance) ping-pong
+    DenoiseGuide *guide;    // normalised normals + albedo, written by the prep pass
+};
+
+template <bool FINAL>
+static void launch_denoise_iter(bool has_n, bool has_a, dim3 grid, dim3 block, hipStream_t st, const float4 *src, float4 *dst,
+                                const DenoiseGuide *guide, const uint2 *color, uint2 *out, uint32_t W, uint32_t H, int step)
+{
+    if (has_n && has_a) hipLaunchKernelGGL((k_denoise_iter<FINAL, true, true>), grid, block, 0, st, src, dst, guide, color, out, W, H, step);
+    else if (has_n) hipLaunchKernelGGL((k_denoise_iter<FINAL, true, false>), grid, block, 0, st, src, dst, guide, color, out, W, H, step);
+    else if (has_a) hipLaunchKernelGGL((k_denoise_iter<FINAL, false, true>), grid, block, 0, st, src, dst, guide, color, out, W, H, step);
+    else hipLaunchKernelGGL((k_denoise_iter<FINAL, false, false>), grid, block, 0, st, src, dst, guide, color, out, W, H, step);
+}
+
+extern "C" {
+
+int lupin_hip_build_denoise_resources(LupinContext *ctx, uint32_t width, uint32_t height, LupinDenoiseResources **out)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!out || width == 0 || height == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "bad denoise resources size");
+    if ((uint64_t)width * height > 0xFFFFFFFFull / 2) return fail(LUPIN_ERR_INVALID_ARGUMENT, "denoise size too large");
+    HIP_TRY(hipSetDevice(ctx->device));
+    LupinDenoiseResources *r = new LupinDenoiseResources();
+    r->ctx = ctx; r->device = ctx->device; r->width = width; r->height = height;
+    r->iv[0] = r->iv[1] = nullptr; r->guide = nullptr;
+    const size_t px = (size_t)width * height;
+    hipError_t e = hipMalloc((void **)&r->iv[0], px * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc((void **)&r->iv[1], px * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc((void **)&r->guide, px * sizeof(DenoiseGuide));
+    if (e != hipSuccess)
+    {
+        hipFree(r->iv[0]); hipFree(r->iv[1]); hipFree(r->guide);
+        delete r;
+        return fail(LUPIN_ERR_OUT_OF_MEMORY, hipGetErrorString(e));
+    }
+    *out = r;
+    return LUPIN_OK;
+}
+
+void lupin_hip_destroy_denoise_resources(LupinDenoiseResources *res)
+{
+    if (!res) return;
+    hipSetDevice(res->device);
+    if (ctx_alive(res->ctx)) sync_all(res->ctx);   // a destroyed context has drained its streams already
+    hipFree(res->iv[0]); hipFree(res->iv[1]); hipFree(res->guide);
+    delete res;
+}
+
+int lupin_hip_denoise(LupinContext *ctx, LupinDenoiseResources *res, const LupinDenoiseDesc *desc)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!res || !desc) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (res->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "denoise resources of another context");
+    if (!desc->pathtrace_output || !desc->denoise_output) return fail(LUPIN_ERR_INVALID_ARGUMENT, "pathtrace_output and denoise_output are required");
+    if (desc->quality > LUPIN_DENOISE_HIGH) return fail(LUPIN_ERR_INVALID_ARGUMENT, "bad denoise quality");
+    const LupinTexture *texs[4] = {desc->pathtrace_output, desc->albedo, desc->normals, desc->denoise_output};
+    for (const LupinTexture *t : texs)
+    {
+        if (!t) continue;
+        if (t->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "texture of another or a destroyed context");
+        // denoising.rs:227-236
+        if (t->width != res->width || t->height != res->height) return fail(LUPIN_ERR_INVALID_ARGUMENT, "texture size differs from the denoise resources' size");
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the inputs may be targets of recorded pathtrace calls: run them, then order the filter after every frame in flight
+    int frc = flush_pending(ctx);
+    if (frc != LUPIN_OK) return frc;
+    join_primary(ctx);
+    const uint32_t W = res->width, H = res->height;
+    const dim3 block(LP_DN_BX, LP_DN_BY), grid((W + LP_DN_BX - 1) / LP_DN_BX, (H + LP_DN_BY - 1) / LP_DN_BY);
+    const uint2 *color = (const uint2 *)desc->pathtrace_output->data;
+    hipLaunchKernelGGL(k_denoise_prep, grid, block, 0, ctx->stream, color, desc->albedo ? (const uint2 *)desc->albedo->data : nullptr,
+                       desc->normals ? (const uint2 *)desc->normals->data : nullptr, res->iv[0], res->guide, W, H);
+    const int passes = 3 + (int)desc->quality;   // Low / Medium / High: 3 / 4 / 5
+    const bool has_n = desc->normals != nullptr, has_a = desc->albedo != nullptr;
+    for (int i = 0; i < passes; i++)
+    {
+        const float4 *src = res->iv[i & 1];
+        if (i + 1 < passes)
+            launch_denoise_iter<false>(has_n, has_a, grid, block, ctx->stream, src, res->iv[(i + 1) & 1], res->guide, color, nullptr, W, H, 1 << i);
+        else
+            launch_denoise_iter<true>(has_n, has_a, grid, block, ctx->stream, src, nullptr, res->guide, color,
+                                      (uint2 *)desc->denoise_output->data, W, H, 1 << i);
+    }
+    HIP_TRY(hipGetLastError());
+    desc->denoise_output->accum32_valid = false;
     return LUPIN_OK;
 }
 
