@@ -472,6 +472,46 @@ inline void denoise(const Device &d, DenoiseResources &res, const DenoiseDesc &d
     check(lupin_hip_denoise(d.raw(), res.raw(), &c));
 }
 
+// Adaptive sampling (no reference counterpart): renders only the 8x8 blocks that have not converged
+struct AdaptiveParams
+{
+    float threshold = 0.01f;   // relative standard error of the mean a block must fall below; 0 = never converge
+    uint32_t min_frames = 8;
+    uint32_t max_frames = 0;   // 0 = no cap
+};
+class AdaptiveResources
+{
+  public:
+    AdaptiveResources(const Device &d, uint32_t width, uint32_t height) : ctx_(d.raw()) { check(lupin_hip_build_adaptive_resources(ctx_, width, height, &res_)); }
+    AdaptiveResources(AdaptiveResources &&o) noexcept : ctx_(o.ctx_), res_(o.res_) { o.res_ = nullptr; }
+    AdaptiveResources(const AdaptiveResources &) = delete;
+    ~AdaptiveResources() { if (res_) lupin_hip_destroy_adaptive_resources(res_); }
+    LupinAdaptiveResources *raw() const { return res_; }
+    // where accum_counter goes back to 0 (camera or scene changed)
+    void reset() { check(lupin_hip_adaptive_reset(ctx_, res_)); }
+    LupinAdaptiveStats stats() const { LupinAdaptiveStats s{}; check(lupin_hip_adaptive_stats(ctx_, res_, &s)); return s; }
+    // any pointer may be null; frames W*H, moments W*H*2 (mean, M2), block_error / block_active ceil(W/8)*ceil(H/8)
+    void download(uint32_t *frames, float *moments, float *block_error, uint8_t *block_active) const
+    {
+        check(lupin_hip_adaptive_download(ctx_, res_, frames, moments, block_error, block_active));
+    }
+  private:
+    LupinContext *ctx_ = nullptr;
+    LupinAdaptiveResources *res_ = nullptr;
+};
+inline AdaptiveResources build_adaptive_resources(const Device &d, uint32_t width, uint32_t height) { return AdaptiveResources(d, width, height); }
+// desc.accum_params (with its prev_frame) is required; desc.tile_params must be empty
+inline void pathtrace_scene_adaptive(const Device &d, const PathtraceResources &res, const Scene &scene, TextureRef render_target,
+                                     PathtraceType type, const PathtraceDesc &desc, AdaptiveResources &ares, const AdaptiveParams &params = {})
+{
+    LupinAccumulationParams ap{};
+    LupinTileParams tp{};
+    LupinPathtraceDesc c{};
+    detail::fill_desc(desc, ap, tp, c);
+    const LupinAdaptiveParams p{params.threshold, params.min_frames, params.max_frames};
+    check(lupin_hip_pathtrace_scene_adaptive(d.raw(), res.raw(), scene.raw(), render_target.raw(), (uint32_t)type, &c, ares.raw(), &p));
+}
+
 }  // namespace lp
 
 namespace lpl {

@@ -486,6 +486,55 @@ void lupin_hip_destroy_denoise_resources(LupinDenoiseResources *res);
  * output's f32 accumulator becomes invalid (lupin_hip_texture_download_rgba32f of it fails). */
 int lupin_hip_denoise(LupinContext *ctx, LupinDenoiseResources *res, const LupinDenoiseDesc *desc);
 
+/* ---- adaptive sampling (no reference counterpart) ----
+ * Renders only the pixels of active 8x8 blocks.  Per pixel p the resources keep n_p, the frames p has taken since the
+ * latest reset, and f32 Welford moments (mean_p, M2_p) of the frame luminance (0.2126 r + 0.7152 g) + 0.0722 b.
+ * For one call with accum_params {prev, base}:
+ *   active p:   exactly what lupin_hip_pathtrace_scene with accum_counter = base + n_p renders at p (same seed, blend,
+ *               f16 rounding / f32 accumulator); then n_p += 1 and the moments take the frame's clamped spp-average
+ *   inactive p: prev's texel copied bit for bit (f32 mode: prev's f32 value if valid, else its f16 texel widened)
+ * After the frame, on the device: e_p = +inf if n_p < 2 or a moment is not finite, else
+ * sqrt(M2_p / (n_p (n_p - 1))) / (mean_p + 1e-3); E_b = max e_p over the block's in-image pixels; a block converged when
+ * E_b < threshold and every n_p >= min_frames; it is active for the next call when it or one of its 8 neighbours has
+ * not converged, and not every n_p has reached max_frames (0 = no cap).  threshold 0: nothing converges.
+ * Ping-ponging a double-buffered texture therefore gives, at every pixel, the ordinary sequence's image at that
+ * pixel's own frame count.  Memory: 12 B per pixel + 14 B per block. */
+typedef struct LupinAdaptiveParams {
+    float    threshold;     /* relative standard error a block must fall below (>= 0; 0 = never converge) */
+    uint32_t min_frames;    /* frames every pixel of a block takes before it may stop */
+    uint32_t max_frames;    /* 0 = no cap */
+} LupinAdaptiveParams;
+
+typedef struct LupinAdaptiveStats {
+    uint64_t active_pixels;     /* in-image pixels of the blocks the next call renders */
+    uint64_t pixel_frames;      /* sum of n_p: pixel-frames rendered since the latest reset */
+    uint32_t calls;             /* adaptive calls since the latest reset */
+    uint32_t max_frames_taken;  /* max n_p */
+} LupinAdaptiveStats;
+
+typedef struct LupinAdaptiveResources LupinAdaptiveResources;
+
+/* State for one width x height, reset (every block active, counts and moments 0). */
+int lupin_hip_build_adaptive_resources(LupinContext *ctx, uint32_t width, uint32_t height, LupinAdaptiveResources **out);
+/* Waits for the context's work, then frees the state. */
+void lupin_hip_destroy_adaptive_resources(LupinAdaptiveResources *res);
+/* Counts and moments 0, every block active: call it where accum_counter goes back to 0 (camera or scene changed).
+ * Enqueued after every frame so far. */
+int lupin_hip_adaptive_reset(LupinContext *ctx, LupinAdaptiveResources *res);
+/* One adaptive frame.  LUPIN_ERR_INVALID_ARGUMENT, nothing written, for: a NULL argument, accum_params or its prev_frame
+ * missing, tile_params given, render_target / prev_frame / resources of different sizes, objects of another context,
+ * a NaN or negative threshold, an unknown pathtrace_type.  prev_frame == render_target: LUPIN_ERR_SAME_TARGET.
+ * Recorded pathtrace calls run first; the call is one wavefront of its own, ordered after the previous call's update. */
+int lupin_hip_pathtrace_scene_adaptive(LupinContext *ctx, const LupinPathtraceResources *res, const LupinScene *scene,
+                                       LupinTexture *render_target, uint32_t pathtrace_type, const LupinPathtraceDesc *desc,
+                                       LupinAdaptiveResources *ares, const LupinAdaptiveParams *params);
+/* Synchronises. */
+int lupin_hip_adaptive_stats(LupinContext *ctx, const LupinAdaptiveResources *ares, LupinAdaptiveStats *out);
+/* Any pointer may be NULL; synchronises.  frames: W*H u32; moments: W*H*2 f32 (mean, M2); block_error (f32, +inf = no
+ * estimate) and block_active (u8): ceil(W/8) * ceil(H/8), row-major. */
+int lupin_hip_adaptive_download(LupinContext *ctx, const LupinAdaptiveResources *ares, uint32_t *frames, float *moments,
+                                float *block_error, uint8_t *block_active);
+
 /* ---- measurement hooks (no reference counterpart; the reference exposes none) ---- */
 
 typedef struct LupinStats {

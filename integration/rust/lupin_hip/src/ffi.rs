@@ -4,7 +4,8 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 macro_rules! opaque { ($($n:ident),*) => { $(#[repr(C)] pub struct $n { _p: [u8; 0] })* } }
-opaque!(LupinContext, LupinPathtraceResources, LupinScene, LupinTexture, LupinDoubleBufferedTexture, LupinComm, LupinDenoiseResources);
+opaque!(LupinContext, LupinPathtraceResources, LupinScene, LupinTexture, LupinDoubleBufferedTexture, LupinComm, LupinDenoiseResources,
+        LupinAdaptiveResources);
 
 pub const LUPIN_OK: c_int = 0;
 pub const LUPIN_SENTINEL_IDX: u32 = 0xFFFF_FFFF;
@@ -65,6 +66,11 @@ pub const LUPIN_DENOISE_HIGH: u32 = 2;
     pub pathtrace_output: *const LupinTexture, pub albedo: *const LupinTexture, pub normals: *const LupinTexture,
     pub denoise_output: *mut LupinTexture, pub quality: u32,
 }
+// adaptive sampling (no reference counterpart)
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinAdaptiveParams { pub threshold: f32, pub min_frames: u32, pub max_frames: u32 }
+#[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinAdaptiveStats {
+    pub active_pixels: u64, pub pixel_frames: u64, pub calls: u32, pub max_frames_taken: u32,
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -124,6 +130,16 @@ extern "C" {
     pub fn lupin_hip_build_denoise_resources(ctx: *mut LupinContext, width: u32, height: u32, out: *mut *mut LupinDenoiseResources) -> c_int;
     pub fn lupin_hip_destroy_denoise_resources(res: *mut LupinDenoiseResources);
     pub fn lupin_hip_denoise(ctx: *mut LupinContext, res: *mut LupinDenoiseResources, desc: *const LupinDenoiseDesc) -> c_int;
+    // adaptive sampling: only 8x8 blocks that have not converged are rendered
+    pub fn lupin_hip_build_adaptive_resources(ctx: *mut LupinContext, width: u32, height: u32, out: *mut *mut LupinAdaptiveResources) -> c_int;
+    pub fn lupin_hip_destroy_adaptive_resources(res: *mut LupinAdaptiveResources);
+    pub fn lupin_hip_adaptive_reset(ctx: *mut LupinContext, res: *mut LupinAdaptiveResources) -> c_int;
+    pub fn lupin_hip_pathtrace_scene_adaptive(ctx: *mut LupinContext, res: *const LupinPathtraceResources, scene: *const LupinScene,
+                                              render_target: *mut LupinTexture, pathtrace_type: u32, desc: *const LupinPathtraceDesc,
+                                              ares: *mut LupinAdaptiveResources, params: *const LupinAdaptiveParams) -> c_int;
+    pub fn lupin_hip_adaptive_stats(ctx: *mut LupinContext, ares: *const LupinAdaptiveResources, out: *mut LupinAdaptiveStats) -> c_int;
+    pub fn lupin_hip_adaptive_download(ctx: *mut LupinContext, ares: *const LupinAdaptiveResources, frames: *mut u32, moments: *mut f32,
+                                       block_error: *mut f32, block_active: *mut u8) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

@@ -13,6 +13,7 @@
 //! | `pathtrace_scene_falsecolor`, `pathtrace_scene_debug`| [`pathtrace_scene_falsecolor`], [`pathtrace_scene_debug`] |
 //! | `tonemap_and_fit_aspect`, `TonemapDesc`              | [`tonemap_and_fit_aspect`]             |
 //! | `build_denoise_resources`, `denoise`, `DenoiseDesc`, `DenoiseQuality` | [`build_denoise_resources`], [`denoise`] (own a-trous filter, not OIDN) |
+//! | (no counterpart)                                     | [`build_adaptive_resources`], [`pathtrace_scene_adaptive`] (adaptive sampling) |
 //!
 //! Like the reference, failures panic (the reference asserts / panics; the C ABI returns a status + message).
 pub mod ffi;
@@ -197,4 +198,26 @@ pub fn denoise(device: &Device, resources: &mut DenoiseResources, desc: &Denoise
                                normals: desc.normals.map_or(ptr::null(), |t| t.raw as *const _), denoise_output: desc.denoise_output.raw,
                                quality: desc.quality as u32 };
     check(unsafe { lupin_hip_denoise(device.raw, resources.raw, &c) });
+}
+
+/// Adaptive sampling's per-pixel / per-block state (no reference counterpart).
+pub struct AdaptiveResources { raw: *mut LupinAdaptiveResources, ctx: *mut LupinContext }
+impl Drop for AdaptiveResources { fn drop(&mut self) { unsafe { lupin_hip_destroy_adaptive_resources(self.raw) } } }
+impl AdaptiveResources {
+    /// Counts and moments to 0, every block active: call it where `accum_counter` goes back to 0.
+    pub fn reset(&mut self) { check(unsafe { lupin_hip_adaptive_reset(self.ctx, self.raw) }); }
+    pub fn stats(&self) -> LupinAdaptiveStats { let mut s = LupinAdaptiveStats::default(); check(unsafe { lupin_hip_adaptive_stats(self.ctx, self.raw, &mut s) }); s }
+}
+pub fn build_adaptive_resources(device: &Device, width: u32, height: u32) -> AdaptiveResources {
+    let mut raw = ptr::null_mut();
+    check(unsafe { lupin_hip_build_adaptive_resources(device.raw, width, height, &mut raw) });
+    AdaptiveResources { raw, ctx: device.raw }
+}
+#[derive(Copy, Clone, Debug)] pub struct AdaptiveParams { pub threshold: f32, pub min_frames: u32, pub max_frames: u32 }
+impl Default for AdaptiveParams { fn default() -> Self { Self { threshold: 0.01, min_frames: 8, max_frames: 0 } } }
+/// One frame of the blocks that have not converged; `desc.accum_params` is required, `desc.tile_params` must be `None`.
+pub fn pathtrace_scene_adaptive(device: &Device, resources: &PathtraceResources, scene: &Scene, render_target: Texture, pathtrace_type: PathtraceType,
+                                desc: &PathtraceDesc, adaptive: &mut AdaptiveResources, params: &AdaptiveParams) {
+    let p = LupinAdaptiveParams { threshold: params.threshold, min_frames: params.min_frames, max_frames: params.max_frames };
+    with_desc(desc, |c| check(unsafe { lupin_hip_pathtrace_scene_adaptive(device.raw, resources.raw, scene.raw, render_target.raw, pathtrace_type as u32, c, adaptive.raw, &p) }));
 }

@@ -137,6 +137,14 @@ class DenoiseDescC(C.Structure):   # LupinDenoiseDesc (denoising.rs:193-206)
                 ("quality", C.c_uint32)]
 
 
+class AdaptiveParamsC(C.Structure):   # LupinAdaptiveParams
+    _fields_ = [("threshold", C.c_float), ("min_frames", C.c_uint32), ("max_frames", C.c_uint32)]
+
+
+class AdaptiveStatsC(C.Structure):   # LupinAdaptiveStats
+    _fields_ = [("active_pixels", C.c_uint64), ("pixel_frames", C.c_uint64), ("calls", C.c_uint32), ("max_frames_taken", C.c_uint32)]
+
+
 class StatsC(C.Structure):
     _fields_ = [("path_bounces", C.c_uint64), ("paths", C.c_uint64), ("extend_launches", C.c_uint64),
                 ("extend_ms", C.c_double), ("shade_ms", C.c_double), ("total_ms", C.c_double),
@@ -204,6 +212,12 @@ SYMBOLS = [
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),
     ("lupin_hip_denoise", C.c_int, [_P, _P, C.POINTER(DenoiseDescC)]),
+    ("lupin_hip_build_adaptive_resources", C.c_int, [_P, _U32, _U32, _PP]),
+    ("lupin_hip_destroy_adaptive_resources", None, [_P]),
+    ("lupin_hip_adaptive_reset", C.c_int, [_P, _P]),
+    ("lupin_hip_pathtrace_scene_adaptive", C.c_int, [_P, _P, _P, _P, _U32, C.POINTER(PathtraceDescC), _P, C.POINTER(AdaptiveParamsC)]),
+    ("lupin_hip_adaptive_stats", C.c_int, [_P, _P, C.POINTER(AdaptiveStatsC)]),
+    ("lupin_hip_adaptive_download", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("lupin_hip_lbvh_depth", _U32, [_U32]),
     ("lupin_hip_lbvh_node_count", C.c_uint64, [_U32]),
     ("lupin_hip_build_bvh_device", C.c_int64, [_P, _P, _U32, _P, _U32, _P, C.c_uint64]),

@@ -12,6 +12,8 @@ data_structures.rs, on top of the C ABI in include/lupin_hip.h:
     lp::build_denoise_resources / denoise / DenoiseDesc / DenoiseQuality
                                          denoising.rs:83-306  -> build_denoise_resources, denoise (the library's own
                                                                  a-trous filter in HIP, not OIDN: DESIGN.md 9)
+    (no reference counterpart)           adaptive sampling   -> AdaptiveParams, build_adaptive_resources,
+                                                                 pathtrace_scene_adaptive
     lp::SceneCPU / validate_scene / build_accel_structures_and_upload
                                          renderer.rs:62-76, data_structures.rs:696-928
 
@@ -845,6 +847,80 @@ def denoise(ctx, resources, desc: DenoiseDesc):
         return None if t is None else t.handle
     c = _abi.DenoiseDescC(h(desc.pathtrace_output), h(desc.albedo), h(desc.normals), h(desc.denoise_output), int(desc.quality))
     check(lib().lupin_hip_denoise(ctx.handle, resources.handle, C.byref(c)))
+
+
+@dataclass
+class AdaptiveParams:  # LupinAdaptiveParams
+    threshold: float = 0.01   # relative standard error of the mean a block must fall below; 0 = no block ever converges
+    min_frames: int = 8       # frames every pixel of a block takes before the block may stop
+    max_frames: int = 0       # 0 = no cap
+
+
+@dataclass
+class AdaptiveStats:  # LupinAdaptiveStats
+    active_pixels: int      # in-image pixels of the blocks the next call renders
+    pixel_frames: int       # sum of the per-pixel frame counts since the latest reset
+    calls: int              # adaptive calls since the latest reset
+    max_frames_taken: int   # largest per-pixel frame count
+
+
+class AdaptiveResources:
+    """Adaptive sampling's state for one width x height (12 B per pixel + 14 B per 8x8 block), created reset."""
+
+    def __init__(self, ctx, width, height):
+        _require_device(ctx, "build_adaptive_resources")
+        self.ctx = ctx
+        self.width, self.height = int(width), int(height)
+        self.blocks_x, self.blocks_y = (self.width + 7) // 8, (self.height + 7) // 8
+        h = C.c_void_p()
+        check(lib().lupin_hip_build_adaptive_resources(ctx.handle, self.width, self.height, C.byref(h)))
+        self.handle = h
+
+    def reset(self):
+        """Counts and moments to 0, every block active: call it where accum_counter goes back to 0."""
+        check(lib().lupin_hip_adaptive_reset(self.ctx.handle, self.handle))
+
+    def stats(self):
+        s = _abi.AdaptiveStatsC()
+        check(lib().lupin_hip_adaptive_stats(self.ctx.handle, self.handle, C.byref(s)))
+        return AdaptiveStats(int(s.active_pixels), int(s.pixel_frames), int(s.calls), int(s.max_frames_taken))
+
+    def download(self):
+        """(frames (H, W) uint32, moments (H, W, 2) float32 [mean, M2], block_error (by, bx) float32, block_active (by, bx) bool)."""
+        frames = np.zeros((self.height, self.width), np.uint32)
+        moments = np.zeros((self.height, self.width, 2), np.float32)
+        err = np.zeros((self.blocks_y, self.blocks_x), np.float32)
+        act = np.zeros((self.blocks_y, self.blocks_x), np.uint8)
+        check(lib().lupin_hip_adaptive_download(self.ctx.handle, self.handle, ptr(frames), ptr(moments), ptr(err), ptr(act)))
+        return frames, moments, err, act.astype(bool)
+
+    def __del__(self):
+        try:
+            if self.handle:
+                lib().lupin_hip_destroy_adaptive_resources(self.handle)
+            self.handle = None
+        except Exception:
+            pass
+
+
+def build_adaptive_resources(ctx, width, height):
+    return AdaptiveResources(ctx, width, height)
+
+
+def pathtrace_scene_adaptive(ctx, resources, scene, render_target, pathtrace_type, desc, adaptive_resources,
+                             params: Optional[AdaptiveParams] = None):
+    """One frame of the pixels whose 8x8 block is active.  desc.accum_params is required: its prev_frame
+    supplies the inactive pixels, bit for bit, and an active pixel p renders as pathtrace_scene would with accum_counter =
+    accum_params.accum_counter + (frames p has taken since the reset)."""
+    assert render_target.format() == "Rgba16Float"
+    if scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "scene was built without a device context; there is no CPU fallback")
+    params = params or AdaptiveParams()
+    keep = []
+    c = _desc_to_c(desc, keep)
+    p = _abi.AdaptiveParamsC(float(params.threshold), int(params.min_frames), int(params.max_frames))
+    check(lib().lupin_hip_pathtrace_scene_adaptive(ctx.handle, resources.handle, scene.handle, render_target.handle,
+                                                   int(pathtrace_type), C.byref(c), adaptive_resources.handle, C.byref(p)))
 
 
 def pathtrace_scene_tiles(ctx, resources, scene, render_target, pathtrace_type, desc, tile_size, rank, world):

@@ -1,7 +1,7 @@
 // lupin_hip.hip -- host side of liblupin_hip.so: the C ABI of include/lupin_hip.h (contexts and their lanes, scene upload,
 // textures, the pathtrace_scene family, measurement hooks, probes).  The stage kernels live in lupin_stages.hpp, the
 // traversal / material / light device functions in lupin_device.hpp, the CPU builders in builders.cpp, the device BLAS
-// builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp.
+// builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp, adaptive sampling's in lupin_adaptive.hpp.
 //
 // THERE IS NO CPU FALLBACK: without a HIP device every entry point that needs one fails with LUPIN_ERR_NO_DEVICE.
 
@@ -20,6 +20,7 @@
 
 #include "lupin_stages.hpp"
 #include "lupin_denoise.hpp"
+#include "lupin_adaptive.hpp"
 #include "lupin_internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -103,7 +104,8 @@ struct LupinContext
     // Frames per wavefront: pathtrace_scene calls that differ only in camera / accum_counter and chain their textures
     // (each call's prev_frame is the previous call's render_target) are recorded here and run as ONE wavefront when the batch is
     // full or anything needs their result (flush_pending: sync, texture reads and writes, another kind of call, teardown).
-    struct PendingFrame { FrameParams fp; LupinTexture *target; const LupinTexture *prev; };
+    // An adaptive call (lupin_hip_pathtrace_scene_adaptive) is a record with `adaptive` set; it is never batched (K == 1).
+    struct PendingFrame { FrameParams fp; LupinTexture *target; const LupinTexture *prev; LupinAdaptiveResources *adaptive = nullptr; };
     std::vector<PendingFrame> pending;
     const LupinScene *pending_scene = nullptr;
     uint32_t pending_type = 0;
@@ -119,6 +121,15 @@ struct LupinPathtraceResources
 {
     LupinContext *ctx;
     LupinBakedPathtraceParams params;
+};
+
+// adaptive sampling's per-pixel and per-block state (lupin_adaptive.hpp)
+struct LupinAdaptiveResources
+{
+    LupinContext *ctx;
+    int device;
+    AdaptiveDev dev;     // device pointers, size and the latest call's parameters
+    uint32_t calls;      // adaptive calls since the latest reset
 };
 
 struct LupinDoubleBufferedTexture
@@ -762,13 +773,17 @@ static void launch_iteration(LupinContext *ctx, Lane *ln, const LupinScene *scen
 
 // the lane-private part of one call: clear the queue counters, first rays, every iteration of the wavefront
 static hipError_t enqueue_wavefront(LupinContext *ctx, Lane *ln, const LupinScene *scene, uint32_t pathtrace_type, bool lds_geo, uint32_t n,
-                                    const Shape &sh, uint32_t iterations)
+                                    const Shape &sh, uint32_t iterations, const AdaptiveDev *ad = nullptr)
 {
     const uint32_t blocks = sh.blocks;
     hipStream_t st = ln->stream;
     hipError_t e = hipMemsetAsync(ln->pb.counts, 0, LP_COUNTER_ROWS * (size_t)ln->counts_capacity * LP_SHARDS * sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_begin, dim3(blocks), dim3(LP_BLOCK), 0, st, (const FrameParams *)ln->d_fp, ln->pb, n);
+    if (ad)
+        hipLaunchKernelGGL(k_begin_adaptive, dim3(blocks), dim3(LP_BLOCK), 0, st, (const FrameParams *)ln->d_fp, ln->pb, n,
+                           (const uint8_t *)ad->block_active, (const uint32_t *)ad->frames, ad->blocks_x);
+    else
+        hipLaunchKernelGGL(k_begin, dim3(blocks), dim3(LP_BLOCK), 0, st, (const FrameParams *)ln->d_fp, ln->pb, n);
     for (uint32_t it = 0; it < iterations; it++)
     {
         switch (pathtrace_type)
@@ -1588,7 +1603,7 @@ int lupin_hip_dbuf_resize(LupinDoubleBufferedTexture *t, uint32_t width, uint32_
 static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res, const LupinScene *scene,
                           LupinTexture *render_target, uint32_t pathtrace_type, const LupinPathtraceDesc *desc,
                           bool tile_set, uint32_t set_tile_size, uint32_t rank, uint32_t world, int falsecolor_type = -1,
-                          const LupinDebugVizDesc *debug = nullptr)
+                          const LupinDebugVizDesc *debug = nullptr, LupinAdaptiveResources *adaptive = nullptr)
 {
     CTX_ALIVE_TRY(ctx);
     if (!ctx || !res || !scene || !render_target || !desc) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
@@ -1701,6 +1716,16 @@ static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res,
     // ---- record the call; run the batch when it is full or cannot grow (DESIGN 5 "Frames per wavefront") ----
     fp.frame_slots = n;
     fp.num_frames = 1;
+    if (adaptive)
+    {
+        // one frame per wavefront: the next call's first rays read the mask this call's update writes
+        int rc = flush_pending(ctx);
+        if (rc != LUPIN_OK) return rc;
+        ctx->pending.push_back({fp, render_target, prev, adaptive});
+        ctx->pending_scene = scene;
+        ctx->pending_type = pathtrace_type;
+        return flush_pending(ctx);
+    }
     const uint32_t max_frames = frames_per_wavefront(ctx, n64);
     const bool batchable = max_frames > 1 && !ctx->counting && !ctx->verify_wide && !ctx->debug_sync && ctx->accum_mode != LUPIN_ACCUM_F32;
     if (!ctx->pending.empty())
@@ -1749,6 +1774,7 @@ static int flush_pending(LupinContext *ctx)
     LupinTexture *render_target = ctx->pending.back().target;    // (f32 accumulation is never batched: K == 1 there)
     const LupinTexture *prev = ctx->pending.front().prev;
     const uint32_t W = fp.width, H = fp.height;
+    LupinAdaptiveResources *adaptive = ctx->pending.front().adaptive;   // (adaptive calls are never batched: K == 1 there)
 
     // Lane choice: consecutive wavefronts alternate over `lanes` streams so that they overlap; per-kernel timing needs them serial.
     // * A wavefront of ONE frame of a scene traced by the persistent kernel does not fill the chip in its middle iterations
@@ -1814,7 +1840,21 @@ static int flush_pending(LupinContext *ctx)
         fk.num_frames = K;
         hipLaunchKernelGGL(k_set_params, dim3(1), dim3(1), 0, st, fk, ln->d_fp + k);
     }
-    if (ctx->use_graph && !ctx->timing && !ctx->counting && !ctx->verify_wide)
+    if (adaptive)
+    {
+        // k_begin_adaptive reads the counts and the mask that the previous adaptive call's update wrote (on its lane, before
+        // its `done`; the resolves chain every call after the one before) and that a reset wrote on the primary stream.
+        // Consecutive one-frame wavefronts change lanes, so wait for both before the first rays.  No graph: launched directly.
+        if (w != 0)
+        {
+            HIP_TRY(hipEventRecord(ctx->marker, ctx->stream));
+            HIP_TRY(hipStreamWaitEvent(st, ctx->marker, 0));
+        }
+        if (ctx->last_lane >= 0 && ctx->last_lane != w)
+            HIP_TRY(hipStreamWaitEvent(st, ctx->lanes[ctx->last_lane].done, 0));
+        HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, lds_geo, n, sh, iterations, &adaptive->dev));
+    }
+    else if (ctx->use_graph && !ctx->timing && !ctx->counting && !ctx->verify_wide)
     {
         // Everything between k_set_params and the resolve depends on the call only through *d_fp, so it is captured once per
         // (scene, dispatch size, integrator, buffers) and replayed: one graph launch instead of 2-4 launches per iteration.
@@ -1887,8 +1927,20 @@ static int flush_pending(LupinContext *ctx)
         if (last_write) rb.store_mask |= 1u << k;
         if (k + 1 < K) ctx->pending[k].target->accum32_valid = false;
     }
-    hipLaunchKernelGGL(k_resolve, dim3((frame_slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, st, fp, ln->pb, frame_slots, rb,
-                       prev ? prev->data : (const __half *)nullptr, prev32, out32);
+    if (adaptive)
+    {
+        const AdaptiveDev &ad = adaptive->dev;
+        const uint32_t nblocks = ad.blocks_x * ad.blocks_y;
+        hipLaunchKernelGGL(k_resolve_adaptive, dim3((frame_slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, st, fp, ln->pb, frame_slots, ad,
+                           render_target->data, prev->data, prev32, out32);
+        HIP_TRY(hipMemsetAsync(ad.stats, 0, 3 * sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_adaptive_update, dim3((nblocks + LP_BLOCK / 64 - 1) / (LP_BLOCK / 64)), dim3(LP_BLOCK), 0, st, ad);
+        hipLaunchKernelGGL(k_adaptive_mask, dim3((nblocks + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, st, ad);
+        adaptive->calls++;
+    }
+    else
+        hipLaunchKernelGGL(k_resolve, dim3((frame_slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, st, fp, ln->pb, frame_slots, rb,
+                           prev ? prev->data : (const __half *)nullptr, prev32, out32);
     HIP_TRY(hipEventRecord(ln->done, st));
     ln->used = true;
     ctx->last_lane = w;
@@ -2364,6 +2416,142 @@ int lupin_hip_denoise(LupinContext *ctx, LupinDenoiseResources *res, const Lupin
     }
     HIP_TRY(hipGetLastError());
     desc->denoise_output->accum32_valid = false;
+    return LUPIN_OK;
+}
+
+}  // extern "C"
+
+// ---- adaptive sampling (no reference counterpart; kernels and rule: lupin_adaptive.hpp) ----
+
+extern "C" {
+
+static void free_adaptive(LupinAdaptiveResources *r)
+{
+    hipFree(r->dev.frames); hipFree(r->dev.moments); hipFree(r->dev.block_error); hipFree(r->dev.block_flags);
+    hipFree(r->dev.block_active); hipFree(r->dev.block_count); hipFree(r->dev.stats);
+    delete r;
+}
+
+static void launch_adaptive_reset(LupinContext *ctx, LupinAdaptiveResources *r)
+{
+    const size_t pixels = (size_t)r->dev.width * r->dev.height;   // >= the block count
+    hipLaunchKernelGGL(k_adaptive_reset, dim3((uint32_t)((pixels + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, ctx->stream, r->dev);
+    r->calls = 0;
+}
+
+int lupin_hip_build_adaptive_resources(LupinContext *ctx, uint32_t width, uint32_t height, LupinAdaptiveResources **out)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!out || width == 0 || height == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "bad adaptive resources size");
+    if ((uint64_t)width * height > 0xFFFFFFFFull / 2) return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive size too large");
+    HIP_TRY(hipSetDevice(ctx->device));
+    LupinAdaptiveResources *r = new LupinAdaptiveResources();
+    memset(&r->dev, 0, sizeof(r->dev));
+    r->ctx = ctx; r->device = ctx->device; r->calls = 0;
+    AdaptiveDev &d = r->dev;
+    d.width = width; d.height = height;
+    d.blocks_x = (width + LP_AD_BLOCK - 1) / LP_AD_BLOCK; d.blocks_y = (height + LP_AD_BLOCK - 1) / LP_AD_BLOCK;
+    const size_t px = (size_t)width * height, nb = (size_t)d.blocks_x * d.blocks_y;
+    hipError_t e = hipMalloc((void **)&d.frames, px * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&d.moments, px * sizeof(float2));
+    if (e == hipSuccess) e = hipMalloc((void **)&d.block_error, nb * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&d.block_flags, nb);
+    if (e == hipSuccess) e = hipMalloc((void **)&d.block_active, nb);
+    if (e == hipSuccess) e = hipMalloc((void **)&d.block_count, nb * sizeof(uint2));
+    if (e == hipSuccess) e = hipMalloc((void **)&d.stats, 3 * sizeof(unsigned long long));
+    if (e != hipSuccess)
+    {
+        free_adaptive(r);
+        return fail(LUPIN_ERR_OUT_OF_MEMORY, hipGetErrorString(e));
+    }
+    launch_adaptive_reset(ctx, r);   // primary stream: every adaptive call waits for it (flush_pending)
+    e = hipGetLastError();
+    if (e != hipSuccess)
+    {
+        hipStreamSynchronize(ctx->stream);
+        free_adaptive(r);
+        return fail(LUPIN_ERR_HIP, hipGetErrorString(e));
+    }
+    *out = r;
+    return LUPIN_OK;
+}
+
+void lupin_hip_destroy_adaptive_resources(LupinAdaptiveResources *res)
+{
+    if (!res) return;
+    hipSetDevice(res->device);
+    if (ctx_alive(res->ctx)) sync_all(res->ctx);   // a destroyed context has drained its streams already
+    free_adaptive(res);
+}
+
+int lupin_hip_adaptive_reset(LupinContext *ctx, LupinAdaptiveResources *res)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!res) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (res->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive resources of another context");
+    HIP_TRY(hipSetDevice(ctx->device));
+    join_primary(ctx);   // after every frame enqueued so far (the latest adaptive call's update among them)
+    launch_adaptive_reset(ctx, res);
+    HIP_TRY(hipGetLastError());
+    return LUPIN_OK;
+}
+
+int lupin_hip_pathtrace_scene_adaptive(LupinContext *ctx, const LupinPathtraceResources *res, const LupinScene *scene,
+                                       LupinTexture *render_target, uint32_t pathtrace_type, const LupinPathtraceDesc *desc,
+                                       LupinAdaptiveResources *ares, const LupinAdaptiveParams *params)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!res || !scene || !render_target || !desc || !ares || !params) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (!desc->accum_params || !desc->accum_params->prev_frame)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive sampling needs accum_params.prev_frame (inactive pixels copy it)");
+    const LupinTexture *prev = desc->accum_params->prev_frame;
+    if (prev == render_target) return fail(LUPIN_ERR_SAME_TARGET, "render_target must differ from accum_params.prev_frame");
+    if (desc->tile_params) return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive sampling renders whole frames: tile_params must be NULL");
+    if (ares->ctx != ctx || render_target->ctx != ctx || prev->ctx != ctx || res->ctx != ctx || scene->ctx != ctx)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "object of another or a destroyed context");
+    if (render_target->width != ares->dev.width || render_target->height != ares->dev.height || prev->width != ares->dev.width ||
+        prev->height != ares->dev.height)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "render_target, prev_frame and adaptive resources differ in size");
+    if (!(params->threshold >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "threshold must be >= 0 (and not NaN)");
+    if (pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
+    ares->dev.threshold = params->threshold;
+    ares->dev.min_frames = params->min_frames;
+    ares->dev.max_frames = params->max_frames;
+    return pathtrace_impl(ctx, res, scene, render_target, pathtrace_type, desc, false, 0, 0, 1, -1, nullptr, ares);
+}
+
+int lupin_hip_adaptive_stats(LupinContext *ctx, const LupinAdaptiveResources *ares, LupinAdaptiveStats *out)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!ares || !out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (ares->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive resources of another context");
+    HIP_TRY(hipSetDevice(ctx->device));
+    join_primary(ctx);
+    unsigned long long s[3];
+    HIP_TRY(hipMemcpyAsync(s, ares->dev.stats, sizeof(s), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    out->active_pixels = s[0];
+    out->pixel_frames = s[1];
+    out->calls = ares->calls;
+    out->max_frames_taken = (uint32_t)s[2];
+    return LUPIN_OK;
+}
+
+int lupin_hip_adaptive_download(LupinContext *ctx, const LupinAdaptiveResources *ares, uint32_t *frames, float *moments,
+                                float *block_error, uint8_t *block_active)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!ares) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (ares->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive resources of another context");
+    HIP_TRY(hipSetDevice(ctx->device));
+    join_primary(ctx);
+    const AdaptiveDev &d = ares->dev;
+    const size_t px = (size_t)d.width * d.height, nb = (size_t)d.blocks_x * d.blocks_y;
+    if (frames) HIP_TRY(hipMemcpyAsync(frames, d.frames, px * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (moments) HIP_TRY(hipMemcpyAsync(moments, d.moments, px * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
+    if (block_error) HIP_TRY(hipMemcpyAsync(block_error, d.block_error, nb * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (block_active) HIP_TRY(hipMemcpyAsync(block_active, d.block_active, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return LUPIN_OK;
 }
 

@@ -215,7 +215,11 @@ __device__ __forceinline__ void queue_append(bool alive, uint32_t slot, uint32_t
 // struct may go out of scope)
 __global__ void k_set_params(FrameParams fp, FrameParams *dst) { *dst = fp; }
 
-__global__ void __launch_bounds__(LP_BLOCK) k_begin(const FrameParams *__restrict__ fpp, PathBuffers pb, uint32_t n)
+// k_begin's body.  ADAPTIVE (k_begin_adaptive, lupin_adaptive.hpp): only pixels of active 8x8 blocks start a path, and a
+// pixel's RNG seed takes accum_counter + the frames that pixel has taken (frames[pixel]).
+template <bool ADAPTIVE>
+__device__ __forceinline__ void begin_paths(const FrameParams *__restrict__ fpp, PathBuffers pb, uint32_t n,
+                                            const uint8_t *__restrict__ block_active, const uint32_t *__restrict__ frames, uint32_t blocks_x)
 {
     const FrameParams fp = *fpp;   // per-frame parameters live in device memory so that a captured graph can be replayed
     uint32_t slot = blockIdx.x * LP_BLOCK + threadIdx.x;
@@ -227,12 +231,15 @@ __global__ void __launch_bounds__(LP_BLOCK) k_begin(const FrameParams *__restric
         frame = slot_frame(fp, slot, pslot);
         slot_to_pixel(fp, pslot, gx, gy);
         live = gx < fp.width && gy < fp.height;   // edge tiles: texels outside the image are never stored (:287)
+        if (ADAPTIVE && live) live = block_active[(gy >> 3) * blocks_x + (gx >> 3)] != 0;
     }
     const uint32_t shard = blockIdx.x % LP_SHARDS;
     queue_append(live, slot, pb.queue[0] + (size_t)shard * pb.shard_cap, &pb.counts[shard]);
     if (!live) return;
     const FrameParams &ff = fpp[frame];   // this frame's camera and accumulation counter
-    uint32_t rng = rng_seed_for(gy * fp.width + gx, ff.pc.accum_counter);
+    uint32_t counter = ff.pc.accum_counter;
+    if (ADAPTIVE) counter += frames[(size_t)gy * fp.width + gx];
+    uint32_t rng = rng_seed_for(gy * fp.width + gx, counter);
     f3 o, d;
     camera_ray(ff, gx, gy, rng, o, d);
     pb.ori_rng[slot] = make_float4(o.x, o.y, o.z, __uint_as_float(rng));
@@ -242,6 +249,11 @@ __global__ void __launch_bounds__(LP_BLOCK) k_begin(const FrameParams *__restric
     pb.color[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     pb.next_hit[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(HIT_MISS));   // `var next_intersection = HitInfo()` (:746)
     pb.next_tri[slot] = 0u;
+}
+
+__global__ void __launch_bounds__(LP_BLOCK) k_begin(const FrameParams *__restrict__ fpp, PathBuffers pb, uint32_t n)
+{
+    begin_paths<false>(fpp, pb, n, nullptr, nullptr, 0u);
 }
 
 // ray_skip_alpha_stochastically (bvh_custom.wgsl:154-180).  The material is consulted only for
