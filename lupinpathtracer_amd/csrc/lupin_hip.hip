@@ -217,9 +217,9 @@ static int ensure_path_buffers(LupinContext *ctx0, Lane *ctx, uint64_t slots, ui
     {
         PathBuffers &pb = ctx->pb;
         void **ptrs[] = {(void **)&ctx->hot, (void **)&ctx->shadow, (void **)&ctx->skey, (void **)&pb.vol0, (void **)&pb.vol1, (void **)&pb.queue[0], (void **)&pb.queue[1],
-                         (void **)&pb.retrace};
-        size_t elem[] = {LP_PATH_RECORD_BYTES, LP_PATH_RECORD_BYTES, 4, 16, 16, 4, 4, 8};   // re-trace tokens: up to two jobs per slot (shadow rays)
-        constexpr int NPTRS = 8;
+                         (void **)&pb.retrace, (void **)&pb.shade_order};
+        size_t elem[] = {LP_PATH_RECORD_BYTES, LP_PATH_RECORD_BYTES, 4, 16, 16, 4, 4, 8, 4};   // re-trace tokens: up to two jobs per slot (shadow rays)
+        constexpr int NPTRS = 9;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         // the lane holds nothing until every allocation has succeeded: a failure part-way (hipMalloc returns through
         // HIP_TRY) must not leave a capacity behind that a later, smaller dispatch would trust
@@ -693,22 +693,30 @@ static void launch_iteration_t(LupinContext *ctx, Lane *ln, const LupinScene *sc
     }
     bool light_stage = false;
     if constexpr (TYPE == LUPIN_PATHTRACE_STANDARD || TYPE == LUPIN_PATHTRACE_MIS) light_stage = use_light_stage(ctx, scene, TYPE);
-    // several material families: sort the queue in windows first, k_shade then finds its 256 paths (nearly) uniform
+    // several material families: sort the queue in windows first, k_shade then finds its 256 paths (nearly) uniform.  The sort
+    // leaves the queue as it is and hands k_shade a permutation (pb.shade_order); shade_dev.sort_shade tells k_shade it ran.
+    // MIS / Direct sort in place: their k_shade keeps its registers, and k_shadow appends in the sorted order as before.
     SceneDev shade_dev = scene->dev;
+    shade_dev.sort_shade = 0;
+    const uint32_t windows = ((blocks / LP_SHARDS) * LP_BLOCK + LP_SORT_WINDOW - 1) / LP_SORT_WINDOW;
+    const uint32_t sort_in_place = TYPE == LUPIN_PATHTRACE_MIS || TYPE == LUPIN_PATHTRACE_DIRECT;
     if (scene->dev.sort_shade && scene->dev.num_instances)
     {
-        const uint32_t windows = ((blocks / LP_SHARDS) * LP_BLOCK + LP_SORT_WINDOW - 1) / LP_SORT_WINDOW;
         // the Standard integrator's persistent tracer leaves the key with the hit; otherwise the pass derives it
         if (TYPE == LUPIN_PATHTRACE_STANDARD && persistent)
-            hipLaunchKernelGGL((k_sort_queue<true, true>), dim3(windows * LP_SHARDS), dim3(LP_BLOCK), 0, st, scene->dev, ln->pb, iter);
+            hipLaunchKernelGGL((k_sort_queue<true, true>), dim3(windows * LP_SHARDS), dim3(LP_BLOCK), 0, st, scene->dev, ln->pb, iter, sort_in_place);
         else
-            hipLaunchKernelGGL((k_sort_queue<TYPE == LUPIN_PATHTRACE_STANDARD, false>), dim3(windows * LP_SHARDS), dim3(LP_BLOCK), 0, st, scene->dev, ln->pb, iter);
-        shade_dev.sort_shade = 0;
+            hipLaunchKernelGGL((k_sort_queue<TYPE == LUPIN_PATHTRACE_STANDARD, false>), dim3(windows * LP_SHARDS), dim3(LP_BLOCK), 0, st, scene->dev, ln->pb, iter, sort_in_place);
+        shade_dev.sort_shade = 1;
     }
     if (scene->simple_matte && ctx->specialize_simple)
         hipLaunchKernelGGL((k_shade<TYPE, LDSGEO, true>), dim3(blocks), dim3(LP_BLOCK), lds, st, shade_dev, fp, ln->pb, iter, ln->stat_counters, stack_words);
     else if (!light_stage)
         hipLaunchKernelGGL((k_shade<TYPE, LDSGEO, false>), dim3(blocks), dim3(LP_BLOCK), lds, st, shade_dev, fp, ln->pb, iter, ln->stat_counters, stack_words);
+    // k_shade read through the permutation and left each verdict at its entry: the survivors go to the next queue in the
+    // queue's order (light stage: k_light_pdf appends, walking the queue in its order; MIS / Direct: k_shadow appends)
+    if (TYPE != LUPIN_PATHTRACE_MIS && TYPE != LUPIN_PATHTRACE_DIRECT && shade_dev.sort_shade && !light_stage)
+        hipLaunchKernelGGL(k_compact_queue, dim3(windows * LP_SHARDS), dim3(LP_BLOCK), 0, st, ln->pb, iter);
     if constexpr (TYPE == LUPIN_PATHTRACE_STANDARD)
     {
         if (light_stage)
@@ -956,7 +964,7 @@ void lupin_hip_destroy_context(LupinContext *ctx)
     {
         PathBuffers &pb = ctx->lanes[k].pb;
         void *ptrs[] = {ctx->lanes[k].hot, ctx->lanes[k].shadow, ctx->lanes[k].skey, pb.vol0, pb.vol1, pb.queue[0], pb.queue[1], pb.counts, ctx->lanes[k].stat_counters,
-                        ctx->lanes[k].work_counters, ctx->lanes[k].wide_counters, pb.retrace};
+                        ctx->lanes[k].work_counters, ctx->lanes[k].wide_counters, pb.retrace, pb.shade_order};
         for (void *p : ptrs) if (p) hipFree(p);
         if (ctx->lanes[k].done) hipEventDestroy(ctx->lanes[k].done);
         if (ctx->lanes[k].graph_exec) hipGraphExecDestroy(ctx->lanes[k].graph_exec);

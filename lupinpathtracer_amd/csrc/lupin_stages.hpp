@@ -82,6 +82,9 @@ struct PathBuffers
     uint32_t *queue[2];   // [parity][shard * shard_cap + i]
     uint32_t *counts;     // counts[k * LP_SHARDS + s] = live paths of shard s entering iteration k
     PathField<uint32_t> skey;     // Standard integrator on the persistent tracer: k_sort_queue's key of the path's hit, written by the tracer (always a plane)
+    // k_sort_queue's output, [shard * shard_cap + i]: the shard position of the queue entry that k_shade's thread i shades.  The
+    // queue itself keeps the order the tracer received it in (see k_sort_queue).
+    uint32_t *shade_order;
     uint32_t *cursors;    // cursors[(2 k + mode) * LP_SHARDS + s]: how much of shard s the persistent tracer's waves have taken in iteration k
     // Wide tracer: queries it could not certify (lupin_device.hpp "Wide traversal") are appended here, per shard, as job
     // tokens (MODE 0: slot; MODE 1: 2 * slot + ray) and re-traced by the binary tracer in the reference's order.
@@ -1341,26 +1344,32 @@ __device__ __forceinline__ bool light_pdf_path(const Geo &geo, const SceneDev &s
     return path_epilogue<TYPE>(fp, fpp, pb, slot, p, sample, cont, false, r4);
 }
 
-// Scenes with several material families: before k_shade, each window of LP_SORT_WINDOW queue entries is counting-sorted in place
-// by what the path will execute (material type of the hit | miss | inside a medium), so that a k_shade wave runs one BSDF
-// family instead of several (a 256-path window inside k_shade left two or three per wave).  Which queue position holds which
-// path does not matter: all path state lives in the path's slot.
+// Scenes with several material families: before k_shade, each window of LP_SORT_WINDOW queue entries is counting-sorted by what
+// the path will execute (material type of the hit | miss | inside a medium), so that a k_shade wave runs one BSDF family
+// instead of several (a 256-path window inside k_shade left two or three per wave).  The sort does not move the queue's
+// entries: it writes the window's material order to pb.shade_order as shard positions, k_shade's thread i shades entry
+// shade_order[i] and leaves its verdict at that entry's own position, and k_compact_queue appends the survivors in the
+// queue's order.  Sorted in place, the next iteration's tracer received its rays in material order instead of pixel order
+// and ran 5 % slower on the 4K frame.  Which queue position holds which path does not change any result: all
+// path state lives in the path's slot.
 #ifndef LP_SORT_WINDOW
 #define LP_SORT_WINDOW 4096
 #endif
 // The key is shade_sort_key (above); FROM_TRACER: the persistent tracer wrote it when it finished the path's query.
+// IN_PLACE (MIS / Direct, whose k_shadow appends): the window's entries are rewritten in material order instead.
 template <bool PEEK_COIN, bool FROM_TRACER>
-__global__ void __launch_bounds__(LP_BLOCK) k_sort_queue(SceneDev sc, PathBuffers pb, uint32_t iter)
+__global__ void __launch_bounds__(LP_BLOCK) k_sort_queue(SceneDev sc, PathBuffers pb, uint32_t iter, uint32_t in_place)
 {
     constexpr uint32_t PER_THREAD = LP_SORT_WINDOW / LP_BLOCK;
     constexpr uint32_t NUM_KEYS = LP_SORT_KEYS;
-    __shared__ uint32_t sorted[LP_SORT_WINDOW];
+    __shared__ uint32_t sorted[LP_SORT_WINDOW];   // shard positions (in place: slots), in material order
     __shared__ uint32_t bins[NUM_KEYS];
     const uint32_t shard = blockIdx.x % LP_SHARDS;
     const uint32_t count = pb.counts[iter * LP_SHARDS + shard];
     const uint32_t base_i = (blockIdx.x / LP_SHARDS) * LP_SORT_WINDOW;
     if (base_i >= count) return;   // block-uniform
     uint32_t *entries = pb.queue[iter & 1] + (size_t)shard * pb.shard_cap + base_i;
+    uint32_t *order = in_place ? entries : pb.shade_order + (size_t)shard * pb.shard_cap + base_i;
     const uint32_t valid = min(LP_SORT_WINDOW, count - base_i);
     if (threadIdx.x < NUM_KEYS) bins[threadIdx.x] = 0u;
     __syncthreads();
@@ -1407,14 +1416,67 @@ __global__ void __launch_bounds__(LP_BLOCK) k_sort_queue(SceneDev sc, PathBuffer
     __syncthreads();
     #pragma unroll
     for (uint32_t r = 0; r < PER_THREAD; r++)
-        if (r * LP_BLOCK + threadIdx.x < valid) sorted[bins[my_key[r]] + my_rank[r]] = my_slot[r];
+        if (r * LP_BLOCK + threadIdx.x < valid) sorted[bins[my_key[r]] + my_rank[r]] = in_place ? my_slot[r] : base_i + r * LP_BLOCK + threadIdx.x;
     __syncthreads();
     #pragma unroll
     for (uint32_t r = 0; r < PER_THREAD; r++)
     {
         const uint32_t j = r * LP_BLOCK + threadIdx.x;
-        if (j < valid) entries[j] = sorted[j];
+        if (j < valid) order[j] = sorted[j];
     }
+}
+
+// After a k_shade that read through pb.shade_order (Standard inline / Naive): each queue entry of the iteration holds its path's
+// slot if the path goes on, else QUEUE_ENTRY_NONE.  One block per window of LP_SORT_WINDOW entries appends the window's
+// survivors to the next iteration's queue of the same shard in the window's order, with one counter atomic: the next tracer
+// gets its rays in the order k_begin created them.  Windows land in any order inside a shard, as waves did before.
+__global__ void __launch_bounds__(LP_BLOCK) k_compact_queue(PathBuffers pb, uint32_t iter)
+{
+    constexpr uint32_t PER_THREAD = LP_SORT_WINDOW / LP_BLOCK;
+    static_assert(PER_THREAD % 4 == 0, "a thread reads its entries as uint4");
+    __shared__ uint32_t wave_total[LP_BLOCK / 64];
+    __shared__ uint32_t window_base;
+    const uint32_t shard = blockIdx.x % LP_SHARDS;
+    const uint32_t count = pb.counts[iter * LP_SHARDS + shard];
+    const uint32_t base_i = (blockIdx.x / LP_SHARDS) * LP_SORT_WINDOW;
+    if (base_i >= count) return;   // block-uniform
+    const uint32_t valid = min(LP_SORT_WINDOW, count - base_i);
+    const uint32_t *entries = pb.queue[iter & 1] + (size_t)shard * pb.shard_cap + base_i;
+    // thread t owns the window's entries [PER_THREAD t, PER_THREAD (t + 1)); shard segments are 1 KB aligned, windows 16 KB
+    const uint32_t first = threadIdx.x * PER_THREAD;
+    uint32_t e[PER_THREAD];
+    if (first + PER_THREAD <= valid)
+    {
+        #pragma unroll
+        for (uint32_t r = 0; r < PER_THREAD / 4; r++)
+        {
+            const uint4 v = reinterpret_cast<const uint4 *>(entries + first)[r];
+            e[4 * r] = v.x; e[4 * r + 1] = v.y; e[4 * r + 2] = v.z; e[4 * r + 3] = v.w;
+        }
+    }
+    else
+    {
+        #pragma unroll
+        for (uint32_t r = 0; r < PER_THREAD; r++) e[r] = first + r < valid ? entries[first + r] : QUEUE_ENTRY_NONE;
+    }
+    uint32_t mine = 0;
+    #pragma unroll
+    for (uint32_t r = 0; r < PER_THREAD; r++) mine += e[r] != QUEUE_ENTRY_NONE ? 1u : 0u;
+    // block-wide exclusive prefix of `mine`, in thread order = window order
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t incl = mine;
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, off); if ((int)lane >= off) incl += v; }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    uint32_t before = incl - mine, total = 0;
+    for (uint32_t w = 0; w < LP_BLOCK / 64; w++) { const uint32_t c = wave_total[w]; if (w < wave) before += c; total += c; }
+    if (total == 0) return;   // block-uniform
+    if (threadIdx.x == 0) window_base = atomicAdd(&pb.counts[(iter + 1) * LP_SHARDS + shard], total);
+    __syncthreads();
+    uint32_t *out = pb.queue[(iter + 1) & 1] + (size_t)shard * pb.shard_cap + window_base + before;
+    #pragma unroll
+    for (uint32_t r = 0; r < PER_THREAD; r++)
+        if (e[r] != QUEUE_ENTRY_NONE) *out++ = e[r];
 }
 
 // SIMPLE: scenes of untextured matte surfaces without environments (LupinScene::simple_matte, decided at upload) get a
@@ -1431,10 +1493,15 @@ __global__ void __attribute__((amdgpu_waves_per_eu(TYPE == 1 ? (DEFER ? LP_MIS_D
     const uint32_t shard = blockIdx.x % LP_SHARDS;
     const uint32_t count = pb.counts[iter * LP_SHARDS + shard];
     const uint32_t i = (blockIdx.x / LP_SHARDS) * LP_BLOCK + threadIdx.x;
+    // sc.sort_shade: k_sort_queue has run and, except for MIS / Direct (sorted in place), thread i shades the entry at shard
+    // position shade_order[i] (see k_sort_queue)
+    constexpr bool PERMUTED = TYPE != LUPIN_PATHTRACE_MIS && TYPE != LUPIN_PATHTRACE_DIRECT;
+    uint32_t *const entries = pb.queue[iter & 1] + (size_t)shard * pb.shard_cap;
     int state = SLOT_DONE;
     bool mine = i < count;
-    uint32_t slot = 0;
-    if (mine) slot = pb.queue[iter & 1][(size_t)shard * pb.shard_cap + i];
+    uint32_t slot = 0, pos = i;
+    if (PERMUTED && mine && sc.sort_shade) pos = pb.shade_order[(size_t)shard * pb.shard_cap + i];
+    if (mine) slot = entries[pos];
     if (mine)
     {
         const float4 orr = pb.ori_rng[slot];
@@ -1442,10 +1509,19 @@ __global__ void __attribute__((amdgpu_waves_per_eu(TYPE == 1 ? (DEFER ? LP_MIS_D
     }
     if (i == 0 && iter == 0) shard_stats[shard * 2 + 1] += (unsigned long long)count * fp.spp;
     if (TYPE == LUPIN_PATHTRACE_MIS || TYPE == LUPIN_PATHTRACE_DIRECT) return;   // k_shadow appends
+    // The verdict goes to the entry's own position.  The general kernels re-read it (kept across the shading it costs them two
+    // VGPRs); the SIMPLE ones keep it (re-read, it costs them scratch).
+    if (!SIMPLE && mine && sc.sort_shade) pos = pb.shade_order[(size_t)shard * pb.shard_cap + i];
     if (DEFER)
     {
-        // with the block sort, thread i shaded some other entry of its block: the tagged entries are a permutation of the block's
-        if (i < count) pb.queue[iter & 1][(size_t)shard * pb.shard_cap + i] = mine ? (slot | ((uint32_t)state << QUEUE_STATE_SHIFT)) : QUEUE_ENTRY_NONE;
+        // k_light_pdf appends: the entry is tagged with the path's state
+        if (mine) entries[pos] = slot | ((uint32_t)state << QUEUE_STATE_SHIFT);
+        return;
+    }
+    if (sc.sort_shade)
+    {
+        // k_compact_queue appends the window's survivors in the queue's order
+        if (mine) entries[pos] = state == SLOT_ALIVE ? slot : QUEUE_ENTRY_NONE;
         return;
     }
     queue_append(state == SLOT_ALIVE, slot, pb.queue[(iter + 1) & 1] + (size_t)shard * pb.shard_cap, &pb.counts[(iter + 1) * LP_SHARDS + shard]);
