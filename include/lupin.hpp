@@ -222,6 +222,12 @@ class Scene   // lp::Scene, software-BVH configuration (renderer.rs:17-60)
     Scene(const Scene &) = delete;
     ~Scene() { if (scene_) lupin_hip_scene_destroy(scene_); }
     LupinScene *raw() const { return scene_; }
+    // Moves the instances in place (lupin_hip_scene_update_instances): one transpose_inverse_transform per instance, in
+    // instance order; the TLAS is rebuilt on the device (or by lupin_build_tlas), nothing else is uploaded again.
+    void update_instances(const std::vector<LupinMat4x3> &transpose_inverse_transforms, bool device_tlas = true)
+    {
+        check(lupin_hip_scene_update_instances(scene_, transpose_inverse_transforms.data(), (uint32_t)transpose_inverse_transforms.size(), device_tlas ? 1 : 0));
+    }
     LupinScene *scene_ = nullptr;
 };
 

@@ -377,6 +377,24 @@ void lupin_hip_destroy_pathtrace_resources(LupinPathtraceResources *res);
 
 /* upload half of lp::build_accel_structures_and_upload (data_structures.rs:696-872) */
 int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinScene **out_scene);
+/* Moves the instances of a scene in place (no counterpart in the reference, whose Scene is immutable once
+ * build_accel_structures_and_upload, data_structures.rs:696-872, has returned): instance i's transform becomes
+ * transpose_inverse_transforms[i] (the Instance field of renderer.rs:115-124), the TLAS is rebuilt over the model boxes
+ * kept from creation -- tlas_builder 0: lupin_build_tlas, 1: lupin_hip_build_tlas_device, the same tree -- and written over
+ * the old one together with the instance rows, the traversal-stack depth and the lights' cull spheres.  mesh_idx, mat_idx,
+ * the instance count, materials, textures and environments stay, and with them the light list and every alias table.
+ * Ordering: pathtrace calls recorded before the update run first and render the old transforms; the call returns once the
+ * new ones are in place.  Errors leave the scene exactly as it was: LUPIN_ERR_INVALID_ARGUMENT for a count other than the
+ * scene's, a transform that gives a non-finite world box, a builder error or a tree too deep for the LDS traversal stack;
+ * LUPIN_ERR_NO_SW_BVH for a scene created without TLAS; whatever a recorded call fails with.
+ * The four-wide hierarchy (lupin_hip_set_traversal) is not rebuilt: after an update, rendering this scene with the wide
+ * traversal selected and lupin_hip_trace_rays_wide return LUPIN_ERR_INVALID_ARGUMENT until the scene is created anew. */
+int lupin_hip_scene_update_instances(LupinScene *scene, const LupinMat4x3 *transpose_inverse_transforms /* num_instances */,
+                                     uint32_t num_instances, int tlas_builder /* 0 = CPU, 1 = device */);
+/* The TLAS the scene is traversed with, in lupin_build_tlas' format (what creation was given, or what the latest update
+ * built): returns the node count (2 * instances; out_nodes may be NULL to query it) or LUPIN_ERR_INVALID_ARGUMENT when
+ * capacity is smaller. */
+int64_t lupin_hip_scene_get_tlas(const LupinScene *scene, LupinTlasNode *out_nodes, uint64_t capacity);
 void lupin_hip_scene_destroy(LupinScene *scene);
 
 /* Rgba16Float render targets + lp::DoubleBufferedTexture (wgpu_utils.rs:279-348) */
@@ -744,6 +762,25 @@ int64_t lupin_hip_build_bvh_device(LupinContext *ctx, const float *verts_pos4, u
  * 2 * triangles - 1 nodes always suffice; vertex positions must be finite).  Synchronous. */
 int64_t lupin_hip_build_bvh_sah_device(LupinContext *ctx, const float *verts_pos4, uint32_t num_verts, uint32_t *indices,
                                        uint32_t num_indices, LupinBvhNode *out_nodes, uint64_t out_capacity);
+
+/* build_tlas (data_structures.rs:545-641) on the device (csrc/tlas.hip): lupin_build_tlas' inputs and output, the same
+ * tree node for node.  The leaf boxes come from the host code lupin_build_tlas uses; the agglomerative clustering
+ * (:572-610), a serial chain of tlas_find_best_match scans (:670-692), runs in one workgroup, each scan a reduction of
+ * (area, index) pairs in which the smaller area, then the smaller index wins -- the first minimum of the reference's
+ * ascending scan.  Boxes equal lupin_build_tlas' as float values (a zero may differ in sign: fminf(+0, -0)).
+ * Returns the node count (2 * num_instances) or a negative status; LUPIN_ERR_INVALID_ARGUMENT, before anything is
+ * launched, for an instance whose world box is not finite, and after the kernel stopped itself: at n^2 + 4n scans (no
+ * input needs them) or at a scan without candidate (every union area NaN or >= FLT_MAX).  Synchronous. */
+int64_t lupin_hip_build_tlas_device(LupinContext *ctx, const LupinInstance *instances, uint32_t num_instances,
+                                    const float *model_aabbs, uint32_t num_meshes, LupinTlasNode *out_nodes);
+/* the calling thread's latest lupin_hip_build_tlas_device (including the one inside lupin_hip_scene_update_instances) */
+typedef struct LupinTlasBuildStats {
+    uint32_t num_instances;
+    uint32_t state_in_lds;   /* 1: the live-slot state was held in LDS, 0: in global memory (more than 5800 instances) */
+    uint64_t scans;          /* tlas_find_best_match scans */
+    float kernel_ms;         /* the clustering kernel, between two events */
+} LupinTlasBuildStats;
+void lupin_hip_tlas_build_stats(LupinTlasBuildStats *out);
 
 /* The four-wide collapse of one mesh's BLAS exactly as lupin_hip_scene_create performs it for the wide tracer (host code,
  * no device needed; DESIGN.md 5 "Wide traversal"): a node's grandchildren are pulled up, largest box first, until it has

@@ -82,6 +82,8 @@ extern "C" {
     pub fn lupin_hip_destroy_pathtrace_resources(res: *mut LupinPathtraceResources);
     pub fn lupin_hip_scene_create(ctx: *mut LupinContext, desc: *const LupinSceneDesc, out: *mut *mut LupinScene) -> c_int;
     pub fn lupin_hip_scene_destroy(scene: *mut LupinScene);
+    // moves the instances in place: new transforms, TLAS rebuilt (tlas_builder 0 = lupin_build_tlas, 1 = on the device)
+    pub fn lupin_hip_scene_update_instances(scene: *mut LupinScene, transpose_inverse_transforms: *const LupinMat4x3, num_instances: u32, tlas_builder: c_int) -> c_int;
     pub fn lupin_hip_texture_create(ctx: *mut LupinContext, w: u32, h: u32, out: *mut *mut LupinTexture) -> c_int;
     pub fn lupin_hip_texture_destroy(tex: *mut LupinTexture);
     pub fn lupin_hip_texture_width(tex: *const LupinTexture) -> u32;
@@ -146,5 +148,8 @@ extern "C" {
     pub fn lupin_hip_build_bvh_sah_device(ctx: *mut LupinContext, verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32,
                                           out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     pub fn lupin_build_tlas(instances: *const LupinInstance, n: u32, model_aabbs: *const f32, num_meshes: u32, out: *mut LupinTlasNode) -> i64;
+    // the same tree built on the GPU (csrc/tlas.hip)
+    pub fn lupin_hip_build_tlas_device(ctx: *mut LupinContext, instances: *const LupinInstance, n: u32, model_aabbs: *const f32, num_meshes: u32,
+                                       out: *mut LupinTlasNode) -> i64;
     pub fn lupin_build_alias_table(weights: *const f32, n: u64, out_bins: *mut LupinAliasBin) -> i64;
 }

@@ -14,6 +14,7 @@
 //! | `tonemap_and_fit_aspect`, `TonemapDesc`              | [`tonemap_and_fit_aspect`]             |
 //! | `build_denoise_resources`, `denoise`, `DenoiseDesc`, `DenoiseQuality` | [`build_denoise_resources`], [`denoise`] (own a-trous filter, not OIDN) |
 //! | (no counterpart)                                     | [`build_adaptive_resources`], [`pathtrace_scene_adaptive`] (adaptive sampling) |
+//! | (no counterpart: `lp::Scene` is immutable)           | [`Scene::update_instances`] (instance transforms moved in place, device-built TLAS) |
 //!
 //! Like the reference, failures panic (the reference asserts / panics; the C ABI returns a status + message).
 pub mod ffi;
@@ -113,6 +114,14 @@ impl Scene {
         let mut raw = ptr::null_mut();
         check(unsafe { lupin_hip_scene_create(device.raw, &desc, &mut raw) });
         Scene { raw }
+    }
+}
+impl Scene {
+    /// Moves the instances in place (no counterpart in the reference): one `transpose_inverse_transform` per
+    /// instance, in instance order; the TLAS is rebuilt on the device (or by `lupin_build_tlas`), nothing else is uploaded again.
+    pub fn update_instances(&mut self, transpose_inverse_transforms: &[LupinMat4x3], device_tlas: bool) {
+        check(unsafe { lupin_hip_scene_update_instances(self.raw, transpose_inverse_transforms.as_ptr(), transpose_inverse_transforms.len() as u32,
+                                                        if device_tlas { 1 } else { 0 }) });
     }
 }
 impl Drop for Scene { fn drop(&mut self) { unsafe { lupin_hip_scene_destroy(self.raw) } } }

@@ -145,6 +145,10 @@ class AdaptiveStatsC(C.Structure):   # LupinAdaptiveStats
     _fields_ = [("active_pixels", C.c_uint64), ("pixel_frames", C.c_uint64), ("calls", C.c_uint32), ("max_frames_taken", C.c_uint32)]
 
 
+class TlasBuildStatsC(C.Structure):   # LupinTlasBuildStats
+    _fields_ = [("num_instances", C.c_uint32), ("state_in_lds", C.c_uint32), ("scans", C.c_uint64), ("kernel_ms", C.c_float)]
+
+
 class StatsC(C.Structure):
     _fields_ = [("path_bounces", C.c_uint64), ("paths", C.c_uint64), ("extend_launches", C.c_uint64),
                 ("extend_ms", C.c_double), ("shade_ms", C.c_double), ("total_ms", C.c_double),
@@ -240,6 +244,10 @@ SYMBOLS = [
     ("lupin_hip_comm_barrier", C.c_int, [_P]),
     ("lupin_build_bvh", C.c_int64, [_P, _U32, _P, _U32, _P, C.c_uint64]),
     ("lupin_build_tlas", C.c_int64, [_P, _U32, _P, _U32, _P]),
+    ("lupin_hip_build_tlas_device", C.c_int64, [_P, _P, _U32, _P, _U32, _P]),
+    ("lupin_hip_tlas_build_stats", None, [_P]),
+    ("lupin_hip_scene_update_instances", C.c_int, [_P, _P, _U32, C.c_int]),
+    ("lupin_hip_scene_get_tlas", C.c_int64, [_P, _P, C.c_uint64]),
     ("lupin_build_alias_table", C.c_int64, [_P, C.c_uint64, _P]),
     ("lupin_mesh_light_weights", C.c_float, [_P, _P, _U32, _P]),
     ("lupin_env_light_weights", None, [_P, _U32, _U32, _P, _P]),

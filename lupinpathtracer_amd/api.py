@@ -502,6 +502,33 @@ def build_tlas(instances, model_aabbs):
     return out[:n]
 
 
+# Scene.update_instances builds the TLAS on the device from this many instances.  Measured (DESIGN.md 11,
+# profiles/scene_update_bench.jsonl): lupin_build_tlas wins at 501 and 2 101 instances, the device builder at 8 101.
+UPDATE_DEVICE_MIN_INSTANCES = 4000
+
+
+def build_tlas_device(ctx, instances, model_aabbs):
+    """build_tlas on the device (csrc/tlas.hip): the same tree as build_tlas, node for node.  Needs a GPU context."""
+    if ctx is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "the device TLAS builder needs a GPU context")
+    inst = np.ascontiguousarray(instances)
+    ab = np.ascontiguousarray(model_aabbs, np.float32).reshape(-1, 6)
+    if len(inst) == 0 or len(ab) == 0:
+        return np.zeros(0, TLAS_NODE_DTYPE)
+    out = np.zeros(2 * len(inst), TLAS_NODE_DTYPE)
+    n = lib().lupin_hip_build_tlas_device(ctx.handle, ptr(inst), len(inst), ptr(ab), len(ab), ptr(out))
+    if n < 0:
+        check(int(n))
+    return out[:n]
+
+
+def tlas_build_stats():
+    """The calling thread's latest build_tlas_device: instances, best-match scans, where the state lived, kernel time."""
+    s = _abi.TlasBuildStatsC()
+    lib().lupin_hip_tlas_build_stats(C.byref(s))
+    return {"num_instances": int(s.num_instances), "state_in_lds": bool(s.state_in_lds), "scans": int(s.scans), "kernel_ms": float(s.kernel_ms)}
+
+
 def build_alias_table(weights):
     """lp::build_alias_table (data_structures.rs:116-193)."""
     w = np.ascontiguousarray(weights, np.float32)
@@ -561,6 +588,42 @@ class Scene:
         self.lights_empty = True
         self.instances_empty = True
         self.stats = {}
+        self.instances = None      # the instance records and per-mesh model boxes the TLAS was built from
+        self.model_aabbs = None
+
+    def update_instances(self, transforms, tlas_builder=None):
+        """Move the scene's instances in place (lupin_hip_scene_update_instances): new transforms, a rebuilt TLAS, nothing
+        else re-uploaded.  transforms: (n, 3, 4) transpose_inverse_transform matrices (the rows of world -> local), or
+        instance records whose mesh_idx / mat_idx equal the scene's.  tlas_builder: "cpu" | "device"; None picks by
+        instance count (the CPU builder below UPDATE_DEVICE_MIN_INSTANCES instances).
+        Calls recorded before the update render the old transforms.  On an error the scene is unchanged.
+        Also refreshes desc.instances, desc.tlas_nodes and .tlas, so the oracle can run on the same object."""
+        if self.handle is None:
+            raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "scene was built without a device context; there is no CPU fallback")
+        if tlas_builder is None:
+            tlas_builder = "device" if len(self.instances) >= UPDATE_DEVICE_MIN_INSTANCES else "cpu"
+        if tlas_builder not in ("cpu", "device"):
+            raise ValueError("tlas_builder must be 'cpu' or 'device'")
+        t = np.asarray(transforms)
+        if t.dtype == INSTANCE_DTYPE:
+            if len(t) == len(self.instances) and not (np.array_equal(t["mesh_idx"], self.instances["mesh_idx"]) and
+                                                      np.array_equal(t["mat_idx"], self.instances["mat_idx"])):
+                raise ValueError("update_instances changes transforms only: mesh_idx and mat_idx must stay as they are")
+            t = t["transpose_inverse_transform"]
+        t = np.ascontiguousarray(t, np.float32).reshape(-1, 3, 4)
+        check(lib().lupin_hip_scene_update_instances(self.handle, ptr(t), len(t), 1 if tlas_builder == "device" else 0))
+        instances = self.instances.copy()
+        instances["transpose_inverse_transform"] = t
+        tlas = np.zeros(2 * len(instances), TLAS_NODE_DTYPE)
+        n = lib().lupin_hip_scene_get_tlas(self.handle, ptr(tlas), len(tlas))
+        if n < 0:
+            check(int(n))
+        tlas = tlas[:n].copy()
+        self._keep += [instances, tlas]
+        self.instances, self.tlas = instances, tlas
+        self.desc.instances = ptr(instances)
+        self.desc.tlas_nodes = ptr(tlas) if len(tlas) else None
+        self.desc.num_tlas_nodes = len(tlas)
 
     def __del__(self):
         try:
@@ -579,7 +642,7 @@ def _array_of(struct, items):
 
 
 def build_accel_structures_and_upload(ctx, scene: SceneCPU, textures: List[TextureCPU], envs_info: List[EnvMapInfo],
-                                      build_sw_and_hw: bool = True, blas_builder: str = "sah") -> Scene:
+                                      build_sw_and_hw: bool = True, blas_builder: str = "sah", tlas_builder: str = "cpu") -> Scene:
     """lp::build_accel_structures_and_upload (data_structures.rs:696-872), software-BVH pipeline.
 
     ctx may be None: the host-side preprocessing still runs and `Scene.desc` is usable (CPU-only
@@ -588,7 +651,12 @@ def build_accel_structures_and_upload(ctx, scene: SceneCPU, textures: List[Textu
     (build_bvh_sah_device; meshes with at least 64 triangles), "lbvh" = the Morton-order device builder
     (build_bvh_device; meshes with at least 64 triangles, smaller ones keep the SAH builder); a callable
     (verts (N,4), indices) -> (nodes, reordered indices) plugs in any other builder that emits the reference's node format.
+    tlas_builder: "cpu" = lupin_build_tlas, "device" = the same tree built on the GPU (build_tlas_device).
     """
+    if tlas_builder not in ("cpu", "device"):
+        raise ValueError("tlas_builder must be 'cpu' or 'device'")
+    if tlas_builder == "device" and ctx is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "the device TLAS builder needs a GPU context")
     if not callable(blas_builder) and blas_builder not in ("sah", "sah_device", "lbvh"):
         raise ValueError("blas_builder must be 'sah', 'sah_device', 'lbvh' or a callable (verts, indices) -> (nodes, reordered indices)")
     if blas_builder in ("lbvh", "sah_device") and ctx is None:
@@ -622,7 +690,7 @@ def build_accel_structures_and_upload(ctx, scene: SceneCPU, textures: List[Textu
             model_aabbs.append(np.array([fm, fm, fm, -fm, -fm, -fm], np.float32))
     model_aabbs = np.array(model_aabbs, np.float32).reshape(-1, 6)
     instances = np.ascontiguousarray(scene.instances)
-    tlas = build_tlas(instances, model_aabbs)
+    tlas = build_tlas_device(ctx, instances, model_aabbs) if tlas_builder == "device" else build_tlas(instances, model_aabbs)
 
     def vbufs(arrs, comps):
         descs = []
@@ -690,6 +758,8 @@ def build_accel_structures_and_upload(ctx, scene: SceneCPU, textures: List[Textu
     out.lights_empty = len(lights) == 0
     out.instances_empty = len(instances) == 0
     out.tlas = tlas
+    out.instances = instances
+    out.model_aabbs = model_aabbs
     out.lights = lights
     out.alias_tables = alias_tables
     out.env_alias_tables = env_alias_tables

@@ -226,6 +226,75 @@ void mat4_inverse(const float m[4][4], float b[4][4])
 
 }  // namespace
 
+// The two ends of build_tlas that lupin_build_tlas and the device builder (tlas.hip) share (declared in lupin_internal.hpp).
+int lupin_internal_tlas_leaves(const LupinInstance *instances, uint32_t num_instances, const float *model_aabbs, uint32_t num_meshes,
+                               LupinTlasNode *out_leaves);
+void lupin_internal_tlas_finish(LupinTlasNode *tlas, uint32_t len);
+bool lupin_internal_tlas_leaves_finite(const LupinInstance *instances, const LupinTlasNode *leaves, uint32_t num_instances);
+
+// The leaves (data_structures.rs:553-569): instance i's model box through its local -> world transform, node i.
+int lupin_internal_tlas_leaves(const LupinInstance *instances, uint32_t num_instances, const float *model_aabbs, uint32_t num_meshes,
+                               LupinTlasNode *out_leaves)
+{
+    for (uint32_t i = 0; i < num_instances; i++)
+    {
+        const LupinInstance &inst = instances[i];
+        if (inst.mesh_idx >= num_meshes) return LUPIN_ERR_INVALID_ARGUMENT;
+        const float *ab = model_aabbs + (size_t)inst.mesh_idx * 6;
+        // transform = transpose_inverse_transform.transpose().inverse()  (local -> world)
+        LupinMat3x4 w2l, l2w;
+        for (int c = 0; c < 4; c++) for (int r = 0; r < 3; r++) w2l.m[c][r] = inst.transpose_inverse_transform.m[r][c];
+        lupin_mat3x4_inverse(&w2l, &l2w);
+        // transform_aabb (base.rs:1113-1134): 8 corners, z fastest
+        Box res = neutral_box();
+        for (int k = 0; k < 8; k++)
+        {
+            float x = (k & 4) ? ab[3] : ab[0], y = (k & 2) ? ab[4] : ab[1], z = (k & 1) ? ab[5] : ab[2];
+            V3 p = {l2w.m[0][0] * x + l2w.m[1][0] * y + l2w.m[2][0] * z + l2w.m[3][0] * 1.0f,
+                    l2w.m[0][1] * x + l2w.m[1][1] * y + l2w.m[2][1] * z + l2w.m[3][1] * 1.0f,
+                    l2w.m[0][2] * x + l2w.m[1][2] * y + l2w.m[2][2] * z + l2w.m[3][2] * 1.0f};
+            res.lo = vmin(res.lo, p);
+            res.hi = vmax(res.hi, p);
+        }
+        LupinTlasNode nd;
+        memset(&nd, 0, sizeof(nd));
+        nd.aabb_min[0] = res.lo.x; nd.aabb_min[1] = res.lo.y; nd.aabb_min[2] = res.lo.z;
+        nd.aabb_max[0] = res.hi.x; nd.aabb_max[1] = res.hi.y; nd.aabb_max[2] = res.hi.z;
+        nd.instance_idx = i;
+        out_leaves[i] = nd;
+    }
+    return LUPIN_OK;
+}
+
+// What the device builder and lupin_hip_scene_update_instances ask of their input: finite transforms and finite, ordered
+// world boxes.  (fminf / fmaxf drop a NaN corner, so a NaN transform leaves Aabb::neutral(), which is finite but inverted.)
+bool lupin_internal_tlas_leaves_finite(const LupinInstance *instances, const LupinTlasNode *leaves, uint32_t num_instances)
+{
+    for (uint32_t i = 0; i < num_instances; i++)
+    {
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) if (!std::isfinite(instances[i].transpose_inverse_transform.m[r][c])) return false;
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(leaves[i].aabb_min[k]) || !std::isfinite(leaves[i].aabb_max[k]) || !(leaves[i].aabb_min[k] <= leaves[i].aabb_max[k])) return false;
+    }
+    return true;
+}
+
+// The tail (data_structures.rs:614-635): reverse so the root is node 0, then remap the children.
+void lupin_internal_tlas_finish(LupinTlasNode *tlas, uint32_t len)
+{
+    std::reverse(tlas, tlas + len);
+    for (uint32_t i = 0; i < len; i++)
+    {
+        // internal nodes: remap children; `right == 0` now legitimately means old index 0
+        bool internal = (tlas[i].left != 0) || (tlas[i].right != 0);
+        if (internal)
+        {
+            tlas[i].left = len - 1 - tlas[i].left;
+            tlas[i].right = len - 1 - tlas[i].right;
+        }
+    }
+}
+
 extern "C" {
 
 void lupin_mat3x4_inverse(const LupinMat3x4 *in, LupinMat3x4 *out)
@@ -290,39 +359,11 @@ int64_t lupin_build_tlas(const LupinInstance *instances, uint32_t num_instances,
     if (num_instances == 0 || num_meshes == 0) return 0;  // data_structures.rs:547
     if (!instances || !model_aabbs || !out_nodes) return LUPIN_ERR_INVALID_ARGUMENT;
 
-    std::vector<uint32_t> node_indices;
-    std::vector<LupinTlasNode> tlas;
-    node_indices.reserve(num_instances);
+    std::vector<uint32_t> node_indices(num_instances);
+    std::vector<LupinTlasNode> tlas(num_instances);
     tlas.reserve((size_t)num_instances * 2);
-
-    for (uint32_t i = 0; i < num_instances; i++)
-    {
-        const LupinInstance &inst = instances[i];
-        if (inst.mesh_idx >= num_meshes) return LUPIN_ERR_INVALID_ARGUMENT;
-        const float *ab = model_aabbs + (size_t)inst.mesh_idx * 6;
-        // transform = transpose_inverse_transform.transpose().inverse()  (local -> world)
-        LupinMat3x4 w2l, l2w;
-        for (int c = 0; c < 4; c++) for (int r = 0; r < 3; r++) w2l.m[c][r] = inst.transpose_inverse_transform.m[r][c];
-        lupin_mat3x4_inverse(&w2l, &l2w);
-        // transform_aabb (base.rs:1113-1134): 8 corners, z fastest
-        Box res = neutral_box();
-        for (int k = 0; k < 8; k++)
-        {
-            float x = (k & 4) ? ab[3] : ab[0], y = (k & 2) ? ab[4] : ab[1], z = (k & 1) ? ab[5] : ab[2];
-            V3 p = {l2w.m[0][0] * x + l2w.m[1][0] * y + l2w.m[2][0] * z + l2w.m[3][0] * 1.0f,
-                    l2w.m[0][1] * x + l2w.m[1][1] * y + l2w.m[2][1] * z + l2w.m[3][1] * 1.0f,
-                    l2w.m[0][2] * x + l2w.m[1][2] * y + l2w.m[2][2] * z + l2w.m[3][2] * 1.0f};
-            res.lo = vmin(res.lo, p);
-            res.hi = vmax(res.hi, p);
-        }
-        LupinTlasNode nd;
-        memset(&nd, 0, sizeof(nd));
-        nd.aabb_min[0] = res.lo.x; nd.aabb_min[1] = res.lo.y; nd.aabb_min[2] = res.lo.z;
-        nd.aabb_max[0] = res.hi.x; nd.aabb_max[1] = res.hi.y; nd.aabb_max[2] = res.hi.z;
-        nd.instance_idx = i;
-        tlas.push_back(nd);
-        node_indices.push_back((uint32_t)tlas.size() - 1);
-    }
+    if (lupin_internal_tlas_leaves(instances, num_instances, model_aabbs, num_meshes, tlas.data()) != LUPIN_OK) return LUPIN_ERR_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < num_instances; i++) node_indices[i] = i;
 
     // tlas_find_best_match (data_structures.rs:670-692)
     auto best_match = [&](uint32_t node_a) -> uint32_t {
@@ -384,17 +425,7 @@ int64_t lupin_build_tlas(const LupinInstance *instances, uint32_t num_instances,
     // push a copy of the root, then reverse so the root is node 0 (data_structures.rs:612-635)
     tlas.push_back(tlas[node_indices[a]]);
     uint32_t len = (uint32_t)tlas.size();
-    std::reverse(tlas.begin(), tlas.end());
-    for (uint32_t i = 0; i < len; i++)
-    {
-        // internal nodes: remap children; `right == 0` now legitimately means old index 0
-        bool internal = (tlas[i].left != 0) || (tlas[i].right != 0);
-        if (internal)
-        {
-            tlas[i].left = len - 1 - tlas[i].left;
-            tlas[i].right = len - 1 - tlas[i].right;
-        }
-    }
+    lupin_internal_tlas_finish(tlas.data(), len);
     memcpy(out_nodes, tlas.data(), (size_t)len * sizeof(LupinTlasNode));
     return (int64_t)len;
 }

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
+#include <cfloat>
 #include <string>
 #include <vector>
 #include <set>
@@ -156,6 +157,14 @@ struct LupinScene
     bool simple_matte = false;                      // only untextured matte materials, no vertex colours, no environments: k_shade<.., SIMPLE>
     bool has_sw_bvh = false;
     bool envs_empty = true, lights_empty = true, instances_empty = true;
+    // host-side copies lupin_hip_scene_update_instances works from
+    std::vector<float> model_aabbs;                 // per mesh: f32 min xyz, max xyz of verts_pos (Aabb::neutral() for an empty mesh)
+    std::vector<InstanceDev> host_instances;        // as uploaded (mesh_idx, mat_idx, blas_root and flags never change)
+    std::vector<uint32_t> light_instance;           // light -> instance
+    std::vector<LupinTlasNode> tlas_nodes;          // the TLAS in lupin_build_tlas' format (lupin_hip_scene_get_tlas)
+    uint32_t nblas = 0, ntlas = 0;                  // the one node array is [nblas BLAS nodes | ntlas TLAS nodes]
+    uint32_t max_blas_depth = 0;
+    bool wide_stale = false;                        // an update moved the instances: the four-wide TLAS describes the old ones
 };
 
 template <typename T>
@@ -1071,6 +1080,101 @@ void lupin_hip_destroy_pathtrace_resources(LupinPathtraceResources *res) { delet
 
 // ---- scene upload ----
 
+// The TLAS as child-pair nodes behind `nblas` BLAS nodes of the one node array (global references), its root reference and
+// its depth.  Returns nullptr or why the nodes are not a tree over `num_instances` instances.
+static const char *tlas_child_pairs(const LupinTlasNode *nodes, uint32_t num_nodes, uint32_t num_instances, uint32_t nblas,
+                                    std::vector<WideNode> &tlas, uint32_t *tlas_root, uint32_t *tlas_depth)
+{
+    std::vector<uint32_t> ref(num_nodes);
+    uint32_t wide_count = 0;
+    for (uint32_t n = 0; n < num_nodes; n++)
+    {
+        const LupinTlasNode &nd = nodes[n];
+        if (nd.left == 0)
+        {
+            if (nd.instance_idx >= num_instances) return "TLAS leaf instance out of range";
+            ref[n] = REF_LEAF | nd.instance_idx;
+        }
+        else
+        {
+            if (nd.left >= num_nodes || nd.right >= num_nodes) return "TLAS child out of range";
+            ref[n] = nblas + wide_count++;
+        }
+    }
+    tlas.resize(wide_count);
+    for (uint32_t n = 0; n < num_nodes; n++)
+    {
+        const LupinTlasNode &nd = nodes[n];
+        if (nd.left == 0) continue;
+        const LupinTlasNode &l = nodes[nd.left];
+        const LupinTlasNode &r = nodes[nd.right];
+        WideNode w;
+        w.a = make_float4(l.aabb_min[0], r.aabb_min[0], l.aabb_min[1], r.aabb_min[1]);
+        w.b = make_float4(l.aabb_min[2], r.aabb_min[2], l.aabb_max[0], r.aabb_max[0]);
+        w.c = make_float4(l.aabb_max[1], r.aabb_max[1], l.aabb_max[2], r.aabb_max[2]);
+        w.d = make_uint4(ref[nd.left], ref[nd.right], 0u, 0u);
+        tlas[ref[n] - nblas] = w;
+    }
+    *tlas_root = ref[0];
+    // depth from the root (bounded walk: a malformed cyclic TLAS is rejected)
+    *tlas_depth = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> st;
+    st.push_back({0u, 0u});
+    uint64_t visited = 0;
+    while (!st.empty())
+    {
+        auto [n, d] = st.back();
+        st.pop_back();
+        if (++visited > (uint64_t)num_nodes * 2 + 2) return "TLAS is not a tree";
+        if (nodes[n].left != 0)
+        {
+            *tlas_depth = std::max(*tlas_depth, d + 1);
+            st.push_back({nodes[n].left, d + 1});
+            st.push_back({nodes[n].right, d + 1});
+        }
+    }
+    return nullptr;
+}
+
+// Conservative world-space bounding sphere of a light instance: `npts` local-space points (`stride` floats apart) that
+// enclose the mesh -- all its vertices at creation, the corners of its model box in an update -- through the inverse of
+// the stored world->local rows, in double, radius padded.  lights_pdf skips lights whose sphere the ray cannot reach; a
+// skipped light contributes exactly +0.0f in the reference's sum, so results do not change.  .w = padded radius squared.
+static float4 light_bound(const LupinMat4x3 &rows, const float *pts, size_t npts, size_t stride)
+{
+    const float (*r)[4] = rows.m;   // 3 rows x 4: world -> local
+    const double a = r[0][0], b = r[0][1], c = r[0][2], d = r[1][0], e = r[1][1], f = r[1][2], g = r[2][0], h = r[2][1], k = r[2][2];
+    const double det = a * (e * k - f * h) - b * (d * k - f * g) + c * (d * h - e * g);
+    float4 bound = make_float4(0.0f, 0.0f, 0.0f, INFINITY);   // singular / non-finite transform: never culled
+    if (std::isfinite(det) && det != 0.0 && npts > 0)
+    {
+        const double inv[3][3] = {{(e * k - f * h) / det, (c * h - b * k) / det, (b * f - c * e) / det},
+                                  {(f * g - d * k) / det, (a * k - c * g) / det, (c * d - a * f) / det},
+                                  {(d * h - e * g) / det, (b * g - a * h) / det, (a * e - b * d) / det}};
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+        bool finite = true;
+        for (size_t v = 0; v < npts; v++)
+        {
+            const double q[3] = {pts[stride * v + 0] - (double)r[0][3], pts[stride * v + 1] - (double)r[1][3], pts[stride * v + 2] - (double)r[2][3]};
+            for (int ax = 0; ax < 3; ax++)
+            {
+                const double w = inv[ax][0] * q[0] + inv[ax][1] * q[1] + inv[ax][2] * q[2];
+                finite = finite && std::isfinite(w);
+                lo[ax] = std::min(lo[ax], w); hi[ax] = std::max(hi[ax], w);
+            }
+        }
+        if (finite)
+        {
+            const double cx = 0.5 * (lo[0] + hi[0]), cy = 0.5 * (lo[1] + hi[1]), cz = 0.5 * (lo[2] + hi[2]);
+            const double rad = 0.5 * std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+            const double cmag = std::fabs(cx) + std::fabs(cy) + std::fabs(cz);
+            const double padded = rad * 1.02 + 1e-4 * (cmag + rad) + 1e-6;
+            bound = make_float4((float)cx, (float)cy, (float)cz, (float)(padded * padded * (1.0 + 1e-6)));
+        }
+    }
+    return bound;
+}
+
 int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinScene **out_scene)
 {
     CTX_ALIVE_TRY(ctx);
@@ -1170,6 +1274,18 @@ int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinS
         if (!ok) { lupin_hip_scene_destroy(sc); return fail(LUPIN_ERR_INVALID_ARGUMENT, "mesh attribute buffer index / size mismatch"); }
         meshes[mi] = md;
 
+        {
+            float box[6] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};   // Aabb::neutral()
+            for (uint32_t v = 0; v < m.num_verts; v++)
+                for (int ax = 0; ax < 3; ax++)
+                {
+                    const float x = m.verts_pos[(size_t)v * 4 + ax];
+                    box[ax] = x < box[ax] ? x : box[ax];
+                    box[3 + ax] = x > box[3 + ax] ? x : box[3 + ax];
+                }
+            sc->model_aabbs.insert(sc->model_aabbs.end(), box, box + 6);
+        }
+
         uint32_t ntris = m.num_indices / 3;
         for (uint32_t i = 0; i < ntris * 3; i++)
             if (m.indices[i] >= m.num_verts) { lupin_hip_scene_destroy(sc); return fail(LUPIN_ERR_INVALID_ARGUMENT, "vertex index out of range"); }
@@ -1222,55 +1338,13 @@ int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinS
     if (s.num_tlas_nodes > 0)
     {
         // TLAS nodes go behind the BLAS nodes in ONE array (no per-lane base select in the traversal step): global references
-        std::vector<uint32_t> ref(s.num_tlas_nodes);
-        const uint32_t nblas = (uint32_t)blas.size();
-        uint32_t wide_count = 0;
-        for (uint32_t n = 0; n < s.num_tlas_nodes; n++)
-        {
-            const LupinTlasNode &nd = s.tlas_nodes[n];
-            if (nd.left == 0)
-            {
-                if (nd.instance_idx >= s.num_instances) { lupin_hip_scene_destroy(sc); return fail(LUPIN_ERR_INVALID_ARGUMENT, "TLAS leaf instance out of range"); }
-                ref[n] = REF_LEAF | nd.instance_idx;
-            }
-            else
-            {
-                if (nd.left >= s.num_tlas_nodes || nd.right >= s.num_tlas_nodes) { lupin_hip_scene_destroy(sc); return fail(LUPIN_ERR_INVALID_ARGUMENT, "TLAS child out of range"); }
-                ref[n] = nblas + wide_count++;
-            }
-        }
-        tlas.resize(wide_count);
-        for (uint32_t n = 0; n < s.num_tlas_nodes; n++)
-        {
-            const LupinTlasNode &nd = s.tlas_nodes[n];
-            if (nd.left == 0) continue;
-            const LupinTlasNode &l = s.tlas_nodes[nd.left];
-            const LupinTlasNode &r = s.tlas_nodes[nd.right];
-            WideNode w;
-            w.a = make_float4(l.aabb_min[0], r.aabb_min[0], l.aabb_min[1], r.aabb_min[1]);
-            w.b = make_float4(l.aabb_min[2], r.aabb_min[2], l.aabb_max[0], r.aabb_max[0]);
-            w.c = make_float4(l.aabb_max[1], r.aabb_max[1], l.aabb_max[2], r.aabb_max[2]);
-            w.d = make_uint4(ref[nd.left], ref[nd.right], 0u, 0u);
-            tlas[ref[n] - nblas] = w;
-        }
-        tlas_root = ref[0];
-        // depth from the root (bounded walk: a malformed cyclic TLAS is rejected)
-        std::vector<std::pair<uint32_t, uint32_t>> st;
-        st.push_back({0u, 0u});
-        uint64_t visited = 0;
-        while (!st.empty())
-        {
-            auto [n, d] = st.back();
-            st.pop_back();
-            if (++visited > (uint64_t)s.num_tlas_nodes * 2 + 2) { lupin_hip_scene_destroy(sc); return fail(LUPIN_ERR_INVALID_ARGUMENT, "TLAS is not a tree"); }
-            if (s.tlas_nodes[n].left != 0)
-            {
-                tlas_depth = std::max(tlas_depth, d + 1);
-                st.push_back({s.tlas_nodes[n].left, d + 1});
-                st.push_back({s.tlas_nodes[n].right, d + 1});
-            }
-        }
+        const char *why = tlas_child_pairs(s.tlas_nodes, s.num_tlas_nodes, s.num_instances, (uint32_t)blas.size(), tlas, &tlas_root, &tlas_depth);
+        if (why) { lupin_hip_scene_destroy(sc); return fail(LUPIN_ERR_INVALID_ARGUMENT, why); }
     }
+    sc->nblas = (uint32_t)blas.size();
+    sc->ntlas = (uint32_t)tlas.size();
+    sc->max_blas_depth = max_blas_depth;
+    sc->tlas_nodes.assign(s.tlas_nodes, s.tlas_nodes + s.num_tlas_nodes);
     sc->stack_entries = tlas_depth + max_blas_depth + 1;
     blas.insert(blas.end(), tlas.begin(), tlas.end());   // the one node array: [BLAS | TLAS]
 
@@ -1360,46 +1434,15 @@ int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinS
         if (nb) alias_bins.insert(alias_bins.end(), s.env_alias_tables[i].bins, s.env_alias_tables[i].bins + nb);
     }
 
-    // Conservative world-space bounding sphere of every light instance (all mesh vertices through the inverse of the
-    // stored world->local rows, in double, radius padded): lights_pdf skips lights whose sphere the ray cannot reach.
-    // A skipped light contributes exactly +0.0f in the reference's sum, so results do not change.
+    // light_bound() of every light instance over all its mesh's vertices
     // (padded to whole groups of four: lights_pdf fetches the bounds four at a time, 64 aligned bytes per scalar load)
     std::vector<float4> light_bounds(((size_t)s.num_lights + 3) / 4 * 4, make_float4(0.0f, 0.0f, 0.0f, -1.0f));
     for (uint32_t i = 0; i < s.num_lights; i++)
     {
         const LupinInstance &in = s.instances[s.lights[i].instance_idx];
         const LupinMeshDesc &m = s.meshes[in.mesh_idx];
-        const float (*r)[4] = in.transpose_inverse_transform.m;   // 3 rows x 4: world -> local
-        const double a = r[0][0], b = r[0][1], c = r[0][2], d = r[1][0], e = r[1][1], f = r[1][2], g = r[2][0], h = r[2][1], k = r[2][2];
-        const double det = a * (e * k - f * h) - b * (d * k - f * g) + c * (d * h - e * g);
-        float4 bound = make_float4(0.0f, 0.0f, 0.0f, INFINITY);   // singular / non-finite transform: never culled (.w = radius squared)
-        if (std::isfinite(det) && det != 0.0 && m.num_verts > 0)
-        {
-            const double inv[3][3] = {{(e * k - f * h) / det, (c * h - b * k) / det, (b * f - c * e) / det},
-                                      {(f * g - d * k) / det, (a * k - c * g) / det, (c * d - a * f) / det},
-                                      {(d * h - e * g) / det, (b * g - a * h) / det, (a * e - b * d) / det}};
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-            bool finite = true;
-            for (uint32_t v = 0; v < m.num_verts; v++)
-            {
-                const double q[3] = {m.verts_pos[4 * v + 0] - (double)r[0][3], m.verts_pos[4 * v + 1] - (double)r[1][3], m.verts_pos[4 * v + 2] - (double)r[2][3]};
-                for (int ax = 0; ax < 3; ax++)
-                {
-                    const double w = inv[ax][0] * q[0] + inv[ax][1] * q[1] + inv[ax][2] * q[2];
-                    finite = finite && std::isfinite(w);
-                    lo[ax] = std::min(lo[ax], w); hi[ax] = std::max(hi[ax], w);
-                }
-            }
-            if (finite)
-            {
-                const double cx = 0.5 * (lo[0] + hi[0]), cy = 0.5 * (lo[1] + hi[1]), cz = 0.5 * (lo[2] + hi[2]);
-                const double rad = 0.5 * std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
-                const double cmag = std::fabs(cx) + std::fabs(cy) + std::fabs(cz);
-                const double padded = rad * 1.02 + 1e-4 * (cmag + rad) + 1e-6;
-                bound = make_float4((float)cx, (float)cy, (float)cz, (float)(padded * padded * (1.0 + 1e-6)));   // .w = padded radius squared
-            }
-        }
-        light_bounds[i] = bound;
+        light_bounds[i] = light_bound(in.transpose_inverse_transform, m.verts_pos, m.num_verts, 4);
+        sc->light_instance.push_back(s.lights[i].instance_idx);
     }
 
     // small scenes: one blob [tlas | blas | tris | instances] in 16-byte words for LDS staging.  Nodes and instances are
@@ -1450,6 +1493,7 @@ int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinS
         lupin_hip_scene_destroy(sc);
         return rc;
     }
+    sc->host_instances = instances;
     dv.tlas = dv.blas;
     dv.tlas_root = tlas_root;
     dv.tlas4_root = tlas4_root;
@@ -1488,6 +1532,134 @@ void lupin_hip_scene_destroy(LupinScene *scene)
     if (ctx_alive(scene->ctx)) sync_all(scene->ctx);   // a destroyed context has drained its streams already
     for (void *p : scene->allocations) hipFree(p);
     delete scene;
+}
+
+// Moves the instances in place.  Everything is validated and built in host staging first; device memory is
+// written only once the new tree exists and every lane that may read the scene has drained, so an error leaves the scene
+// rendering exactly as before.
+int lupin_hip_scene_update_instances(LupinScene *scene, const LupinMat4x3 *transpose_inverse_transforms, uint32_t num_instances, int tlas_builder)
+{
+    if (!scene || !transpose_inverse_transforms) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    LupinContext *ctx = scene->ctx;
+    CTX_ALIVE_TRY(ctx);
+    if (tlas_builder != 0 && tlas_builder != 1) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown tlas_builder (0 = CPU, 1 = device)");
+    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    const uint32_t n = scene->dev.num_instances;
+    if (num_instances != n) return fail(LUPIN_ERR_INVALID_ARGUMENT, "update_instances: the instance count cannot change (" + std::to_string(num_instances) + " transforms for " + std::to_string(n) + " instances)");
+    if (n == 0) return LUPIN_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // calls recorded so far render the old transforms; their failure is this call's (not dropped as join_primary drops it)
+    { int frc = flush_pending(ctx); if (frc != LUPIN_OK) return frc; }
+
+    // ---- staging: instance records, TLAS, child pairs, light bounds ----
+    std::vector<LupinInstance> inst(n);
+    std::vector<InstanceDev> instances = scene->host_instances;
+    for (uint32_t i = 0; i < n; i++)
+    {
+        memset(&inst[i], 0, sizeof(LupinInstance));
+        inst[i].transpose_inverse_transform = transpose_inverse_transforms[i];
+        inst[i].mesh_idx = instances[i].mesh_idx;
+        inst[i].mat_idx = instances[i].mat_idx;
+        const float (*m)[4] = transpose_inverse_transforms[i].m;
+        instances[i].r0 = make_float4(m[0][0], m[0][1], m[0][2], m[0][3]);
+        instances[i].r1 = make_float4(m[1][0], m[1][1], m[1][2], m[1][3]);
+        instances[i].r2 = make_float4(m[2][0], m[2][1], m[2][2], m[2][3]);
+    }
+    const uint32_t num_meshes = (uint32_t)(scene->model_aabbs.size() / 6);
+    std::vector<LupinTlasNode> nodes((size_t)n * 2);
+    if (tlas_builder == 0)
+    {
+        // the device builder rejects non-finite world boxes itself; the CPU builder would cluster them
+        if (lupin_internal_tlas_leaves(inst.data(), n, scene->model_aabbs.data(), num_meshes, nodes.data()) != LUPIN_OK)
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "instance mesh_idx out of range");
+        if (!lupin_internal_tlas_leaves_finite(inst.data(), nodes.data(), n))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "instance with a non-finite transform or world-space box (NaN / infinite / singular transform)");
+    }
+    const int64_t built = tlas_builder == 0 ? lupin_build_tlas(inst.data(), n, scene->model_aabbs.data(), num_meshes, nodes.data())
+                                            : lupin_hip_build_tlas_device(ctx, inst.data(), n, scene->model_aabbs.data(), num_meshes, nodes.data());
+    if (built < 0) return tlas_builder == 0 ? fail((int)built, "lupin_build_tlas failed") : (int)built;   // the device builder left its message
+    if (built != (int64_t)n * 2) return fail(LUPIN_ERR_INVALID_ARGUMENT, "TLAS builder returned an unexpected node count");
+    std::vector<WideNode> tlas;
+    uint32_t tlas_root = REF_LEAF, tlas_depth = 0;
+    if (const char *why = tlas_child_pairs(nodes.data(), (uint32_t)built, n, scene->nblas, tlas, &tlas_root, &tlas_depth)) return fail(LUPIN_ERR_INVALID_ARGUMENT, why);
+    // a binary tree over n leaves has n - 1 inner nodes: the TLAS segment of the node array keeps its size
+    if (tlas.size() != scene->ntlas) return fail(LUPIN_ERR_INVALID_ARGUMENT, "rebuilt TLAS does not fit the scene's TLAS segment");
+    const uint32_t stack_entries = tlas_depth + scene->max_blas_depth + 1;
+    SceneDev &dv = scene->dev;
+    {
+        // the limit every render applies (pathtrace_impl / flush_pending), here before anything is written
+        const bool lds_geo = dv.geo_blob_words && ctx->lds_geometry;
+        const size_t lds = (size_t)stack_entries * LP_BLOCK * sizeof(uint32_t) + (lds_geo ? (size_t)dv.geo_blob_words * 16 : 0);
+        if (lds > 160 * 1024) return fail(LUPIN_ERR_INVALID_ARGUMENT, "BVH too deep for the LDS traversal stack");
+    }
+    const size_t nlights = scene->light_instance.size();
+    std::vector<float4> light_bounds((nlights + 3) / 4 * 4, make_float4(0.0f, 0.0f, 0.0f, -1.0f));
+    for (size_t i = 0; i < nlights; i++)
+    {
+        // the eight corners of the mesh's model box instead of all its vertices: a sphere that contains them contains the mesh
+        const uint32_t ii = scene->light_instance[i];
+        const float *ab = scene->model_aabbs.data() + (size_t)instances[ii].mesh_idx * 6;
+        float corners[8][3];
+        for (int k = 0; k < 8; k++) { corners[k][0] = (k & 4) ? ab[3] : ab[0]; corners[k][1] = (k & 2) ? ab[4] : ab[1]; corners[k][2] = (k & 1) ? ab[5] : ab[2]; }
+        const bool empty_mesh = ab[0] > ab[3];   // Aabb::neutral(): creation never culls such a light either
+        light_bounds[i] = light_bound(inst[ii].transpose_inverse_transform, &corners[0][0], empty_mesh ? 0 : 8, 3);
+    }
+    // the LDS-staged copy of small scenes: records of LP_GEO_LDS_STRIDE words, nodes by global index, then instances
+    std::vector<float4> blob_tlas, blob_inst;
+    if (dv.geo_blob_words)
+    {
+        auto append = [](std::vector<float4> &dst, const void *p, size_t count) {
+            const float4 *f = reinterpret_cast<const float4 *>(p);
+            for (size_t r = 0; r < count; r++)
+            {
+                dst.insert(dst.end(), f + r * 4, f + (r + 1) * 4);
+                dst.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            }
+        };
+        append(blob_tlas, tlas.data(), tlas.size());
+        append(blob_inst, instances.data(), instances.size());
+        const size_t tlas_word = (size_t)dv.geo_off_blas + (size_t)scene->nblas * LP_GEO_LDS_STRIDE;
+        if (tlas_word + blob_tlas.size() > dv.geo_off_tris || (size_t)dv.geo_off_inst + blob_inst.size() > dv.geo_blob_words)
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "staged geometry layout mismatch");
+    }
+
+    // ---- every lane that may still read the scene drains, then the writes ----
+    for (int k = 0; k < LP_MAX_LANES; k++)
+        if (ctx->lanes[k].stream) HIP_TRY(hipStreamSynchronize(ctx->lanes[k].stream));
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(const_cast<InstanceDev *>(dv.instances), instances.data(), instances.size() * sizeof(InstanceDev), hipMemcpyHostToDevice, st));
+    if (!tlas.empty()) HIP_TRY(hipMemcpyAsync(const_cast<WideNode *>(dv.blas) + scene->nblas, tlas.data(), tlas.size() * sizeof(WideNode), hipMemcpyHostToDevice, st));
+    if (nlights) HIP_TRY(hipMemcpyAsync(const_cast<float4 *>(dv.light_bounds), light_bounds.data(), light_bounds.size() * sizeof(float4), hipMemcpyHostToDevice, st));
+    if (dv.geo_blob_words)
+    {
+        float4 *blob = const_cast<float4 *>(dv.geo_blob);
+        if (!blob_tlas.empty()) HIP_TRY(hipMemcpyAsync(blob + dv.geo_off_blas + (size_t)scene->nblas * LP_GEO_LDS_STRIDE, blob_tlas.data(), blob_tlas.size() * sizeof(float4), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(blob + dv.geo_off_inst, blob_inst.data(), blob_inst.size() * sizeof(float4), hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // the staging vectors go out of scope; later calls on any lane see the new scene
+    dv.tlas_root = tlas_root;
+    scene->stack_entries = stack_entries;
+    scene->host_instances.swap(instances);
+    scene->tlas_nodes.swap(nodes);
+    // launch shapes cached per scene depend on the stack size; a captured wavefront holds the old root
+    memset(scene->persistent_blocks, 0, sizeof(scene->persistent_blocks));
+    memset(scene->wide_blocks, 0, sizeof(scene->wide_blocks));
+    memset(scene->short_blocks, 0, sizeof(scene->short_blocks));
+    static std::atomic<uint64_t> next_update_id{1ull << 40};   // disjoint from the ids scene_create hands out
+    scene->id = next_update_id.fetch_add(1);
+    // The four-wide TLAS has no fixed size and is not re-collapsed: refuse the wide tracer for this scene from now on.
+    if (scene->has_wide) { scene->has_wide = false; scene->wide_stale = true; }
+    return LUPIN_OK;
+}
+
+int64_t lupin_hip_scene_get_tlas(const LupinScene *scene, LupinTlasNode *out_nodes, uint64_t capacity)
+{
+    if (!scene) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    const uint64_t count = scene->tlas_nodes.size();
+    if (!out_nodes) return (int64_t)count;
+    if (capacity < count) return fail(LUPIN_ERR_INVALID_ARGUMENT, "node buffer too small");
+    if (count) memcpy(out_nodes, scene->tlas_nodes.data(), count * sizeof(LupinTlasNode));
+    return (int64_t)count;
 }
 
 // ---- textures / double buffering ----
@@ -1608,6 +1780,9 @@ int lupin_hip_dbuf_resize(LupinDoubleBufferedTexture *t, uint32_t width, uint32_
 
 // ---- the hot path ----
 
+static const char *const kWideStale = "lupin_hip_scene_update_instances moved this scene's instances and its four-wide hierarchy was not rebuilt: "
+                                      "use the binary traversal or create the scene anew";
+
 static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res, const LupinScene *scene,
                           LupinTexture *render_target, uint32_t pathtrace_type, const LupinPathtraceDesc *desc,
                           bool tile_set, uint32_t set_tile_size, uint32_t rank, uint32_t world, int falsecolor_type = -1,
@@ -1619,6 +1794,7 @@ static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res,
     if (falsecolor_type > 11) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown falsecolor_type");
     if (debug && debug->viz_type > LUPIN_DEBUG_VIZ_NUM_BOUNCES) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown viz_type");
     if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");   // renderer.rs:774-777
+    if (scene->wide_stale && ctx->wide_traversal) return fail(LUPIN_ERR_INVALID_ARGUMENT, kWideStale);
     const uint32_t W = render_target->width, H = render_target->height;
     const LupinTexture *prev = desc->accum_params ? desc->accum_params->prev_frame : nullptr;
     if (prev && prev == render_target) return fail(LUPIN_ERR_SAME_TARGET, "render_target must differ from accum_params.prev_frame");
@@ -2153,6 +2329,7 @@ static int trace_rays_impl(LupinContext *ctx, const LupinScene *scene, uint32_t 
 {
     CTX_ALIVE_TRY(ctx);
     if (!ctx || !scene || !ori_xyz || !dir_xyz || !out_hit || !out_dst || !out_uv || !out_instance || !out_tri) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (out_flag && scene->wide_stale) return fail(LUPIN_ERR_INVALID_ARGUMENT, kWideStale);
     if (out_flag && !scene->has_wide) return fail(LUPIN_ERR_INVALID_ARGUMENT, "this scene has no four-wide hierarchy (it is small enough to be staged in LDS)");
     if (n == 0) return LUPIN_OK;
     HIP_TRY(hipSetDevice(ctx->device));

@@ -22,3 +22,8 @@ void lupin_internal_join_primary(LupinContext *ctx);         // primary stream w
 int lupin_internal_sync_all(LupinContext *ctx);              // host waits for every lane
 int lupin_internal_tiles_copy(LupinContext *ctx, const LupinTexture *tex, void *packed, uint32_t tile_size, uint32_t rank, uint32_t world,
                               uint64_t capacity_px, int mode);   // k_tiles_copy on the primary stream
+// the two ends of build_tlas that lupin_build_tlas and the device builder share (builders.cpp)
+int lupin_internal_tlas_leaves(const LupinInstance *instances, uint32_t num_instances, const float *model_aabbs, uint32_t num_meshes,
+                               LupinTlasNode *out_leaves);   // LUPIN_OK | LUPIN_ERR_INVALID_ARGUMENT (mesh_idx out of range)
+bool lupin_internal_tlas_leaves_finite(const LupinInstance *instances, const LupinTlasNode *leaves, uint32_t num_instances);   // transforms and world boxes
+void lupin_internal_tlas_finish(LupinTlasNode *tlas, uint32_t len);   // reversal + child remap
