@@ -671,6 +671,30 @@ typedef enum LupinScatterMode
 } LupinScatterMode;
 int lupin_hip_scatter_probe(LupinContext *ctx, uint32_t n, const float *records, float *out);
 
+/* Light-sampling probe: sample_lights (pathtracer.wgsl:2468-2514) and sample_lights_pdf (:2516-2549 with
+ * compute_instance_lights_pdf, bvh_custom.wgsl:112-152) of the device over n host records on `scene`, through the
+ * geometry accessor the scene's kernels use (staged in LDS, or global memory).  Host arrays in and out; synchronous;
+ * calls recorded on the context run first.  The tests require the result to be bit-identical to oracle_light_probe.
+ *
+ * Input record, LUPIN_LIGHT_IN_FLOATS floats:
+ *   [0] mode (LupinLightMode, as a float)  [1..3] pos  [4..6] incoming  [7] ray epsilon
+ *   [8] RNG state: the u32's bits stored in the float's place (not a float value)   [9..11] unused
+ * Output record, LUPIN_LIGHT_OUT_FLOATS floats:
+ *   [0..2] direction  [3] pdf  [4] RNG state afterwards (bits, as in the input)  [5..7] 0.
+ * Modes:
+ *   SAMPLE  direction = sample_lights(pos) drawn from the record's RNG state; pdf = sample_lights_pdf(pos, direction)
+ *   PDF     pdf = sample_lights_pdf(pos, incoming) at the given incoming, which need not have unit length;
+ *           direction = incoming, RNG state unchanged
+ * Any other mode writes a zero direction and pdf and returns the RNG state unchanged. */
+#define LUPIN_LIGHT_IN_FLOATS 12
+#define LUPIN_LIGHT_OUT_FLOATS 8
+typedef enum LupinLightMode
+{
+    LUPIN_LIGHT_SAMPLE = 0,
+    LUPIN_LIGHT_PDF = 1
+} LupinLightMode;
+int lupin_hip_light_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n, const float *records, float *out);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

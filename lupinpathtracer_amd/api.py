@@ -1145,3 +1145,38 @@ def scatter_probe(ctx, records):
     out = np.zeros((len(rec), SCATTER_OUT_FLOATS), np.float32)
     check(lib().lupin_hip_scatter_probe(ctx.handle, len(rec), ptr(rec), ptr(out)))
     return out
+
+
+# lupin_hip_light_probe record layout (include/lupin_hip.h)
+LIGHT_IN_FLOATS = 12
+LIGHT_OUT_FLOATS = 8
+
+
+class LightMode(enum.IntEnum):
+    SAMPLE = 0
+    PDF = 1
+
+
+def light_records(mode, pos, incoming=None, ray_epsilon=0.001, rng=0):
+    """(n, LIGHT_IN_FLOATS) float32 records for light_probe / oracle.light_probe: `pos` (n, 3), `incoming` (n, 3) or None,
+    `ray_epsilon` and `rng` (u32 states, stored as bits) scalars or (n,) arrays."""
+    pos = np.asarray(pos, np.float32).reshape(-1, 3)
+    rec = np.zeros((len(pos), LIGHT_IN_FLOATS), np.float32)
+    rec[:, 0] = np.float32(int(mode))
+    rec[:, 1:4] = pos
+    if incoming is not None:
+        rec[:, 4:7] = np.asarray(incoming, np.float32).reshape(-1, 3)
+    rec[:, 7] = np.asarray(ray_epsilon, np.float32)
+    rec.view(np.uint32)[:, 8] = np.asarray(rng, np.uint32)
+    return rec
+
+
+def light_probe(ctx, scene, records):
+    """sample_lights / sample_lights_pdf of the device on `scene` over (n, LIGHT_IN_FLOATS) float32 records; returns the
+    (n, LIGHT_OUT_FLOATS) float32 outputs: direction, pdf, RNG state afterwards (bits; read it with .view(np.uint32)), 0."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "light_probe needs a GPU context and an uploaded scene; there is no CPU fallback")
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, LIGHT_IN_FLOATS)
+    out = np.zeros((len(rec), LIGHT_OUT_FLOATS), np.float32)
+    check(lib().lupin_hip_light_probe(ctx.handle, scene.handle, len(rec), ptr(rec), ptr(out)))
+    return out

@@ -2432,6 +2432,38 @@ int lupin_hip_scatter_probe(LupinContext *ctx, uint32_t n, const float *records,
     return LUPIN_OK;
 }
 
+int lupin_hip_light_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n, const float *records, float *out)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !scene || !records || !out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context");
+    if (n == 0) return LUPIN_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t stack_words = scene->stack_entries * LP_BLOCK;
+    const bool lds_geo = scene->dev.geo_blob_words && ctx->lds_geometry;
+    const size_t lds = (size_t)stack_words * sizeof(uint32_t) + (lds_geo ? (size_t)scene->dev.geo_blob_words * 16 : 0);
+    if (lds > 160 * 1024) return fail(LUPIN_ERR_INVALID_ARGUMENT, "BVH too deep for the LDS traversal stack");
+    join_primary(ctx);   // recorded calls run first
+    const size_t in_bytes = (size_t)n * LUPIN_LIGHT_IN_FLOATS * 4, out_bytes = (size_t)n * LUPIN_LIGHT_OUT_FLOATS * 4;
+    float *din = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc((void **)&din, in_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&dout, out_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(din, records, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+    {
+        const dim3 grid((n + LP_BLOCK - 1) / LP_BLOCK), block(LP_BLOCK);
+        if (lds_geo) hipLaunchKernelGGL(k_light_probe<true>, grid, block, lds, ctx->stream, scene->dev, n, din, dout, stack_words);
+        else hipLaunchKernelGGL(k_light_probe<false>, grid, block, lds, ctx->stream, scene->dev, n, din, dout, stack_words);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    // freed on every path (hipFree(nullptr) is a no-op)
+    hipFree(din); hipFree(dout);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("lupin_hip_light_probe: ") + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
 static int pack_common(LupinContext *ctx, const LupinTexture *tex, uint32_t tile_size, uint32_t rank, uint32_t world, void *packed, int unpack)
 {
     if (!ctx || !tex || !packed || tile_size == 0 || world == 0 || rank >= world) return fail(LUPIN_ERR_INVALID_ARGUMENT, "bad pack arguments");

@@ -2186,6 +2186,36 @@ __global__ void __launch_bounds__(LP_BLOCK) k_scatter_probe(uint32_t n, const fl
     o[6] = pdf; o[7] = 0.0f;
 }
 
+// lights_sample / lights_pdf of lupin_device.hpp over a batch of records (layout and modes: lupin_hip_light_probe in
+// include/lupin_hip.h): the force-inlined functions the shade and light-pdf kernels call, through either geometry
+// accessor, with the traversal stack in LDS.  Whole blocks run (make_geo<true> has a barrier); lanes past n do nothing.
+template <bool LDSGEO>
+__global__ void __launch_bounds__(LP_BLOCK) k_light_probe(SceneDev sc, uint32_t n, const float *in, float *out, uint32_t stack_words)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const auto geo = make_geo<LDSGEO>(sc, lds_stack, stack_words);
+    const uint32_t i = blockIdx.x * LP_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float *r = in + (size_t)i * LUPIN_LIGHT_IN_FLOATS;
+    const uint32_t mode = (uint32_t)r[0];
+    const f3 pos = mk3(r[1], r[2], r[3]);
+    f3 dir = mk3(r[4], r[5], r[6]);
+    const float eps = r[7];
+    uint32_t rng = __float_as_uint(r[8]);
+    float pdf = 0.0f;
+    if (mode == LUPIN_LIGHT_SAMPLE)
+    {
+        dir = lights_sample(sc, pos, rng);
+        pdf = lights_pdf(geo, sc, lds_stack, pos, dir, eps);
+    }
+    else if (mode == LUPIN_LIGHT_PDF) pdf = lights_pdf(geo, sc, lds_stack, pos, dir, eps);
+    else dir = splat(0.0f);
+    float *o = out + (size_t)i * LUPIN_LIGHT_OUT_FLOATS;
+    o[0] = dir.x; o[1] = dir.y; o[2] = dir.z;
+    o[3] = pdf; o[4] = __uint_as_float(rng);
+    o[5] = 0.0f; o[6] = 0.0f; o[7] = 0.0f;
+}
+
 // Tile pack / unpack for the multi-GPU gather.  Payload of a rank = its tiles in ascending order (include/lupin_tiles.h),
 // each tile row-major, 8 B per pixel.  One block per tile: the block first sums the pixel counts of the owner's earlier
 // tiles (a few hundred terms at most, strided over the threads), then copies the tile's rows.

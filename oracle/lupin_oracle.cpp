@@ -2498,6 +2498,41 @@ int oracle_scatter_probe(uint32_t n, const float *records, float *out)
     return 0;
 }
 
+// Batched light-sampling probe: the record layout and modes of lupin_hip_light_probe (include/lupin_hip.h), evaluated
+// with Inv::sample_lights and Inv::sample_lights_pdf.  `flags` carries the push constants' *_EMPTY bits.  The device probe
+// must match it bit for bit, the RNG state included.
+int oracle_light_probe(const LupinSceneDesc *scene, uint32_t flags, uint32_t n, const float *records, float *out)
+{
+    if (!scene || !records || !out) return -1;
+    #pragma omp parallel for schedule(dynamic, 256)
+    for (int64_t i = 0; i < (int64_t)n; i++)
+    {
+        const float *r = records + (size_t)i * LUPIN_LIGHT_IN_FLOATS;
+        Inv inv;
+        inv.s = scene; memset(&inv.constants, 0, sizeof(inv.constants));
+        inv.constants.ray_epsilon = r[7]; inv.constants.flags = flags;
+        inv.MAX_BOUNCES = 0; inv.SAMPLES_PER_PIXEL = 0;
+        memcpy(&inv.RNG_STATE, &r[8], 4);
+        const uint32_t mode = (uint32_t)r[0];
+        const vec3f pos = {r[1], r[2], r[3]};
+        vec3f dir = {r[4], r[5], r[6]};
+        float pdf = 0.0f;
+        if (mode == LUPIN_LIGHT_SAMPLE)
+        {
+            dir = inv.sample_lights(pos, v3(0.0f));
+            pdf = inv.sample_lights_pdf(pos, dir);
+        }
+        else if (mode == LUPIN_LIGHT_PDF) pdf = inv.sample_lights_pdf(pos, dir);
+        else dir = v3(0.0f);
+        float *w = out + (size_t)i * LUPIN_LIGHT_OUT_FLOATS;
+        w[0] = dir.x; w[1] = dir.y; w[2] = dir.z;
+        w[3] = pdf;
+        memcpy(&w[4], &inv.RNG_STATE, 4);
+        w[5] = 0.0f; w[6] = 0.0f; w[7] = 0.0f;
+    }
+    return 0;
+}
+
 // tonemap_and_fit_aspect (tonemapping.rs:155-224 + tonemapping.wgsl) evaluated at target pixel centres: viewport /
 // scissor (:163-167,:216-217), aspect-fit scale of the quad (:168-174), vertex positions pos * scale with tex coords
 // 0..1 (wgsl:24-48), fragment: clamp-to-edge linear sample, max(.,0), * exp2(exposure), tonemap_filmic,

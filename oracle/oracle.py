@@ -52,6 +52,8 @@ def lib():
                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         h.oracle_scatter_probe.restype = C.c_int
         h.oracle_scatter_probe.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
+        h.oracle_light_probe.restype = C.c_int
+        h.oracle_light_probe.argtypes = [C.POINTER(_abi.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         h.oracle_float_to_half.restype = C.c_uint16
         h.oracle_float_to_half.argtypes = [C.c_float]
         h.oracle_float_to_half_rtz.restype = C.c_uint16
@@ -188,6 +190,17 @@ def scatter_probe(records):
     out = np.zeros((len(rec), 8), np.float32)
     if lib().oracle_scatter_probe(len(rec), _abi.ptr(rec), _abi.ptr(out)) != 0:
         raise RuntimeError("oracle_scatter_probe failed")
+    return out
+
+
+def light_probe(scene, records):
+    """oracle_light_probe on `scene` over (n, 12) float32 records (layout of lupin_hip_light_probe, include/lupin_hip.h);
+    returns the (n, 8) float32 outputs: direction, pdf, RNG state afterwards (bits), 0."""
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, 12)
+    out = np.zeros((len(rec), 8), np.float32)
+    flags = scene_flags(scene, CameraParams())   # the *_EMPTY flags of the push constants
+    if lib().oracle_light_probe(C.byref(scene.desc), flags, len(rec), _abi.ptr(rec), _abi.ptr(out)) != 0:
+        raise RuntimeError("oracle_light_probe failed")
     return out
 
 
