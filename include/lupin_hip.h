@@ -695,6 +695,44 @@ typedef enum LupinLightMode
 } LupinLightMode;
 int lupin_hip_light_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n, const float *records, float *out);
 
+/* Surface probe: what runs between a hit and the scattering functions -- sample_texture (pathtracer.wgsl:1413-1416 with
+ * the linear / Repeat sampler of wgpu_utils.rs:244-256), get_material_point (:1265-1342) with vec3f_srgb_to_linear (:2729)
+ * and get_vert_color (:1757-1770), compute_shading_normal (:1344-1384) with get_vert_normal (:1730-1755) and
+ * compute_tangents_from_uv (:1699-1727), compute_tri_geom_normal (:2561-2576), sample_environments (:1386-1410) with
+ * dir_to_env_uv (:2579-2587) -- of the device over n host records on `scene`, through the geometry accessor the scene's
+ * kernels use (staged in LDS, or global memory).  Host arrays in and out; synchronous; calls recorded on the context run
+ * first.  The tests require the result to be bit-identical to oracle_surface_probe.
+ *
+ * Input record, LUPIN_SURFACE_IN_FLOATS floats ("bits": the u32's bits stored in the float's place, not a float value):
+ *   [0] mode (LupinSurfaceMode, as a float)
+ *   [1] instance index (bits), in TEXTURE mode the texture index (bits)
+ *   [2] triangle index within the instance's mesh (bits): the numbering lupin_hip_trace_rays returns
+ *   [3..4] barycentric u, v of the hit (weights: 1 - u - v, u, v), in TEXTURE mode the texture coordinates u, v
+ *   [5..7] direction (ENVIRONMENT mode; it need not have unit length)
+ * Output record, LUPIN_SURFACE_OUT_FLOATS floats; what a mode does not name is 0:
+ *   TEXTURE          [0..3] sample_texture(texture, (u, v)) rgba, as sampled (no sRGB decode)
+ *   MATERIAL         get_material_point: [0] mat_type (bits)  [1..3] emission  [4..6] color  [7] opacity  [8] roughness
+ *                    [9] metallic  [10] ior  [11..13] density  [14..16] scattering  [17] sc_anisotropy
+ *   MATERIAL_SIMPLE  the same layout from the specialisation the shade kernel uses on a scene of untextured matte
+ *                    materials without vertex colours or environments; any other scene: LUPIN_ERR_INVALID_ARGUMENT
+ *   OPACITY          [0] the material point's opacity as the tracer's alpha test computes it on its own
+ *   NORMAL           [0..2] compute_shading_normal  [3..5] compute_tri_geom_normal
+ *   ENVIRONMENT      [0..2] sample_environments(direction)  [3..4] dir_to_env_uv(direction, 0) (0 without environments)
+ * Any other mode writes zeros.  An instance, triangle or texture index outside the scene fails the whole call with
+ * LUPIN_ERR_INVALID_ARGUMENT before anything is launched. */
+#define LUPIN_SURFACE_IN_FLOATS 8
+#define LUPIN_SURFACE_OUT_FLOATS 20
+typedef enum LupinSurfaceMode
+{
+    LUPIN_SURFACE_TEXTURE = 0,
+    LUPIN_SURFACE_MATERIAL = 1,
+    LUPIN_SURFACE_MATERIAL_SIMPLE = 2,
+    LUPIN_SURFACE_OPACITY = 3,
+    LUPIN_SURFACE_NORMAL = 4,
+    LUPIN_SURFACE_ENVIRONMENT = 5
+} LupinSurfaceMode;
+int lupin_hip_surface_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n, const float *records, float *out);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

@@ -213,6 +213,7 @@ SYMBOLS = [
     ("lupin_hip_detmath_probe", C.c_int, [_P, C.c_int, _U32, _P, _P, _P]),
     ("lupin_hip_scatter_probe", C.c_int, [_P, _U32, _P, _P]),
     ("lupin_hip_light_probe", C.c_int, [_P, _P, _U32, _P, _P]),
+    ("lupin_hip_surface_probe", C.c_int, [_P, _P, _U32, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),

@@ -1180,3 +1180,48 @@ def light_probe(ctx, scene, records):
     out = np.zeros((len(rec), LIGHT_OUT_FLOATS), np.float32)
     check(lib().lupin_hip_light_probe(ctx.handle, scene.handle, len(rec), ptr(rec), ptr(out)))
     return out
+
+
+# lupin_hip_surface_probe record layout (include/lupin_hip.h)
+SURFACE_IN_FLOATS = 8
+SURFACE_OUT_FLOATS = 20
+
+
+class SurfaceMode(enum.IntEnum):
+    TEXTURE = 0
+    MATERIAL = 1
+    MATERIAL_SIMPLE = 2
+    OPACITY = 3
+    NORMAL = 4
+    ENVIRONMENT = 5
+
+
+def surface_records(mode, index=0, tri=0, uv=None, direction=None, n=None):
+    """(n, SURFACE_IN_FLOATS) float32 records for surface_probe / oracle.surface_probe.  `mode` a SurfaceMode or (n,) array
+    of them; `index` the instance (TEXTURE mode: the texture) and `tri` the triangle within its mesh, as trace_rays returns
+    them (u32, stored as bits); `uv` (n, 2) the hit's barycentrics (TEXTURE mode: the texture coordinates); `direction`
+    (n, 3) for ENVIRONMENT mode."""
+    for a in (uv, direction, mode, index, tri):
+        if n is None and a is not None and np.ndim(a) > 0:
+            n = len(a)
+    rec = np.zeros((n or 1, SURFACE_IN_FLOATS), np.float32)
+    rec[:, 0] = np.asarray(mode, np.float32)
+    rec.view(np.uint32)[:, 1] = np.asarray(index, np.uint32)
+    rec.view(np.uint32)[:, 2] = np.asarray(tri, np.uint32)
+    if uv is not None:
+        rec[:, 3:5] = np.asarray(uv, np.float32).reshape(-1, 2)
+    if direction is not None:
+        rec[:, 5:8] = np.asarray(direction, np.float32).reshape(-1, 3)
+    return rec
+
+
+def surface_probe(ctx, scene, records):
+    """sample_texture / material point / opacity / shading and geometric normal / environment radiance of the device on
+    `scene` over (n, SURFACE_IN_FLOATS) float32 records; returns the (n, SURFACE_OUT_FLOATS) float32 outputs (layout per
+    mode: include/lupin_hip.h; the material type is stored as bits: read it with .view(np.uint32))."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "surface_probe needs a GPU context and an uploaded scene; there is no CPU fallback")
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, SURFACE_IN_FLOATS)
+    out = np.zeros((len(rec), SURFACE_OUT_FLOATS), np.float32)
+    check(lib().lupin_hip_surface_probe(ctx.handle, scene.handle, len(rec), ptr(rec), ptr(out)))
+    return out

@@ -161,6 +161,8 @@ struct LupinScene
     std::vector<float> model_aabbs;                 // per mesh: f32 min xyz, max xyz of verts_pos (Aabb::neutral() for an empty mesh)
     std::vector<InstanceDev> host_instances;        // as uploaded (mesh_idx, mat_idx, blas_root and flags never change)
     std::vector<uint32_t> light_instance;           // light -> instance
+    std::vector<uint32_t> mesh_tri_count;           // per mesh; with num_textures what lupin_hip_surface_probe checks a record's indices against
+    uint32_t num_textures = 0;
     std::vector<LupinTlasNode> tlas_nodes;          // the TLAS in lupin_build_tlas' format (lupin_hip_scene_get_tlas)
     uint32_t nblas = 0, ntlas = 0;                  // the one node array is [nblas BLAS nodes | ntlas TLAS nodes]
     uint32_t max_blas_depth = 0;
@@ -1287,6 +1289,7 @@ int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinS
         }
 
         uint32_t ntris = m.num_indices / 3;
+        sc->mesh_tri_count.push_back(ntris);
         for (uint32_t i = 0; i < ntris * 3; i++)
             if (m.indices[i] >= m.num_verts) { lupin_hip_scene_destroy(sc); return fail(LUPIN_ERR_INVALID_ARGUMENT, "vertex index out of range"); }
         for (uint32_t t = 0; t < ntris; t++)
@@ -1404,6 +1407,7 @@ int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinS
     // ---- textures ----
     std::vector<TextureDev> textures(s.num_textures);
     std::vector<uint8_t> texels;
+    sc->num_textures = s.num_textures;
     for (uint32_t i = 0; i < s.num_textures; i++)
     {
         const LupinTextureDesc &t = s.textures[i];
@@ -2461,6 +2465,55 @@ int lupin_hip_light_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n
     // freed on every path (hipFree(nullptr) is a no-op)
     hipFree(din); hipFree(dout);
     if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("lupin_hip_light_probe: ") + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+int lupin_hip_surface_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n, const float *records, float *out)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !scene || !records || !out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context");
+    if (n == 0) return LUPIN_OK;
+    // every index a record names is checked here: the kernel dereferences them as they are
+    for (uint32_t i = 0; i < n; i++)
+    {
+        const float *r = records + (size_t)i * LUPIN_SURFACE_IN_FLOATS;
+        const uint32_t mode = surface_probe_mode(r[0]);
+        uint32_t a, tri;
+        memcpy(&a, &r[1], 4); memcpy(&tri, &r[2], 4);
+        if (mode == LUPIN_SURFACE_TEXTURE)
+        {
+            if (a >= scene->num_textures) return fail(LUPIN_ERR_INVALID_ARGUMENT, "lupin_hip_surface_probe: texture index out of range");
+        }
+        else if (mode >= LUPIN_SURFACE_MATERIAL && mode <= LUPIN_SURFACE_NORMAL)
+        {
+            if (a >= scene->host_instances.size()) return fail(LUPIN_ERR_INVALID_ARGUMENT, "lupin_hip_surface_probe: instance index out of range");
+            if (tri >= scene->mesh_tri_count[scene->host_instances[a].mesh_idx]) return fail(LUPIN_ERR_INVALID_ARGUMENT, "lupin_hip_surface_probe: triangle index out of range");
+            if (mode == LUPIN_SURFACE_MATERIAL_SIMPLE && !scene->simple_matte)
+                return fail(LUPIN_ERR_INVALID_ARGUMENT, "lupin_hip_surface_probe: MATERIAL_SIMPLE on a scene that is not one of untextured matte materials");
+        }
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const bool lds_geo = scene->dev.geo_blob_words && ctx->lds_geometry;
+    const size_t lds = lds_geo ? (size_t)scene->dev.geo_blob_words * 16 : 0;
+    join_primary(ctx);   // recorded calls run first
+    const size_t in_bytes = (size_t)n * LUPIN_SURFACE_IN_FLOATS * 4, out_bytes = (size_t)n * LUPIN_SURFACE_OUT_FLOATS * 4;
+    float *din = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc((void **)&din, in_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&dout, out_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(din, records, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+    {
+        const dim3 grid((n + LP_BLOCK - 1) / LP_BLOCK), block(LP_BLOCK);
+        if (lds_geo) hipLaunchKernelGGL(k_surface_probe<true>, grid, block, lds, ctx->stream, scene->dev, n, din, dout);
+        else hipLaunchKernelGGL(k_surface_probe<false>, grid, block, lds, ctx->stream, scene->dev, n, din, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    // freed on every path (hipFree(nullptr) is a no-op)
+    hipFree(din); hipFree(dout);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("lupin_hip_surface_probe: ") + hipGetErrorString(e));
     return LUPIN_OK;
 }
 

@@ -2216,6 +2216,66 @@ __global__ void __launch_bounds__(LP_BLOCK) k_light_probe(SceneDev sc, uint32_t 
     o[5] = 0.0f; o[6] = 0.0f; o[7] = 0.0f;
 }
 
+// The mode of a surface-probe record: host validation and kernel read it with this one expression (NaN, negative and
+// large values are "no mode": zeros are written)
+__host__ __device__ inline uint32_t surface_probe_mode(float m) { return (m >= 0.0f && m < 6.0f) ? (uint32_t)m : 0xFFFFFFFFu; }
+
+// sample_texture, material_point<false / true>, surface_opacity, shading_normal, geometric_normal and environment_radiance
+// of lupin_device.hpp over a batch of records (layout and modes: lupin_hip_surface_probe in include/lupin_hip.h): the
+// force-inlined functions the tracer and the shade kernels call, through either geometry accessor.  The host has checked
+// every index against the scene.  Whole blocks run (make_geo<true> has a barrier); lanes past n do nothing.
+template <bool LDSGEO>
+__global__ void __launch_bounds__(LP_BLOCK) k_surface_probe(SceneDev sc, uint32_t n, const float *in, float *out)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const auto geo = make_geo<LDSGEO>(sc, lds_stack, 0u);
+    const uint32_t i = blockIdx.x * LP_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float *r = in + (size_t)i * LUPIN_SURFACE_IN_FLOATS;
+    const uint32_t mode = surface_probe_mode(r[0]);
+    float o[LUPIN_SURFACE_OUT_FLOATS];
+    #pragma unroll
+    for (int k = 0; k < LUPIN_SURFACE_OUT_FLOATS; k++) o[k] = 0.0f;
+    if (mode == LUPIN_SURFACE_TEXTURE)
+    {
+        const float4 t = sample_texture(sc, __float_as_uint(r[1]), r[3], r[4]);
+        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+    }
+    else if (mode == LUPIN_SURFACE_ENVIRONMENT)
+    {
+        const f3 dir = mk3(r[5], r[6], r[7]);
+        const f3 e = environment_radiance(sc, dir);
+        o[0] = e.x; o[1] = e.y; o[2] = e.z;
+        if (sc.num_envs > 0) dir_to_env_uv(sc.environments[0], dir, o[3], o[4]);
+    }
+    else if (mode <= LUPIN_SURFACE_NORMAL)
+    {
+        const uint32_t inst = __float_as_uint(r[1]);
+        const uint32_t gtri = sc.inst_meshes[inst].tri_offset + __float_as_uint(r[2]);
+        const Surface s = resolve_surface(sc, inst, gtri, r[3], r[4]);
+        if (mode == LUPIN_SURFACE_OPACITY) o[0] = surface_opacity(sc, s);
+        else if (mode == LUPIN_SURFACE_NORMAL)
+        {
+            const f3 ns = shading_normal(geo, sc, s), ng = geometric_normal(geo, s.in, s.gtri);
+            o[0] = ns.x; o[1] = ns.y; o[2] = ns.z; o[3] = ng.x; o[4] = ng.y; o[5] = ng.z;
+        }
+        else
+        {
+            const MatPoint m = mode == LUPIN_SURFACE_MATERIAL ? material_point<false>(sc, s) : material_point<true>(sc, s);
+            o[0] = __uint_as_float(m.type);
+            o[1] = m.emission.x; o[2] = m.emission.y; o[3] = m.emission.z;
+            o[4] = m.color.x; o[5] = m.color.y; o[6] = m.color.z;
+            o[7] = m.opacity; o[8] = m.roughness; o[9] = m.metallic; o[10] = m.ior;
+            o[11] = m.density.x; o[12] = m.density.y; o[13] = m.density.z;
+            o[14] = m.scattering.x; o[15] = m.scattering.y; o[16] = m.scattering.z;
+            o[17] = m.anisotropy;
+        }
+    }
+    float *w = out + (size_t)i * LUPIN_SURFACE_OUT_FLOATS;
+    #pragma unroll
+    for (int k = 0; k < LUPIN_SURFACE_OUT_FLOATS; k++) w[k] = o[k];
+}
+
 // Tile pack / unpack for the multi-GPU gather.  Payload of a rank = its tiles in ascending order (include/lupin_tiles.h),
 // each tile row-major, 8 B per pixel.  One block per tile: the block first sums the pixel counts of the owner's earlier
 // tiles (a few hundred terms at most, strided over the threads), then copies the tile's rows.

@@ -2399,6 +2399,29 @@ int oracle_trace_rays(const LupinSceneDesc *scene, uint32_t n, const float *ori_
     return 0;
 }
 
+// The first camera ray of every pixel of a width x height frame, as pathtrace_main / pathtrace_falsecolor_main generate it
+// (init_rng, random_vec2f for the pixel offset, compute_camera_ray; pathtracer.wgsl:296-310): origin and direction, 3 floats
+// each per pixel, row-major.  Tests feed them to the closest-hit probes to recover the primary hits of a one-sample frame.
+int oracle_camera_rays(const LupinPushConstants *constants, uint32_t width, uint32_t height, float *out_ori, float *out_dir)
+{
+    if (!constants || !out_ori || !out_dir) return -1;
+    for (uint32_t gy = 0; gy < height; gy++)
+        for (uint32_t gx = 0; gx < width; gx++)
+        {
+            Inv inv;
+            inv.s = nullptr; inv.constants = *constants;
+            inv.MAX_BOUNCES = 0; inv.SAMPLES_PER_PIXEL = 1;
+            inv.init_rng(gy * width + gx);
+            vec2f ro = inv.random_vec2f();
+            vec2f pixel_offset = {ro.x - 0.5f, ro.y - 0.5f};
+            Ray r = inv.compute_camera_ray(gx, gy, width, height, pixel_offset);
+            const size_t o = ((size_t)gy * width + gx) * 3;
+            out_ori[o] = r.ori.x; out_ori[o + 1] = r.ori.y; out_ori[o + 2] = r.ori.z;
+            out_dir[o] = r.dir.x; out_dir[o + 1] = r.dir.y; out_dir[o + 2] = r.dir.z;
+        }
+    return 0;
+}
+
 // RNG stream probe: first `count` random_f32() outputs for (pixel linear index, accum_counter)
 // (pathtracer.wgsl:1563-1600).
 void oracle_rng_stream(uint32_t global_id, uint32_t accum_counter, uint32_t count, float *out)
@@ -2529,6 +2552,110 @@ int oracle_light_probe(const LupinSceneDesc *scene, uint32_t flags, uint32_t n, 
         w[3] = pdf;
         memcpy(&w[4], &inv.RNG_STATE, 4);
         w[5] = 0.0f; w[6] = 0.0f; w[7] = 0.0f;
+    }
+    return 0;
+}
+
+// Batched surface probe: the record layout and modes of lupin_hip_surface_probe (include/lupin_hip.h), evaluated with
+// Inv::sample_texture, get_material_point, compute_shading_normal, compute_tri_geom_normal, sample_environments and
+// dir_to_env_uv.  Returns -1 for a null argument, -2 for an index outside the scene, -3 for MATERIAL_SIMPLE on a scene
+// that is not one of untextured matte materials without vertex colours or environments; nothing is written then.
+// The device probe must match it bit for bit.
+static uint32_t surface_mode(float m) { return (m >= 0.0f && m < 6.0f) ? (uint32_t)m : 0xFFFFFFFFu; }
+int oracle_surface_probe(const LupinSceneDesc *scene, uint32_t flags, uint32_t n, const float *records, float *out)
+{
+    if (!scene || !records || !out) return -1;
+    bool simple = scene->num_instances > 0 && scene->num_environments == 0 && scene->num_color_buffers == 0;
+    for (uint32_t i = 0; i < scene->num_instances && simple; i++)
+    {
+        const LupinMaterial &mat = scene->materials[scene->instances[i].mat_idx];
+        simple = mat.mat_type == LUPIN_MAT_MATTE && mat.color_tex_idx == SENTINEL_IDX && mat.emission_tex_idx == SENTINEL_IDX &&
+                 mat.roughness_tex_idx == SENTINEL_IDX && mat.scattering_tex_idx == SENTINEL_IDX && mat.normal_tex_idx == SENTINEL_IDX;
+    }
+    for (uint32_t i = 0; i < n; i++)
+    {
+        const float *r = records + (size_t)i * LUPIN_SURFACE_IN_FLOATS;
+        const uint32_t mode = surface_mode(r[0]), a = bits(r[1]), tri = bits(r[2]);
+        if (mode == LUPIN_SURFACE_TEXTURE) { if (a >= scene->num_textures) return -2; }
+        else if (mode >= LUPIN_SURFACE_MATERIAL && mode <= LUPIN_SURFACE_NORMAL)
+        {
+            if (a >= scene->num_instances || tri >= scene->meshes[scene->instances[a].mesh_idx].num_indices / 3) return -2;
+            if (mode == LUPIN_SURFACE_MATERIAL_SIMPLE && !simple) return -3;
+        }
+    }
+    #pragma omp parallel for schedule(static, 4096)
+    for (int64_t i = 0; i < (int64_t)n; i++)
+    {
+        const float *r = records + (size_t)i * LUPIN_SURFACE_IN_FLOATS;
+        float *w = out + (size_t)i * LUPIN_SURFACE_OUT_FLOATS;
+        for (int k = 0; k < LUPIN_SURFACE_OUT_FLOATS; k++) w[k] = 0.0f;
+        Inv inv;
+        inv.s = scene; memset(&inv.constants, 0, sizeof(inv.constants));
+        inv.constants.flags = flags;
+        inv.MAX_BOUNCES = 0; inv.SAMPLES_PER_PIXEL = 0;
+        const uint32_t mode = surface_mode(r[0]);
+        HitInfo hit;
+        hit.hit = true; hit.instance_idx = bits(r[1]); hit.tri_idx = bits(r[2]); hit.uv = {r[3], r[4]};
+        switch (mode)
+        {
+            case LUPIN_SURFACE_TEXTURE:
+            {
+                const vec4f t = inv.sample_texture(bits(r[1]), {r[3], r[4]});
+                w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+                break;
+            }
+            case LUPIN_SURFACE_MATERIAL:
+            case LUPIN_SURFACE_MATERIAL_SIMPLE:
+            {
+                MaterialPoint m;
+                if (mode == LUPIN_SURFACE_MATERIAL) m = inv.get_material_point(hit);
+                else
+                {
+                    // get_material_point with what such a scene makes constant: every sample and the vertex colour are 1,
+                    // the type is matte (no density; roughness clamped up)
+                    const LupinMaterial &mat = scene->materials[scene->instances[hit.instance_idx].mat_idx];
+                    m.mat_type = LUPIN_MAT_MATTE;
+                    m.color = v3(1.0f) * v3(mat.color[0], mat.color[1], mat.color[2]) * v3(1.0f);
+                    m.opacity = 1.0f * mat.color[3] * 1.0f;
+                    m.emission = v3(1.0f) * v3(mat.emission[0], mat.emission[1], mat.emission[2]);
+                    m.roughness = 1.0f * mat.roughness;
+                    m.roughness *= m.roughness;
+                    m.roughness = clamp_(m.roughness, MIN_ROUGHNESS, 1.0f);
+                    m.density = v3(0.0f);
+                    m.ior = mat.ior;
+                    m.scattering = v3(1.0f) * v3(mat.scattering[0], mat.scattering[1], mat.scattering[2]);
+                    m.sc_anisotropy = mat.sc_anisotropy;
+                    m.metallic = 1.0f * mat.metallic;
+                }
+                memcpy(&w[0], &m.mat_type, 4);
+                w[1] = m.emission.x; w[2] = m.emission.y; w[3] = m.emission.z;
+                w[4] = m.color.x; w[5] = m.color.y; w[6] = m.color.z;
+                w[7] = m.opacity; w[8] = m.roughness; w[9] = m.metallic; w[10] = m.ior;
+                w[11] = m.density.x; w[12] = m.density.y; w[13] = m.density.z;
+                w[14] = m.scattering.x; w[15] = m.scattering.y; w[16] = m.scattering.z;
+                w[17] = m.sc_anisotropy;
+                break;
+            }
+            case LUPIN_SURFACE_OPACITY:
+                w[0] = inv.get_material_point(hit).opacity;
+                break;
+            case LUPIN_SURFACE_NORMAL:
+            {
+                const vec3f ns = inv.compute_shading_normal(hit), ng = inv.compute_tri_geom_normal(hit.instance_idx, hit.tri_idx);
+                w[0] = ns.x; w[1] = ns.y; w[2] = ns.z; w[3] = ng.x; w[4] = ng.y; w[5] = ng.z;
+                break;
+            }
+            case LUPIN_SURFACE_ENVIRONMENT:
+            {
+                const vec3f dir = {r[5], r[6], r[7]};
+                const vec3f e = inv.sample_environments(dir);
+                w[0] = e.x; w[1] = e.y; w[2] = e.z;
+                if (inv.num_envs() > 0) { const vec2f uv = inv.dir_to_env_uv(dir, 0); w[3] = uv.x; w[4] = uv.y; }
+                break;
+            }
+            default:
+                break;
+        }
     }
     return 0;
 }

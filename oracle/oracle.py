@@ -54,6 +54,10 @@ def lib():
         h.oracle_scatter_probe.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
         h.oracle_light_probe.restype = C.c_int
         h.oracle_light_probe.argtypes = [C.POINTER(_abi.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        h.oracle_surface_probe.restype = C.c_int
+        h.oracle_surface_probe.argtypes = [C.POINTER(_abi.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        h.oracle_camera_rays.restype = C.c_int
+        h.oracle_camera_rays.argtypes = [C.POINTER(_abi.PushConstants), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         h.oracle_float_to_half.restype = C.c_uint16
         h.oracle_float_to_half.argtypes = [C.c_float]
         h.oracle_float_to_half_rtz.restype = C.c_uint16
@@ -202,6 +206,39 @@ def light_probe(scene, records):
     if lib().oracle_light_probe(C.byref(scene.desc), flags, len(rec), _abi.ptr(rec), _abi.ptr(out)) != 0:
         raise RuntimeError("oracle_light_probe failed")
     return out
+
+
+class SurfaceProbeError(ValueError):
+    """oracle_surface_probe refused the records: `code` -2 = an index outside the scene, -3 = MATERIAL_SIMPLE on a scene
+    that is not simple (the cases in which lupin_hip_surface_probe returns LUPIN_ERR_INVALID_ARGUMENT)."""
+
+    def __init__(self, code):
+        super().__init__(f"oracle_surface_probe failed ({code})")
+        self.code = code
+
+
+def surface_probe(scene, records, handle=None):
+    """oracle_surface_probe on `scene` over (n, 8) float32 records (layout of lupin_hip_surface_probe, include/lupin_hip.h);
+    returns the (n, 20) float32 outputs.  `handle`: another build of the oracle library to call (a sanitised one)."""
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, 8)
+    out = np.zeros((len(rec), 20), np.float32)
+    flags = scene_flags(scene, CameraParams())   # the *_EMPTY flags of the push constants
+    fn = lib().oracle_surface_probe if handle is None else handle.oracle_surface_probe
+    rc = fn(C.byref(scene.desc), C.c_uint32(flags), C.c_uint32(len(rec)), C.c_void_p(rec.ctypes.data), C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise SurfaceProbeError(rc)
+    return out
+
+
+def camera_rays(scene, width, height, camera_params, camera_transform, accum_counter=0, advanced=None):
+    """Origin and direction, (height, width, 3) float32 each, of every pixel's first camera ray in a frame rendered with these
+    parameters (the rays of a one-sample pathtrace / falsecolor call)."""
+    pc = push_constants(scene, camera_params, camera_transform, 0, accum_counter, advanced)
+    ori = np.zeros((height, width, 3), np.float32)
+    dir_ = np.zeros((height, width, 3), np.float32)
+    if lib().oracle_camera_rays(C.byref(pc), width, height, _abi.ptr(ori), _abi.ptr(dir_)) != 0:
+        raise RuntimeError("oracle_camera_rays failed")
+    return ori, dir_
 
 
 def effective_cpus():

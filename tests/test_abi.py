@@ -22,6 +22,9 @@ def test_every_declared_symbol_is_exported(built):
     handle = C.CDLL(_abi.LIB_PATH)
     names = header_functions()
     assert len(names) >= 35
+    for probe in ("lupin_hip_scatter_probe", "lupin_hip_light_probe", "lupin_hip_surface_probe"):
+        assert probe in names
+    assert (api.SURFACE_IN_FLOATS, api.SURFACE_OUT_FLOATS) == (8, 20) and len(api.SurfaceMode) == 6
     for n in names:
         assert hasattr(handle, n), f"{n} declared in lupin_hip.h but not exported"
     bound = {n for n, _, _ in _abi.SYMBOLS}
