@@ -267,7 +267,10 @@ __global__ void __launch_bounds__(LP_BLOCK) k_begin(const FrameParams *__restric
 #define LP_EXTEND_WAVES 4
 #endif
 #ifndef LP_SHADE_WAVES
-#define LP_SHADE_WAVES 3
+#define LP_SHADE_WAVES 4   // the inline march runs with nothing of the surface alive (integrate_vertex): 126 VGPRs
+#endif
+#ifndef LP_DIRECT_SHADE_WAVES
+#define LP_DIRECT_SHADE_WAVES 3   // two marches per vertex (light ray, mixture): 128 VGPRs only with scratch
 #endif
 #ifndef LP_DEFER_SHADE_WAVES
 #define LP_DEFER_SHADE_WAVES 4   // k_shade without the light-pdf march (the light-pdf stage runs it)
@@ -922,6 +925,9 @@ struct PathRegs
     bool pending;
     f3 pend_f;
     float pend_bp;
+    // whether this vertex changed `radiance` as stored (only emitters do): decided where the emission is added, so the value
+    // loaded at the start of the iteration need not stay alive to the end of it for the comparison
+    bool radiance_dirty;
 };
 
 // weight check and Russian roulette (:720-729)
@@ -937,6 +943,37 @@ __device__ __forceinline__ bool weight_checks_and_roulette(PathRegs &p)
     return true;
 }
 
+// volume stack: push when empty, otherwise pop (:667-681) -- depth never exceeds 1.  With `vol_pb` the medium a path enters goes
+// to its slot here, not at the end of the iteration: nothing later in the vertex reads it, so its seven registers are free
+// again before the light-pdf march.  (The words stored are the same; a path that ends at this very vertex has them stored
+// for nothing -- no one reads a finished path's medium.)
+__device__ __forceinline__ void update_volume_stack(PathRegs &p, const MatPoint &mp, f3 normal, f3 outgoing, f3 incoming, PathBuffers *vol_pb, uint32_t vol_slot)
+{
+    if (mat_is_volumetric(mp) && dot3(normal, outgoing) * dot3(normal, incoming) < 0.0f)
+    {
+        if (!p.in_medium)
+        {
+            p.medium.density = mp.density;
+            p.medium.scattering = mp.scattering;
+            p.medium.anisotropy = mp.anisotropy;
+            p.in_medium = true;
+            if (vol_pb)
+            {
+                vol_pb->vol0[vol_slot] = make_float4(mp.density.x, mp.density.y, mp.density.z, mp.anisotropy);
+                vol_pb->vol1[vol_slot] = make_float4(mp.scattering.x, mp.scattering.y, mp.scattering.z, 0.0f);
+            }
+        }
+        else p.in_medium = false;
+    }
+}
+
+// The values a vertex carries across its light-pdf march pass through an empty asm: whatever computes them cannot sink
+// below the march, where it would keep the material point, the normal and the outgoing direction alive across it.
+__device__ __forceinline__ void pin_before_march(f3 &f, float &bp)
+{
+    asm volatile("" : "+v"(f.x), "+v"(f.y), "+v"(f.z), "+v"(bp));
+}
+
 // One iteration of the integrator loop body after the closest-hit query.  Returns true when the
 // path continues with (ori, dir) set for the next bounce, false on `break`.
 // TYPE 0: pathtrace_standard (:588-733)   1: pathtrace_mis (:737-933)
@@ -950,13 +987,14 @@ __device__ __forceinline__ bool weight_checks_and_roulette(PathRegs &p)
 // sequence of draws is the reference's).
 template <int TYPE, typename Geo, bool SIMPLE = false, bool DEFER = false>
 __device__ __forceinline__ bool integrate_vertex(const Geo &geo, const SceneDev &sc, uint32_t *stack, const FrameParams &fp, PathRegs &p,
-                                 float4 hitrec, uint32_t hit_tri, ShadowRays &sh)
+                                 float4 hitrec, uint32_t hit_tri, ShadowRays &sh, PathBuffers *vol_pb = nullptr, uint32_t vol_slot = 0u)
 {
     static_assert(!DEFER || TYPE == LUPIN_PATHTRACE_STANDARD || TYPE == LUPIN_PATHTRACE_MIS, "the light-pdf stage serves the Standard and MIS integrators");
     constexpr bool DEFER_WEIGHT = DEFER && TYPE == LUPIN_PATHTRACE_STANDARD;   // MIS defers the two shadow-ray weights instead (below)
     const float eps = fp.pc.ray_epsilon;
     const uint32_t hit_inst = __float_as_uint(hitrec.w);
     p.pending = false;
+    p.radiance_dirty = false;
     if (hit_inst == HIT_MISS)
     {
         if (TYPE != LUPIN_PATHTRACE_DIRECT || p.next_emission)
@@ -982,6 +1020,9 @@ __device__ __forceinline__ bool integrate_vertex(const Geo &geo, const SceneDev 
     const f3 outgoing = neg(p.dir);
     f3 incoming = splat(0.0f);
     f3 hit_pos;
+    bool march = false;   // inline Standard / Direct: the weight update waits for sample_lights_pdf(hit_pos, incoming)
+    f3 march_f = splat(0.0f);
+    float march_bp = 0.0f;
     if (!in_volume)
     {
         hit_pos = add(p.ori, scale(p.dir, hit_dst));
@@ -990,17 +1031,26 @@ __device__ __forceinline__ bool integrate_vertex(const Geo &geo, const SceneDev 
         const f3 normal = shading_normal(geo, sc, s);
 
         if (TYPE == LUPIN_PATHTRACE_STANDARD || TYPE == LUPIN_PATHTRACE_NAIVE || p.next_emission)
+        {
+            const f3 before = p.radiance;
             p.radiance = add(p.radiance, mul(p.weight, mp.emission));
+            p.radiance_dirty = p.radiance.x != before.x || p.radiance.y != before.y || p.radiance.z != before.z;
+        }
 
         const bool delta = mat_is_delta(mp);
+        bool volume_done = false;   // the inline one-sample mixture updates the volume stack itself, ahead of its march
 
         if (TYPE == LUPIN_PATHTRACE_DIRECT)   // light ray before choosing the continuation (:1117-1146)
         {
             if (!delta)
             {
                 f3 li = lights_sample(sc, hit_pos, p.rng);
+                // before the march, so that its terms are dead when the march runs (a matte-only kernel has next to none of
+                // them and is better off with the march first)
+                f3 bsdfcos;
+                if (!SIMPLE) bsdfcos = bsdf_eval(mp, normal, outgoing, li);
                 float pdf = lights_pdf(geo, sc, stack, hit_pos, li, eps);
-                f3 bsdfcos = bsdf_eval(mp, normal, outgoing, li);
+                if (SIMPLE) bsdfcos = bsdf_eval(mp, normal, outgoing, li);
                 if (none_zero3(bsdfcos) && pdf > 0.0f)
                 {
                     // radiance += weight * bsdfcos * emission(light_ray) / pdf   -- traced by k_shadow (:1125-1138)
@@ -1032,8 +1082,14 @@ __device__ __forceinline__ bool integrate_vertex(const Geo &geo, const SceneDev 
                 }
                 else
                 {
-                    float prob = 0.5f * bsdf_pdf(mp, normal, outgoing, incoming) + 0.5f * lights_pdf(geo, sc, stack, hit_pos, incoming, eps);
-                    p.weight = mul(p.weight, divs(bsdf_eval(mp, normal, outgoing, incoming), prob));
+                    // Everything that reads the material point, the normal or the outgoing direction comes before the
+                    // light-pdf march, the volume-stack update included (no random number is drawn in between); the march
+                    // itself follows below, where this branch and the in-medium one meet.
+                    march_bp = bsdf_pdf(mp, normal, outgoing, incoming);
+                    march_f = bsdf_eval(mp, normal, outgoing, incoming);
+                    update_volume_stack(p, mp, normal, outgoing, incoming, vol_pb, vol_slot);
+                    volume_done = true;
+                    march = true;
                 }
             }
             else if (TYPE == LUPIN_PATHTRACE_NAIVE)
@@ -1113,18 +1169,7 @@ __device__ __forceinline__ bool integrate_vertex(const Geo &geo, const SceneDev 
             if (TYPE == LUPIN_PATHTRACE_MIS) p.next_emission = true;
         }
 
-        // volume stack: push when empty, otherwise pop (:667-681) -- depth never exceeds 1
-        if (mat_is_volumetric(mp) && dot3(normal, outgoing) * dot3(normal, incoming) < 0.0f)
-        {
-            if (!p.in_medium)
-            {
-                p.medium.density = mp.density;
-                p.medium.scattering = mp.scattering;
-                p.medium.anisotropy = mp.anisotropy;
-                p.in_medium = true;
-            }
-            else p.in_medium = false;
-        }
+        if (!volume_done) update_volume_stack(p, mp, normal, outgoing, incoming, vol_pb, vol_slot);
     }
     else
     {
@@ -1155,12 +1200,28 @@ __device__ __forceinline__ bool integrate_vertex(const Geo &geo, const SceneDev 
                 p.pend_f = phase_eval(p.medium, outgoing, incoming);
                 p.pending = true;
             }
-            else
+            else if (TYPE == LUPIN_PATHTRACE_MIS)
             {
                 float prob = 0.5f * phase_pdf(p.medium, outgoing, incoming) + 0.5f * lights_pdf(geo, sc, stack, hit_pos, incoming, eps);
                 p.weight = mul(p.weight, divs(phase_eval(p.medium, outgoing, incoming), prob));
             }
+            else
+            {
+                march_bp = phase_pdf(p.medium, outgoing, incoming);
+                march_f = phase_eval(p.medium, outgoing, incoming);
+                march = true;
+            }
         }
+    }
+
+    // The one-sample mixture's weight update (:652-656), for a surface and for a medium alike: weight *= f / (0.5 pdf + 0.5
+    // sample_lights_pdf).  One copy of the march, and what is alive across it is (hit_pos, incoming, f, pdf) and the path's
+    // own state: nothing of the surface, the material point or the previous ray.
+    if (march)
+    {
+        pin_before_march(march_f, march_bp);
+        float prob = 0.5f * march_bp + 0.5f * lights_pdf(geo, sc, stack, hit_pos, incoming, eps);
+        p.weight = mul(p.weight, divs(march_f, prob));
     }
 
     p.ori = hit_pos;
@@ -1170,11 +1231,11 @@ __device__ __forceinline__ bool integrate_vertex(const Geo &geo, const SceneDev 
 }
 
 // End of an iteration of the Standard / Naive loop for one path: a continuing path gets its state written back, a finished
-// one is folded into the pixel and the pixel's next camera sample started (:234-239).  `r4` is the radiance as stored (only
-// emitters change it).  Returns whether the slot still has work.
+// one is folded into the pixel and the pixel's next camera sample started (:234-239).  `radiance_dirty`: the radiance differs
+// from the stored one (only emitters change it).  Returns whether the slot still has work.
 template <int TYPE>
 __device__ __forceinline__ bool path_epilogue(const FrameParams &fp, const FrameParams *fpp, PathBuffers &pb, uint32_t slot, PathRegs &p, uint32_t sample, bool cont,
-                                              bool vol_dirty, float4 r4)
+                                              bool vol_dirty, bool radiance_dirty)
 {
     bool alive = false;
     if (cont)
@@ -1186,7 +1247,7 @@ __device__ __forceinline__ bool path_epilogue(const FrameParams &fp, const Frame
             pb.vol1[slot] = make_float4(p.medium.scattering.x, p.medium.scattering.y, p.medium.scattering.z, 0.0f);
         }
         pb.weight[slot] = make_float4(p.weight.x, p.weight.y, p.weight.z, 0.0f);
-        if (p.radiance.x != r4.x || p.radiance.y != r4.y || p.radiance.z != r4.z)   // only emitters touch it
+        if (radiance_dirty)   // only emitters touch it
             pb.radiance[slot] = make_float4(p.radiance.x, p.radiance.y, p.radiance.z, 0.0f);
     }
     else
@@ -1263,8 +1324,13 @@ __device__ __forceinline__ int shade_path(const Geo &geo, const SceneDev &sc, ui
     sh.pb = (TYPE == LUPIN_PATHTRACE_MIS || TYPE == LUPIN_PATHTRACE_DIRECT) ? &pb : nullptr;
     sh.slot = slot;
     sh.flags = 0u;
-    bool cont = integrate_vertex<TYPE, Geo, SIMPLE, DEFER>(geo, sc, stack, fp, p, hitrec, hit_tri, sh);
-    const bool vol_dirty = p.in_medium && !was_in_medium;
+    // the kernels that march inline write a newly entered medium where the path enters it (update_volume_stack)
+    constexpr bool EARLY_VOL = !DEFER && (TYPE == LUPIN_PATHTRACE_STANDARD || TYPE == LUPIN_PATHTRACE_DIRECT);
+    bool cont = integrate_vertex<TYPE, Geo, SIMPLE, DEFER>(geo, sc, stack, fp, p, hitrec, hit_tri, sh, EARLY_VOL ? &pb : nullptr, slot);
+    // The fields' addresses are formed again from the slot for the write-back (a multiply-add each) instead of staying alive,
+    // two registers per field, from the loads above across the whole vertex.
+    if (EARLY_VOL) asm volatile("" : "+v"(slot));
+    const bool vol_dirty = !EARLY_VOL && p.in_medium && !was_in_medium;
     if (DEFER && cont && p.pending)
     {
         // k_light_pdf finishes this iteration: park what it needs (the bounce count is still this iteration's)
@@ -1274,7 +1340,7 @@ __device__ __forceinline__ int shade_path(const Geo &geo, const SceneDev &sc, ui
             pb.vol1[slot] = make_float4(p.medium.scattering.x, p.medium.scattering.y, p.medium.scattering.z, 0.0f);
         }
         if (was_in_medium) pb.weight[slot] = make_float4(p.weight.x, p.weight.y, p.weight.z, 0.0f);   // only the transmittance term changed it
-        if (p.radiance.x != r4.x || p.radiance.y != r4.y || p.radiance.z != r4.z)
+        if (p.radiance_dirty)
             pb.radiance[slot] = make_float4(p.radiance.x, p.radiance.y, p.radiance.z, 0.0f);
         pb.sh_f0[slot] = make_float4(p.pend_f.x, p.pend_f.y, p.pend_f.z, p.pend_bp);
         const uint32_t nm = ((uint32_t)p.bounce & META_BOUNCE_MASK) | (p.in_medium ? META_VOLUME : 0u) |
@@ -1308,7 +1374,7 @@ __device__ __forceinline__ int shade_path(const Geo &geo, const SceneDev &sc, ui
         pb.sh_org[slot].w = __uint_as_float(sh.flags);
         return SLOT_ALIVE;
     }
-    return path_epilogue<TYPE>(fp, fpp, pb, slot, p, sample, cont, vol_dirty, r4) ? SLOT_ALIVE : SLOT_DONE;
+    return path_epilogue<TYPE>(fp, fpp, pb, slot, p, sample, cont, vol_dirty, p.radiance_dirty) ? SLOT_ALIVE : SLOT_DONE;
 }
 
 // The light-pdf stage's share of an iteration (Standard): sample_lights_pdf for the direction k_shade chose
@@ -1341,7 +1407,7 @@ __device__ __forceinline__ bool light_pdf_path(const Geo &geo, const SceneDev &s
     float4 r4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (!cont) r4 = pb.radiance[slot];   // a finished path is folded into the pixel
     p.radiance = mk3(r4.x, r4.y, r4.z);
-    return path_epilogue<TYPE>(fp, fpp, pb, slot, p, sample, cont, false, r4);
+    return path_epilogue<TYPE>(fp, fpp, pb, slot, p, sample, cont, false, p.radiance.x != r4.x || p.radiance.y != r4.y || p.radiance.z != r4.z);
 }
 
 // Scenes with several material families: before k_shade, each window of LP_SORT_WINDOW queue entries is counting-sorted by what
@@ -1483,7 +1549,7 @@ __global__ void __launch_bounds__(LP_BLOCK) k_compact_queue(PathBuffers pb, uint
 // k_shade in which those facts are compile-time constants: same arithmetic on the paths that exist, none of the code
 // for the ones that cannot.
 template <int TYPE, bool LDSGEO, bool SIMPLE, bool DEFER = false>
-__global__ void __attribute__((amdgpu_waves_per_eu(TYPE == 1 ? (DEFER ? LP_MIS_DEFER_SHADE_WAVES : LP_MIS_SHADE_WAVES) : (SIMPLE ? LP_SIMPLE_SHADE_WAVES : (DEFER ? LP_DEFER_SHADE_WAVES : LP_SHADE_WAVES)), 8))) __launch_bounds__(LP_BLOCK) k_shade(SceneDev sc, const FrameParams *__restrict__ fpp, PathBuffers pb, uint32_t iter,
+__global__ void __attribute__((amdgpu_waves_per_eu(TYPE == 1 ? (DEFER ? LP_MIS_DEFER_SHADE_WAVES : LP_MIS_SHADE_WAVES) : (SIMPLE ? LP_SIMPLE_SHADE_WAVES : (DEFER ? LP_DEFER_SHADE_WAVES : (TYPE == 3 ? LP_DIRECT_SHADE_WAVES : LP_SHADE_WAVES))), 8))) __launch_bounds__(LP_BLOCK) k_shade(SceneDev sc, const FrameParams *__restrict__ fpp, PathBuffers pb, uint32_t iter,
                                                     unsigned long long *shard_stats, uint32_t stack_words)
 {
     const FrameParams fp = *fpp;
