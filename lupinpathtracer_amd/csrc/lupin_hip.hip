@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cfloat>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <set>
 #include <mutex>
@@ -147,9 +148,10 @@ struct LupinScene
     SceneDev dev{};
     std::vector<void *> allocations;
     uint32_t stack_entries = 1;
-    uint32_t persistent_blocks[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // grid of k_extend_persistent per integrator (lazy); [1]: sharing the chip with other lanes' stages
-    uint32_t wide_blocks[4] = {0, 0, 0, 0};         // grid of its four-wide instantiation
-    uint32_t short_blocks[4] = {0, 0, 0, 0};        // grid of its short-stack instantiation
+    // grids of k_extend_persistent per integrator, filled on first use by resident_grid (so `mutable`: a render takes the scene const)
+    mutable uint32_t persistent_blocks[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // binary; [1]: sharing the chip with other lanes' stages
+    mutable uint32_t wide_blocks[4] = {0, 0, 0, 0};         // its four-wide instantiation
+    mutable uint32_t short_blocks[4] = {0, 0, 0, 0};        // its short-stack instantiation
     bool has_wide = false;                          // the four-wide hierarchies were built (scenes traversed from global memory)
     uint64_t leaky_triangles = 0;                   // triangles outside some box above them (reference builder: bins vs partition)
     uint64_t id = 0;                                // unique per created scene (graph cache key)
@@ -510,87 +512,73 @@ static uint32_t blas_depth(const LupinBvhNode *nodes, uint32_t count)
     return best;
 }
 
-// grid of the persistent tracer: as many blocks as the device keeps resident with this scene's traversal-stack size
-// (whole waves per shard); queried once per scene and integrator, outside any stream capture
-template <int TYPE>
-static uint32_t persistent_grid_t(LupinContext *ctx, const LupinScene *scene, size_t lds, bool shares_chip)
+// ------------------------------------------------------------------------------------------------
+// Launch plan.  A run-time choice becomes a kernel variant through with_type / with_bool at the launch that needs it (an
+// `if constexpr` keeps out the combinations that are never launched); whatever a kernel asks of LDS is added in traversal_lds.
+// ------------------------------------------------------------------------------------------------
+
+// f(std::integral_constant<int, TYPE>) for the integrator `type` (pathtrace_impl has checked its range)
+template <typename F>
+static auto with_type(uint32_t type, F &&f)
 {
-    uint32_t &cached = const_cast<LupinScene *>(scene)->persistent_blocks[shares_chip ? 1 : 0][TYPE];
-    if (cached == 0)
+    switch (type)
     {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_extend_persistent<TYPE, false, 0, false>, LP_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        // With frames in flight the persistent tracer of one frame shares the chip with the shading of another: when five
-        // or more of its blocks fit per CU, three leave that room and the pair finishes sooner (materials1 / environments1
-        // +5 %); deeper scenes fit four at most and are latency-bound, they keep them all (bistro-class -9 % with two).
-        if (shares_chip && per_cu > 4) per_cu = 3;
-        cached = std::max(64u, ctx->num_cus * (uint32_t)per_cu / 64u * 64u);
+    case LUPIN_PATHTRACE_STANDARD: return f(std::integral_constant<int, LUPIN_PATHTRACE_STANDARD>{});
+    case LUPIN_PATHTRACE_MIS: return f(std::integral_constant<int, LUPIN_PATHTRACE_MIS>{});
+    case LUPIN_PATHTRACE_NAIVE: return f(std::integral_constant<int, LUPIN_PATHTRACE_NAIVE>{});
+    default: return f(std::integral_constant<int, LUPIN_PATHTRACE_DIRECT>{});
     }
-    return cached;
+}
+// f(std::true_type) or f(std::false_type)
+template <typename F>
+static auto with_bool(bool b, F &&f)
+{
+    if (b) return f(std::true_type{});
+    return f(std::false_type{});
 }
 
-// grid of the four-wide instantiation (its own LDS footprint and register count)
-template <int TYPE>
-static uint32_t wide_grid_t(LupinContext *ctx, const LupinScene *scene, size_t lds)
+// What the traversal of one launch takes of LDS: `stack_words` of per-lane stacks in front of the scene's staged geometry.
+struct TraversalLds
 {
-    uint32_t &cached = const_cast<LupinScene *>(scene)->wide_blocks[TYPE];
+    bool geo = false;            // the kernel reads the scene from LDS (its LDSGEO instantiation)
+    uint32_t stack_words = 0;
+    size_t lds = 0;              // bytes
+};
+static constexpr size_t LP_LDS_LIMIT = 160 * 1024;   // the LDS of a CU, which one block may have to itself
+
+// small scenes are staged in LDS by the one-ray-per-lane kernels (LUPIN_LDS_GEOMETRY=0: never)
+static bool stages_geometry(const LupinContext *ctx, const LupinScene *scene) { return scene->dev.geo_blob_words && ctx->lds_geometry; }
+
+// `stack_entries` per lane: the scene's depth bound, a tracer's own bound, or 0 for a kernel that never traverses.
+// `stage` is false for the kernels that read the geometry from global memory whatever the scene (the persistent tracers, k_trace).
+static int traversal_lds(const LupinContext *ctx, const LupinScene *scene, uint32_t stack_entries, bool stage, TraversalLds *out)
+{
+    out->geo = stage && stages_geometry(ctx, scene);
+    out->stack_words = stack_entries * LP_BLOCK;
+    out->lds = (size_t)out->stack_words * sizeof(uint32_t) + (out->geo ? (size_t)scene->dev.geo_blob_words * 16 : 0);
+    if (out->lds > LP_LDS_LIMIT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "BVH too deep for the LDS traversal stack");
+    return LUPIN_OK;
+}
+
+// Grid of a persistent tracer: as many blocks of `kernel` as the device keeps resident with `lds` bytes each (whole waves
+// per shard), after `per_cu_rule` has had its say.  Queried once per scene, integrator and instantiation, outside any
+// stream capture, and kept in `cached`.
+template <typename Kernel, typename Rule = int (*)(int)>
+static uint32_t resident_grid(const LupinContext *ctx, Kernel kernel, size_t lds, uint32_t &cached, Rule per_cu_rule = [](int per_cu) { return per_cu; })
+{
     if (cached == 0)
     {
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_extend_persistent<TYPE, false, 0, false, true, false>, LP_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        cached = std::max(64u, ctx->num_cus * (uint32_t)per_cu / 64u * 64u);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, LP_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+        cached = std::max(64u, ctx->num_cus * (uint32_t)per_cu_rule(per_cu) / 64u * 64u);
     }
     return cached;
-}
-// grid of the short-stack instantiation of the binary tracer
-template <int TYPE>
-static uint32_t short_grid_t(LupinContext *ctx, const LupinScene *scene, size_t lds)
-{
-    uint32_t &cached = const_cast<LupinScene *>(scene)->short_blocks[TYPE];
-    if (cached == 0)
-    {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_extend_persistent<TYPE, false, 0, false, false, false, true>, LP_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        cached = std::max(64u, ctx->num_cus * (uint32_t)per_cu / 64u * 64u);
-    }
-    return cached;
-}
-static uint32_t short_grid(LupinContext *ctx, const LupinScene *scene, uint32_t type, size_t lds)
-{
-    switch (type)
-    {
-    case LUPIN_PATHTRACE_STANDARD: return short_grid_t<LUPIN_PATHTRACE_STANDARD>(ctx, scene, lds);
-    case LUPIN_PATHTRACE_MIS: return short_grid_t<LUPIN_PATHTRACE_MIS>(ctx, scene, lds);
-    case LUPIN_PATHTRACE_NAIVE: return short_grid_t<LUPIN_PATHTRACE_NAIVE>(ctx, scene, lds);
-    default: return short_grid_t<LUPIN_PATHTRACE_DIRECT>(ctx, scene, lds);
-    }
-}
-static uint32_t wide_grid(LupinContext *ctx, const LupinScene *scene, uint32_t type, size_t lds)
-{
-    switch (type)
-    {
-    case LUPIN_PATHTRACE_STANDARD: return wide_grid_t<LUPIN_PATHTRACE_STANDARD>(ctx, scene, lds);
-    case LUPIN_PATHTRACE_MIS: return wide_grid_t<LUPIN_PATHTRACE_MIS>(ctx, scene, lds);
-    case LUPIN_PATHTRACE_NAIVE: return wide_grid_t<LUPIN_PATHTRACE_NAIVE>(ctx, scene, lds);
-    default: return wide_grid_t<LUPIN_PATHTRACE_DIRECT>(ctx, scene, lds);
-    }
 }
 
 // The phase-scheduled persistent tracer serves scenes traversed from global memory; scenes staged in LDS (a few dozen node
 // visits per ray) are faster with one ray per lane (k_extend; Cornell box 6.4 vs 5.4 Gsamples/s in round 1).
 // LUPIN_EXTEND=simple forces k_extend everywhere.
 static bool use_persistent(const LupinContext *ctx, bool lds_geo) { return ctx->persistent_extend != 0 && !lds_geo; }
-static uint32_t persistent_grid(LupinContext *ctx, const LupinScene *scene, uint32_t type, bool lds_geo, size_t lds, bool shares_chip)
-{
-    if (!use_persistent(ctx, lds_geo)) return 0;
-    switch (type)
-    {
-    case LUPIN_PATHTRACE_STANDARD: return persistent_grid_t<LUPIN_PATHTRACE_STANDARD>(ctx, scene, lds, shares_chip);
-    case LUPIN_PATHTRACE_MIS: return persistent_grid_t<LUPIN_PATHTRACE_MIS>(ctx, scene, lds, shares_chip);
-    case LUPIN_PATHTRACE_NAIVE: return persistent_grid_t<LUPIN_PATHTRACE_NAIVE>(ctx, scene, lds, shares_chip);
-    default: return persistent_grid_t<LUPIN_PATHTRACE_DIRECT>(ctx, scene, lds, shares_chip);
-    }
-}
 
 // LUPIN_LIGHT_STAGE=1: sample_lights_pdf of the Standard / MIS integrators runs in its own stage (k_light_pdf / k_light_pdf_mis) instead of inline
 // in k_shade.  Same results; off by default (faster kernel for kernel, slower with frames in flight).
@@ -605,96 +593,114 @@ static bool use_light_stage(const LupinContext *ctx, const LupinScene *scene, ui
 }
 
 // launch shape of one call's stage kernels
+struct TracerGrid
+{
+    uint32_t blocks = 0;         // 0 = off
+    size_t lds = 0;
+    uint32_t stack_words = 0;
+};
 struct Shape
 {
     uint32_t blocks = 0;         // one thread per slot, LP_SHARDS-aligned
-    uint32_t pblocks = 0;        // persistent tracer (binary hierarchy); 0 = the one-ray-per-lane k_extend
-    size_t lds = 0;              // traversal stacks (+ staged geometry)
-    uint32_t stack_words = 0;
-    uint32_t wblocks = 0;        // four-wide tracer; 0 = off
-    size_t wlds = 0;
-    uint32_t wstack_words = 0;
-    uint32_t sblocks = 0;        // short-stack first pass of the binary tracer; 0 = off
-    size_t slds = 0;
-    uint32_t sstack_words = 0;
+    bool lds_geo = false;        // the stage kernels read the scene from LDS
+    TracerGrid binary;           // persistent tracer (binary hierarchy); blocks == 0 = the one-ray-per-lane k_extend.  Its lds and
+                                 // stack_words, traversal stacks (+ staged geometry), serve every one-thread-per-slot stage as well
+    TracerGrid wide;             // four-wide tracer
+    TracerGrid shrt;             // short-stack first pass of the binary tracer
+    size_t verify_lds = 0;       // k_verify_wide walks both hierarchies: the larger of the binary and the four-wide stacks
 };
+
+// The persistent tracers of one call: which run, their LDS and their grids.  `t` is the call's traversal_lds.
+static void plan_tracers(LupinContext *ctx, const LupinScene *scene, uint32_t type, bool chip_to_itself, const TraversalLds &t, Shape *sh)
+{
+    // a tracer's own stack bound, never staged geometry; both are below limits checked before (40 KB; less than t.lds)
+    auto stacks = [&](uint32_t entries) { TraversalLds x; traversal_lds(ctx, scene, entries, false, &x); return TracerGrid{0u, x.lds, x.stack_words}; };
+    // the wide tracer keeps (reference, distance) pairs on a bounded stack; a query that would overflow it is re-traced
+    const TracerGrid wide_stacks = stacks(2u * ctx->wide_stack_pairs);
+    sh->lds_geo = t.geo;
+    sh->binary = TracerGrid{0u, t.lds, t.stack_words};
+    sh->verify_lds = std::max(t.lds, wide_stacks.lds);
+    if (!use_persistent(ctx, t.geo)) return;
+    const bool wide = scene->has_wide && ctx->wide_traversal;
+    // A fifth block per CU for scenes whose depth bound asks for more than 32 KB of stack per block (bistro-class: 40):
+    // the tracer is bound by latency x waves (four blocks instead of three: -18 %, five instead of four: -10 %), and the
+    // stack a query actually uses is far below the bound (bistro-class 4K: 33 of 3.5 G queries need more than 20 entries).
+    // Only with the chip to itself: sharing it, the larger tracer loses more to the other lanes' stages than it gains.
+    const bool shrt = !wide && chip_to_itself && ctx->short_stack && scene->stack_entries > ctx->short_stack;
+    if (wide) sh->wide = wide_stacks;
+    if (shrt) sh->shrt = stacks(ctx->short_stack);
+    with_type(type, [&](auto T) {
+        constexpr int TYPE = decltype(T)::value;
+        // With frames in flight the persistent tracer of one frame shares the chip with the shading of another: when five
+        // or more of its blocks fit per CU, three leave that room and the pair finishes sooner (materials1 / environments1
+        // +5 %); deeper scenes fit four at most and are latency-bound, they keep them all (bistro-class -9 % with two).
+        const bool shares_chip = !chip_to_itself;
+        sh->binary.blocks = resident_grid(ctx, k_extend_persistent<TYPE, false, 0, false>, sh->binary.lds, scene->persistent_blocks[shares_chip ? 1 : 0][TYPE],
+                                          [=](int per_cu) { return shares_chip && per_cu > 4 ? 3 : per_cu; });
+        // the other instantiations have their own LDS footprint and register count
+        if (wide) sh->wide.blocks = resident_grid(ctx, k_extend_persistent<TYPE, false, 0, false, true, false>, sh->wide.lds, scene->wide_blocks[TYPE]);
+        if (shrt) sh->shrt.blocks = resident_grid(ctx, k_extend_persistent<TYPE, false, 0, false, false, false, true>, sh->shrt.lds, scene->short_blocks[TYPE]);
+    });
+}
 
 // the tracing stage of MODE 0 (closest hits of the integrator loop) or 1 (recorded shadow rays) on the persistent tracer
 template <int TYPE, int MODE>
 static void launch_persistent_tracer(LupinContext *ctx, Lane *ln, const LupinScene *scene, const Shape &sh, uint32_t iter)
 {
-    hipStream_t st = ln->stream;
-    const FrameParams *fp = ln->d_fp;
-    unsigned long long *work = ln->work_counters, *wide = ln->wide_counters;
-    {
-        if (sh.wblocks)
+    auto launch = [&](auto kernel, const TracerGrid &g) {
+        hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(LP_BLOCK), g.lds, ln->stream, scene->dev, (const FrameParams *)ln->d_fp, ln->pb, iter, ln->stat_counters,
+                           LP_REFILL_MIN, g.stack_words, LP_NODE_STEPS, ln->work_counters, ln->wide_counters);
+    };
+    with_bool(ctx->counting, [&](auto C) {
+        constexpr bool COUNT = decltype(C)::value;
+        if (sh.wide.blocks)
         {
             // four-wide traversal with the exactness certificate, then the queries it did not certify in the reference's order
-            if (ctx->counting)
-            {
-                hipLaunchKernelGGL((k_extend_persistent<TYPE, false, MODE, true, true, false>), dim3(sh.wblocks), dim3(LP_BLOCK), sh.wlds, st,
-                                   scene->dev, fp, ln->pb, iter, ln->stat_counters, LP_REFILL_MIN, sh.wstack_words, LP_NODE_STEPS, work, wide);
-                hipLaunchKernelGGL((k_extend_persistent<TYPE, false, MODE, true, false, true>), dim3(sh.pblocks), dim3(LP_BLOCK), sh.lds, st,
-                                   scene->dev, fp, ln->pb, iter, ln->stat_counters, LP_REFILL_MIN, sh.stack_words, LP_NODE_STEPS, work, wide);
-            }
-            else
-            {
-                hipLaunchKernelGGL((k_extend_persistent<TYPE, false, MODE, false, true, false>), dim3(sh.wblocks), dim3(LP_BLOCK), sh.wlds, st,
-                                   scene->dev, fp, ln->pb, iter, ln->stat_counters, LP_REFILL_MIN, sh.wstack_words, LP_NODE_STEPS, work, wide);
-                hipLaunchKernelGGL((k_extend_persistent<TYPE, false, MODE, false, false, true>), dim3(sh.pblocks), dim3(LP_BLOCK), sh.lds, st,
-                                   scene->dev, fp, ln->pb, iter, ln->stat_counters, LP_REFILL_MIN, sh.stack_words, LP_NODE_STEPS, work, wide);
-            }
+            launch(k_extend_persistent<TYPE, false, MODE, COUNT, true, false>, sh.wide);
+            launch(k_extend_persistent<TYPE, false, MODE, COUNT, false, true>, sh.binary);
             return;
         }
-    }
-    if (sh.sblocks && !ctx->counting)
-    {
-        // the binary traversal on a short stack (one more block per CU), then the few queries that needed the full one
-        hipLaunchKernelGGL((k_extend_persistent<TYPE, false, MODE, false, false, false, true>), dim3(sh.sblocks), dim3(LP_BLOCK), sh.slds, st,
-                           scene->dev, fp, ln->pb, iter, ln->stat_counters, LP_REFILL_MIN, sh.sstack_words, LP_NODE_STEPS, work, wide);
-        hipLaunchKernelGGL((k_extend_persistent<TYPE, false, MODE, false, false, true>), dim3(sh.pblocks), dim3(LP_BLOCK), sh.lds, st,
-                           scene->dev, fp, ln->pb, iter, ln->stat_counters, LP_REFILL_MIN, sh.stack_words, LP_NODE_STEPS, work, wide);
-        return;
-    }
-    if (ctx->counting)
-        hipLaunchKernelGGL((k_extend_persistent<TYPE, false, MODE, true>), dim3(sh.pblocks), dim3(LP_BLOCK), sh.lds, st,
-                           scene->dev, fp, ln->pb, iter, ln->stat_counters, LP_REFILL_MIN, sh.stack_words, LP_NODE_STEPS, work, wide);
-    else
-        hipLaunchKernelGGL((k_extend_persistent<TYPE, false, MODE, false>), dim3(sh.pblocks), dim3(LP_BLOCK), sh.lds, st,
-                           scene->dev, fp, ln->pb, iter, ln->stat_counters, LP_REFILL_MIN, sh.stack_words, LP_NODE_STEPS, work, wide);
+        if constexpr (!COUNT)   // the short-stack pass does not count work
+        {
+            if (sh.shrt.blocks)
+            {
+                // the binary traversal on a short stack (one more block per CU), then the few queries that needed the full one
+                launch(k_extend_persistent<TYPE, false, MODE, false, false, false, true>, sh.shrt);
+                launch(k_extend_persistent<TYPE, false, MODE, false, false, true>, sh.binary);
+                return;
+            }
+        }
+        launch(k_extend_persistent<TYPE, false, MODE, COUNT>, sh.binary);
+    });
 }
 
 template <int TYPE, bool LDSGEO>
-static void launch_iteration_t(LupinContext *ctx, Lane *ln, const LupinScene *scene, const Shape &sh, uint32_t iter)
+static void launch_iteration(LupinContext *ctx, Lane *ln, const LupinScene *scene, const Shape &sh, uint32_t iter)
 {
-    const uint32_t blocks = sh.blocks, pblocks = sh.pblocks, stack_words = sh.stack_words;
-    const size_t lds = sh.lds;
+    const uint32_t blocks = sh.blocks, stack_words = sh.binary.stack_words;
+    const size_t lds = sh.binary.lds;
     hipStream_t st = ln->stream;
     const FrameParams *fp = ln->d_fp;
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     if (ctx->timing) { e0 = get_event(ctx); e1 = get_event(ctx); e2 = get_event(ctx); hipEventRecord(e0, st); }
-    const bool persistent = pblocks != 0;
+    const bool persistent = sh.binary.blocks != 0;
     unsigned long long *work = ln->work_counters;
     if constexpr (!LDSGEO)
     {
         if (ctx->verify_wide && scene->has_wide)   // checker only: every query of this iteration, binary vs wide, one ray per lane
-            hipLaunchKernelGGL(k_verify_wide<0>, dim3(blocks), dim3(LP_BLOCK), std::max(lds, (size_t)ctx->wide_stack_pairs * 2u * LP_BLOCK * sizeof(uint32_t)), st,
+            hipLaunchKernelGGL(k_verify_wide<0>, dim3(blocks), dim3(LP_BLOCK), sh.verify_lds, st,
                                scene->dev, fp, ln->pb, iter, ctx->wide_stack_pairs, ln->wide_counters + 2);
     }
     bool traced = false;
     if constexpr (!LDSGEO) { if (persistent) { launch_persistent_tracer<TYPE, 0>(ctx, ln, scene, sh, iter); traced = true; } }
     if (!traced)
     {
-        const bool opaque = scene->all_opaque && ctx->specialize_simple;
-        if (ctx->counting)
-        {
-            if (opaque) hipLaunchKernelGGL((k_extend<TYPE, LDSGEO, true, true>), dim3(blocks), dim3(LP_BLOCK), lds, st, scene->dev, fp, ln->pb, iter, ln->stat_counters, stack_words, work);
-            else hipLaunchKernelGGL((k_extend<TYPE, LDSGEO, false, true>), dim3(blocks), dim3(LP_BLOCK), lds, st, scene->dev, fp, ln->pb, iter, ln->stat_counters, stack_words, work);
-        }
-        else if (opaque)
-            hipLaunchKernelGGL((k_extend<TYPE, LDSGEO, true, false>), dim3(blocks), dim3(LP_BLOCK), lds, st, scene->dev, fp, ln->pb, iter, ln->stat_counters, stack_words, work);
-        else
-            hipLaunchKernelGGL((k_extend<TYPE, LDSGEO, false, false>), dim3(blocks), dim3(LP_BLOCK), lds, st, scene->dev, fp, ln->pb, iter, ln->stat_counters, stack_words, work);
+        with_bool(scene->all_opaque && ctx->specialize_simple, [&](auto O) {
+            with_bool(ctx->counting, [&](auto C) {
+                hipLaunchKernelGGL((k_extend<TYPE, LDSGEO, decltype(O)::value, decltype(C)::value>), dim3(blocks), dim3(LP_BLOCK), lds, st, scene->dev, fp, ln->pb, iter,
+                                   ln->stat_counters, stack_words, work);
+            });
+        });
     }
     if (ctx->timing) hipEventRecord(e1, st);
     if (ctx->debug_sync)
@@ -757,15 +763,14 @@ static void launch_iteration_t(LupinContext *ctx, Lane *ln, const LupinScene *sc
             {
                 // large scenes: the shadow rays go through the phase-scheduled persistent tracer as well, then a light finish pass
                 if (ctx->verify_wide && scene->has_wide)
-                    hipLaunchKernelGGL(k_verify_wide<1>, dim3(blocks), dim3(LP_BLOCK), std::max(lds, (size_t)ctx->wide_stack_pairs * 2u * LP_BLOCK * sizeof(uint32_t)), st,
+                    hipLaunchKernelGGL(k_verify_wide<1>, dim3(blocks), dim3(LP_BLOCK), sh.verify_lds, st,
                                        scene->dev, fp, ln->pb, iter, ctx->wide_stack_pairs, ln->wide_counters + 2);
                 launch_persistent_tracer<TYPE, 1>(ctx, ln, scene, sh, iter);
                 hipLaunchKernelGGL((k_shadow<TYPE, false, true>), dim3(blocks), dim3(LP_BLOCK), lds, st, scene->dev, fp, ln->pb, iter, stack_words);
                 pretraced = true;
             }
         }
-        if (pretraced) {}   // (k_shadow<.., PRETRACED> has run)
-        else
+        if (!pretraced)
             hipLaunchKernelGGL((k_shadow<TYPE, LDSGEO, false>), dim3(blocks), dim3(LP_BLOCK), lds, st, scene->dev, fp, ln->pb, iter, stack_words);
     }
     if (ctx->debug_sync)
@@ -783,15 +788,8 @@ static void launch_iteration_t(LupinContext *ctx, Lane *ln, const LupinScene *sc
     ctx->extend_launches++;
 }
 
-template <int TYPE>
-static void launch_iteration(LupinContext *ctx, Lane *ln, const LupinScene *scene, bool lds_geo, const Shape &sh, uint32_t iter)
-{
-    if (lds_geo) launch_iteration_t<TYPE, true>(ctx, ln, scene, sh, iter);
-    else launch_iteration_t<TYPE, false>(ctx, ln, scene, sh, iter);
-}
-
 // the lane-private part of one call: clear the queue counters, first rays, every iteration of the wavefront
-static hipError_t enqueue_wavefront(LupinContext *ctx, Lane *ln, const LupinScene *scene, uint32_t pathtrace_type, bool lds_geo, uint32_t n,
+static hipError_t enqueue_wavefront(LupinContext *ctx, Lane *ln, const LupinScene *scene, uint32_t pathtrace_type, uint32_t n,
                                     const Shape &sh, uint32_t iterations, const AdaptiveDev *ad = nullptr)
 {
     const uint32_t blocks = sh.blocks;
@@ -803,16 +801,11 @@ static hipError_t enqueue_wavefront(LupinContext *ctx, Lane *ln, const LupinScen
                            (const uint8_t *)ad->block_active, (const uint32_t *)ad->frames, ad->blocks_x);
     else
         hipLaunchKernelGGL(k_begin, dim3(blocks), dim3(LP_BLOCK), 0, st, (const FrameParams *)ln->d_fp, ln->pb, n);
-    for (uint32_t it = 0; it < iterations; it++)
-    {
-        switch (pathtrace_type)
-        {
-        case LUPIN_PATHTRACE_STANDARD: launch_iteration<LUPIN_PATHTRACE_STANDARD>(ctx, ln, scene, lds_geo, sh, it); break;
-        case LUPIN_PATHTRACE_MIS: launch_iteration<LUPIN_PATHTRACE_MIS>(ctx, ln, scene, lds_geo, sh, it); break;
-        case LUPIN_PATHTRACE_NAIVE: launch_iteration<LUPIN_PATHTRACE_NAIVE>(ctx, ln, scene, lds_geo, sh, it); break;
-        default: launch_iteration<LUPIN_PATHTRACE_DIRECT>(ctx, ln, scene, lds_geo, sh, it); break;
-        }
-    }
+    with_type(pathtrace_type, [&](auto T) {
+        with_bool(sh.lds_geo, [&](auto G) {
+            for (uint32_t it = 0; it < iterations; it++) launch_iteration<decltype(T)::value, decltype(G)::value>(ctx, ln, scene, sh, it);
+        });
+    });
     return hipSuccess;
 }
 
@@ -832,6 +825,28 @@ static hipError_t sync_all(LupinContext *ctx)
     for (int k = 0; k < LP_MAX_LANES && e == hipSuccess; k++)
         if (ctx->lanes[k].stream) e = hipStreamSynchronize(ctx->lanes[k].stream);
     return e;
+}
+
+// "Records in, launch, records out" on the primary stream, in scratch buffers that live for the call.  `launch` gets the
+// device copies of `in` (in order) and the output buffer and enqueues the kernel; errors are reported under `who`.
+struct ProbeInput { const void *host; size_t bytes; };
+template <size_t N, typename Launch>
+static int run_probe(LupinContext *ctx, const char *who, const ProbeInput (&in)[N], void *out, size_t out_bytes, Launch launch)
+{
+    DeviceBuffer din[N], dout;
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < N && e == hipSuccess; k++) e = DeviceBuffer::make(in[k].bytes, &din[k]);
+    if (e == hipSuccess) e = DeviceBuffer::make(out_bytes, &dout);
+    for (size_t k = 0; k < N && e == hipSuccess; k++) e = hipMemcpyAsync(din[k].get(), in[k].host, in[k].bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+    {
+        launch(din, dout.as<float>());
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout.get(), out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return LUPIN_OK;
 }
 
 // Handles outlive their context in host code that tears down in the wrong order (garbage-collected hosts do): every entry
@@ -1592,9 +1607,8 @@ int lupin_hip_scene_update_instances(LupinScene *scene, const LupinMat4x3 *trans
     SceneDev &dv = scene->dev;
     {
         // the limit every render applies (pathtrace_impl / flush_pending), here before anything is written
-        const bool lds_geo = dv.geo_blob_words && ctx->lds_geometry;
-        const size_t lds = (size_t)stack_entries * LP_BLOCK * sizeof(uint32_t) + (lds_geo ? (size_t)dv.geo_blob_words * 16 : 0);
-        if (lds > 160 * 1024) return fail(LUPIN_ERR_INVALID_ARGUMENT, "BVH too deep for the LDS traversal stack");
+        TraversalLds t;
+        if (int rc = traversal_lds(ctx, scene, stack_entries, true, &t)) return rc;
     }
     const size_t nlights = scene->light_instance.size();
     std::vector<float4> light_bounds((nlights + 3) / 4 * 4, make_float4(0.0f, 0.0f, 0.0f, -1.0f));
@@ -1883,20 +1897,16 @@ static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res,
     if (falsecolor_type >= 0 || debug)
     {
         const uint32_t fblocks = (n + LP_BLOCK - 1) / LP_BLOCK;
-        const uint32_t fstack_words = scene->stack_entries * LP_BLOCK;
-        const bool flds = scene->dev.geo_blob_words && ctx->lds_geometry;
-        const size_t flds_bytes = (size_t)fstack_words * sizeof(uint32_t) + (flds ? (size_t)scene->dev.geo_blob_words * 16 : 0);
-        if (flds_bytes > 160 * 1024) return fail(LUPIN_ERR_INVALID_ARGUMENT, "BVH too deep for the LDS traversal stack");
+        TraversalLds t;
+        if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
         const __half *pv = prev ? prev->data : (const __half *)nullptr;
         render_target->accum32_valid = false;
         join_primary(ctx);
-        if (debug)
-        {
-            if (flds) hipLaunchKernelGGL(k_debug<true>, dim3(fblocks), dim3(LP_BLOCK), flds_bytes, ctx->stream, scene->dev, fp, n, pv, render_target->data, fstack_words);
-            else hipLaunchKernelGGL(k_debug<false>, dim3(fblocks), dim3(LP_BLOCK), flds_bytes, ctx->stream, scene->dev, fp, n, pv, render_target->data, fstack_words);
-        }
-        else if (flds) hipLaunchKernelGGL(k_falsecolor<true>, dim3(fblocks), dim3(LP_BLOCK), flds_bytes, ctx->stream, scene->dev, fp, n, pv, render_target->data, fstack_words);
-        else hipLaunchKernelGGL(k_falsecolor<false>, dim3(fblocks), dim3(LP_BLOCK), flds_bytes, ctx->stream, scene->dev, fp, n, pv, render_target->data, fstack_words);
+        with_bool(t.geo, [&](auto G) {
+            constexpr bool LDSGEO = decltype(G)::value;
+            if (debug) hipLaunchKernelGGL(k_debug<LDSGEO>, dim3(fblocks), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev, fp, n, pv, render_target->data, t.stack_words);
+            else hipLaunchKernelGGL(k_falsecolor<LDSGEO>, dim3(fblocks), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev, fp, n, pv, render_target->data, t.stack_words);
+        });
         HIP_TRY(hipGetLastError());
         return LUPIN_OK;
     }
@@ -1971,7 +1981,7 @@ static int flush_pending(LupinContext *ctx)
     //   wavefronts only take LDS, registers and cache from each other: one lane, every stage with the chip to itself
     //   (bistro-class 4K, eight frames: 159 ms per step on one lane, 175 - 183 on two, 177 on three; profiles/r03_batch_matrix_short.txt).
     // * Launch-bound LDS-resident scenes are best with four lanes (Cornell box 8.0 against 7.2 Gsamples/s on one).
-    const bool lds_scene = scene->dev.geo_blob_words && ctx->lds_geometry;
+    const bool lds_scene = stages_geometry(ctx, scene);
     const int lanes = ctx->lanes_from_env ? ctx->num_lanes : std::min(lds_scene ? 4 : (K > 1 ? 1 : LP_MAX_LANES), ctx->num_lanes);
     const bool chip_to_itself = lanes == 1 || ctx->timing;
     const int w = ctx->timing ? 0 : (int)(ctx->call_index % (uint64_t)lanes);
@@ -1990,38 +2000,19 @@ static int flush_pending(LupinContext *ctx)
     const uint32_t blocks_per_shard = (blocks_needed + LP_SHARDS - 1) / LP_SHARDS;
     const uint32_t blocks = blocks_per_shard * LP_SHARDS;
     ln->pb.shard_cap = blocks_per_shard * LP_BLOCK;
-    const uint32_t stack_words = scene->stack_entries * LP_BLOCK;
-    const bool lds_geo = scene->dev.geo_blob_words && ctx->lds_geometry;
-    const size_t lds = (size_t)stack_words * sizeof(uint32_t) + (lds_geo ? (size_t)scene->dev.geo_blob_words * 16 : 0);
-    if (lds > 160 * 1024) return fail(LUPIN_ERR_INVALID_ARGUMENT, "BVH too deep for the LDS traversal stack");
+    TraversalLds t;
+    if (int trc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return trc;
 
     hipEvent_t t0 = nullptr, t1 = nullptr;
     if (ctx->timing) { t0 = get_event(ctx); t1 = get_event(ctx); hipEventRecord(t0, st); }
 
-    const uint32_t pblocks = persistent_grid(ctx, scene, pathtrace_type, lds_geo, lds, !chip_to_itself);
     Shape sh;
-    sh.blocks = blocks; sh.pblocks = pblocks; sh.lds = lds; sh.stack_words = stack_words;
-    if (pblocks && !lds_geo && scene->has_wide && ctx->wide_traversal)
-    {
-        // the wide tracer keeps (reference, distance) pairs on a bounded stack; a query that would overflow it is re-traced
-        sh.wstack_words = 2u * ctx->wide_stack_pairs * LP_BLOCK;
-        sh.wlds = (size_t)sh.wstack_words * sizeof(uint32_t);
-        sh.wblocks = wide_grid(ctx, scene, pathtrace_type, sh.wlds);
-    }
-    if (pblocks && !lds_geo && !sh.wblocks && chip_to_itself && ctx->short_stack && scene->stack_entries > ctx->short_stack)
-    {
-        // A fifth block per CU for scenes whose depth bound asks for more than 32 KB of stack per block (bistro-class: 40):
-        // the tracer is bound by latency x waves (four blocks instead of three: -18 %, five instead of four: -10 %), and the
-        // stack a query actually uses is far below the bound (bistro-class 4K: 33 of 3.5 G queries need more than 20 entries).
-        // Only with the chip to itself: sharing it, the larger tracer loses more to the other lanes' stages than it gains.
-        sh.sstack_words = ctx->short_stack * LP_BLOCK;
-        sh.slds = (size_t)sh.sstack_words * sizeof(uint32_t);
-        sh.sblocks = short_grid(ctx, scene, pathtrace_type, sh.slds);
-    }
+    sh.blocks = blocks;
+    plan_tracers(ctx, scene, pathtrace_type, chip_to_itself, t, &sh);
     ctx->last_lanes = lanes;
-    ctx->last_wide = sh.wblocks != 0;
+    ctx->last_wide = sh.wide.blocks != 0;
     ctx->last_batch = K;
-    ctx->last_short = sh.sblocks ? ctx->short_stack : 0u;
+    ctx->last_short = sh.shrt.blocks ? ctx->short_stack : 0u;
     for (uint32_t k = 0; k < K; k++)
     {
         FrameParams fk = ctx->pending[k].fp;
@@ -2040,7 +2031,7 @@ static int flush_pending(LupinContext *ctx)
         }
         if (ctx->last_lane >= 0 && ctx->last_lane != w)
             HIP_TRY(hipStreamWaitEvent(st, ctx->lanes[ctx->last_lane].done, 0));
-        HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, lds_geo, n, sh, iterations, &adaptive->dev));
+        HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations, &adaptive->dev));
     }
     else if (ctx->use_graph && !ctx->timing && !ctx->counting && !ctx->verify_wide)
     {
@@ -2048,17 +2039,18 @@ static int flush_pending(LupinContext *ctx)
         // (scene, dispatch size, integrator, buffers) and replayed: one graph launch instead of 2-4 launches per iteration.
         Lane::GraphKey key;
         key.scene_id = scene->id; key.pb_generation = ln->pb_generation; key.n = n; key.blocks = blocks; key.type = pathtrace_type;
-        key.iterations = iterations; key.stack_words = stack_words; key.lds = (uint32_t)lds; key.pblocks = pblocks;
+        key.iterations = iterations; key.stack_words = sh.binary.stack_words; key.lds = (uint32_t)sh.binary.lds; key.pblocks = sh.binary.blocks;
         key.persistent = ctx->persistent_extend;
-        key.persistent_shadow = ctx->persistent_shadow ? 1 : 0; key.lds_geometry = lds_geo ? 1 : 0;
-        key.wide_blocks = sh.wblocks ? sh.wblocks : sh.sblocks; key.wide_stack_words = sh.wblocks ? sh.wstack_words : sh.sstack_words;
+        key.persistent_shadow = ctx->persistent_shadow ? 1 : 0; key.lds_geometry = sh.lds_geo ? 1 : 0;
+        const TracerGrid &first_pass = sh.wide.blocks ? sh.wide : sh.shrt;   // at most one of the two runs
+        key.wide_blocks = first_pass.blocks; key.wide_stack_words = first_pass.stack_words;
         const bool have = ln->graph_exec && key == ln->graph_key;
         if (!have && ln->graph_exec && !(key == ln->seen_key))
         {
             // the lane holds a graph of another shape and this one is new (shapes alternate, e.g. edge tiles): capturing
             // costs about a millisecond, so launch directly and re-capture only if the shape repeats
             ln->seen_key = key;
-            HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, lds_geo, n, sh, iterations));
+            HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations));
         }
         else
         {
@@ -2067,7 +2059,7 @@ static int flush_pending(LupinContext *ctx)
                 if (ln->graph_exec) { hipGraphExecDestroy(ln->graph_exec); ln->graph_exec = nullptr; }
                 if (ln->graph) { hipGraphDestroy(ln->graph); ln->graph = nullptr; }
                 HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                hipError_t ce = enqueue_wavefront(ctx, ln, scene, pathtrace_type, lds_geo, n, sh, iterations);
+                hipError_t ce = enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations);
                 hipError_t ee = hipStreamEndCapture(st, &ln->graph);
                 if (ce != hipSuccess || ee != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(ce != hipSuccess ? ce : ee));
                 HIP_TRY(hipGraphInstantiate(&ln->graph_exec, ln->graph, nullptr, nullptr, 0));
@@ -2079,7 +2071,7 @@ static int flush_pending(LupinContext *ctx)
         }
     }
     else
-        HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, lds_geo, n, sh, iterations));
+        HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations));
     // The frames meet here: the resolve reads prev_frame and overwrites render_target, so it is ordered after everything
     // enqueued so far on the other lane (the previous call's resolve) and, for lane 1, on the primary stream (texture
     // uploads / copies).  The path state itself is private to the lane.
@@ -2245,10 +2237,11 @@ int lupin_hip_measure_copy_bandwidth(LupinContext *ctx, uint64_t bytes, uint32_t
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(sync_all(ctx));
     const size_t n = bytes / 16;
-    float4 *a = nullptr, *b = nullptr;
-    hipError_t e = hipMalloc((void **)&a, n * 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&b, n * 16);
-    if (e != hipSuccess) { if (a) hipFree(a); return fail(LUPIN_ERR_OUT_OF_MEMORY, hipGetErrorString(e)); }
+    DeviceBuffer da, db;
+    hipError_t e = DeviceBuffer::make(n * 16, &da);
+    if (e == hipSuccess) e = DeviceBuffer::make(n * 16, &db);
+    if (e != hipSuccess) return fail(LUPIN_ERR_OUT_OF_MEMORY, hipGetErrorString(e));
+    float4 *a = da.as<float4>(), *b = db.as<float4>();
     hipEvent_t e0 = get_event(ctx), e1 = get_event(ctx);
     HIP_TRY(hipMemsetAsync(a, 0x3C, n * 16, ctx->stream));
     const uint32_t blocks = (uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK);   // one 16-byte element per thread: the shape that reaches the guide's 6.29 TB/s (tools/calib/copy_probe.hip)
@@ -2261,7 +2254,6 @@ int lupin_hip_measure_copy_bandwidth(LupinContext *ctx, uint64_t bytes, uint32_t
     float ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     ctx->ev_pool.push_back(e0); ctx->ev_pool.push_back(e1);
-    hipFree(a); hipFree(b);
     *out_gb_per_s = ms > 0.0f ? 2.0 * (double)(n * 16) * reps / (ms * 1e-3) / 1e9 : 0.0;   // bytes read + bytes written
     return LUPIN_OK;
 }
@@ -2337,39 +2329,37 @@ static int trace_rays_impl(LupinContext *ctx, const LupinScene *scene, uint32_t 
     if (out_flag && !scene->has_wide) return fail(LUPIN_ERR_INVALID_ARGUMENT, "this scene has no four-wide hierarchy (it is small enough to be staged in LDS)");
     if (n == 0) return LUPIN_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    float *d_ori = nullptr, *d_dir = nullptr, *d_dst = nullptr, *d_uv = nullptr;
-    uint32_t *d_hit = nullptr, *d_inst = nullptr, *d_tri = nullptr, *d_flag = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_ori, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_dir, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_dst, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&d_uv, (size_t)n * 8));
-    HIP_TRY(hipMalloc((void **)&d_hit, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&d_inst, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&d_tri, (size_t)n * 4));
-    if (out_flag) HIP_TRY(hipMalloc((void **)&d_flag, (size_t)n * 4));
+    // stacks only: both kernels read the geometry from global memory
+    TraversalLds t;
+    if (int rc = traversal_lds(ctx, scene, out_flag ? 2u * ctx->wide_stack_pairs : scene->stack_entries, false, &t)) return rc;
+    DeviceBuffer b_ori, b_dir, b_dst, b_uv, b_hit, b_inst, b_tri, b_flag;   // freed on every path out of here
+    HIP_TRY(DeviceBuffer::make((size_t)n * 12, &b_ori));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 12, &b_dir));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &b_dst));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 8, &b_uv));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &b_hit));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &b_inst));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &b_tri));
+    if (out_flag) HIP_TRY(DeviceBuffer::make((size_t)n * 4, &b_flag));
+    float *d_ori = b_ori.as<float>(), *d_dir = b_dir.as<float>(), *d_dst = b_dst.as<float>(), *d_uv = b_uv.as<float>();
+    uint32_t *d_hit = b_hit.as<uint32_t>(), *d_inst = b_inst.as<uint32_t>(), *d_tri = b_tri.as<uint32_t>(), *d_flag = b_flag.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(d_ori, ori_xyz, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_dir, dir_xyz, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
     if (out_flag)
     {
-        const size_t lds = (size_t)ctx->wide_stack_pairs * 2u * LP_BLOCK * sizeof(uint32_t);
-        hipLaunchKernelGGL(k_trace_wide, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), lds, ctx->stream, scene->dev, n, d_ori, d_dir, ray_epsilon,
+        hipLaunchKernelGGL(k_trace_wide, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev, n, d_ori, d_dir, ray_epsilon,
                            ctx->wide_stack_pairs, d_hit, d_dst, d_uv, d_inst, d_tri, d_flag);
         HIP_TRY(hipMemcpyAsync(out_flag, d_flag, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     else
-    {
-        const size_t lds = (size_t)scene->stack_entries * LP_BLOCK * sizeof(uint32_t);
-        hipLaunchKernelGGL(k_trace, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), lds, ctx->stream, scene->dev, n, d_ori, d_dir, ray_epsilon,
+        hipLaunchKernelGGL(k_trace, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev, n, d_ori, d_dir, ray_epsilon,
                            d_hit, d_dst, d_uv, d_inst, d_tri);
-    }
     HIP_TRY(hipMemcpyAsync(out_hit, d_hit, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out_dst, d_dst, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out_uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out_instance, d_inst, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out_tri, d_tri, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    hipFree(d_ori); hipFree(d_dir); hipFree(d_dst); hipFree(d_uv); hipFree(d_hit); hipFree(d_inst); hipFree(d_tri);
-    if (d_flag) hipFree(d_flag);
     return LUPIN_OK;
 }
 
@@ -2393,23 +2383,9 @@ int lupin_hip_detmath_probe(LupinContext *ctx, int fn, uint32_t n, const float *
     if (!ctx || !x || !y || !out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return LUPIN_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    float *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void **)&dx, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dy, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-    {
-        hipLaunchKernelGGL(k_detmath, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, ctx->stream, fn, n, dx, dy, dout);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    // freed on every path (hipFree(nullptr) is a no-op)
-    hipFree(dx); hipFree(dy); hipFree(dout);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("lupin_hip_detmath_probe: ") + hipGetErrorString(e));
-    return LUPIN_OK;
+    return run_probe(ctx, "lupin_hip_detmath_probe", {{x, (size_t)n * 4}, {y, (size_t)n * 4}}, out, (size_t)n * 4, [&](const DeviceBuffer *in, float *dout) {
+        hipLaunchKernelGGL(k_detmath, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, ctx->stream, fn, n, in[0].as<float>(), in[1].as<float>(), dout);
+    });
 }
 
 int lupin_hip_scatter_probe(LupinContext *ctx, uint32_t n, const float *records, float *out)
@@ -2419,21 +2395,9 @@ int lupin_hip_scatter_probe(LupinContext *ctx, uint32_t n, const float *records,
     if (n == 0) return LUPIN_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t in_bytes = (size_t)n * LUPIN_SCATTER_IN_FLOATS * 4, out_bytes = (size_t)n * LUPIN_SCATTER_OUT_FLOATS * 4;
-    float *din = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void **)&din, in_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, out_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(din, records, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-    {
-        hipLaunchKernelGGL(k_scatter_probe, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, ctx->stream, n, din, dout);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    // freed on every path (hipFree(nullptr) is a no-op)
-    hipFree(din); hipFree(dout);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("lupin_hip_scatter_probe: ") + hipGetErrorString(e));
-    return LUPIN_OK;
+    return run_probe(ctx, "lupin_hip_scatter_probe", {{records, in_bytes}}, out, out_bytes, [&](const DeviceBuffer *in, float *dout) {
+        hipLaunchKernelGGL(k_scatter_probe, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, ctx->stream, n, in[0].as<float>(), dout);
+    });
 }
 
 int lupin_hip_light_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n, const float *records, float *out)
@@ -2443,29 +2407,16 @@ int lupin_hip_light_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n
     if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context");
     if (n == 0) return LUPIN_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t stack_words = scene->stack_entries * LP_BLOCK;
-    const bool lds_geo = scene->dev.geo_blob_words && ctx->lds_geometry;
-    const size_t lds = (size_t)stack_words * sizeof(uint32_t) + (lds_geo ? (size_t)scene->dev.geo_blob_words * 16 : 0);
-    if (lds > 160 * 1024) return fail(LUPIN_ERR_INVALID_ARGUMENT, "BVH too deep for the LDS traversal stack");
+    TraversalLds t;
+    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
     join_primary(ctx);   // recorded calls run first
     const size_t in_bytes = (size_t)n * LUPIN_LIGHT_IN_FLOATS * 4, out_bytes = (size_t)n * LUPIN_LIGHT_OUT_FLOATS * 4;
-    float *din = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void **)&din, in_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, out_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(din, records, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-    {
-        const dim3 grid((n + LP_BLOCK - 1) / LP_BLOCK), block(LP_BLOCK);
-        if (lds_geo) hipLaunchKernelGGL(k_light_probe<true>, grid, block, lds, ctx->stream, scene->dev, n, din, dout, stack_words);
-        else hipLaunchKernelGGL(k_light_probe<false>, grid, block, lds, ctx->stream, scene->dev, n, din, dout, stack_words);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    // freed on every path (hipFree(nullptr) is a no-op)
-    hipFree(din); hipFree(dout);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("lupin_hip_light_probe: ") + hipGetErrorString(e));
-    return LUPIN_OK;
+    return run_probe(ctx, "lupin_hip_light_probe", {{records, in_bytes}}, out, out_bytes, [&](const DeviceBuffer *in, float *dout) {
+        with_bool(t.geo, [&](auto G) {
+            hipLaunchKernelGGL(k_light_probe<decltype(G)::value>, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev, n,
+                               in[0].as<float>(), dout, t.stack_words);
+        });
+    });
 }
 
 int lupin_hip_surface_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n, const float *records, float *out)
@@ -2494,27 +2445,16 @@ int lupin_hip_surface_probe(LupinContext *ctx, const LupinScene *scene, uint32_t
         }
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    const bool lds_geo = scene->dev.geo_blob_words && ctx->lds_geometry;
-    const size_t lds = lds_geo ? (size_t)scene->dev.geo_blob_words * 16 : 0;
+    TraversalLds t;   // the staged geometry, if any: this kernel never traverses
+    if (int rc = traversal_lds(ctx, scene, 0, true, &t)) return rc;
     join_primary(ctx);   // recorded calls run first
     const size_t in_bytes = (size_t)n * LUPIN_SURFACE_IN_FLOATS * 4, out_bytes = (size_t)n * LUPIN_SURFACE_OUT_FLOATS * 4;
-    float *din = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc((void **)&din, in_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, out_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(din, records, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-    {
-        const dim3 grid((n + LP_BLOCK - 1) / LP_BLOCK), block(LP_BLOCK);
-        if (lds_geo) hipLaunchKernelGGL(k_surface_probe<true>, grid, block, lds, ctx->stream, scene->dev, n, din, dout);
-        else hipLaunchKernelGGL(k_surface_probe<false>, grid, block, lds, ctx->stream, scene->dev, n, din, dout);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    // freed on every path (hipFree(nullptr) is a no-op)
-    hipFree(din); hipFree(dout);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("lupin_hip_surface_probe: ") + hipGetErrorString(e));
-    return LUPIN_OK;
+    return run_probe(ctx, "lupin_hip_surface_probe", {{records, in_bytes}}, out, out_bytes, [&](const DeviceBuffer *in, float *dout) {
+        with_bool(t.geo, [&](auto G) {
+            hipLaunchKernelGGL(k_surface_probe<decltype(G)::value>, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev, n,
+                               in[0].as<float>(), dout);
+        });
+    });
 }
 
 static int pack_common(LupinContext *ctx, const LupinTexture *tex, uint32_t tile_size, uint32_t rank, uint32_t world, void *packed, int unpack)

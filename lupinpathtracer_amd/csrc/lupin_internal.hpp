@@ -2,7 +2,32 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
+#include <utility>
 #include "../../include/lupin_hip.h"
+
+// A scratch device allocation that lives as long as its holder: hipMalloc in make(), hipFree in the destructor.  Move-only.
+class DeviceBuffer
+{
+    void *p_ = nullptr;
+
+public:
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { std::swap(p_, o.p_); return *this; }   // o's destructor frees what this held
+    ~DeviceBuffer() { if (p_) hipFree(p_); }
+    // *out holds `bytes` of device memory, or stays as it was if the allocation fails
+    static hipError_t make(size_t bytes, DeviceBuffer *out)
+    {
+        DeviceBuffer b;
+        const hipError_t e = hipMalloc(&b.p_, bytes);
+        if (e == hipSuccess) *out = std::move(b);
+        return e;
+    }
+    void *get() const { return p_; }
+    template <typename T> T *as() const { return static_cast<T *>(p_); }
+};
 
 struct LupinTexture
 {

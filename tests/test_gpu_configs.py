@@ -174,7 +174,7 @@ def test_work_counting_does_not_change_the_image(gpu_ctx):
     res = api.build_pathtrace_resources(gpu_ctx, api.BakedPathtraceParams(max_bounces=8, samples_per_pixel=4))
     desc = api.PathtraceDesc(camera_params=cam.params, camera_transform=cam.transform)
     a, b = api.Texture(gpu_ctx, W, H), api.Texture(gpu_ctx, W, H)
-    for ptype in (0, 1, 3):
+    for ptype in (0, 1, 2, 3):
         gpu_ctx.stats_reset(0)
         api.pathtrace_scene(gpu_ctx, res, scene, a, ptype, desc)
         plain = gpu_ctx.stats()
