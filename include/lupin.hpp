@@ -518,6 +518,27 @@ inline void pathtrace_scene_adaptive(const Device &d, const PathtraceResources &
     check(lupin_hip_pathtrace_scene_adaptive(d.raw(), res.raw(), scene.raw(), render_target.raw(), (uint32_t)type, &c, ares.raw(), &p));
 }
 
+
+// radiance queries (no reference counterpart): the integrators over caller-supplied rays
+enum class RayMode : uint32_t { Direction = LUPIN_RAY_DIRECTION, CosineHemisphere = LUPIN_RAY_COSINE_HEMISPHERE };
+struct RayQueryDesc
+{
+    PathtraceType pathtrace_type = PathtraceType::Standard;
+    uint32_t max_bounces = 8;
+    uint32_t samples = 1;
+    uint32_t flags = 0;            // LUPIN_RAYS_DEVICE_POINTERS: records, out and out_rays are device memory
+    uint32_t max_slots = 0;        // paths per wavefront; 0 = the library's default
+    AdvancedParams advanced;
+};
+// records: n x 8 floats (origin | RNG bits, direction or normal | mode bits); out: n x 4; out_rays: nullptr or n * samples x 8
+inline void pathtrace_rays(const Device &d, const Scene &scene, const RayQueryDesc &desc, uint64_t n, const float *records, float *out,
+                           float *out_rays = nullptr)
+{
+    const LupinRayQueryDesc c{(uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.flags, desc.max_slots,
+                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
+    check(lupin_hip_pathtrace_rays(d.raw(), scene.raw(), &c, n, records, out, out_rays));
+}
+
 }  // namespace lp
 
 namespace lpl {

@@ -733,6 +733,55 @@ typedef enum LupinSurfaceMode
 } LupinSurfaceMode;
 int lupin_hip_surface_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n, const float *records, float *out);
 
+/* ---- radiance queries (no reference counterpart) ----
+ * The full integrators over caller-supplied rays: the radiance arriving along each ray, or at a surface point over its
+ * cosine-weighted hemisphere, instead of a camera pixel's texel.
+ *
+ * Record, LUPIN_RAY_RECORD_FLOATS floats ("bits": the u32's bits stored in the float's place, not a float value):
+ *   [0..2] origin   [3] RNG state (bits)   [4..6] unit direction (mode 0) or unit surface normal (mode 1)   [7] mode (bits)
+ * Result, LUPIN_RAY_RESULT_FLOATS floats: r, g, b, 1.0f -- the mean of the `samples` per-path radiances, each clamped at
+ * advanced.max_radiance as a pixel's samples are, summed in f32 in sample order from zero and divided by (float)samples.
+ * Path s of record i is slot i * samples + s.  Its RNG state is the record's word for s == 0 and
+ * hash_u32(word + s * 0x9E3779B9) otherwise; it starts at bounce 0, outside any medium, exactly as a camera path does.
+ *   LUPIN_RAY_DIRECTION          the direction as given
+ *   LUPIN_RAY_COSINE_HEMISPHERE  two numbers drawn from the slot's RNG state, then the matte BSDF's cosine-weighted
+ *                                direction about the normal; the origin is the record's (offset it off the surface)
+ * out_rays (NULL, or n * samples records): every slot's first ray and its RNG state after the ray's generation, as a mode-0
+ * record; querying such a record with samples = 1 replays that one path.
+ *
+ * The call runs the calls recorded on the context first (and returns their error, if any), then its own wavefronts one
+ * after another, and returns when `out` is complete.  (The recorded calls run once the descriptor and the pointers have
+ * passed their checks and before the records, the hierarchy's depth and device pointers' contents are looked at: a call
+ * refused for those has still run them, one refused for its descriptor or a null pointer has not.)  A wavefront carries at
+ * most desc->max_slots paths (0: LUPIN_RAYS_DEFAULT_MAX_SLOTS), rounded down to whole records, at least one record; the path state is sized for that, not for
+ * n * samples.  Frames rendered before and after are what they would be without the call.
+ *
+ * With LUPIN_RAYS_DEVICE_POINTERS in desc->flags, records, out and out_rays are device memory of the context's device,
+ * 16-byte aligned, and the caller has finished writing the records; nothing is copied to or from the host.
+ *
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing traced and `out` untouched, for: a NULL argument; an unknown pathtrace_type, flag or
+ * record mode; samples == 0 or above 2^27; max_bounces >= 4095; n * samples above 2^38; a scene of another or of a destroyed
+ * context; a record with a non-finite origin, direction or normal; a direction or normal whose squared length is further
+ * than 1e-4 from 1; a hierarchy too deep for the traversal stack (as a render).  Host records are checked on the host,
+ * device records by a kernel whose count the host reads before the first wavefront.  n == 0: LUPIN_OK, nothing touched.
+ * Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_RAY_RECORD_FLOATS 8
+#define LUPIN_RAY_RESULT_FLOATS 4
+#define LUPIN_RAYS_DEFAULT_MAX_SLOTS 4194304u   /* paths per wavefront when desc.max_slots is 0: 1.3 GB of path state */
+enum { LUPIN_RAY_DIRECTION = 0, LUPIN_RAY_COSINE_HEMISPHERE = 1 };      /* record mode */
+enum { LUPIN_RAYS_DEVICE_POINTERS = 1u };                               /* desc.flags  */
+typedef struct LupinRayQueryDesc {
+    uint32_t pathtrace_type;        /* LupinPathtraceType, all four */
+    uint32_t max_bounces;           /* not taken from LupinPathtraceResources: no resources object is needed */
+    uint32_t samples;               /* S >= 1 paths per record */
+    uint32_t flags;
+    uint32_t max_slots;             /* 0 = library default; paths per wavefront */
+    LupinAdvancedParams advanced;   /* max_radiance, ray_epsilon as in pathtrace_scene */
+} LupinRayQueryDesc;
+int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const LupinRayQueryDesc *desc,
+                             uint64_t n, const float *records /* n x 8 */, float *out /* n x 4 */,
+                             float *out_rays /* NULL, or n*S x 8 */);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

@@ -71,6 +71,13 @@ pub const LUPIN_DENOISE_HIGH: u32 = 2;
 #[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinAdaptiveStats {
     pub active_pixels: u64, pub pixel_frames: u64, pub calls: u32, pub max_frames_taken: u32,
 }
+// radiance queries (no reference counterpart)
+pub const LUPIN_RAY_DIRECTION: u32 = 0;
+pub const LUPIN_RAY_COSINE_HEMISPHERE: u32 = 1;
+pub const LUPIN_RAYS_DEVICE_POINTERS: u32 = 1;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinRayQueryDesc {
+    pub pathtrace_type: u32, pub max_bounces: u32, pub samples: u32, pub flags: u32, pub max_slots: u32, pub advanced: LupinAdvancedParams,
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -142,6 +149,9 @@ extern "C" {
     pub fn lupin_hip_adaptive_stats(ctx: *mut LupinContext, ares: *const LupinAdaptiveResources, out: *mut LupinAdaptiveStats) -> c_int;
     pub fn lupin_hip_adaptive_download(ctx: *mut LupinContext, ares: *const LupinAdaptiveResources, frames: *mut u32, moments: *mut f32,
                                        block_error: *mut f32, block_active: *mut u8) -> c_int;
+    // radiance queries: the integrators over n caller-supplied rays (records n x 8 f32, out n x 4, out_rays null or n * samples x 8)
+    pub fn lupin_hip_pathtrace_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinRayQueryDesc, n: u64,
+                                    records: *const f32, out: *mut f32, out_rays: *mut f32) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

@@ -145,6 +145,11 @@ class AdaptiveStatsC(C.Structure):   # LupinAdaptiveStats
     _fields_ = [("active_pixels", C.c_uint64), ("pixel_frames", C.c_uint64), ("calls", C.c_uint32), ("max_frames_taken", C.c_uint32)]
 
 
+class RayQueryDescC(C.Structure):   # LupinRayQueryDesc
+    _fields_ = [("pathtrace_type", C.c_uint32), ("max_bounces", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32),
+                ("max_slots", C.c_uint32), ("advanced", AdvancedParamsC)]
+
+
 class TlasBuildStatsC(C.Structure):   # LupinTlasBuildStats
     _fields_ = [("num_instances", C.c_uint32), ("state_in_lds", C.c_uint32), ("scans", C.c_uint64), ("kernel_ms", C.c_float)]
 
@@ -214,6 +219,7 @@ SYMBOLS = [
     ("lupin_hip_scatter_probe", C.c_int, [_P, _U32, _P, _P]),
     ("lupin_hip_light_probe", C.c_int, [_P, _P, _U32, _P, _P]),
     ("lupin_hip_surface_probe", C.c_int, [_P, _P, _U32, _P, _P]),
+    ("lupin_hip_pathtrace_rays", C.c_int, [_P, _P, C.POINTER(RayQueryDescC), C.c_uint64, _P, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),

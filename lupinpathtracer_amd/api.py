@@ -1225,3 +1225,114 @@ def surface_probe(ctx, scene, records):
     out = np.zeros((len(rec), SURFACE_OUT_FLOATS), np.float32)
     check(lib().lupin_hip_surface_probe(ctx.handle, scene.handle, len(rec), ptr(rec), ptr(out)))
     return out
+
+
+# ---- radiance queries: lupin_hip_pathtrace_rays (include/lupin_hip.h) ----
+RAY_RECORD_FLOATS = 8
+RAY_RESULT_FLOATS = 4
+RAYS_DEVICE_POINTERS = 1
+RAYS_DEFAULT_MAX_SLOTS = 1 << 22   # LUPIN_RAYS_DEFAULT_MAX_SLOTS: paths per wavefront when RayQueryDesc.max_slots is 0
+
+
+class RayMode(enum.IntEnum):
+    DIRECTION = 0            # floats 4..6 are the ray's unit direction
+    COSINE_HEMISPHERE = 1    # floats 4..6 are a unit surface normal; the direction is cosine-sampled about it
+
+
+@dataclass
+class RayQueryDesc:  # LupinRayQueryDesc
+    pathtrace_type: int = PathtraceType.Standard
+    max_bounces: int = 8
+    samples: int = 1
+    flags: int = 0
+    max_slots: int = 0       # paths per wavefront; 0 = the library's default
+    advanced: AdvancedParams = field(default_factory=AdvancedParams)
+
+
+def _hash_u32(x):
+    """hash_u32 of the device (pathtracer.wgsl:1561-1570) on uint32 arrays."""
+    x = np.asarray(x, np.uint32).copy()
+    with np.errstate(over="ignore"):
+        x ^= x >> np.uint32(17); x *= np.uint32(0xed5ad4bb)
+        x ^= x >> np.uint32(11); x *= np.uint32(0xac4c1b51)
+        x ^= x >> np.uint32(15); x *= np.uint32(0x31848bab)
+        x ^= x >> np.uint32(14)
+    return x
+
+
+def rng_seed_for(index, counter=0):
+    """The device's rng_seed_for in numpy: the u32 RNG state a pixel with linear index `index` starts a frame of
+    accum_counter `counter` with.  Scalars or arrays; seeds records the way pixels are seeded."""
+    index = np.asarray(index, np.uint32)
+    counter = np.asarray(counter, np.uint32)
+    with np.errstate(over="ignore"):
+        return _hash_u32((index * np.uint32(19349663)) ^ (counter * np.uint32(83492791)))
+
+
+def ray_sample_seed(word, s):
+    """RNG state of path `s` of a record whose RNG word is `word`: the word itself for s == 0, hash_u32(word + s * 0x9E3779B9)
+    otherwise."""
+    word = np.asarray(word, np.uint32)
+    s = np.asarray(s, np.uint32)
+    with np.errstate(over="ignore"):
+        return np.where(s == 0, word, _hash_u32(word + s * np.uint32(0x9E3779B9))).astype(np.uint32)
+
+
+def ray_records(ori, dir_or_normal, rng=0, mode=RayMode.DIRECTION):
+    """(n, RAY_RECORD_FLOATS) float32 records for pathtrace_rays: `ori` (n, 3); `dir_or_normal` (n, 3), the unit direction
+    (mode DIRECTION) or the unit surface normal (mode COSINE_HEMISPHERE); `rng` u32 states and `mode`, scalars or (n,)
+    arrays, both stored as bits."""
+    ori = np.asarray(ori, np.float32).reshape(-1, 3)
+    rec = np.zeros((len(ori), RAY_RECORD_FLOATS), np.float32)
+    rec[:, 0:3] = ori
+    rec[:, 4:7] = np.asarray(dir_or_normal, np.float32).reshape(-1, 3)
+    rec.view(np.uint32)[:, 3] = np.asarray(rng, np.uint32)
+    rec.view(np.uint32)[:, 7] = np.asarray(mode, np.uint32)
+    return rec
+
+
+def pathtrace_rays(ctx, scene, records, desc: Optional[RayQueryDesc] = None, want_rays=False):
+    """The radiance along (or, mode COSINE_HEMISPHERE, arriving at) every record: (n, 4) r, g, b, 1 -- the mean over
+    desc.samples paths per record.  `records` is an (n, RAY_RECORD_FLOATS) float32 numpy array (see ray_records), or a
+    contiguous float32 torch tensor on the context's device: then torch's current stream is synchronised, the tensors' device
+    memory is used in place and tensors are returned.  With want_rays also the (n * samples, RAY_RECORD_FLOATS) first rays,
+    as mode-DIRECTION records that replay one path each.  Blocks until the result is complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "pathtrace_rays needs a GPU context and an uploaded scene; there is no CPU fallback")
+    desc = desc or RayQueryDesc()
+    flags = int(desc.flags)
+    c = _abi.RayQueryDescC(int(desc.pathtrace_type), int(desc.max_bounces), int(desc.samples), flags, int(desc.max_slots),
+                           _abi.AdvancedParamsC(desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon))
+    if hasattr(records, "data_ptr"):   # a torch tensor
+        import torch
+        t = records
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == RAY_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+        if t.device.index != ctx.device_ordinal:
+            raise ValueError("records are on another device than the context")
+        n = int(t.shape[0])
+        out = torch.zeros((n, RAY_RESULT_FLOATS), dtype=torch.float32, device=t.device)
+        rays = torch.zeros((n * int(desc.samples), RAY_RECORD_FLOATS), dtype=torch.float32, device=t.device) if want_rays else None
+        torch.cuda.current_stream(t.device).synchronize()   # the records (and the zero fills) are written
+        c.flags = flags | RAYS_DEVICE_POINTERS
+        check(lib().lupin_hip_pathtrace_rays(ctx.handle, scene.handle, C.byref(c), n, C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(rays.data_ptr()) if want_rays else None))
+        return (out, rays) if want_rays else out
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, RAY_RECORD_FLOATS)
+    out = np.zeros((len(rec), RAY_RESULT_FLOATS), np.float32)
+    rays = np.zeros((len(rec) * int(desc.samples), RAY_RECORD_FLOATS), np.float32) if want_rays else None
+    check(lib().lupin_hip_pathtrace_rays(ctx.handle, scene.handle, C.byref(c), len(rec), ptr(rec), ptr(out), ptr(rays)))
+    return (out, rays) if want_rays else out
+
+
+def bake_irradiance(ctx, scene, points, normals, samples=64, pathtrace_type=PathtraceType.Standard, max_bounces=8, advanced=None,
+                    counter=0, max_slots=0):
+    """Irradiance (n, 3) at `points` (n, 3) with unit `normals` (n, 3): pi * the mean radiance over `samples` cosine-weighted
+    paths per point (mode COSINE_HEMISPHERE records, point i seeded with rng_seed_for(i, counter)).
+    The paths start AT the points given: the caller offsets them off the surface (along the normal, by more than
+    advanced.ray_epsilon times the scene's scale), or the first ray may hit the surface it starts on."""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    rec = ray_records(points, normals, rng_seed_for(np.arange(len(points), dtype=np.uint32), counter), RayMode.COSINE_HEMISPHERE)
+    desc = RayQueryDesc(pathtrace_type, max_bounces, samples, 0, max_slots, advanced or AdvancedParams())
+    out = pathtrace_rays(ctx, scene, rec, desc)
+    return np.float32(np.pi) * out[:, :3]
