@@ -539,6 +539,41 @@ inline void pathtrace_rays(const Device &d, const Scene &scene, const RayQueryDe
     check(lupin_hip_pathtrace_rays(d.raw(), scene.raw(), &c, n, records, out, out_rays));
 }
 
+// lightmap baking (no reference counterpart): the charts' triangles rasterised to texels, every owned texel
+// path-traced over its hemisphere
+struct LightmapChart
+{
+    uint32_t instance_idx = 0;
+    float scale_u = 1.0f, scale_v = 1.0f, offset_u = 0.0f, offset_v = 0.0f;   // atlas uv = mesh uv * scale + offset
+};
+struct LightmapDesc
+{
+    uint32_t width = 0, height = 0;
+    PathtraceType pathtrace_type = PathtraceType::Standard;
+    uint32_t max_bounces = 8;
+    uint32_t samples = 64;
+    uint32_t max_slots = 0;
+    uint32_t flags = 0;            // LUPIN_LIGHTMAP_SMOOTH_NORMALS
+    uint32_t dilate = 0;           // gutter passes
+    uint32_t counter = 0;
+    float surface_offset = 0.0f;   // world units along the geometric normal; the caller chooses (> 0)
+    AdvancedParams advanced;
+};
+// out_rgba: height x width x 4 floats; out_records: nullptr or height x width x 8; returns the number of owned texels
+inline uint64_t bake_lightmap(const Device &d, const Scene &scene, const LightmapDesc &desc, const LightmapChart *charts, uint32_t num_charts,
+                              float *out_rgba, float *out_records = nullptr)
+{
+    const LupinLightmapDesc c{desc.width, desc.height, (uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.max_slots, desc.flags,
+                              desc.dilate, desc.counter, desc.surface_offset,
+                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
+    std::vector<LupinLightmapChart> cc(num_charts);
+    for (uint32_t k = 0; k < num_charts; k++)
+        cc[k] = LupinLightmapChart{charts[k].instance_idx, charts[k].scale_u, charts[k].scale_v, charts[k].offset_u, charts[k].offset_v};
+    uint64_t covered = 0;
+    check(lupin_hip_bake_lightmap(d.raw(), scene.raw(), &c, cc.data(), num_charts, out_rgba, out_records, &covered));
+    return covered;
+}
+
 }  // namespace lp
 
 namespace lpl {

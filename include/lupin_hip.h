@@ -782,6 +782,79 @@ int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const L
                              uint64_t n, const float *records /* n x 8 */, float *out /* n x 4 */,
                              float *out_rays /* NULL, or n*S x 8 */);
 
+/* ---- lightmap baking (no reference counterpart) ----
+ * Irradiance on the scene's surfaces, laid out by the meshes' texcoords: every chart places one instance's UVs in the atlas
+ * (atlas uv = mesh uv * scale + offset), its triangles are rasterised to texels, and every owned texel is path-traced over
+ * the cosine-weighted hemisphere of the surface point its centre maps to, with `samples` paths, by the radiance query above.
+ *
+ * Rasterisation, every operation one rounded f32 operation (no contraction).  Vertex k of a triangle in texel space is
+ * t_k = ((u_k * scale_u + offset_u) * W, (v_k * scale_v + offset_v) * H); texel (x, y) has the centre c = (x + 0.5, y + 0.5),
+ * row 0 is v in [0, 1/H) (no flip).  edge(a, b, p) = (b.x-a.x)*(p.y-a.y) - (b.y-a.y)*(p.x-a.x); area2 = edge(t0, t1, t2);
+ * a triangle with a non-finite UV or with area2 zero or not finite is skipped.  e0 = edge(t1, t2, c), e1 = edge(t2, t0, c),
+ * e2 = edge(t0, t1, c), all four negated when area2 < 0; the centre is covered when e0, e1, e2 >= 0; u = e1 / area2,
+ * v = e2 / area2, weights 1-u-v, u, v.  Only the texels of the triangle's bounding box are looked at: columns
+ * floor(clamp(min x, 0, W)) .. min(floor(clamp(max x, 0, W)), W - 1), rows alike -- clamped in float, so UVs of 1e30 or
+ * below zero cover nothing inside and never reach an integer.  A covered centre belongs to the smallest key among the
+ * triangles covering it; the key of triangle t of chart c is the sum of the triangle counts of the charts before c, plus t
+ * (t in the scene's own triangle order: that of the indices handed to lupin_hip_scene_create).
+ *
+ * The record of an owned texel (a mode-1 record of the query): local point v0*w + v1*u + v2*v, to world through the inverse
+ * of the instance's world -> local affine as light sampling computes it; n_g = the geometric normal, reference winding;
+ * n = n_g, or with LUPIN_LIGHTMAP_SMOOTH_NORMALS on a mesh with normals the interpolated vertex normal in world space,
+ * negated if n . n_g < 0 (normal maps are not applied); origin = world + n_g * surface_offset; RNG word =
+ * rng_seed_for(y * W + x, counter).  Records are traced in ascending texel order, empty texels cost no paths.
+ *
+ * out_rgba (H x W x 4, host): pi * the query's mean radiance and alpha 1.0f on owned texels, zeros elsewhere; then
+ * `dilate` gutter passes: a texel not filled yet takes the f32 mean of its filled 8-neighbours (summed dy -1..1 outer,
+ * dx -1..1 inner, divided by their count) and counts as filled from the next pass on; its alpha stays 0.
+ * out_records (NULL, or H x W x 8, host): every owned texel's record at its place, zeros elsewhere.
+ * out_num_covered (NULL ok): the number of owned texels.
+ *
+ * Ordering as lupin_hip_pathtrace_rays: recorded calls run first (their error is returned), the call returns when out_rgba
+ * is complete, frames before and after are unchanged.  LUPIN_ERR_INVALID_ARGUMENT with the outputs untouched for: a NULL
+ * argument (out_records and out_num_covered may be NULL); width or height 0 or above LUPIN_LIGHTMAP_MAX_SIZE;
+ * num_charts == 0; an instance index out of range; a mesh without texcoords; a non-finite scale or offset; surface_offset not
+ * finite and positive; an unknown flag; dilate above LUPIN_LIGHTMAP_MAX_DILATE; 2^32 - 1 or more (chart, triangle) pairs;
+ * everything the query refuses (among it a record whose normal is not finite: a triangle with UV area but without area in
+ * space).  An atlas without an owned texel: LUPIN_OK, all zeros.  Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_LIGHTMAP_MAX_SIZE 16384u
+#define LUPIN_LIGHTMAP_MAX_DILATE 64u
+enum { LUPIN_LIGHTMAP_SMOOTH_NORMALS = 1u };                            /* desc.flags */
+typedef struct LupinLightmapChart {     /* one instance's place in the atlas */
+    uint32_t instance_idx;
+    float scale_u;
+    float scale_v;
+    float offset_u;
+    float offset_v;
+} LupinLightmapChart;
+typedef struct LupinLightmapDesc {
+    uint32_t width;                 /* atlas texels, 1 .. LUPIN_LIGHTMAP_MAX_SIZE */
+    uint32_t height;
+    uint32_t pathtrace_type;        /* as LupinRayQueryDesc */
+    uint32_t max_bounces;
+    uint32_t samples;
+    uint32_t max_slots;
+    uint32_t flags;
+    uint32_t dilate;                /* gutter passes, 0 .. LUPIN_LIGHTMAP_MAX_DILATE */
+    uint32_t counter;               /* seeds: rng_seed_for(texel linear index, counter) */
+    float surface_offset;           /* world units along the geometric normal; finite, > 0 */
+    LupinAdvancedParams advanced;
+} LupinLightmapDesc;
+int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc,
+                            const LupinLightmapChart *charts, uint32_t num_charts, float *out_rgba /* H*W*4 */,
+                            float *out_records /* NULL, or H*W*8 */, uint64_t *out_num_covered /* NULL ok */);
+/* The calling thread's latest successful bake, host-clock milliseconds of its phases (each ends synchronised). */
+typedef struct LupinLightmapStats {
+    uint64_t covered_texels;
+    uint32_t keys;                  /* (chart, triangle) pairs rasterised */
+    float raster_ms;
+    float compact_ms;               /* count, scan, emit */
+    float trace_ms;                 /* the radiance query */
+    float scatter_dilate_ms;
+    float download_ms;
+} LupinLightmapStats;
+void lupin_hip_lightmap_stats(LupinLightmapStats *out);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

@@ -78,6 +78,18 @@ pub const LUPIN_RAYS_DEVICE_POINTERS: u32 = 1;
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinRayQueryDesc {
     pub pathtrace_type: u32, pub max_bounces: u32, pub samples: u32, pub flags: u32, pub max_slots: u32, pub advanced: LupinAdvancedParams,
 }
+// lightmap baking (no reference counterpart)
+pub const LUPIN_LIGHTMAP_SMOOTH_NORMALS: u32 = 1;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmapChart {
+    pub instance_idx: u32, pub scale_u: f32, pub scale_v: f32, pub offset_u: f32, pub offset_v: f32,
+}
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmapDesc {
+    pub width: u32, pub height: u32, pub pathtrace_type: u32, pub max_bounces: u32, pub samples: u32, pub max_slots: u32, pub flags: u32,
+    pub dilate: u32, pub counter: u32, pub surface_offset: f32, pub advanced: LupinAdvancedParams,
+}
+#[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinLightmapStats {
+    pub covered_texels: u64, pub keys: u32, pub raster_ms: f32, pub compact_ms: f32, pub trace_ms: f32, pub scatter_dilate_ms: f32, pub download_ms: f32,
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -152,6 +164,11 @@ extern "C" {
     // radiance queries: the integrators over n caller-supplied rays (records n x 8 f32, out n x 4, out_rays null or n * samples x 8)
     pub fn lupin_hip_pathtrace_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinRayQueryDesc, n: u64,
                                     records: *const f32, out: *mut f32, out_rays: *mut f32) -> c_int;
+    // lightmap baking: out_rgba height x width x 4 f32, out_records null or height x width x 8, out_num_covered null ok
+    pub fn lupin_hip_bake_lightmap(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinLightmapDesc,
+                                   charts: *const LupinLightmapChart, num_charts: u32, out_rgba: *mut f32, out_records: *mut f32,
+                                   out_num_covered: *mut u64) -> c_int;
+    pub fn lupin_hip_lightmap_stats(out: *mut LupinLightmapStats);
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

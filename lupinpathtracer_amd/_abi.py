@@ -150,6 +150,21 @@ class RayQueryDescC(C.Structure):   # LupinRayQueryDesc
                 ("max_slots", C.c_uint32), ("advanced", AdvancedParamsC)]
 
 
+class LightmapChartC(C.Structure):   # LupinLightmapChart
+    _fields_ = [("instance_idx", C.c_uint32), ("scale_u", C.c_float), ("scale_v", C.c_float), ("offset_u", C.c_float), ("offset_v", C.c_float)]
+
+
+class LightmapDescC(C.Structure):   # LupinLightmapDesc
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("pathtrace_type", C.c_uint32), ("max_bounces", C.c_uint32),
+                ("samples", C.c_uint32), ("max_slots", C.c_uint32), ("flags", C.c_uint32), ("dilate", C.c_uint32), ("counter", C.c_uint32),
+                ("surface_offset", C.c_float), ("advanced", AdvancedParamsC)]
+
+
+class LightmapStatsC(C.Structure):   # LupinLightmapStats
+    _fields_ = [("covered_texels", C.c_uint64), ("keys", C.c_uint32), ("raster_ms", C.c_float), ("compact_ms", C.c_float),
+                ("trace_ms", C.c_float), ("scatter_dilate_ms", C.c_float), ("download_ms", C.c_float)]
+
+
 class TlasBuildStatsC(C.Structure):   # LupinTlasBuildStats
     _fields_ = [("num_instances", C.c_uint32), ("state_in_lds", C.c_uint32), ("scans", C.c_uint64), ("kernel_ms", C.c_float)]
 
@@ -220,6 +235,8 @@ SYMBOLS = [
     ("lupin_hip_light_probe", C.c_int, [_P, _P, _U32, _P, _P]),
     ("lupin_hip_surface_probe", C.c_int, [_P, _P, _U32, _P, _P]),
     ("lupin_hip_pathtrace_rays", C.c_int, [_P, _P, C.POINTER(RayQueryDescC), C.c_uint64, _P, _P, _P]),
+    ("lupin_hip_bake_lightmap", C.c_int, [_P, _P, C.POINTER(LightmapDescC), C.POINTER(LightmapChartC), _U32, _P, _P, C.POINTER(C.c_uint64)]),
+    ("lupin_hip_lightmap_stats", None, [C.POINTER(LightmapStatsC)]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),

@@ -1336,3 +1336,89 @@ def bake_irradiance(ctx, scene, points, normals, samples=64, pathtrace_type=Path
     desc = RayQueryDesc(pathtrace_type, max_bounces, samples, 0, max_slots, advanced or AdvancedParams())
     out = pathtrace_rays(ctx, scene, rec, desc)
     return np.float32(np.pi) * out[:, :3]
+
+
+# ---- lightmap baking: lupin_hip_bake_lightmap (include/lupin_hip.h) ----
+LIGHTMAP_SMOOTH_NORMALS = 1
+LIGHTMAP_MAX_SIZE = 16384
+LIGHTMAP_MAX_DILATE = 64
+LIGHTMAP_OFFSET_FRACTION = 1e-4   # default surface_offset: this fraction of the scene's largest world extent
+
+
+@dataclass
+class LightmapChart:  # LupinLightmapChart: atlas uv = mesh uv * scale + offset
+    instance_idx: int = 0
+    scale_u: float = 1.0
+    scale_v: float = 1.0
+    offset_u: float = 0.0
+    offset_v: float = 0.0
+
+
+@dataclass
+class LightmapDesc:  # LupinLightmapDesc
+    width: int = 0
+    height: int = 0
+    pathtrace_type: int = PathtraceType.Standard
+    max_bounces: int = 8
+    samples: int = 64
+    max_slots: int = 0
+    flags: int = 0
+    dilate: int = 0
+    counter: int = 0
+    surface_offset: float = 0.0
+    advanced: AdvancedParams = field(default_factory=AdvancedParams)
+
+
+def scene_world_extent(scene):
+    """The largest side of the box around the scene's instances in world space, from the model boxes the TLAS was built
+    from: every instance's eight box corners through the inverse of its world -> local affine.  0.0 for an empty scene."""
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    for inst in scene.instances:
+        box = np.asarray(scene.model_aabbs[int(inst["mesh_idx"])], np.float64)
+        if not np.all(box[:3] <= box[3:]):
+            continue   # Aabb::neutral(): a mesh without vertices
+        m = np.asarray(inst["transpose_inverse_transform"], np.float64)      # 3 x 4 rows of world -> local
+        inv = np.linalg.inv(m[:, :3])
+        corners = np.array([[box[0 + 3 * (k & 1)], box[1 + 3 * ((k >> 1) & 1)], box[2 + 3 * ((k >> 2) & 1)]] for k in range(8)])
+        world = (corners - m[:, 3]) @ inv.T
+        lo, hi = np.minimum(lo, world.min(axis=0)), np.maximum(hi, world.max(axis=0))
+    return float((hi - lo).max()) if np.all(np.isfinite(hi - lo)) else 0.0
+
+
+def lightmap_stats():
+    """The calling thread's latest successful bake_lightmap: covered texels, (chart, triangle) pairs, host-clock ms per phase."""
+    s = _abi.LightmapStatsC()
+    lib().lupin_hip_lightmap_stats(C.byref(s))
+    return {"covered_texels": int(s.covered_texels), "keys": int(s.keys), "raster_ms": float(s.raster_ms), "compact_ms": float(s.compact_ms),
+            "trace_ms": float(s.trace_ms), "scatter_dilate_ms": float(s.scatter_dilate_ms), "download_ms": float(s.download_ms)}
+
+
+def bake_lightmap(ctx, scene, charts, width, height, samples=64, pathtrace_type=PathtraceType.Standard, max_bounces=8, advanced=None,
+                  counter=0, max_slots=0, smooth_normals=False, dilate=0, surface_offset=None, want_records=False):
+    """The scene's irradiance as a lightmap: (height, width, 4) float32, rgb = pi * the mean radiance over `samples`
+    cosine-weighted paths from the surface point under each texel centre, alpha 1 on rasterised texels and 0 elsewhere
+    (gutter texels filled by `dilate` passes keep alpha 0).  Row 0 is v in [0, 1 / height): no flip.
+    `charts`: LightmapChart items (or (instance_idx, scale_u, scale_v, offset_u, offset_v) tuples); the mesh's texcoords times
+    the scale plus the offset are the instance's place in the atlas.  Where charts or triangles overlap, the first chart and
+    the lowest triangle own the texel.  smooth_normals: hemispheres about the interpolated vertex normals where the mesh has
+    them (the origin is still offset along the geometric normal).
+    surface_offset (world units along the geometric normal) defaults to LIGHTMAP_OFFSET_FRACTION = 1e-4 times the
+    largest world extent of the scene, taken from the instances' model boxes (scene_world_extent), and to 1e-4 for a scene
+    without extent.  With want_records also the (height, width, 8) ray records of the owned texels (zeros elsewhere).
+    Blocks until the result is complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_lightmap needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if surface_offset is None:
+        surface_offset = LIGHTMAP_OFFSET_FRACTION * (scene_world_extent(scene) or 1.0)
+    adv = advanced or AdvancedParams()
+    items = [c if isinstance(c, LightmapChart) else LightmapChart(*c) for c in charts]
+    c_charts = (_abi.LightmapChartC * max(1, len(items)))(*[_abi.LightmapChartC(int(c.instance_idx), c.scale_u, c.scale_v, c.offset_u, c.offset_v)
+                                                           for c in items])
+    d = _abi.LightmapDescC(int(width), int(height), int(pathtrace_type), int(max_bounces), int(samples), int(max_slots),
+                           LIGHTMAP_SMOOTH_NORMALS if smooth_normals else 0, int(dilate), int(counter), float(surface_offset),
+                           _abi.AdvancedParamsC(adv.max_radiance, adv.rng_seed, adv.ray_epsilon))
+    shape_ok = 0 < int(width) <= LIGHTMAP_MAX_SIZE and 0 < int(height) <= LIGHTMAP_MAX_SIZE
+    out = np.zeros((int(height), int(width), 4) if shape_ok else (1, 1, 4), np.float32)      # a refused size: the library says so
+    rec = np.zeros((int(height), int(width), RAY_RECORD_FLOATS) if shape_ok else (1, 1, RAY_RECORD_FLOATS), np.float32) if want_records else None
+    check(lib().lupin_hip_bake_lightmap(ctx.handle, scene.handle, C.byref(d), c_charts, len(items), ptr(out), ptr(rec), None))
+    return (out, rec) if want_records else out

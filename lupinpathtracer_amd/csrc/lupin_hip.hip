@@ -2,7 +2,7 @@
 // textures, the pathtrace_scene family, measurement hooks, probes).  The stage kernels live in lupin_stages.hpp, the
 // traversal / material / light device functions in lupin_device.hpp, the CPU builders in builders.cpp, the device BLAS
 // builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp, adaptive sampling's in lupin_adaptive.hpp, the radiance
-// queries' in lupin_rays.hpp.
+// queries' in lupin_rays.hpp, lightmap baking's in lupin_lightmap.hpp.
 //
 // THERE IS NO CPU FALLBACK: without a HIP device every entry point that needs one fails with LUPIN_ERR_NO_DEVICE.
 
@@ -20,11 +20,13 @@
 #include <mutex>
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 
 #include "lupin_stages.hpp"
 #include "lupin_denoise.hpp"
 #include "lupin_adaptive.hpp"
 #include "lupin_rays.hpp"
+#include "lupin_lightmap.hpp"
 #include "lupin_internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -166,6 +168,7 @@ struct LupinScene
     std::vector<InstanceDev> host_instances;        // as uploaded (mesh_idx, mat_idx, blas_root and flags never change)
     std::vector<uint32_t> light_instance;           // light -> instance
     std::vector<uint32_t> mesh_tri_count;           // per mesh; with num_textures what lupin_hip_surface_probe checks a record's indices against
+    std::vector<uint8_t> mesh_has_texcoords;        // per mesh; lupin_hip_bake_lightmap refuses a chart on a mesh without them
     uint32_t num_textures = 0;
     std::vector<LupinTlasNode> tlas_nodes;          // the TLAS in lupin_build_tlas' format (lupin_hip_scene_get_tlas)
     uint32_t nblas = 0, ntlas = 0;                  // the one node array is [nblas BLAS nodes | ntlas TLAS nodes]
@@ -1317,6 +1320,7 @@ int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinS
 
         uint32_t ntris = m.num_indices / 3;
         sc->mesh_tri_count.push_back(ntris);
+        sc->mesh_has_texcoords.push_back(md.texcoords_base != LUPIN_SENTINEL_IDX);
         for (uint32_t i = 0; i < ntris * 3; i++)
             if (m.indices[i] >= m.num_verts) { lupin_hip_scene_destroy(sc); return fail(LUPIN_ERR_INVALID_ARGUMENT, "vertex index out of range"); }
         for (uint32_t t = 0; t < ntris; t++)
@@ -2597,6 +2601,143 @@ int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const L
     }
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+// ---- lightmap baking (no reference counterpart; kernels: lupin_lightmap.hpp) ----
+
+static thread_local LupinLightmapStats g_lightmap_stats = {0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+void lupin_hip_lightmap_stats(LupinLightmapStats *out) { if (out) *out = g_lightmap_stats; }
+
+int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc, const LupinLightmapChart *charts,
+                            uint32_t num_charts, float *out_rgba, float *out_records, uint64_t *out_num_covered)
+{
+    const char *who = "lupin_hip_bake_lightmap";
+    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !scene || !desc || !charts || !out_rgba) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    const uint32_t W = desc->width, H = desc->height;
+    if (W == 0 || H == 0 || W > LUPIN_LIGHTMAP_MAX_SIZE || H > LUPIN_LIGHTMAP_MAX_SIZE)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "width and height must be in [1, 16384]");
+    if (num_charts == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "no charts");
+    if (desc->flags & ~(uint32_t)LUPIN_LIGHTMAP_SMOOTH_NORMALS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (desc->dilate > LUPIN_LIGHTMAP_MAX_DILATE) return fail(LUPIN_ERR_INVALID_ARGUMENT, "dilate must be <= 64");
+    if (!(std::isfinite(desc->surface_offset) && desc->surface_offset > 0.0f))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "surface_offset must be finite and positive");
+    // what the query refuses in a descriptor, here as well: an atlas without an owned texel never reaches the query
+    if (desc->pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
+    if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
+    if (desc->max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
+    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    if (scene->wide_stale && ctx->wide_traversal) return fail(LUPIN_ERR_INVALID_ARGUMENT, kWideStale);
+    std::vector<LmChartDev> h_charts(num_charts);
+    uint64_t total_keys = 0;
+    for (uint32_t c = 0; c < num_charts; c++)
+    {
+        const LupinLightmapChart &ch = charts[c];
+        if (ch.instance_idx >= scene->host_instances.size()) return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": instance index out of range");
+        const uint32_t mesh = scene->host_instances[ch.instance_idx].mesh_idx;
+        if (!scene->mesh_has_texcoords[mesh]) return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": the instance's mesh has no texcoords");
+        if (!(std::isfinite(ch.scale_u) && std::isfinite(ch.scale_v) && std::isfinite(ch.offset_u) && std::isfinite(ch.offset_v)))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": non-finite scale or offset");
+        h_charts[c] = LmChartDev{ch.instance_idx, (uint32_t)total_keys, scene->mesh_tri_count[mesh], 0u, ch.scale_u, ch.scale_v, ch.offset_u, ch.offset_v};
+        total_keys += scene->mesh_tri_count[mesh];
+        if (total_keys >= 0xFFFFFFFFull) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the charts hold 2^32 - 1 or more triangles");
+    }
+    // the calls recorded so far run first, whatever becomes of this one from here on
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = flush_pending(ctx)) return rc;
+    join_primary(ctx);
+    hipStream_t st = ctx->lanes[0].stream;   // the primary stream, the query's own
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<float, std::milli>(clk::now() - t0).count(); };
+    LupinLightmapStats stats = {0, (uint32_t)total_keys, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+
+    const uint32_t texels = W * H;
+    const uint32_t texel_blocks = (texels + LP_BLOCK - 1) / LP_BLOCK;
+    DeviceBuffer d_charts, d_owner, d_totals;
+    HIP_TRY(DeviceBuffer::make(h_charts.size() * sizeof(LmChartDev), &d_charts));
+    HIP_TRY(DeviceBuffer::make((size_t)texels * 4, &d_owner));
+    HIP_TRY(DeviceBuffer::make(((size_t)texel_blocks + 1) * 4, &d_totals));
+    auto t0 = clk::now();
+    HIP_TRY(hipMemcpyAsync(d_charts.get(), h_charts.data(), h_charts.size() * sizeof(LmChartDev), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_owner.get(), 0xFF, (size_t)texels * 4, st));
+    if (total_keys)
+        hipLaunchKernelGGL(k_lm_raster, dim3((uint32_t)((total_keys + LP_BLOCK / 64 - 1) / (LP_BLOCK / 64))), dim3(LP_BLOCK), 0, st, scene->dev,
+                           d_charts.as<LmChartDev>(), num_charts, (uint32_t)total_keys, W, H, d_owner.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    stats.raster_ms = ms_since(t0);
+
+    t0 = clk::now();
+    hipLaunchKernelGGL(k_lm_count, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, d_owner.as<uint32_t>(), texels, d_totals.as<uint32_t>());
+    hipLaunchKernelGGL(k_lm_scan, dim3(1), dim3(LP_LM_SCAN_THREADS), 0, st, d_totals.as<uint32_t>(), texel_blocks);
+    HIP_TRY(hipGetLastError());
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, d_totals.as<uint32_t>() + texel_blocks, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n > texels) return fail(LUPIN_ERR_HIP, std::string(who) + ": the compaction counted more texels than the atlas has");
+    stats.covered_texels = n;
+    if (n == 0)
+    {
+        memset(out_rgba, 0, (size_t)texels * 16);
+        if (out_records) memset(out_records, 0, (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4);
+        if (out_num_covered) *out_num_covered = 0;
+        stats.compact_ms = ms_since(t0);
+        g_lightmap_stats = stats;
+        return LUPIN_OK;
+    }
+    DeviceBuffer d_rec, d_texel, d_mean;
+    HIP_TRY(DeviceBuffer::make((size_t)n * LUPIN_RAY_RECORD_FLOATS * 4, &d_rec));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &d_texel));
+    HIP_TRY(DeviceBuffer::make((size_t)n * LUPIN_RAY_RESULT_FLOATS * 4, &d_mean));
+    hipLaunchKernelGGL(k_lm_emit, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, scene->dev, d_charts.as<LmChartDev>(), num_charts, W, H,
+                       d_owner.as<uint32_t>(), d_totals.as<uint32_t>(), desc->flags, desc->counter, desc->surface_offset, d_rec.as<float4>(),
+                       d_texel.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    stats.compact_ms = ms_since(t0);
+
+    // one query on the device records: its validation, its chunks
+    t0 = clk::now();
+    const LupinRayQueryDesc q{desc->pathtrace_type, desc->max_bounces, desc->samples, LUPIN_RAYS_DEVICE_POINTERS, desc->max_slots, desc->advanced};
+    if (int rc = lupin_hip_pathtrace_rays(ctx, scene, &q, n, d_rec.as<float>(), d_mean.as<float>(), nullptr)) return rc;
+    stats.trace_ms = ms_since(t0);
+
+    t0 = clk::now();
+    DeviceBuffer d_rgba[2], d_filled[2], d_plane;
+    const int planes = desc->dilate ? 2 : 1;
+    for (int k = 0; k < planes; k++)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)texels * 16, &d_rgba[k]));
+        HIP_TRY(DeviceBuffer::make((size_t)texels, &d_filled[k]));
+    }
+    HIP_TRY(hipMemsetAsync(d_rgba[0].get(), 0, (size_t)texels * 16, st));
+    HIP_TRY(hipMemsetAsync(d_filled[0].get(), 0, (size_t)texels, st));
+    if (out_records)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, &d_plane));
+        HIP_TRY(hipMemsetAsync(d_plane.get(), 0, (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, st));
+    }
+    hipLaunchKernelGGL(k_lm_scatter, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, st, n, d_texel.as<uint32_t>(), d_mean.as<float4>(),
+                       d_rec.as<float4>(), d_rgba[0].as<float4>(), d_filled[0].as<uint8_t>(), d_plane.as<float4>());
+    int cur = 0;
+    for (uint32_t pass = 0; pass < desc->dilate; pass++, cur ^= 1)
+        hipLaunchKernelGGL(k_lm_dilate, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, W, H, d_rgba[cur].as<float4>(), d_filled[cur].as<uint8_t>(),
+                           d_rgba[cur ^ 1].as<float4>(), d_filled[cur ^ 1].as<uint8_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    stats.scatter_dilate_ms = ms_since(t0);
+
+    t0 = clk::now();
+    HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba[cur].get(), (size_t)texels * 16, hipMemcpyDeviceToHost, st));
+    if (out_records) HIP_TRY(hipMemcpyAsync(out_records, d_plane.get(), (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    stats.download_ms = ms_since(t0);
+    if (out_num_covered) *out_num_covered = n;
+    g_lightmap_stats = stats;
     return LUPIN_OK;
 }
 
