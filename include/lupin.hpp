@@ -574,6 +574,38 @@ inline uint64_t bake_lightmap(const Device &d, const Scene &scene, const Lightma
     return covered;
 }
 
+// light-probe baking (no reference counterpart): radiance over the sphere at points in space, as L2 SH
+struct ProbeDesc
+{
+    PathtraceType pathtrace_type = PathtraceType::Standard;
+    uint32_t max_bounces = 8;
+    uint32_t samples = 1024;
+    uint32_t flags = 0;            // LUPIN_PROBES_DEVICE_POINTERS: probes, out_sh and out_rays are device memory
+    uint32_t max_slots = 0;        // paths per wavefront; 0 = the library's default
+    AdvancedParams advanced;
+};
+// probes: n x 4 floats (position | RNG bits); out_sh: n x 9 x 4 (r, g, b, w per coefficient); out_rays: nullptr or n * samples x 8
+inline void bake_probes(const Device &d, const Scene &scene, const ProbeDesc &desc, uint64_t n, const float *probes, float *out_sh,
+                        float *out_rays = nullptr)
+{
+    const LupinProbeDesc c{(uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.flags, desc.max_slots,
+                           LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
+    check(lupin_hip_bake_probes(d.raw(), scene.raw(), &c, n, probes, out_sh, out_rays));
+}
+// Irradiance (r, g, b) at a surface with unit normal n from one probe's 9 x 4 coefficients: Ramamoorthi-Hanrahan, the clamped
+// cosine's band factors pi, 2 pi / 3, pi / 4 on the basis of include/lupin_hip.h evaluated at n
+inline std::array<float, 3> sh_irradiance(const float *coeffs, float nx, float ny, float nz)
+{
+    const float k0 = 0.28209479f, k1 = 0.48860251f, k2 = 1.09254843f, k3 = 0.31539157f, k4 = 0.54627422f;
+    const float pi = 3.14159265358979323846f, a0 = pi, a1 = 2.0f * pi / 3.0f, a2 = pi / 4.0f;
+    const float y[LUPIN_PROBE_SH_COEFFS] = {a0 * k0, a1 * (k1 * ny), a1 * (k1 * nz), a1 * (k1 * nx), a2 * ((k2 * nx) * ny), a2 * ((k2 * ny) * nz),
+                                            a2 * (k3 * ((3.0f * nz) * nz - 1.0f)), a2 * ((k2 * nx) * nz), a2 * (k4 * (nx * nx - ny * ny))};
+    std::array<float, 3> e{0.0f, 0.0f, 0.0f};
+    for (int j = 0; j < LUPIN_PROBE_SH_COEFFS; j++)
+        for (int c = 0; c < 3; c++) e[c] += coeffs[4 * j + c] * y[j];
+    return e;
+}
+
 }  // namespace lp
 
 namespace lpl {

@@ -855,6 +855,63 @@ typedef struct LupinLightmapStats {
 } LupinLightmapStats;
 void lupin_hip_lightmap_stats(LupinLightmapStats *out);
 
+/* ---- light-probe baking (no reference counterpart) ----
+ * The radiance arriving at points in space from every direction, projected onto the nine real spherical harmonics of bands
+ * 0..2: what lights everything a lightmap cannot cover.  Every probe is path-traced along `samples` uniformly distributed
+ * directions by the integrators of the radiance query above, and reduced on the device.  Every float operation below is
+ * one rounded f32 operation (no contraction).
+ *
+ * Probe, LUPIN_PROBE_FLOATS floats: [0..2] position   [3] RNG word (bits).
+ * Path s of probe i is slot i * samples + s.  Its RNG state is the query's: the probe's word for s == 0 and
+ * hash_u32(word + s * 0x9E3779B9) otherwise; it starts at bounce 0, outside any medium, exactly as a query path does.
+ * Direction: two numbers r0, r1 drawn from the slot's state, then
+ *   z = 1.0f - 2.0f * r1;  rad = sqrtf(max(0.0f, 1.0f - z * z));  (s, c) = sincos(2.0f * pi * r0);  w = (rad * c, rad * s, z)
+ * in world axes (sincos: the library's lpm_sincosf, lupin_detmath.h).
+ * out_rays (NULL, or n * samples records of the query): the probe's position, the state after the two draws, w and mode 0;
+ * querying such a record with samples = 1 replays that one path.
+ *
+ * Basis, w = (x, y, z) in world axes, k0 = 0.28209479f, k1 = 0.48860251f, k2 = 1.09254843f, k3 = 0.31539157f,
+ * k4 = 0.54627422f:
+ *   Y0 = k0          Y1 = k1*y        Y2 = k1*z                        Y3 = k1*x        Y4 = (k2*x)*y
+ *   Y5 = (k2*y)*z    Y6 = k3*((3.0f*z)*z - 1.0f)                       Y7 = (k2*x)*z    Y8 = k4*(x*x - y*y)
+ *
+ * Reduction, per probe, as one wave of 64 lanes: lane l takes the samples s = l, l + 64, l + 128, ... < samples in ascending
+ * order and adds, from +0.0f, acc[j][c] += L_s[c] * Yj(w_s) for c in r, g, b and acc[j][3] += Yj(w_s); L_s is the path's
+ * radiance, clamped at advanced.max_radiance as a pixel's samples are, w_s the direction above.  Then for offset = 32, 16, 8,
+ * 4, 2, 1: acc = acc + acc of lane (l xor offset).  The result is (acc * (4.0f * pi)) / (float)samples.
+ *
+ * out_sh (n x LUPIN_PROBE_SH_COEFFS x 4): coefficient j of probe i is (r, g, b, w); L(w) ~ sum_j out_sh[i][j].rgb * Yj(w).
+ * The w channel is the projection of the sample pattern itself (2 sqrt(pi), 0, ..., 0 for perfect sampling): it does not
+ * depend on the scene, and a caller who wants ratio estimates divides by it.
+ *
+ * Chunks, ordering and failure are lupin_hip_pathtrace_rays': recorded calls run first (their error is returned; they have
+ * run once the descriptor and the pointers have passed their checks), a wavefront holds whole probes, at most
+ * desc->max_slots paths (0: LUPIN_RAYS_DEFAULT_MAX_SLOTS), at least one probe; the call returns when out_sh is complete;
+ * frames rendered before and after are what they would be without the call.  With LUPIN_PROBES_DEVICE_POINTERS in
+ * desc->flags, probes, out_sh and out_rays are device memory of the context's device, 16-byte aligned, and nothing is copied
+ * to or from the host.
+ *
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing traced and the outputs untouched, for: a NULL argument (out_rays may be NULL); an unknown
+ * pathtrace_type or flag; samples == 0 or above 2^27; max_bounces >= 4095; n * samples above 2^38; a scene of another or of a
+ * destroyed context; a probe with a non-finite position (host probes are checked on the host, device probes by a kernel
+ * whose count the host reads before the first wavefront); device pointers not 16-byte aligned; a hierarchy too deep for the
+ * traversal stack (as a render).  n == 0: LUPIN_OK, nothing touched.  Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_PROBE_FLOATS 4
+#define LUPIN_PROBE_SH_COEFFS 9
+#define LUPIN_PROBE_RESULT_FLOATS 36
+enum { LUPIN_PROBES_DEVICE_POINTERS = 1u };                             /* desc.flags */
+typedef struct LupinProbeDesc {
+    uint32_t pathtrace_type;        /* as LupinRayQueryDesc */
+    uint32_t max_bounces;
+    uint32_t samples;               /* S >= 1 paths per probe */
+    uint32_t flags;
+    uint32_t max_slots;             /* 0 = library default; paths per wavefront */
+    LupinAdvancedParams advanced;
+} LupinProbeDesc;
+int lupin_hip_bake_probes(LupinContext *ctx, const LupinScene *scene, const LupinProbeDesc *desc,
+                          uint64_t n, const float *probes /* n x 4 */, float *out_sh /* n x 9 x 4 */,
+                          float *out_rays /* NULL, or n*S x 8 */);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

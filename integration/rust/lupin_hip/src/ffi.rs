@@ -90,6 +90,14 @@ pub const LUPIN_LIGHTMAP_SMOOTH_NORMALS: u32 = 1;
 #[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinLightmapStats {
     pub covered_texels: u64, pub keys: u32, pub raster_ms: f32, pub compact_ms: f32, pub trace_ms: f32, pub scatter_dilate_ms: f32, pub download_ms: f32,
 }
+// light-probe baking (no reference counterpart)
+pub const LUPIN_PROBE_FLOATS: usize = 4;
+pub const LUPIN_PROBE_SH_COEFFS: usize = 9;
+pub const LUPIN_PROBE_RESULT_FLOATS: usize = 36;
+pub const LUPIN_PROBES_DEVICE_POINTERS: u32 = 1;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinProbeDesc {
+    pub pathtrace_type: u32, pub max_bounces: u32, pub samples: u32, pub flags: u32, pub max_slots: u32, pub advanced: LupinAdvancedParams,
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -169,6 +177,9 @@ extern "C" {
                                    charts: *const LupinLightmapChart, num_charts: u32, out_rgba: *mut f32, out_records: *mut f32,
                                    out_num_covered: *mut u64) -> c_int;
     pub fn lupin_hip_lightmap_stats(out: *mut LupinLightmapStats);
+    // light-probe baking: probes n x 4 f32 (position | RNG word), out_sh n x 9 x 4 (r, g, b, w per L2 SH coefficient), out_rays null or n * samples x 8
+    pub fn lupin_hip_bake_probes(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinProbeDesc, n: u64,
+                                 probes: *const f32, out_sh: *mut f32, out_rays: *mut f32) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

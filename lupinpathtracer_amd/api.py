@@ -1422,3 +1422,62 @@ def bake_lightmap(ctx, scene, charts, width, height, samples=64, pathtrace_type=
     rec = np.zeros((int(height), int(width), RAY_RECORD_FLOATS) if shape_ok else (1, 1, RAY_RECORD_FLOATS), np.float32) if want_records else None
     check(lib().lupin_hip_bake_lightmap(ctx.handle, scene.handle, C.byref(d), c_charts, len(items), ptr(out), ptr(rec), None))
     return (out, rec) if want_records else out
+
+
+# ---- light-probe baking: lupin_hip_bake_probes (include/lupin_hip.h) ----
+PROBE_FLOATS = 4
+PROBE_SH_COEFFS = 9
+PROBE_RESULT_FLOATS = 36
+PROBES_DEVICE_POINTERS = 1
+SH_BAND_FACTORS = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)   # the clamped cosine's, per coefficient
+
+
+@dataclass
+class ProbeDesc:  # LupinProbeDesc
+    pathtrace_type: int = PathtraceType.Standard
+    max_bounces: int = 8
+    samples: int = 1024
+    flags: int = 0
+    max_slots: int = 0       # paths per wavefront; 0 = the library's default
+    advanced: AdvancedParams = field(default_factory=AdvancedParams)
+
+
+def sh_basis(dirs):
+    """(..., 9) float64: the real spherical harmonics of bands 0..2 at the unit vectors `dirs` (..., 3), in world x, y, z and
+    in the order of include/lupin_hip.h -- 1, y, z, x, xy, yz, 3z^2 - 1, xz, x^2 - y^2, each with its normalisation."""
+    d = np.asarray(dirs, np.float64)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    k0, k1 = 0.5 * np.sqrt(1.0 / np.pi), np.sqrt(3.0 / (4.0 * np.pi))
+    k2, k3, k4 = 0.5 * np.sqrt(15.0 / np.pi), 0.25 * np.sqrt(5.0 / np.pi), 0.25 * np.sqrt(15.0 / np.pi)
+    return np.stack([np.full_like(x, k0), k1 * y, k1 * z, k1 * x, k2 * x * y, k2 * y * z, k3 * (3.0 * z * z - 1.0), k2 * x * z,
+                     k4 * (x * x - y * y)], axis=-1)
+
+
+def sh_irradiance(coeffs, normals):
+    """Irradiance (..., 3) float64 at surfaces with unit `normals` (..., 3) from probe coefficients `coeffs` (..., 9, 3 or 4;
+    only r, g, b are read): Ramamoorthi-Hanrahan, sum_j A_j coeffs[j] Y_j(n) with the clamped cosine's band factors
+    A = pi, 2 pi / 3, pi / 4.  Exact for radiance that has no bands above 2.  Leading dimensions broadcast."""
+    c = np.asarray(coeffs, np.float64)[..., :3]
+    return np.einsum("...j,...jc->...c", sh_basis(normals) * SH_BAND_FACTORS, c)
+
+
+def bake_probes(ctx, scene, positions, samples=1024, pathtrace_type=PathtraceType.Standard, max_bounces=8, advanced=None, counter=0,
+                max_slots=0, want_rays=False):
+    """Light probes at `positions` (n, 3): (n, 9, 4) float32, coefficient j of probe i as (r, g, b, w) -- the radiance arriving
+    at the point over the whole sphere, path-traced along `samples` uniform directions and projected onto sh_basis on the
+    device; L(w) ~ sum_j out[i, j, :3] * sh_basis(w)[j].  The w channel is the projection of the sample pattern itself
+    (2 sqrt(pi), 0, ... for perfect sampling).  Probe i is seeded with rng_seed_for(i, counter).  With want_rays also the
+    (n * samples, RAY_RECORD_FLOATS) first rays as mode-DIRECTION records of pathtrace_rays.  Blocks until complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_probes needs a GPU context and an uploaded scene; there is no CPU fallback")
+    pos = np.asarray(positions, np.float32).reshape(-1, 3)
+    probes = np.zeros((len(pos), PROBE_FLOATS), np.float32)
+    probes[:, :3] = pos
+    probes.view(np.uint32)[:, 3] = rng_seed_for(np.arange(len(pos), dtype=np.uint32), counter)
+    adv = advanced or AdvancedParams()
+    c = _abi.ProbeDescC(int(pathtrace_type), int(max_bounces), int(samples), 0, int(max_slots),
+                        _abi.AdvancedParamsC(adv.max_radiance, adv.rng_seed, adv.ray_epsilon))
+    out = np.zeros((len(pos), PROBE_SH_COEFFS, 4), np.float32)
+    rays = np.zeros((len(pos) * int(samples), RAY_RECORD_FLOATS), np.float32) if want_rays else None
+    check(lib().lupin_hip_bake_probes(ctx.handle, scene.handle, C.byref(c), len(pos), ptr(probes), ptr(out), ptr(rays)))
+    return (out, rays) if want_rays else out

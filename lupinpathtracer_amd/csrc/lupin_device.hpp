@@ -1210,6 +1210,16 @@ LP_DEV f3 sample_cos_hemisphere(f3 normal, float r0, float r1)
     lpm_sincosf(phi, &s, &c);
     return normalize3(from_z_frame(normal, mk3(r * c, r * s, z)));
 }
+// Uniform on the sphere in world axes, as light-probe baking states it (include/lupin_hip.h).  Not sample_unit_sphere
+// below, the reference's sampler, whose z runs the other way.
+LP_DEV f3 sample_uniform_sphere(float r0, float r1)
+{
+    float z = 1.0f - 2.0f * r1;
+    float rad = sqrtf(fmaxf(0.0f, 1.0f - z * z));
+    float s, c;
+    lpm_sincosf(2.0f * LP_PI * r0, &s, &c);
+    return mk3(rad * c, rad * s, z);
+}
 LP_DEV float cos_hemisphere_pdf(f3 normal, f3 direction)
 {
     float cosw = dot3(normal, direction);

@@ -2,7 +2,7 @@
 // textures, the pathtrace_scene family, measurement hooks, probes).  The stage kernels live in lupin_stages.hpp, the
 // traversal / material / light device functions in lupin_device.hpp, the CPU builders in builders.cpp, the device BLAS
 // builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp, adaptive sampling's in lupin_adaptive.hpp, the radiance
-// queries' in lupin_rays.hpp, lightmap baking's in lupin_lightmap.hpp.
+// queries' in lupin_rays.hpp, light-probe baking's in lupin_probes.hpp, lightmap baking's in lupin_lightmap.hpp.
 //
 // THERE IS NO CPU FALLBACK: without a HIP device every entry point that needs one fails with LUPIN_ERR_NO_DEVICE.
 
@@ -26,6 +26,7 @@
 #include "lupin_denoise.hpp"
 #include "lupin_adaptive.hpp"
 #include "lupin_rays.hpp"
+#include "lupin_probes.hpp"
 #include "lupin_lightmap.hpp"
 #include "lupin_internal.hpp"
 
@@ -801,9 +802,18 @@ struct RayBegin
     float4 *out_rays;        // the chunk's first slot, or nullptr
 };
 
+// first rays of a probe bake's chunk (lupin_hip_bake_probes): k_begin_probes
+struct ProbeBegin
+{
+    const float4 *probes;    // the chunk's first probe
+    uint32_t samples;
+    float4 *out_rays;        // the chunk's first slot, or nullptr
+};
+
 // the lane-private part of one call: clear the queue counters, first rays, every iteration of the wavefront
 static hipError_t enqueue_wavefront(LupinContext *ctx, Lane *ln, const LupinScene *scene, uint32_t pathtrace_type, uint32_t n,
-                                    const Shape &sh, uint32_t iterations, const AdaptiveDev *ad = nullptr, const RayBegin *rays = nullptr)
+                                    const Shape &sh, uint32_t iterations, const AdaptiveDev *ad = nullptr, const RayBegin *rays = nullptr,
+                                    const ProbeBegin *probes = nullptr)
 {
     const uint32_t blocks = sh.blocks;
     hipStream_t st = ln->stream;
@@ -814,6 +824,8 @@ static hipError_t enqueue_wavefront(LupinContext *ctx, Lane *ln, const LupinScen
                            (const uint8_t *)ad->block_active, (const uint32_t *)ad->frames, ad->blocks_x);
     else if (rays)
         hipLaunchKernelGGL(k_begin_rays, dim3(blocks), dim3(LP_BLOCK), 0, st, ln->pb, n, rays->records, rays->samples, rays->out_rays);
+    else if (probes)
+        hipLaunchKernelGGL(k_begin_probes, dim3(blocks), dim3(LP_BLOCK), 0, st, ln->pb, n, probes->probes, probes->samples, probes->out_rays);
     else
         hipLaunchKernelGGL(k_begin, dim3(blocks), dim3(LP_BLOCK), 0, st, (const FrameParams *)ln->d_fp, ln->pb, n);
     with_type(pathtrace_type, [&](auto T) {
@@ -2481,6 +2493,39 @@ static constexpr uint64_t LP_RAYS_DEFAULT_SLOTS = LUPIN_RAYS_DEFAULT_MAX_SLOTS;
 static constexpr uint64_t LP_RAYS_MAX_CHUNK_SLOTS = 1ull << 27;   // the largest dispatch a render accepts (QUEUE_SLOT_MASK / 8)
 static constexpr uint64_t LP_RAYS_MAX_PATHS = 1ull << 38;         // n * samples: record and slot indices, byte offsets and grids stay far from their types' ends
 
+// What the wavefronts of a radiance query and of a probe bake share.  The frame parameters of paths that are slots, not pixels:
+static FrameParams query_frame_params(const LupinScene *scene, uint32_t pathtrace_type, uint32_t max_bounces, const LupinAdvancedParams &advanced)
+{
+    FrameParams fp;
+    memset(&fp, 0, sizeof(fp));
+    LupinPushConstants &pc = fp.pc;
+    if (scene->envs_empty) pc.flags |= LUPIN_FLAG_ENVS_EMPTY;
+    if (scene->lights_empty) pc.flags |= LUPIN_FLAG_LIGHTS_EMPTY;
+    if (scene->instances_empty) pc.flags |= LUPIN_FLAG_INSTANCES_EMPTY;
+    pc.pathtrace_type = pathtrace_type;
+    pc.max_radiance = advanced.max_radiance;
+    pc.rng_seed = advanced.rng_seed;
+    pc.ray_epsilon = advanced.ray_epsilon;
+    fp.height = fp.reg_h = 1;
+    fp.max_bounces = max_bounces;
+    fp.spp = 1;            // a path that ends is never followed by a camera sample (path_epilogue)
+    fp.num_frames = 1;
+    return fp;
+}
+// ... and the launch shape of one chunk of `slots` paths (the lane's shard capacity and fp's width with it)
+static Shape query_chunk_shape(LupinContext *ctx, const LupinScene *scene, uint32_t pathtrace_type, const TraversalLds &t, uint32_t slots, Lane *ln,
+                               FrameParams *fp)
+{
+    fp->width = fp->reg_w = fp->frame_slots = slots;
+    const uint32_t blocks_needed = (slots + LP_BLOCK - 1) / LP_BLOCK;
+    const uint32_t blocks_per_shard = (blocks_needed + LP_SHARDS - 1) / LP_SHARDS;
+    ln->pb.shard_cap = blocks_per_shard * LP_BLOCK;
+    Shape sh;
+    sh.blocks = blocks_per_shard * LP_SHARDS;
+    plan_tracers(ctx, scene, pathtrace_type, true, t, &sh);
+    return sh;
+}
+
 int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const LupinRayQueryDesc *desc, uint64_t n, const float *records,
                              float *out, float *out_rays)
 {
@@ -2550,32 +2595,13 @@ int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const L
         if (out_rays) HIP_TRY(DeviceBuffer::make((size_t)(chunk_records * S) * LUPIN_RAY_RECORD_FLOATS * 4, &d_rays));
     }
 
-    FrameParams fp;
-    memset(&fp, 0, sizeof(fp));
-    LupinPushConstants &pc = fp.pc;
-    if (scene->envs_empty) pc.flags |= LUPIN_FLAG_ENVS_EMPTY;
-    if (scene->lights_empty) pc.flags |= LUPIN_FLAG_LIGHTS_EMPTY;
-    if (scene->instances_empty) pc.flags |= LUPIN_FLAG_INSTANCES_EMPTY;
-    pc.pathtrace_type = desc->pathtrace_type;
-    pc.max_radiance = desc->advanced.max_radiance;
-    pc.rng_seed = desc->advanced.rng_seed;
-    pc.ray_epsilon = desc->advanced.ray_epsilon;
-    fp.height = fp.reg_h = 1;
-    fp.max_bounces = desc->max_bounces;
-    fp.spp = 1;            // a path that ends is never followed by a camera sample (path_epilogue)
-    fp.num_frames = 1;
+    FrameParams fp = query_frame_params(scene, desc->pathtrace_type, desc->max_bounces, desc->advanced);
 
     for (uint64_t first = 0; first < n; first += chunk_records)
     {
         const uint64_t recs = std::min(chunk_records, n - first);
         const uint32_t slots = (uint32_t)(recs * S);
-        fp.width = fp.reg_w = fp.frame_slots = slots;
-        const uint32_t blocks_needed = (slots + LP_BLOCK - 1) / LP_BLOCK;
-        const uint32_t blocks_per_shard = (blocks_needed + LP_SHARDS - 1) / LP_SHARDS;
-        ln->pb.shard_cap = blocks_per_shard * LP_BLOCK;
-        Shape sh;
-        sh.blocks = blocks_per_shard * LP_SHARDS;
-        plan_tracers(ctx, scene, desc->pathtrace_type, true, t, &sh);
+        const Shape sh = query_chunk_shape(ctx, scene, desc->pathtrace_type, t, slots, ln, &fp);
 
         const float *src = records + first * LUPIN_RAY_RECORD_FLOATS;
         float *dst = out + first * LUPIN_RAY_RESULT_FLOATS;
@@ -2596,6 +2622,109 @@ int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const L
         if (!on_device)
         {
             HIP_TRY(hipMemcpyAsync(dst, d_out.get(), (size_t)recs * LUPIN_RAY_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
+            if (out_rays) HIP_TRY(hipMemcpyAsync(dst_rays, d_rays.get(), (size_t)slots * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+// ---- light-probe baking (no reference counterpart; kernels: lupin_probes.hpp) ----
+
+int lupin_hip_bake_probes(LupinContext *ctx, const LupinScene *scene, const LupinProbeDesc *desc, uint64_t n, const float *probes, float *out_sh,
+                          float *out_rays)
+{
+    const char *who = "lupin_hip_bake_probes";
+    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !scene || !desc || !probes || !out_sh) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (desc->pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
+    if (desc->flags & ~(uint32_t)LUPIN_PROBES_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
+    if (desc->max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
+    const uint64_t S = desc->samples;
+    if (n > LP_RAYS_MAX_PATHS / S) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n * samples must not exceed 2^38");
+    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    if (scene->wide_stale && ctx->wide_traversal) return fail(LUPIN_ERR_INVALID_ARGUMENT, kWideStale);
+    const bool on_device = (desc->flags & LUPIN_PROBES_DEVICE_POINTERS) != 0;
+    if (on_device && (((uintptr_t)probes | (uintptr_t)out_sh | (uintptr_t)out_rays) & 15u))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device pointers must be 16-byte aligned");
+    if (n == 0) return LUPIN_OK;
+    // the calls recorded so far run first, whatever becomes of this one from here on
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = flush_pending(ctx)) return rc;
+    if (!on_device)
+        for (uint64_t i = 0; i < n; i++)
+        {
+            const float *p = probes + i * LUPIN_PROBE_FLOATS;
+            if (!probe_position_ok(p[0], p[1], p[2])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "probe " + std::to_string(i) + ": non-finite position");
+        }
+    TraversalLds t;
+    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
+    join_primary(ctx);   // the primary stream waits for the latest of the recorded calls
+    Lane *ln = &ctx->lanes[0];   // one lane for every chunk: its stream is the primary stream
+    hipStream_t st = ln->stream;
+
+    if (on_device)
+    {
+        DeviceBuffer bad;
+        HIP_TRY(DeviceBuffer::make(sizeof(unsigned long long), &bad));
+        HIP_TRY(hipMemsetAsync(bad.get(), 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_probes_validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st,
+                           reinterpret_cast<const float4 *>(probes), (unsigned long long)n, bad.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        unsigned long long count = 0;
+        HIP_TRY(hipMemcpyAsync(&count, bad.get(), sizeof(count), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (count) return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " probe(s): non-finite position");
+    }
+
+    const uint64_t max_slots = std::min(desc->max_slots ? (uint64_t)desc->max_slots : LP_RAYS_DEFAULT_SLOTS, LP_RAYS_MAX_CHUNK_SLOTS);
+    const uint64_t chunk_probes = std::min(n, std::max<uint64_t>(1, max_slots / S));
+    const uint32_t iterations = desc->max_bounces + 1;
+    int rc = ensure_path_buffers(ctx, ln, chunk_probes * S, iterations);
+    if (rc != LUPIN_OK) return rc;
+    set_path_layout(ln, ctx->path_records < 0 ? (scene->dev.sort_shade != 0) : ctx->path_records != 0);
+
+    // host arrays: one chunk's probes, coefficients and first rays at a time through device buffers that live for the call
+    DeviceBuffer d_probes, d_out, d_rays;
+    if (!on_device)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)chunk_probes * LUPIN_PROBE_FLOATS * 4, &d_probes));
+        HIP_TRY(DeviceBuffer::make((size_t)chunk_probes * LUPIN_PROBE_RESULT_FLOATS * 4, &d_out));
+        if (out_rays) HIP_TRY(DeviceBuffer::make((size_t)(chunk_probes * S) * LUPIN_RAY_RECORD_FLOATS * 4, &d_rays));
+    }
+
+    FrameParams fp = query_frame_params(scene, desc->pathtrace_type, desc->max_bounces, desc->advanced);
+
+    for (uint64_t first = 0; first < n; first += chunk_probes)
+    {
+        const uint64_t count = std::min(chunk_probes, n - first);
+        const uint32_t slots = (uint32_t)(count * S);
+        const Shape sh = query_chunk_shape(ctx, scene, desc->pathtrace_type, t, slots, ln, &fp);
+
+        const float *src = probes + first * LUPIN_PROBE_FLOATS;
+        float *dst = out_sh + first * LUPIN_PROBE_RESULT_FLOATS;
+        float *dst_rays = out_rays ? out_rays + first * S * LUPIN_RAY_RECORD_FLOATS : nullptr;
+        ProbeBegin pbg{reinterpret_cast<const float4 *>(src), desc->samples, reinterpret_cast<float4 *>(dst_rays)};
+        float4 *resolve_to = reinterpret_cast<float4 *>(dst);
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(d_probes.get(), src, (size_t)count * LUPIN_PROBE_FLOATS * 4, hipMemcpyHostToDevice, st));
+            pbg.probes = d_probes.as<float4>();
+            pbg.out_rays = out_rays ? d_rays.as<float4>() : nullptr;
+            resolve_to = d_out.as<float4>();
+        }
+        hipLaunchKernelGGL(k_set_params, dim3(1), dim3(1), 0, st, fp, ln->d_fp);
+        HIP_TRY(enqueue_wavefront(ctx, ln, scene, desc->pathtrace_type, slots, sh, iterations, nullptr, nullptr, &pbg));
+        hipLaunchKernelGGL(k_resolve_probes, dim3((uint32_t)((count + LP_PROBES_PER_BLOCK - 1) / LP_PROBES_PER_BLOCK)), dim3(LP_BLOCK), 0, st, ln->pb,
+                           (uint32_t)count, pbg.probes, desc->samples, resolve_to);
+        HIP_TRY(hipGetLastError());
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(dst, d_out.get(), (size_t)count * LUPIN_PROBE_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
             if (out_rays) HIP_TRY(hipMemcpyAsync(dst_rays, d_rays.get(), (size_t)slots * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
         }
     }
