@@ -518,6 +518,55 @@ inline void pathtrace_scene_adaptive(const Device &d, const PathtraceResources &
     check(lupin_hip_pathtrace_scene_adaptive(d.raw(), res.raw(), scene.raw(), render_target.raw(), (uint32_t)type, &c, ares.raw(), &p));
 }
 
+// Reprojection of the adaptive history (no reference counterpart): when the camera or instances move, carry the
+// accumulated image, the per-pixel frame counts and the moments over to the new view instead of resetting them
+struct ReprojectDesc
+{
+    CameraParams camera_params;   // the NEW view
+    Mat3x4 camera_transform = mat3x4_identity();
+    float ray_epsilon = 0.001f;
+    float depth_tolerance = 0.02f;   // relative
+    uint32_t max_history = 0;        // 0 = no cap
+    // empty = no instance moved; else one transpose_inverse_transform per instance: what the scene held when history_in was rendered
+    std::vector<LupinMat4x3> prev_instance_transforms;
+};
+class ReprojectResources
+{
+  public:
+    ReprojectResources(const Device &d, uint32_t width, uint32_t height) : ctx_(d.raw()) { check(lupin_hip_build_reproject_resources(ctx_, width, height, &res_)); }
+    ReprojectResources(ReprojectResources &&o) noexcept : ctx_(o.ctx_), res_(o.res_) { o.res_ = nullptr; }
+    ReprojectResources(const ReprojectResources &) = delete;
+    ~ReprojectResources() { if (res_) lupin_hip_destroy_reproject_resources(res_); }
+    LupinReprojectResources *raw() const { return res_; }
+    // forget the previous view: wherever AdaptiveResources::reset is called
+    void invalidate() { check(lupin_hip_reproject_invalidate(ctx_, res_)); }
+    // device milliseconds of the latest call's trace and gather kernels; needs lupin_hip_stats_reset(ctx, LUPIN_STATS_KERNEL_TIMING)
+    void timings(float &trace_ms, float &gather_ms) const { check(lupin_hip_reproject_timings(ctx_, res_, &trace_ms, &gather_ms)); }
+    // which: 0 the latest call's view, 1 the one before; any pointer may be null; inst / tri / depth W*H, uv W*H*2
+    void download(int which, uint32_t *inst, uint32_t *tri, float *uv, float *depth) const
+    {
+        check(lupin_hip_reproject_download(ctx_, res_, which, inst, tri, uv, depth));
+    }
+  private:
+    LupinContext *ctx_ = nullptr;
+    LupinReprojectResources *res_ = nullptr;
+};
+inline ReprojectResources build_reproject_resources(const Device &d, uint32_t width, uint32_t height) { return ReprojectResources(d, width, height); }
+inline void adaptive_reproject(const Device &d, AdaptiveResources &ares, ReprojectResources &res, const Scene &scene, const ReprojectDesc &desc,
+                               TextureRef history_in, TextureRef history_out)
+{
+    LupinReprojectDesc c{};
+    c.camera_params = LupinCameraParams{desc.camera_params.is_orthographic ? 1u : 0u, desc.camera_params.lens, desc.camera_params.film,
+                                        desc.camera_params.aspect, desc.camera_params.focus, desc.camera_params.aperture};
+    c.camera_transform = desc.camera_transform;
+    c.ray_epsilon = desc.ray_epsilon;
+    c.depth_tolerance = desc.depth_tolerance;
+    c.max_history = desc.max_history;
+    c.prev_instance_transforms = desc.prev_instance_transforms.empty() ? nullptr : desc.prev_instance_transforms.data();
+    c.num_instances = (uint32_t)desc.prev_instance_transforms.size();
+    check(lupin_hip_adaptive_reproject(d.raw(), ares.raw(), res.raw(), scene.raw(), &c, history_in.raw(), history_out.raw()));
+}
+
 
 // radiance queries (no reference counterpart): the integrators over caller-supplied rays
 enum class RayMode : uint32_t { Direction = LUPIN_RAY_DIRECTION, CosineHemisphere = LUPIN_RAY_COSINE_HEMISPHERE };

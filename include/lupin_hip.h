@@ -553,6 +553,75 @@ int lupin_hip_adaptive_stats(LupinContext *ctx, const LupinAdaptiveResources *ar
 int lupin_hip_adaptive_download(LupinContext *ctx, const LupinAdaptiveResources *ares, uint32_t *frames, float *moments,
                                 float *block_error, uint8_t *block_active);
 
+/* ---- reprojection of the adaptive history (no reference counterpart) ----
+ * When the camera or an instance moves, lupin_hip_adaptive_reproject rewrites the accumulated image and the adaptive state
+ * for the new view, so that the next lupin_hip_pathtrace_scene_adaptive call continues every pixel from the history of the
+ * surface point it now shows instead of from zero samples (the alternative: lupin_hip_adaptive_reset).  One call
+ *   1. traces the pinhole ray through every pixel centre of the new view (camera_ray with zero jitter and zero aperture;
+ *      opacity is not consulted: cut-outs count as opaque) and records instance | global triangle | u, v | camera-space z;
+ *   2. per hit pixel: local point v0 (1 - u - v) + v1 u + v2 v -> world as the instance stood when history_in was rendered
+ *      (prev_instance_transforms, or the scene's current rows) -> the previous call's camera space -> its continuous
+ *      pixel coordinates, snapped to 1/64 pixel -> bilinear 2 x 2 taps of history_in and the adaptive state.  A tap counts
+ *      when it lies inside the image with a bilinear weight > 0, its n_q >= 1, the previous view saw the same instance
+ *      there and |z_prev[q] - z| <= depth_tolerance * z.  With W the sum of the counting weights:
+ *        colour = sum w c_q / W,  n = min n_q (capped at max_history),  mean = sum w mean_q / W,
+ *        M2 = sum w s_q / W with s_q = M2_q where n_q == n, else (M2_q / n_q) n.
+ *      A pixel whose ray missed, whose point lies behind the previous camera or with W == 0 (disoccluded), and every pixel
+ *      of the first call after the resources were built or invalidated, takes n = 0, zero moments and texel (0, 0, 0, 1);
+ *   3. the adaptive resources' counts and moments take the gathered values, every block becomes active with no error
+ *      estimate and cleared flags, the statistics are recomputed (active pixels = W H, sum and max of n_p), and the new
+ *      view's visibility and camera become the previous ones.
+ * Colour is read from history_in's f32 accumulator when that is valid, else from its f16 texel, and stored to history_out
+ * as f16 rounded to nearest even whatever lupin_hip_set_store_rounding says (toward zero would darken the image by up to
+ * 2^-11 per call); in f32 accumulation mode it also goes to history_out's accumulator, which becomes valid (otherwise
+ * invalid).  An unmoved view copies history_in, n_p and the moments exactly at every hit pixel.
+ * Memory: two visibility buffers of 20 B per pixel and 12 B per pixel of gather output: 52 B per pixel, plus 48 B per
+ * instance on the device and twice that in pinned host memory.
+ * Out of scope: tiles and multi-GPU (whole frames of one device only); reprojection of background pixels (a miss starts
+ * afresh); motion of anything but the camera and instance transforms (deforming meshes, materials, lights, environments:
+ * invalidate or reset); depth of field in the reprojection itself (both views are taken as pinhole views). */
+typedef struct LupinReprojectResources LupinReprojectResources;
+
+typedef struct LupinReprojectDesc {
+    LupinCameraParams camera_params;      /* the NEW view */
+    LupinMat3x4       camera_transform;
+    float             ray_epsilon;        /* as advanced.ray_epsilon */
+    float             depth_tolerance;    /* relative; finite, >= 0 */
+    uint32_t          max_history;        /* 0 = no cap; else n_p <= max_history after the call */
+    const LupinMat4x3 *prev_instance_transforms;  /* NULL = no instance moved; else num_instances entries in
+                                                     lupin_hip_scene_update_instances' format: what the scene held
+                                                     when history_in was rendered */
+    uint32_t          num_instances;
+} LupinReprojectDesc;
+
+/* State for one width x height; no previous view yet. */
+int lupin_hip_build_reproject_resources(LupinContext *ctx, uint32_t width, uint32_t height, LupinReprojectResources **out);
+/* Waits for the context's work, then frees the state. */
+void lupin_hip_destroy_reproject_resources(LupinReprojectResources *res);
+/* Forgets the previous view: the next lupin_hip_adaptive_reproject gives n = 0 everywhere.  Call it wherever
+ * lupin_hip_adaptive_reset is called. */
+int lupin_hip_reproject_invalidate(LupinContext *ctx, LupinReprojectResources *res);
+/* LUPIN_ERR_INVALID_ARGUMENT, nothing written, for: a NULL argument, textures or resources of different sizes, objects of
+ * another context, a non-finite or negative depth_tolerance, num_instances other than the scene's when transforms are
+ * given, a previous transform whose inverse is not finite.  history_in == history_out: LUPIN_ERR_SAME_TARGET.  A scene
+ * without TLAS would give LUPIN_ERR_NO_SW_BVH as in the other entry points; lupin_hip_scene_create makes no such scene.
+ * Recorded pathtrace calls run first (their target may be history_in); the work is enqueued on the context's primary
+ * stream after every frame enqueued so far and the call returns without waiting for the device, with two exceptions: a
+ * call whose scene has more instances than any earlier call's on these resources reallocates the instance rows and waits
+ * for the stream, and a third call in flight waits for the first one's copy of them.  The host inverts one 3x4 matrix per
+ * instance in every call. */
+int lupin_hip_adaptive_reproject(LupinContext *ctx, LupinAdaptiveResources *ares, LupinReprojectResources *res, const LupinScene *scene,
+                                 const LupinReprojectDesc *desc, const LupinTexture *history_in, LupinTexture *history_out);
+/* Device time in milliseconds of the latest call's trace kernel and gather kernel (hipEvents around each launch), when that
+ * call ran after lupin_hip_stats_reset(ctx, LUPIN_STATS_KERNEL_TIMING); LUPIN_ERR_INVALID_ARGUMENT otherwise.  Waits for
+ * the gather. */
+int lupin_hip_reproject_timings(LupinContext *ctx, const LupinReprojectResources *res, float *trace_ms, float *gather_ms);
+/* The visibility buffer of the latest call's view (which = 0) or of the call before it (1); any pointer may be NULL;
+ * synchronises.  inst (HIT_MISS = 0xFFFFFFFF), tri (global triangle: the scene's meshes' triangles in order) and depth:
+ * W*H each; uv: W*H*2. */
+int lupin_hip_reproject_download(LupinContext *ctx, const LupinReprojectResources *res, int which, uint32_t *inst, uint32_t *tri, float *uv,
+                                 float *depth);
+
 /* ---- measurement hooks (no reference counterpart; the reference exposes none) ---- */
 
 typedef struct LupinStats {

@@ -5,7 +5,7 @@ use std::os::raw::{c_char, c_int, c_void};
 
 macro_rules! opaque { ($($n:ident),*) => { $(#[repr(C)] pub struct $n { _p: [u8; 0] })* } }
 opaque!(LupinContext, LupinPathtraceResources, LupinScene, LupinTexture, LupinDoubleBufferedTexture, LupinComm, LupinDenoiseResources,
-        LupinAdaptiveResources);
+        LupinAdaptiveResources, LupinReprojectResources);
 
 pub const LUPIN_OK: c_int = 0;
 pub const LUPIN_SENTINEL_IDX: u32 = 0xFFFF_FFFF;
@@ -70,6 +70,11 @@ pub const LUPIN_DENOISE_HIGH: u32 = 2;
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinAdaptiveParams { pub threshold: f32, pub min_frames: u32, pub max_frames: u32 }
 #[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinAdaptiveStats {
     pub active_pixels: u64, pub pixel_frames: u64, pub calls: u32, pub max_frames_taken: u32,
+}
+// reprojection of the adaptive history (no reference counterpart)
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinReprojectDesc {
+    pub camera_params: LupinCameraParams, pub camera_transform: LupinMat3x4, pub ray_epsilon: f32, pub depth_tolerance: f32, pub max_history: u32,
+    pub prev_instance_transforms: *const LupinMat4x3, pub num_instances: u32,
 }
 // radiance queries (no reference counterpart)
 pub const LUPIN_RAY_DIRECTION: u32 = 0;
@@ -169,6 +174,15 @@ extern "C" {
     pub fn lupin_hip_adaptive_stats(ctx: *mut LupinContext, ares: *const LupinAdaptiveResources, out: *mut LupinAdaptiveStats) -> c_int;
     pub fn lupin_hip_adaptive_download(ctx: *mut LupinContext, ares: *const LupinAdaptiveResources, frames: *mut u32, moments: *mut f32,
                                        block_error: *mut f32, block_active: *mut u8) -> c_int;
+    // reprojection: carries the image and the adaptive state over to a new view (camera or instances moved)
+    pub fn lupin_hip_build_reproject_resources(ctx: *mut LupinContext, width: u32, height: u32, out: *mut *mut LupinReprojectResources) -> c_int;
+    pub fn lupin_hip_destroy_reproject_resources(res: *mut LupinReprojectResources);
+    pub fn lupin_hip_reproject_invalidate(ctx: *mut LupinContext, res: *mut LupinReprojectResources) -> c_int;
+    pub fn lupin_hip_adaptive_reproject(ctx: *mut LupinContext, ares: *mut LupinAdaptiveResources, res: *mut LupinReprojectResources, scene: *const LupinScene,
+                                        desc: *const LupinReprojectDesc, history_in: *const LupinTexture, history_out: *mut LupinTexture) -> c_int;
+    pub fn lupin_hip_reproject_timings(ctx: *mut LupinContext, res: *const LupinReprojectResources, trace_ms: *mut f32, gather_ms: *mut f32) -> c_int;
+    pub fn lupin_hip_reproject_download(ctx: *mut LupinContext, res: *const LupinReprojectResources, which: c_int, inst: *mut u32, tri: *mut u32,
+                                        uv: *mut f32, depth: *mut f32) -> c_int;
     // radiance queries: the integrators over n caller-supplied rays (records n x 8 f32, out n x 4, out_rays null or n * samples x 8)
     pub fn lupin_hip_pathtrace_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinRayQueryDesc, n: u64,
                                     records: *const f32, out: *mut f32, out_rays: *mut f32) -> c_int;

@@ -14,6 +14,7 @@
 //! | `tonemap_and_fit_aspect`, `TonemapDesc`              | [`tonemap_and_fit_aspect`]             |
 //! | `build_denoise_resources`, `denoise`, `DenoiseDesc`, `DenoiseQuality` | [`build_denoise_resources`], [`denoise`] (own a-trous filter, not OIDN) |
 //! | (no counterpart)                                     | [`build_adaptive_resources`], [`pathtrace_scene_adaptive`] (adaptive sampling) |
+//! | (no counterpart)                                     | [`build_reproject_resources`], [`adaptive_reproject`] (reprojection of its history) |
 //! | (no counterpart: `lp::Scene` is immutable)           | [`Scene::update_instances`] (instance transforms moved in place, device-built TLAS) |
 //!
 //! Like the reference, failures panic (the reference asserts / panics; the C ABI returns a status + message).
@@ -229,4 +230,50 @@ pub fn pathtrace_scene_adaptive(device: &Device, resources: &PathtraceResources,
                                 desc: &PathtraceDesc, adaptive: &mut AdaptiveResources, params: &AdaptiveParams) {
     let p = LupinAdaptiveParams { threshold: params.threshold, min_frames: params.min_frames, max_frames: params.max_frames };
     with_desc(desc, |c| check(unsafe { lupin_hip_pathtrace_scene_adaptive(device.raw, resources.raw, scene.raw, render_target.raw, pathtrace_type as u32, c, adaptive.raw, &p) }));
+}
+
+/// Visibility buffers and the previous view of [`adaptive_reproject`] (no reference counterpart).
+pub struct ReprojectResources { raw: *mut LupinReprojectResources, ctx: *mut LupinContext, width: u32, height: u32 }
+impl Drop for ReprojectResources { fn drop(&mut self) { unsafe { lupin_hip_destroy_reproject_resources(self.raw) } } }
+impl ReprojectResources {
+    /// Forgets the previous view: call it wherever [`AdaptiveResources::reset`] is called.
+    pub fn invalidate(&mut self) { check(unsafe { lupin_hip_reproject_invalidate(self.ctx, self.raw) }); }
+    /// Visibility of the latest call's view (`which` = 0) or of the call before it (1); synchronises.  Every slice that is
+    /// given must hold width * height entries (`uv`: twice that); `inst` is `u32::MAX` where the ray missed.
+    pub fn download(&self, which: i32, inst: Option<&mut [u32]>, tri: Option<&mut [u32]>, uv: Option<&mut [f32]>, depth: Option<&mut [f32]>) {
+        let px = (self.width as usize) * (self.height as usize);
+        assert!(inst.as_ref().map_or(true, |s| s.len() == px) && tri.as_ref().map_or(true, |s| s.len() == px));
+        assert!(uv.as_ref().map_or(true, |s| s.len() == 2 * px) && depth.as_ref().map_or(true, |s| s.len() == px));
+        check(unsafe { lupin_hip_reproject_download(self.ctx, self.raw, which, inst.map_or(ptr::null_mut(), |s| s.as_mut_ptr()),
+                                                    tri.map_or(ptr::null_mut(), |s| s.as_mut_ptr()), uv.map_or(ptr::null_mut(), |s| s.as_mut_ptr()),
+                                                    depth.map_or(ptr::null_mut(), |s| s.as_mut_ptr())) });
+    }
+    /// Device milliseconds `(trace, gather)` of the latest call's two kernels; the call must have run in the kernel-timing stats mode.
+    pub fn timings(&self) -> (f32, f32) {
+        let (mut t, mut g) = (0f32, 0f32);
+        check(unsafe { lupin_hip_reproject_timings(self.ctx, self.raw, &mut t, &mut g) });
+        (t, g)
+    }
+}
+pub fn build_reproject_resources(device: &Device, width: u32, height: u32) -> ReprojectResources {
+    let mut raw = ptr::null_mut();
+    check(unsafe { lupin_hip_build_reproject_resources(device.raw, width, height, &mut raw) });
+    ReprojectResources { raw, ctx: device.raw, width, height }
+}
+pub struct ReprojectDesc<'a> {
+    pub camera_params: CameraParams, pub camera_transform: LupinMat3x4, pub ray_epsilon: f32, pub depth_tolerance: f32, pub max_history: u32,
+    /// `None`: no instance moved; else one `transpose_inverse_transform` per instance, as the scene held them when `history_in` was rendered.
+    pub prev_instance_transforms: Option<&'a [LupinMat4x3]>,
+}
+/// Rewrites the accumulated image and the adaptive state for the new view; the next adaptive call continues from them.
+pub fn adaptive_reproject(device: &Device, adaptive: &mut AdaptiveResources, resources: &mut ReprojectResources, scene: &Scene, desc: &ReprojectDesc,
+                          history_in: Texture, history_out: Texture) {
+    let cp = &desc.camera_params;
+    let c = LupinReprojectDesc {
+        camera_params: LupinCameraParams { is_orthographic: cp.is_orthographic as u32, lens: cp.lens, film: cp.film, aspect: cp.aspect, focus: cp.focus, aperture: cp.aperture },
+        camera_transform: desc.camera_transform, ray_epsilon: desc.ray_epsilon, depth_tolerance: desc.depth_tolerance, max_history: desc.max_history,
+        prev_instance_transforms: desc.prev_instance_transforms.map_or(ptr::null(), |t| t.as_ptr()),
+        num_instances: desc.prev_instance_transforms.map_or(0, |t| t.len() as u32),
+    };
+    check(unsafe { lupin_hip_adaptive_reproject(device.raw, adaptive.raw, resources.raw, scene.raw, &c, history_in.raw, history_out.raw) });
 }

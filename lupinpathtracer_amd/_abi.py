@@ -145,6 +145,11 @@ class AdaptiveStatsC(C.Structure):   # LupinAdaptiveStats
     _fields_ = [("active_pixels", C.c_uint64), ("pixel_frames", C.c_uint64), ("calls", C.c_uint32), ("max_frames_taken", C.c_uint32)]
 
 
+class ReprojectDescC(C.Structure):   # LupinReprojectDesc
+    _fields_ = [("camera_params", CameraParamsC), ("camera_transform", Mat3x4), ("ray_epsilon", C.c_float), ("depth_tolerance", C.c_float),
+                ("max_history", C.c_uint32), ("prev_instance_transforms", C.c_void_p), ("num_instances", C.c_uint32)]
+
+
 class RayQueryDescC(C.Structure):   # LupinRayQueryDesc
     _fields_ = [("pathtrace_type", C.c_uint32), ("max_bounces", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32),
                 ("max_slots", C.c_uint32), ("advanced", AdvancedParamsC)]
@@ -253,6 +258,12 @@ SYMBOLS = [
     ("lupin_hip_pathtrace_scene_adaptive", C.c_int, [_P, _P, _P, _P, _U32, C.POINTER(PathtraceDescC), _P, C.POINTER(AdaptiveParamsC)]),
     ("lupin_hip_adaptive_stats", C.c_int, [_P, _P, C.POINTER(AdaptiveStatsC)]),
     ("lupin_hip_adaptive_download", C.c_int, [_P, _P, _P, _P, _P, _P]),
+    ("lupin_hip_build_reproject_resources", C.c_int, [_P, _U32, _U32, _PP]),
+    ("lupin_hip_destroy_reproject_resources", None, [_P]),
+    ("lupin_hip_reproject_invalidate", C.c_int, [_P, _P]),
+    ("lupin_hip_adaptive_reproject", C.c_int, [_P, _P, _P, _P, C.POINTER(ReprojectDescC), _P, _P]),
+    ("lupin_hip_reproject_timings", C.c_int, [_P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("lupin_hip_reproject_download", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P]),
     ("lupin_hip_lbvh_depth", _U32, [_U32]),
     ("lupin_hip_lbvh_node_count", C.c_uint64, [_U32]),
     ("lupin_hip_build_bvh_device", C.c_int64, [_P, _P, _U32, _P, _U32, _P, C.c_uint64]),

@@ -14,6 +14,8 @@ data_structures.rs, on top of the C ABI in include/lupin_hip.h:
                                                                  a-trous filter in HIP, not OIDN: DESIGN.md 9)
     (no reference counterpart)           adaptive sampling   -> AdaptiveParams, build_adaptive_resources,
                                                                  pathtrace_scene_adaptive
+    (no reference counterpart)           its reprojection    -> ReprojectDesc, build_reproject_resources,
+                                                                 adaptive_reproject
     lp::SceneCPU / validate_scene / build_accel_structures_and_upload
                                          renderer.rs:62-76, data_structures.rs:696-928
 
@@ -991,6 +993,91 @@ def pathtrace_scene_adaptive(ctx, resources, scene, render_target, pathtrace_typ
     p = _abi.AdaptiveParamsC(float(params.threshold), int(params.min_frames), int(params.max_frames))
     check(lib().lupin_hip_pathtrace_scene_adaptive(ctx.handle, resources.handle, scene.handle, render_target.handle,
                                                    int(pathtrace_type), C.byref(c), adaptive_resources.handle, C.byref(p)))
+
+
+@dataclass
+class ReprojectDesc:  # LupinReprojectDesc
+    camera_params: CameraParams = field(default_factory=CameraParams)   # the NEW view
+    camera_transform: np.ndarray = field(default_factory=identity_mat3x4)
+    ray_epsilon: float = 0.001
+    depth_tolerance: float = 0.02    # relative to the expected depth
+    max_history: int = 0             # 0 = no cap; else every n_p <= max_history after the call
+    # None = no instance moved; else (n, 3, 4) transpose_inverse_transform matrices (or instance records): what the scene held
+    # when history_in was rendered
+    prev_instance_transforms: Optional[np.ndarray] = None
+
+
+class ReprojectResources:
+    """Two visibility buffers, the previous view and the gather's output for one width x height (52 B per pixel)."""
+
+    def __init__(self, ctx, width, height):
+        _require_device(ctx, "build_reproject_resources")
+        self.ctx = ctx
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        check(lib().lupin_hip_build_reproject_resources(ctx.handle, self.width, self.height, C.byref(h)))
+        self.handle = h
+
+    def invalidate(self):
+        """Forget the previous view (the next adaptive_reproject gives n = 0 everywhere): wherever AdaptiveResources.reset is called."""
+        check(lib().lupin_hip_reproject_invalidate(self.ctx.handle, self.handle))
+
+    def timings(self):
+        """(trace_ms, gather_ms): device time of the latest call's two kernels; that call must have run after
+        Context.stats_reset(1).  Waits for the gather."""
+        t, g = C.c_float(), C.c_float()
+        check(lib().lupin_hip_reproject_timings(self.ctx.handle, self.handle, C.byref(t), C.byref(g)))
+        return float(t.value), float(g.value)
+
+    def download(self, which=0):
+        """Visibility of the latest call's view (which = 0) or of the call before it (1): (inst (H, W) uint32 with 0xFFFFFFFF =
+        miss, tri (H, W) uint32 global triangle, uv (H, W, 2) float32, depth (H, W) float32 camera-space z)."""
+        inst = np.zeros((self.height, self.width), np.uint32)
+        tri = np.zeros((self.height, self.width), np.uint32)
+        uv = np.zeros((self.height, self.width, 2), np.float32)
+        depth = np.zeros((self.height, self.width), np.float32)
+        check(lib().lupin_hip_reproject_download(self.ctx.handle, self.handle, int(which), ptr(inst), ptr(tri), ptr(uv), ptr(depth)))
+        return inst, tri, uv, depth
+
+    def __del__(self):
+        try:
+            if self.handle:
+                lib().lupin_hip_destroy_reproject_resources(self.handle)
+            self.handle = None
+        except Exception:
+            pass
+
+
+def build_reproject_resources(ctx, width, height):
+    return ReprojectResources(ctx, width, height)
+
+
+def adaptive_reproject(ctx, adaptive_resources, resources, scene, desc: ReprojectDesc, history_in, history_out):
+    """Carry history_in, the per-pixel frame counts and the moments over to desc's view: history_out and the
+    adaptive state then hold, per pixel, the history of the surface point the pixel now shows (n = 0 where there is none),
+    and the next pathtrace_scene_adaptive call with prev_frame = history_out continues from them."""
+    if scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "scene was built without a device context; there is no CPU fallback")
+    c = _abi.ReprojectDescC()
+    cp = desc.camera_params
+    c.camera_params = _abi.CameraParamsC(1 if cp.is_orthographic else 0, cp.lens, cp.film, cp.aspect, cp.focus, cp.aperture)
+    m = np.asarray(desc.camera_transform, np.float32).reshape(4, 3)
+    for col in range(4):
+        for row in range(3):
+            c.camera_transform.m[col][row] = float(m[col][row])
+    c.ray_epsilon = float(desc.ray_epsilon)
+    c.depth_tolerance = float(desc.depth_tolerance)
+    c.max_history = int(desc.max_history)
+    t = None
+    if desc.prev_instance_transforms is not None:
+        t = np.asarray(desc.prev_instance_transforms)
+        if t.dtype == INSTANCE_DTYPE:
+            t = t["transpose_inverse_transform"]
+        t = np.ascontiguousarray(t, np.float32).reshape(-1, 3, 4)
+        c.prev_instance_transforms = t.ctypes.data
+        c.num_instances = len(t)
+    check(lib().lupin_hip_adaptive_reproject(ctx.handle, adaptive_resources.handle, resources.handle, scene.handle, C.byref(c),
+                                             history_in.handle, history_out.handle))
 
 
 def pathtrace_scene_tiles(ctx, resources, scene, render_target, pathtrace_type, desc, tile_size, rank, world):

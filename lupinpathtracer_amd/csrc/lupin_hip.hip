@@ -1,8 +1,9 @@
 // lupin_hip.hip -- host side of liblupin_hip.so: the C ABI of include/lupin_hip.h (contexts and their lanes, scene upload,
 // textures, the pathtrace_scene family, measurement hooks, probes).  The stage kernels live in lupin_stages.hpp, the
 // traversal / material / light device functions in lupin_device.hpp, the CPU builders in builders.cpp, the device BLAS
-// builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp, adaptive sampling's in lupin_adaptive.hpp, the radiance
-// queries' in lupin_rays.hpp, light-probe baking's in lupin_probes.hpp, lightmap baking's in lupin_lightmap.hpp.
+// builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp, adaptive sampling's in lupin_adaptive.hpp, its
+// reprojection's in lupin_reproject.hpp, the radiance queries' in lupin_rays.hpp, light-probe baking's in lupin_probes.hpp,
+// lightmap baking's in lupin_lightmap.hpp.
 //
 // THERE IS NO CPU FALLBACK: without a HIP device every entry point that needs one fails with LUPIN_ERR_NO_DEVICE.
 
@@ -25,6 +26,7 @@
 #include "lupin_stages.hpp"
 #include "lupin_denoise.hpp"
 #include "lupin_adaptive.hpp"
+#include "lupin_reproject.hpp"
 #include "lupin_rays.hpp"
 #include "lupin_probes.hpp"
 #include "lupin_lightmap.hpp"
@@ -3174,6 +3176,286 @@ int lupin_hip_adaptive_download(LupinContext *ctx, const LupinAdaptiveResources 
     if (moments) HIP_TRY(hipMemcpyAsync(moments, d.moments, px * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
     if (block_error) HIP_TRY(hipMemcpyAsync(block_error, d.block_error, nb * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (block_active) HIP_TRY(hipMemcpyAsync(block_active, d.block_active, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return LUPIN_OK;
+}
+
+}  // extern "C"
+
+// ---- reprojection of the adaptive history (no reference counterpart; kernels and rule: lupin_reproject.hpp) ----
+
+struct LupinReprojectResources
+{
+    LupinContext *ctx;
+    int device;
+    uint32_t width, height;
+    ReprojectVis vis[2];             // [cur] is written by a call's trace; [cur ^ 1] is the previous call's
+    int cur;
+    uint32_t *frames;                // the gather's output, swapped with the adaptive resources' arrays after it
+    float2 *moments;
+    bool prev_valid;
+    LupinPushConstants prev_pc;      // the previous call's camera
+    LupinMat3x4 prev_cam_inv;
+    // previous local -> world rows of every instance: two pinned staging buffers used in turn (a call never waits for the
+    // copy of the call before it) and their device copy, allocated by the first call, grown on demand
+    float4 *h_rows[2], *d_rows;
+    uint32_t rows_capacity;          // instances
+    hipEvent_t rows_copied[2];       // staging buffer k may be rewritten once rows_copied[k] has passed
+    int rows_next;
+    // LUPIN_STATS_KERNEL_TIMING: events before the trace, between trace and gather, after the gather of the latest call
+    hipEvent_t ev[3];
+    bool timed;                      // the latest call recorded them
+};
+
+extern "C" {
+
+static void free_vis(ReprojectVis &v) { hipFree(v.inst); hipFree(v.tri); hipFree(v.uv); hipFree(v.depth); }
+static void free_reproject(LupinReprojectResources *r)
+{
+    free_vis(r->vis[0]); free_vis(r->vis[1]);
+    hipFree(r->frames); hipFree(r->moments); hipFree(r->d_rows);
+    for (int k = 0; k < 2; k++)
+    {
+        if (r->h_rows[k]) hipHostFree(r->h_rows[k]);
+        if (r->rows_copied[k]) hipEventDestroy(r->rows_copied[k]);
+    }
+    for (int k = 0; k < 3; k++)
+        if (r->ev[k]) hipEventDestroy(r->ev[k]);
+    delete r;
+}
+
+int lupin_hip_build_reproject_resources(LupinContext *ctx, uint32_t width, uint32_t height, LupinReprojectResources **out)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!out || width == 0 || height == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "bad reproject resources size");
+    if ((uint64_t)width * height > 0xFFFFFFFFull / 2) return fail(LUPIN_ERR_INVALID_ARGUMENT, "reproject size too large");
+    HIP_TRY(hipSetDevice(ctx->device));
+    LupinReprojectResources *r = new LupinReprojectResources();
+    memset(r, 0, sizeof(*r));
+    r->ctx = ctx; r->device = ctx->device; r->width = width; r->height = height;
+    const size_t px = (size_t)width * height;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess; k++)
+    {
+        ReprojectVis &v = r->vis[k];
+        e = hipMalloc((void **)&v.inst, px * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&v.tri, px * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&v.uv, px * sizeof(float2));
+        if (e == hipSuccess) e = hipMalloc((void **)&v.depth, px * sizeof(float));
+        // a download before the first call reads misses, not uninitialised memory
+        if (e == hipSuccess) e = hipMemsetAsync(v.inst, 0xFF, px * sizeof(uint32_t), ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(v.tri, 0, px * sizeof(uint32_t), ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(v.uv, 0, px * sizeof(float2), ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(v.depth, 0, px * sizeof(float), ctx->stream);
+    }
+    if (e == hipSuccess) e = hipMalloc((void **)&r->frames, px * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&r->moments, px * sizeof(float2));
+    for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipEventCreateWithFlags(&r->rows_copied[k], hipEventDisableTiming);
+    for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipEventCreate(&r->ev[k]);
+    if (e != hipSuccess)
+    {
+        hipStreamSynchronize(ctx->stream);
+        free_reproject(r);
+        return fail(LUPIN_ERR_OUT_OF_MEMORY, hipGetErrorString(e));
+    }
+    *out = r;
+    return LUPIN_OK;
+}
+
+void lupin_hip_destroy_reproject_resources(LupinReprojectResources *res)
+{
+    if (!res) return;
+    hipSetDevice(res->device);
+    if (ctx_alive(res->ctx)) sync_all(res->ctx);   // a destroyed context has drained its streams already
+    free_reproject(res);
+}
+
+int lupin_hip_reproject_invalidate(LupinContext *ctx, LupinReprojectResources *res)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!res) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (res->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "reproject resources of another context");
+    res->prev_valid = false;   // host state only: the next call's gather is launched with prev_valid = 0
+    return LUPIN_OK;
+}
+
+int lupin_hip_adaptive_reproject(LupinContext *ctx, LupinAdaptiveResources *ares, LupinReprojectResources *res, const LupinScene *scene,
+                                 const LupinReprojectDesc *desc, const LupinTexture *history_in, LupinTexture *history_out)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!ares || !res || !scene || !desc || !history_in || !history_out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (ares->ctx != ctx || res->ctx != ctx || scene->ctx != ctx || history_in->ctx != ctx || history_out->ctx != ctx)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "object of another or a destroyed context");
+    if (history_in == history_out) return fail(LUPIN_ERR_SAME_TARGET, "history_out must differ from history_in");
+    const uint32_t W = res->width, H = res->height;
+    if (ares->dev.width != W || ares->dev.height != H || history_in->width != W || history_in->height != H || history_out->width != W ||
+        history_out->height != H)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "history_in, history_out, adaptive and reproject resources differ in size");
+    if (!(desc->depth_tolerance >= 0.0f) || !std::isfinite(desc->depth_tolerance))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "depth_tolerance must be finite and >= 0");
+    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    const uint32_t ninst = scene->dev.num_instances;
+    if (desc->prev_instance_transforms && desc->num_instances != ninst)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "prev_instance_transforms: " + std::to_string(desc->num_instances) + " transforms for " + std::to_string(ninst) + " instances");
+    // previous local -> world of every instance: the inverse of its world -> local rows (Mat3x4::inverse, as the loaders use it)
+    std::vector<float4> rows((size_t)ninst * 3u);
+    for (uint32_t i = 0; i < ninst; i++)
+    {
+        LupinMat3x4 w2l, l2w;
+        if (desc->prev_instance_transforms)
+        {
+            const float (*m)[4] = desc->prev_instance_transforms[i].m;
+            for (int c = 0; c < 4; c++) for (int r = 0; r < 3; r++) w2l.m[c][r] = m[r][c];
+        }
+        else
+        {
+            const InstanceDev &in = scene->host_instances[i];
+            const float4 rr[3] = {in.r0, in.r1, in.r2};
+            for (int r = 0; r < 3; r++) { w2l.m[0][r] = rr[r].x; w2l.m[1][r] = rr[r].y; w2l.m[2][r] = rr[r].z; w2l.m[3][r] = rr[r].w; }
+        }
+        lupin_mat3x4_inverse(&w2l, &l2w);
+        for (int r = 0; r < 3; r++)
+        {
+            rows[(size_t)i * 3 + r] = make_float4(l2w.m[0][r], l2w.m[1][r], l2w.m[2][r], l2w.m[3][r]);
+            // a caller's transform must invert; the scene's own rows were accepted at upload (a singular one reprojects nowhere: NaN fails every tap)
+            if (desc->prev_instance_transforms && !(std::isfinite(l2w.m[0][r]) && std::isfinite(l2w.m[1][r]) && std::isfinite(l2w.m[2][r]) && std::isfinite(l2w.m[3][r])))
+                return fail(LUPIN_ERR_INVALID_ARGUMENT, "prev_instance_transforms[" + std::to_string(i) + "] has no finite inverse");
+        }
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    TraversalLds t;
+    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
+    // history_in may be the target of recorded pathtrace calls: run them, then order the work after every frame in flight
+    int frc = flush_pending(ctx);
+    if (frc != LUPIN_OK) return frc;
+    join_primary(ctx);
+    hipStream_t st = ctx->stream;
+    if (ninst > res->rows_capacity)
+    {
+        // the first call allocates; only a later call with a scene of more instances finds buffers that an earlier call's
+        // copy or gather may still read, and waits for them
+        if (res->rows_capacity) HIP_TRY(hipStreamSynchronize(st));
+        if (res->d_rows) { hipFree(res->d_rows); res->d_rows = nullptr; }
+        for (int k = 0; k < 2; k++)
+            if (res->h_rows[k]) { hipHostFree(res->h_rows[k]); res->h_rows[k] = nullptr; }
+        res->rows_capacity = 0;
+        HIP_TRY(hipMalloc((void **)&res->d_rows, (size_t)ninst * 3 * sizeof(float4)));
+        for (int k = 0; k < 2; k++) HIP_TRY(hipHostMalloc((void **)&res->h_rows[k], (size_t)ninst * 3 * sizeof(float4)));
+        res->rows_capacity = ninst;
+    }
+    float4 *out32 = nullptr;
+    if (ctx->accum_mode == LUPIN_ACCUM_F32)
+    {
+        if (!history_out->accum32)
+        {
+            HIP_TRY(hipMalloc((void **)&history_out->accum32, (size_t)W * H * 16));
+            HIP_TRY(hipMemsetAsync(history_out->accum32, 0, (size_t)W * H * 16, st));
+        }
+        out32 = history_out->accum32;
+    }
+    if (ninst)
+    {
+        const int k = res->rows_next;
+        res->rows_next ^= 1;
+        HIP_TRY(hipEventSynchronize(res->rows_copied[k]));   // the copy of the call before the previous one: passed unless three calls are in flight
+        memcpy(res->h_rows[k], rows.data(), rows.size() * sizeof(float4));
+        HIP_TRY(hipMemcpyAsync(res->d_rows, res->h_rows[k], rows.size() * sizeof(float4), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(res->rows_copied[k], st));
+    }
+    res->timed = ctx->timing;
+
+    // ---- step 1: the new view's visibility ----
+    FrameParams fp;
+    memset(&fp, 0, sizeof(fp));
+    LupinPushConstants &pc = fp.pc;
+    if (desc->camera_params.is_orthographic) pc.flags |= LUPIN_FLAG_CAMERA_ORTHO;
+    const LupinMat3x4 &ct = desc->camera_transform;
+    for (int c = 0; c < 4; c++) { pc.camera_transform.m[c][0] = ct.m[c][0]; pc.camera_transform.m[c][1] = ct.m[c][1]; pc.camera_transform.m[c][2] = ct.m[c][2]; pc.camera_transform.m[c][3] = (c == 3) ? 1.0f : 0.0f; }
+    pc.camera_lens = desc->camera_params.lens;
+    pc.camera_film = desc->camera_params.film;
+    pc.camera_aspect = desc->camera_params.aspect;
+    pc.camera_focus = desc->camera_params.focus;
+    pc.ray_epsilon = desc->ray_epsilon;
+    fp.width = W; fp.height = H; fp.reg_w = W; fp.reg_h = H;
+    LupinMat3x4 cam_inv;
+    lupin_mat3x4_inverse(&ct, &cam_inv);
+    const uint32_t n = W * H;
+    const ReprojectVis cur = res->vis[res->cur], prev = res->vis[res->cur ^ 1];
+    if (res->timed) hipEventRecord(res->ev[0], st);
+    with_bool(t.geo, [&](auto G) {
+        constexpr bool LDSGEO = decltype(G)::value;
+        hipLaunchKernelGGL(k_reproject_trace<LDSGEO>, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, st, scene->dev, fp, n, cam_inv, cur, t.stack_words);
+    });
+
+    if (res->timed) hipEventRecord(res->ev[1], st);
+
+    // ---- step 2: gather the previous view's image and state ----
+    ReprojectArgs a;
+    memset(&a, 0, sizeof(a));
+    a.width = W; a.height = H;
+    a.prev_pc = res->prev_pc;
+    a.prev_cam_inv = res->prev_cam_inv;
+    a.prev_local_to_world = res->d_rows;
+    a.tris = scene->dev.tris;
+    a.depth_tolerance = desc->depth_tolerance;
+    a.max_history = desc->max_history;
+    a.prev_valid = res->prev_valid ? 1u : 0u;
+    a.cur = cur; a.prev = prev;
+    a.frames_in = ares->dev.frames; a.moments_in = ares->dev.moments;
+    a.frames_out = res->frames; a.moments_out = res->moments;
+    a.hist_in = (const uint2 *)history_in->data;
+    a.hist_in32 = (history_in->accum32 && history_in->accum32_valid) ? history_in->accum32 : nullptr;
+    a.hist_out = (uint2 *)history_out->data;
+    a.hist_out32 = out32;
+    hipLaunchKernelGGL(k_reproject_gather, dim3((W + LP_DN_BX - 1) / LP_DN_BX, (H + LP_DN_BY - 1) / LP_DN_BY), dim3(LP_DN_BX, LP_DN_BY), 0, st, a);
+    if (res->timed) hipEventRecord(res->ev[2], st);
+
+    // ---- step 3: the gathered counts and moments become the adaptive state; every block active; statistics ----
+    std::swap(ares->dev.frames, res->frames);
+    std::swap(ares->dev.moments, res->moments);
+    const AdaptiveDev &ad = ares->dev;
+    const uint32_t nblocks = ad.blocks_x * ad.blocks_y;
+    HIP_TRY(hipMemsetAsync(ad.stats, 0, 3 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_reproject_refresh, dim3((nblocks + LP_BLOCK / 64 - 1) / (LP_BLOCK / 64)), dim3(LP_BLOCK), 0, st, ad);
+    hipLaunchKernelGGL(k_adaptive_mask, dim3((nblocks + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, st, ad);
+    history_out->accum32_valid = out32 != nullptr;
+    res->cur ^= 1;
+    res->prev_pc = pc;
+    res->prev_cam_inv = cam_inv;
+    res->prev_valid = true;
+    HIP_TRY(hipGetLastError());
+    return LUPIN_OK;
+}
+
+int lupin_hip_reproject_timings(LupinContext *ctx, const LupinReprojectResources *res, float *trace_ms, float *gather_ms)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!res || !trace_ms || !gather_ms) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (res->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "reproject resources of another context");
+    if (!res->timed) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the latest lupin_hip_adaptive_reproject did not run under LUPIN_STATS_KERNEL_TIMING");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipEventSynchronize(res->ev[2]));
+    HIP_TRY(hipEventElapsedTime(trace_ms, res->ev[0], res->ev[1]));
+    HIP_TRY(hipEventElapsedTime(gather_ms, res->ev[1], res->ev[2]));
+    return LUPIN_OK;
+}
+
+int lupin_hip_reproject_download(LupinContext *ctx, const LupinReprojectResources *res, int which, uint32_t *inst, uint32_t *tri, float *uv,
+                                 float *depth)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!res) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (res->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "reproject resources of another context");
+    if (which != 0 && which != 1) return fail(LUPIN_ERR_INVALID_ARGUMENT, "which: 0 = current, 1 = previous");
+    HIP_TRY(hipSetDevice(ctx->device));
+    join_primary(ctx);
+    // after a call the buffer its trace wrote is vis[cur ^ 1] (the roles were swapped): that is the current view's
+    const ReprojectVis &v = res->vis[res->cur ^ 1 ^ which];
+    const size_t px = (size_t)res->width * res->height;
+    if (inst) HIP_TRY(hipMemcpyAsync(inst, v.inst, px * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (tri) HIP_TRY(hipMemcpyAsync(tri, v.tri, px * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (uv) HIP_TRY(hipMemcpyAsync(uv, v.uv, px * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
+    if (depth) HIP_TRY(hipMemcpyAsync(depth, v.depth, px * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return LUPIN_OK;
 }

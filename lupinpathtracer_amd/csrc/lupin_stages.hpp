@@ -133,25 +133,40 @@ __device__ __forceinline__ uint32_t slot_frame(const FrameParams &fp, uint32_t s
 // Camera (compute_camera_ray, pathtracer.wgsl:505-542) -- draws 2 (jitter) + 2 (lens) numbers
 // ------------------------------------------------------------------------------------------------
 
-LP_FN void camera_ray(const FrameParams &fp, uint32_t gx, uint32_t gy, uint32_t &rng, f3 &ori, f3 &dir)
+// film extent along x and y
+LP_FN void camera_film_size(float film, float aspect, float &fsx, float &fsy)
+{
+    fsx = (aspect >= 1.0f) ? film : film * aspect;
+    fsy = (aspect >= 1.0f) ? film / aspect : film;
+}
+
+// PINHOLE: no number is drawn; jitter offset 0 and aperture 0, i.e. the ray through the pixel centre that the reprojection's
+// primary trace follows and its projection inverts (lupin_reproject.hpp).  One body, so both rays are the same expressions.
+template <bool PINHOLE>
+LP_FN void camera_ray_of(const FrameParams &fp, uint32_t gx, uint32_t gy, uint32_t &rng, f3 &ori, f3 &dir)
 {
     const LupinPushConstants &pc = fp.pc;
-    float j0 = rnd(rng), j1 = rnd(rng);
+    float j0 = 0.5f, j1 = 0.5f;
+    if constexpr (!PINHOLE) { j0 = rnd(rng); j1 = rnd(rng); }
     float offx = j0 - 0.5f, offy = j1 - 0.5f;
     float resx = (float)fp.width, resy = (float)fp.height;
     float pcx = (float)gx + 0.5f, pcy = (resy - (float)gy) + 0.5f;
     float uvx = (pcx + offx) / resx, uvy = (pcy + offy) / resy;
 
     float lens = pc.camera_lens, film = pc.camera_film, aspect = pc.camera_aspect;
-    float focus = pc.camera_focus, aperture = pc.camera_aperture;
-    float fsx = (aspect >= 1.0f) ? film : film * aspect;
-    float fsy = (aspect >= 1.0f) ? film / aspect : film;
+    float focus = pc.camera_focus, aperture = PINHOLE ? 0.0f : pc.camera_aperture;
+    float fsx, fsy;
+    camera_film_size(film, aspect, fsx, fsy);
     // random_in_disk (:1623-1629)
-    float d0 = rnd(rng), d1 = rnd(rng);
-    float dr = sqrtf(d1);
-    float ds, dc;
-    lpm_sincosf(2.0f * LP_PI * d0, &ds, &dc);
-    float lux = dc * dr, luy = ds * dr;
+    float lux = 0.0f, luy = 0.0f;
+    if constexpr (!PINHOLE)
+    {
+        float d0 = rnd(rng), d1 = rnd(rng);
+        float dr = sqrtf(d1);
+        float ds, dc;
+        lpm_sincosf(2.0f * LP_PI * d0, &ds, &dc);
+        lux = dc * dr; luy = ds * dr;
+    }
 
     f3 e, d;
     if (pc.flags & LUPIN_FLAG_CAMERA_ORTHO)
@@ -178,6 +193,16 @@ LP_FN void camera_ray(const FrameParams &fp, uint32_t gx, uint32_t gy, uint32_t 
     dir = normalize3(mk3(m[0][0] * d.x + m[1][0] * d.y + m[2][0] * d.z + m[3][0] * 0.0f,
                          m[0][1] * d.x + m[1][1] * d.y + m[2][1] * d.z + m[3][1] * 0.0f,
                          m[0][2] * d.x + m[1][2] * d.y + m[2][2] * d.z + m[3][2] * 0.0f));
+}
+
+LP_FN void camera_ray(const FrameParams &fp, uint32_t gx, uint32_t gy, uint32_t &rng, f3 &ori, f3 &dir)
+{
+    camera_ray_of<false>(fp, gx, gy, rng, ori, dir);
+}
+LP_FN void camera_ray_centre(const FrameParams &fp, uint32_t gx, uint32_t gy, f3 &ori, f3 &dir)
+{
+    uint32_t unused = 0u;
+    camera_ray_of<true>(fp, gx, gy, unused, ori, dir);
 }
 
 __device__ __forceinline__ void slot_to_pixel(const FrameParams &fp, uint32_t slot, uint32_t &gx, uint32_t &gy)
