@@ -100,13 +100,19 @@ def local_to_world_rows(transpose_inverse_transforms):
     return np.stack([api.mat3x4_inverse(np.ascontiguousarray(r.T)).T for r in t]).astype(np.float32) if len(t) else np.zeros((0, 3, 4), np.float32)
 
 
+def mesh_arrays(scene, i):
+    """Views of mesh i as the scene holds it: (vertex positions (V, 4) float32, the builder's reordered indices (3 T,) uint32)."""
+    md = scene.desc.meshes[i]
+    v = np.ctypeslib.as_array(C.cast(md.verts_pos, C.POINTER(C.c_float)), (md.num_verts, 4)) if md.num_verts else np.zeros((0, 4), np.float32)
+    idx = np.ctypeslib.as_array(C.cast(md.indices, C.POINTER(C.c_uint32)), (md.num_indices,)) if md.num_indices else np.zeros(0, np.uint32)
+    return v, idx
+
+
 def scene_triangles(scene):
     """(vertices (T, 3, 3) of every global triangle: the meshes' triangles in order, as uploaded; first global triangle per mesh)."""
     tris, offsets, total = [], [], 0
     for i in range(scene.desc.num_meshes):
-        md = scene.desc.meshes[i]
-        v = np.ctypeslib.as_array(C.cast(md.verts_pos, C.POINTER(C.c_float)), (md.num_verts, 4)) if md.num_verts else np.zeros((0, 4), np.float32)
-        idx = np.ctypeslib.as_array(C.cast(md.indices, C.POINTER(C.c_uint32)), (md.num_indices,)) if md.num_indices else np.zeros(0, np.uint32)
+        v, idx = mesh_arrays(scene, i)
         offsets.append(total)
         tris.append(v[idx.reshape(-1, 3)][:, :, :3].astype(np.float32))
         total += len(idx) // 3
