@@ -655,6 +655,66 @@ inline std::array<float, 3> sh_irradiance(const float *coeffs, float nx, float n
     return e;
 }
 
+// occlusion queries (no reference counterpart): any-hit segment tests and ambient occlusion.  Geometric
+// visibility: material opacity is not consulted.
+enum class OcclusionMode : uint32_t { Direction = LUPIN_OCCLUSION_DIRECTION, CosineHemisphere = LUPIN_OCCLUSION_COSINE_HEMISPHERE };
+struct OcclusionDesc
+{
+    OcclusionMode mode = OcclusionMode::Direction;
+    uint32_t samples = 1;          // slots per record; 1 in direction mode
+    uint32_t flags = 0;            // LUPIN_OCCLUSION_DEVICE_POINTERS: records and out_blocked are device memory
+    float ray_epsilon = 0.001f;
+};
+// records: n x 8 floats (origin | RNG bits, unit direction or normal | tmax); out_blocked: n counts of blocked slots
+inline void occlusion_rays(const Device &d, const Scene &scene, const OcclusionDesc &desc, uint64_t n, const float *records, uint32_t *out_blocked)
+{
+    const LupinOcclusionDesc c{(uint32_t)desc.mode, desc.samples, desc.flags, desc.ray_epsilon};
+    check(lupin_hip_occlusion_rays(d.raw(), scene.raw(), &c, n, records, out_blocked));
+}
+// Whether nothing lies between p[i] and q[i] (n x 3 floats each), in f32: dir = (q - p) / len, tmax = len - ray_epsilon.
+// A pair no further apart than 2 * ray_epsilon is refused (std::invalid_argument).
+inline std::vector<uint8_t> visible(const Device &d, const Scene &scene, uint64_t n, const float *p, const float *q, float ray_epsilon = 0.001f)
+{
+    std::vector<float> rec(n * LUPIN_OCCLUSION_RECORD_FLOATS, 0.0f);
+    for (uint64_t i = 0; i < n; i++)
+    {
+        const float dx = q[3 * i] - p[3 * i], dy = q[3 * i + 1] - p[3 * i + 1], dz = q[3 * i + 2] - p[3 * i + 2];
+        const float len = std::sqrt((dx * dx + dy * dy) + dz * dz);
+        if (!(len > 2.0f * ray_epsilon)) throw std::invalid_argument("lp::visible: a segment is not longer than 2 * ray_epsilon");
+        float *r = &rec[i * LUPIN_OCCLUSION_RECORD_FLOATS];
+        r[0] = p[3 * i]; r[1] = p[3 * i + 1]; r[2] = p[3 * i + 2];
+        r[4] = dx / len; r[5] = dy / len; r[6] = dz / len;
+        r[7] = len - ray_epsilon;
+    }
+    std::vector<uint32_t> blocked(n, 0u);
+    OcclusionDesc desc;
+    desc.ray_epsilon = ray_epsilon;
+    occlusion_rays(d, scene, desc, n, rec.data(), blocked.data());
+    std::vector<uint8_t> out(n);
+    for (uint64_t i = 0; i < n; i++) out[i] = blocked[i] == 0u;
+    return out;
+}
+// 1 - blocked / samples over `samples` cosine-weighted directions of length `radius` about normals[i], from origins[i] (n x 3
+// floats each; the caller has moved the origins off the surface); rng_words: n RNG states, one per point
+inline std::vector<float> ambient_occlusion(const Device &d, const Scene &scene, uint64_t n, const float *origins, const float *normals,
+                                            const uint32_t *rng_words, float radius, uint32_t samples = 64, float ray_epsilon = 0.001f)
+{
+    std::vector<float> rec(n * LUPIN_OCCLUSION_RECORD_FLOATS, 0.0f);
+    for (uint64_t i = 0; i < n; i++)
+    {
+        float *r = &rec[i * LUPIN_OCCLUSION_RECORD_FLOATS];
+        r[0] = origins[3 * i]; r[1] = origins[3 * i + 1]; r[2] = origins[3 * i + 2];
+        std::memcpy(&r[3], &rng_words[i], 4);
+        r[4] = normals[3 * i]; r[5] = normals[3 * i + 1]; r[6] = normals[3 * i + 2];
+        r[7] = radius;
+    }
+    std::vector<uint32_t> blocked(n, 0u);
+    occlusion_rays(d, scene, OcclusionDesc{OcclusionMode::CosineHemisphere, samples, 0u, ray_epsilon}, n, rec.data(), blocked.data());
+    std::vector<float> out(n);
+    for (uint64_t i = 0; i < n; i++) out[i] = 1.0f - (float)blocked[i] / (float)samples;
+    return out;
+}
+
 }  // namespace lp
 
 namespace lpl {

@@ -981,6 +981,54 @@ int lupin_hip_bake_probes(LupinContext *ctx, const LupinScene *scene, const Lupi
                           uint64_t n, const float *probes /* n x 4 */, float *out_sh /* n x 9 x 4 */,
                           float *out_rays /* NULL, or n*S x 8 */);
 
+/* ---- occlusion queries (no reference counterpart) ----
+ * "Is anything in the way?": line of sight, ambient occlusion, probe validity, a caller's own shadow terms.  An any-hit
+ * traversal of the binary hierarchy that stops at the first triangle it accepts.
+ *
+ * Record, LUPIN_OCCLUSION_RECORD_FLOATS floats ("bits": the u32's bits stored in the float's place):
+ *   [0..2] origin   [3] RNG state (bits; ignored in direction mode)   [4..6] unit direction (mode 0) or unit surface normal
+ *   (mode 1)   [7] tmax (a float; +inf or any value >= FLT_MAX: unbounded)
+ * A segment (origin o, direction d, ray_epsilon, tmax) is BLOCKED iff some triangle the traversal tests is hit at a ray
+ * parameter t with ray_epsilon <= t < tmax, t in world units along d as lupin_hip_trace_rays reports it.  The traversal
+ * enters every node whose box the ray reaches below tmax; with tmax unbounded the answer is lupin_hip_trace_rays' `hit`,
+ * ray for ray, and a segment blocked at tmax is blocked at every larger tmax.
+ * Material opacity is NOT consulted: this is geometric visibility.  Emissive, transparent and alpha-textured surfaces block
+ * like any other; the stochastic alpha skip belongs to the integrators.
+ *
+ * Record i expands into desc->samples slots, slot = i * samples + s:
+ *   LUPIN_OCCLUSION_DIRECTION          the direction as given; samples must be 1
+ *   LUPIN_OCCLUSION_COSINE_HEMISPHERE  the slot's RNG state and direction exactly as LUPIN_RAY_COSINE_HEMISPHERE derives them
+ *                                      in a radiance query: the record's word for s == 0, hash_u32(word + s * 0x9E3779B9)
+ *                                      otherwise, two numbers drawn, the matte BSDF's cosine-weighted direction about the
+ *                                      normal -- bit for bit the out_rays of lupin_hip_pathtrace_rays on the same record
+ * out_blocked[i]: the number of record i's slots that are blocked, 0 .. samples.
+ *
+ * The call runs the calls recorded on the context first (and returns their error, if any), then its own launches, and
+ * returns when out_blocked is complete; frames rendered before and after are what they would be without the call.  Large
+ * batches run as successive launches of at most 2^30 slots.  With LUPIN_OCCLUSION_DEVICE_POINTERS in desc->flags, records
+ * (16-byte aligned) and out_blocked (4-byte aligned) are device memory of the context's device and nothing is copied to or
+ * from the host; host arrays go through staging buffers the context keeps and reuses from call to call.  It works on a
+ * scene whose four-wide hierarchy is stale after lupin_hip_scene_update_instances: only the binary hierarchy is read.
+ *
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing traced and out_blocked untouched, for: a NULL argument; an unknown mode or flag;
+ * samples == 0 or above 2^27; direction mode with samples != 1; n * samples above 2^38; a scene of another or of a destroyed
+ * context; a record with a non-finite origin, direction or normal; a direction or normal whose squared length is further
+ * than 1e-4 from 1; a tmax that is NaN or <= 0; a ray_epsilon that is not finite or is negative; misaligned device pointers;
+ * a hierarchy too deep for the traversal stack (as a render).  Host records are checked on the host, device records by a
+ * kernel whose count the host reads before the first launch.  n == 0: LUPIN_OK, nothing touched.
+ * Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_OCCLUSION_RECORD_FLOATS 8
+enum { LUPIN_OCCLUSION_DIRECTION = 0, LUPIN_OCCLUSION_COSINE_HEMISPHERE = 1 };   /* desc.mode  */
+enum { LUPIN_OCCLUSION_DEVICE_POINTERS = 1u };                                   /* desc.flags */
+typedef struct LupinOcclusionDesc {
+    uint32_t mode;
+    uint32_t samples;               /* S >= 1 slots per record; 1 in direction mode */
+    uint32_t flags;
+    float ray_epsilon;              /* finite, >= 0; hits below it are ignored, as in pathtrace_scene */
+} LupinOcclusionDesc;
+int lupin_hip_occlusion_rays(LupinContext *ctx, const LupinScene *scene, const LupinOcclusionDesc *desc,
+                             uint64_t n, const float *records /* n x 8 */, uint32_t *out_blocked /* n */);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

@@ -103,6 +103,14 @@ pub const LUPIN_PROBES_DEVICE_POINTERS: u32 = 1;
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinProbeDesc {
     pub pathtrace_type: u32, pub max_bounces: u32, pub samples: u32, pub flags: u32, pub max_slots: u32, pub advanced: LupinAdvancedParams,
 }
+// occlusion queries (no reference counterpart)
+pub const LUPIN_OCCLUSION_RECORD_FLOATS: usize = 8;
+pub const LUPIN_OCCLUSION_DIRECTION: u32 = 0;
+pub const LUPIN_OCCLUSION_COSINE_HEMISPHERE: u32 = 1;
+pub const LUPIN_OCCLUSION_DEVICE_POINTERS: u32 = 1;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinOcclusionDesc {
+    pub mode: u32, pub samples: u32, pub flags: u32, pub ray_epsilon: f32,
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -194,6 +202,9 @@ extern "C" {
     // light-probe baking: probes n x 4 f32 (position | RNG word), out_sh n x 9 x 4 (r, g, b, w per L2 SH coefficient), out_rays null or n * samples x 8
     pub fn lupin_hip_bake_probes(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinProbeDesc, n: u64,
                                  probes: *const f32, out_sh: *mut f32, out_rays: *mut f32) -> c_int;
+    // occlusion queries: records n x 8 f32 (origin | RNG bits, unit direction or normal | tmax), out_blocked n counts
+    pub fn lupin_hip_occlusion_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinOcclusionDesc, n: u64,
+                                    records: *const f32, out_blocked: *mut u32) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

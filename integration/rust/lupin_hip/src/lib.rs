@@ -277,3 +277,16 @@ pub fn adaptive_reproject(device: &Device, adaptive: &mut AdaptiveResources, res
     };
     check(unsafe { lupin_hip_adaptive_reproject(device.raw, adaptive.raw, resources.raw, scene.raw, &c, history_in.raw, history_out.raw) });
 }
+
+// ---- occlusion queries (no reference counterpart) ----
+#[derive(Copy, Clone, PartialEq, Eq)] pub enum OcclusionMode { Direction = 0, CosineHemisphere = 1 }
+/// Per record (8 floats: origin | RNG bits, unit direction or normal | tmax), the number of its `samples` slots whose segment is
+/// blocked by some triangle at `ray_epsilon <= t < tmax`.  Geometric visibility: material opacity is not consulted.
+pub fn occlusion_rays(device: &Device, scene: &Scene, records: &[f32], mode: OcclusionMode, samples: u32, ray_epsilon: f32) -> Vec<u32> {
+    assert!(records.len() % LUPIN_OCCLUSION_RECORD_FLOATS == 0);
+    let n = records.len() / LUPIN_OCCLUSION_RECORD_FLOATS;
+    let mut out = vec![0u32; n];
+    let c = LupinOcclusionDesc { mode: mode as u32, samples, flags: 0, ray_epsilon };
+    check(unsafe { lupin_hip_occlusion_rays(device.raw, scene.raw, &c, n as u64, records.as_ptr(), out.as_mut_ptr()) });
+    out
+}

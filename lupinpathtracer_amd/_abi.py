@@ -175,6 +175,10 @@ class ProbeDescC(C.Structure):   # LupinProbeDesc
                 ("max_slots", C.c_uint32), ("advanced", AdvancedParamsC)]
 
 
+class OcclusionDescC(C.Structure):   # LupinOcclusionDesc
+    _fields_ = [("mode", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32), ("ray_epsilon", C.c_float)]
+
+
 class TlasBuildStatsC(C.Structure):   # LupinTlasBuildStats
     _fields_ = [("num_instances", C.c_uint32), ("state_in_lds", C.c_uint32), ("scans", C.c_uint64), ("kernel_ms", C.c_float)]
 
@@ -248,6 +252,7 @@ SYMBOLS = [
     ("lupin_hip_bake_lightmap", C.c_int, [_P, _P, C.POINTER(LightmapDescC), C.POINTER(LightmapChartC), _U32, _P, _P, C.POINTER(C.c_uint64)]),
     ("lupin_hip_lightmap_stats", None, [C.POINTER(LightmapStatsC)]),
     ("lupin_hip_bake_probes", C.c_int, [_P, _P, C.POINTER(ProbeDescC), C.c_uint64, _P, _P, _P]),
+    ("lupin_hip_occlusion_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),

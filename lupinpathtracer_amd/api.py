@@ -1568,3 +1568,93 @@ def bake_probes(ctx, scene, positions, samples=1024, pathtrace_type=PathtraceTyp
     rays = np.zeros((len(pos) * int(samples), RAY_RECORD_FLOATS), np.float32) if want_rays else None
     check(lib().lupin_hip_bake_probes(ctx.handle, scene.handle, C.byref(c), len(pos), ptr(probes), ptr(out), ptr(rays)))
     return (out, rays) if want_rays else out
+
+
+# ---- occlusion queries: lupin_hip_occlusion_rays (include/lupin_hip.h) ----
+OCCLUSION_RECORD_FLOATS = 8
+OCCLUSION_DEVICE_POINTERS = 1
+
+
+class OcclusionMode(enum.IntEnum):
+    DIRECTION = 0            # floats 4..6 are the segment's unit direction; one slot per record
+    COSINE_HEMISPHERE = 1    # floats 4..6 are a unit surface normal; `samples` cosine-weighted directions about it
+
+
+def occlusion_records(ori, dir_or_normal, tmax=np.inf, rng=0):
+    """(n, OCCLUSION_RECORD_FLOATS) float32 records for occlusion_rays: `ori` (n, 3); `dir_or_normal` (n, 3), the unit
+    direction (mode DIRECTION) or the unit surface normal (mode COSINE_HEMISPHERE); `tmax` floats (inf: unbounded) and `rng`
+    u32 states (stored as bits; ignored in direction mode), scalars or (n,) arrays."""
+    ori = np.asarray(ori, np.float32).reshape(-1, 3)
+    rec = np.zeros((len(ori), OCCLUSION_RECORD_FLOATS), np.float32)
+    rec[:, 0:3] = ori
+    rec[:, 4:7] = np.asarray(dir_or_normal, np.float32).reshape(-1, 3)
+    rec.view(np.uint32)[:, 3] = np.asarray(rng, np.uint32)
+    rec[:, 7] = np.asarray(tmax, np.float32)
+    return rec
+
+
+def occlusion_rays(ctx, scene, records, mode=OcclusionMode.DIRECTION, samples=1, ray_epsilon=0.001):
+    """Per record, the number of its `samples` slots whose segment is blocked (some triangle at ray_epsilon <= t < tmax):
+    (n,) uint32.  Geometric visibility: opacity is not consulted.  `records` is an (n, OCCLUSION_RECORD_FLOATS) float32 numpy
+    array (see occlusion_records), or a contiguous float32 torch tensor on the context's device: then torch's current stream
+    is synchronised, the device memory is used in place and an int32 tensor is returned.  Blocks until complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "occlusion_rays needs a GPU context and an uploaded scene; there is no CPU fallback")
+    c = _abi.OcclusionDescC(int(mode), int(samples), 0, float(ray_epsilon))
+    if hasattr(records, "data_ptr"):   # a torch tensor
+        import torch
+        t = records
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == OCCLUSION_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+        if t.device.index != ctx.device_ordinal:
+            raise ValueError("records are on another device than the context")
+        out = torch.zeros((int(t.shape[0]),), dtype=torch.int32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()   # the records (and the zero fill) are written
+        c.flags = OCCLUSION_DEVICE_POINTERS
+        check(lib().lupin_hip_occlusion_rays(ctx.handle, scene.handle, C.byref(c), int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, OCCLUSION_RECORD_FLOATS)
+    out = np.zeros(len(rec), np.uint32)
+    check(lib().lupin_hip_occlusion_rays(ctx.handle, scene.handle, C.byref(c), len(rec), ptr(rec), ptr(out)))
+    return out
+
+
+def occluded(ctx, scene, ori, dir_, tmax=np.inf, ray_epsilon=0.001):
+    """(n,) bool: whether the segment from `ori` (n, 3) along the unit direction `dir_` (n, 3) is blocked before `tmax`."""
+    return occlusion_rays(ctx, scene, occlusion_records(ori, dir_, tmax), OcclusionMode.DIRECTION, 1, ray_epsilon) != 0
+
+
+def segment_records(p, q, ray_epsilon):
+    """Direction-mode records of the segments p -> q ((n, 3) each), in float32: d = q - p, len = sqrt(dot(d, d)),
+    dir = d / len, tmax = len - ray_epsilon (the far end point's own surface does not block).  ValueError for a pair with
+    len <= 2 * ray_epsilon: nothing of such a segment lies between the two epsilons."""
+    p, q = np.asarray(p, np.float32).reshape(-1, 3), np.asarray(q, np.float32).reshape(-1, 3)
+    eps = np.float32(ray_epsilon)
+    d = q - p
+    length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], dtype=np.float32)
+    if not np.all(length > np.float32(2.0) * eps):
+        raise ValueError("segment_records: a segment is not longer than 2 * ray_epsilon")
+    return occlusion_records(p, d / length[:, None], length - eps)
+
+
+def visible(ctx, scene, p, q, ray_epsilon=0.001):
+    """(n,) bool: whether nothing lies between the points p and q ((n, 3) each); see segment_records."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "visible needs a GPU context and an uploaded scene; there is no CPU fallback")
+    return occlusion_rays(ctx, scene, segment_records(p, q, ray_epsilon), OcclusionMode.DIRECTION, 1, ray_epsilon) == 0
+
+
+def ambient_occlusion(ctx, scene, points, normals, radius, samples=64, ray_epsilon=0.001, counter=0, surface_offset=None):
+    """Ambient occlusion (n,) float32 at `points` (n, 3) with unit `normals` (n, 3): 1 - blocked / samples over `samples`
+    cosine-weighted directions per point, each tested up to `radius` (a scalar or (n,) array).  Point i is seeded with
+    rng_seed_for(i, counter), as bake_irradiance seeds it.  The origins are the points moved along their normals by
+    `surface_offset` world units (default: LIGHTMAP_OFFSET_FRACTION of the scene's extent, bake_lightmap's default)."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "ambient_occlusion needs a GPU context and an uploaded scene; there is no CPU fallback")
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    normals = np.asarray(normals, np.float32).reshape(-1, 3)
+    if surface_offset is None:
+        surface_offset = LIGHTMAP_OFFSET_FRACTION * scene_world_extent(scene)
+    rec = occlusion_records(points + normals * np.float32(surface_offset), normals, radius, rng_seed_for(np.arange(len(points), dtype=np.uint32), counter))
+    blocked = occlusion_rays(ctx, scene, rec, OcclusionMode.COSINE_HEMISPHERE, samples, ray_epsilon)
+    return np.float32(1.0) - blocked.astype(np.float32) / np.float32(samples)

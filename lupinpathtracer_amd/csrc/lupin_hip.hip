@@ -3,7 +3,7 @@
 // traversal / material / light device functions in lupin_device.hpp, the CPU builders in builders.cpp, the device BLAS
 // builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp, adaptive sampling's in lupin_adaptive.hpp, its
 // reprojection's in lupin_reproject.hpp, the radiance queries' in lupin_rays.hpp, light-probe baking's in lupin_probes.hpp,
-// lightmap baking's in lupin_lightmap.hpp.
+// lightmap baking's in lupin_lightmap.hpp, the occlusion queries' in lupin_occlusion.hpp.
 //
 // THERE IS NO CPU FALLBACK: without a HIP device every entry point that needs one fails with LUPIN_ERR_NO_DEVICE.
 
@@ -30,6 +30,7 @@
 #include "lupin_rays.hpp"
 #include "lupin_probes.hpp"
 #include "lupin_lightmap.hpp"
+#include "lupin_occlusion.hpp"
 #include "lupin_internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -124,6 +125,10 @@ struct LupinContext
     int last_lanes = 0;                    // frames in flight the latest pathtrace call could use (reported by lupin_hip_stats_get)
     bool last_wide = false;                // ... and whether it ran the four-wide tracer
     uint32_t last_batch = 0, last_short = 0;   // frames the latest wavefront carried; its first-pass stack entries (0 = one pass)
+    // lupin_hip_occlusion_rays: the bad-record counter of its device check, and the staging of host arrays (one chunk's records
+    // and counts), kept from call to call and grown when a call needs more; freed with the context
+    DeviceBuffer occ_bad, occ_records, occ_counts;
+    size_t occ_records_bytes = 0, occ_counts_bytes = 0;
 };
 
 struct LupinPathtraceResources
@@ -2729,6 +2734,107 @@ int lupin_hip_bake_probes(LupinContext *ctx, const LupinScene *scene, const Lupi
             HIP_TRY(hipMemcpyAsync(dst, d_out.get(), (size_t)count * LUPIN_PROBE_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
             if (out_rays) HIP_TRY(hipMemcpyAsync(dst_rays, d_rays.get(), (size_t)slots * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
         }
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+// ---- occlusion queries (no reference counterpart; kernels: lupin_occlusion.hpp) ----
+
+static constexpr uint64_t LP_OCCLUSION_MAX_LAUNCH_SLOTS = 1ull << 30;    // slots of one launch: slot indices and the grid's threads fit 32 bits
+static constexpr uint64_t LP_OCCLUSION_MAX_STAGED_RECORDS = 1ull << 22;  // host arrays: records of one launch (128 MB of staging)
+
+// *buf holds at least `bytes`: kept when it is large enough, replaced otherwise (the stream has finished with the old one:
+// every call ends synchronised)
+static hipError_t occlusion_staging(DeviceBuffer *buf, size_t *have, size_t bytes)
+{
+    if (*have >= bytes) return hipSuccess;
+    DeviceBuffer b;
+    const hipError_t e = DeviceBuffer::make(bytes, &b);
+    if (e == hipSuccess) { *buf = std::move(b); *have = bytes; }
+    return e;
+}
+
+int lupin_hip_occlusion_rays(LupinContext *ctx, const LupinScene *scene, const LupinOcclusionDesc *desc, uint64_t n, const float *records,
+                             uint32_t *out_blocked)
+{
+    const char *who = "lupin_hip_occlusion_rays";
+    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !scene || !desc || !records || !out_blocked) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (desc->mode > LUPIN_OCCLUSION_COSINE_HEMISPHERE) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown mode");
+    if (desc->flags & ~(uint32_t)LUPIN_OCCLUSION_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
+    if (desc->mode == LUPIN_OCCLUSION_DIRECTION && desc->samples != 1) return fail(LUPIN_ERR_INVALID_ARGUMENT, "direction mode takes samples == 1");
+    const uint64_t S = desc->samples;
+    if (n > LP_RAYS_MAX_PATHS / S) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n * samples must not exceed 2^38");
+    if (!(std::isfinite(desc->ray_epsilon) && desc->ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
+    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    // (a stale four-wide hierarchy is no obstacle: only the binary one is read)
+    const bool on_device = (desc->flags & LUPIN_OCCLUSION_DEVICE_POINTERS) != 0;
+    if (on_device && (((uintptr_t)records & 15u) || ((uintptr_t)out_blocked & 3u)))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device records must be 16-byte aligned, device counts 4-byte aligned");
+    if (n == 0) return LUPIN_OK;
+    // the calls recorded so far run first, whatever becomes of this one from here on
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = flush_pending(ctx)) return rc;
+    if (!on_device)
+        for (uint64_t i = 0; i < n; i++)
+        {
+            const float *r = records + i * LUPIN_OCCLUSION_RECORD_FLOATS;
+            if (!occlusion_record_ok(r[0], r[1], r[2], r[4], r[5], r[6], r[7]))
+                return fail(LUPIN_ERR_INVALID_ARGUMENT, "record " + std::to_string(i) + ": non-finite component, direction or normal not of unit length, or tmax NaN or not positive");
+        }
+    TraversalLds t;
+    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
+    join_primary(ctx);   // the primary stream waits for the latest of the recorded calls
+    hipStream_t st = ctx->stream;
+
+    if (on_device)
+    {
+        size_t have = ctx->occ_bad.get() ? sizeof(unsigned long long) : 0;
+        HIP_TRY(occlusion_staging(&ctx->occ_bad, &have, sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(ctx->occ_bad.get(), 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_occlusion_validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, records, (unsigned long long)n,
+                           ctx->occ_bad.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        unsigned long long count = 0;
+        HIP_TRY(hipMemcpyAsync(&count, ctx->occ_bad.get(), sizeof(count), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (count)
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " record(s): non-finite component, direction or normal not of unit length, or tmax NaN or not positive");
+    }
+
+    uint64_t chunk_records = std::min(n, std::max<uint64_t>(1, LP_OCCLUSION_MAX_LAUNCH_SLOTS / S));
+    if (!on_device)
+    {
+        chunk_records = std::min(chunk_records, LP_OCCLUSION_MAX_STAGED_RECORDS);
+        HIP_TRY(occlusion_staging(&ctx->occ_records, &ctx->occ_records_bytes, (size_t)chunk_records * LUPIN_OCCLUSION_RECORD_FLOATS * 4));
+        HIP_TRY(occlusion_staging(&ctx->occ_counts, &ctx->occ_counts_bytes, (size_t)chunk_records * 4));
+    }
+    for (uint64_t first = 0; first < n; first += chunk_records)
+    {
+        const uint64_t recs = std::min(chunk_records, n - first);
+        const uint32_t slots = (uint32_t)(recs * S);
+        const float *src = records + first * LUPIN_OCCLUSION_RECORD_FLOATS;
+        uint32_t *dst = out_blocked + first;
+        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
+        uint32_t *d_cnt = dst;
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(ctx->occ_records.get(), src, (size_t)recs * LUPIN_OCCLUSION_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
+            d_rec = ctx->occ_records.as<float4>();
+            d_cnt = ctx->occ_counts.as<uint32_t>();
+        }
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)recs * 4, st));
+        with_bool(t.geo, [&](auto G) {
+            hipLaunchKernelGGL(k_occlusion<decltype(G)::value>, dim3((slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, st, scene->dev, slots, d_rec,
+                               desc->samples, desc->mode, desc->ray_epsilon, d_cnt, t.stack_words);
+        });
+        HIP_TRY(hipGetLastError());
+        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_cnt, (size_t)recs * 4, hipMemcpyDeviceToHost, st));
     }
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
