@@ -802,6 +802,31 @@ typedef enum LupinSurfaceMode
 } LupinSurfaceMode;
 int lupin_hip_surface_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n, const float *records, float *out);
 
+/* Camera probe: compute_camera_ray (pathtracer.wgsl:505-542) with random_in_disk (:1623-1629) and transform_ray
+ * (:2662-2669) of the device over n host records, for an image of width x height pixels.  The camera enters the frame
+ * parameters through the code lupin_hip_pathtrace_scene fills them with; camera_transform's first three rows are the
+ * LupinMat3x4 a render takes, and its last row, (0, 0, 0, 1) in every render, is passed on as given: the ray does not
+ * depend on it (transform_point divides by no w).  Host arrays in and out; synchronous; calls recorded on the context run
+ * first.  The tests hold the result to tests/camera_ref.py in float64.
+ *
+ * Input record, LUPIN_CAMERA_IN_WORDS uint32:  [0] pixel x  [1] pixel y  [2] RNG state  [3] mode (LupinCameraMode)
+ * Output record, LUPIN_CAMERA_OUT_FLOATS floats:
+ *   [0..2] origin  [3..5] direction  [6] RNG state afterwards (the u32's bits stored in the float's place)  [7] 0.
+ * Modes:
+ *   RAY         the ray a sample of that pixel starts with: four numbers are drawn from the record's RNG state, two for the
+ *               pixel offset, then two for the lens (also at aperture 0)
+ *   RAY_CENTRE  the pinhole ray through the pixel centre the reprojection traces: nothing is drawn, aperture 0
+ * Any other mode writes zeros and returns the RNG state unchanged.  Pixels need not lie inside the image. */
+#define LUPIN_CAMERA_IN_WORDS 4
+#define LUPIN_CAMERA_OUT_FLOATS 8
+typedef enum LupinCameraMode
+{
+    LUPIN_CAMERA_RAY = 0,
+    LUPIN_CAMERA_RAY_CENTRE = 1
+} LupinCameraMode;
+int lupin_hip_camera_probe(LupinContext *ctx, uint32_t width, uint32_t height, const LupinCameraParams *camera_params,
+                           const LupinMat4 *camera_transform, uint32_t n, const uint32_t *records, float *out);
+
 /* ---- radiance queries (no reference counterpart) ----
  * The full integrators over caller-supplied rays: the radiance arriving along each ray, or at a surface point over its
  * cosine-weighted hemisphere, instead of a camera pixel's texel.

@@ -248,6 +248,7 @@ SYMBOLS = [
     ("lupin_hip_scatter_probe", C.c_int, [_P, _U32, _P, _P]),
     ("lupin_hip_light_probe", C.c_int, [_P, _P, _U32, _P, _P]),
     ("lupin_hip_surface_probe", C.c_int, [_P, _P, _U32, _P, _P]),
+    ("lupin_hip_camera_probe", C.c_int, [_P, _U32, _U32, C.POINTER(CameraParamsC), C.POINTER(Mat4), _U32, _P, _P]),
     ("lupin_hip_pathtrace_rays", C.c_int, [_P, _P, C.POINTER(RayQueryDescC), C.c_uint64, _P, _P, _P]),
     ("lupin_hip_bake_lightmap", C.c_int, [_P, _P, C.POINTER(LightmapDescC), C.POINTER(LightmapChartC), _U32, _P, _P, C.POINTER(C.c_uint64)]),
     ("lupin_hip_lightmap_stats", None, [C.POINTER(LightmapStatsC)]),

@@ -1314,6 +1314,49 @@ def surface_probe(ctx, scene, records):
     return out
 
 
+# lupin_hip_camera_probe record layout (include/lupin_hip.h)
+CAMERA_IN_WORDS = 4
+CAMERA_OUT_FLOATS = 8
+
+
+class CameraMode(enum.IntEnum):
+    RAY = 0
+    RAY_CENTRE = 1
+
+
+def camera_transform_mat4(transform):
+    """The 4 columns x 4 rows matrix lupin_hip_camera_probe and oracle.camera_probe take, as a (4, 4) float32 array [column][row]:
+    from a (4, 3) LupinMat3x4 (the last row becomes the renderer's (0, 0, 0, 1)) or from 16 numbers taken as they are."""
+    m = np.asarray(transform, np.float32)
+    if m.size == 12:
+        m = np.concatenate([m.reshape(4, 3), np.array([[0.0], [0.0], [0.0], [1.0]], np.float32)], axis=1)
+    return np.ascontiguousarray(m.reshape(4, 4), np.float32)
+
+
+def camera_records(gx, gy, rng_state, mode=CameraMode.RAY):
+    """(n, CAMERA_IN_WORDS) uint32 records for camera_probe / oracle.camera_probe: pixel, RNG state, CameraMode."""
+    gx = np.asarray(gx, np.uint32).reshape(-1)
+    rec = np.zeros((len(gx), CAMERA_IN_WORDS), np.uint32)
+    rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = gx, np.asarray(gy, np.uint32), np.asarray(rng_state, np.uint32), np.asarray(mode, np.uint32)
+    return rec
+
+
+def camera_probe(ctx, width, height, camera_params, camera_transform, records):
+    """camera_ray / camera_ray_centre of the device for a width x height image over (n, CAMERA_IN_WORDS) uint32 records;
+    `camera_transform` as camera_transform_mat4 takes it.  Returns (ori (n, 3) float32, dir (n, 3) float32, RNG state
+    afterwards (n,) uint32)."""
+    if ctx is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "camera_probe needs a GPU context; there is no CPU fallback")
+    rec = np.ascontiguousarray(records, np.uint32).reshape(-1, CAMERA_IN_WORDS)
+    out = np.zeros((len(rec), CAMERA_OUT_FLOATS), np.float32)
+    cp = camera_params
+    c = _abi.CameraParamsC(1 if cp.is_orthographic else 0, cp.lens, cp.film, cp.aspect, cp.focus, cp.aperture)
+    m4 = _abi.Mat4()
+    C.memmove(C.byref(m4), camera_transform_mat4(camera_transform).ctypes.data, 64)
+    check(lib().lupin_hip_camera_probe(ctx.handle, int(width), int(height), C.byref(c), C.byref(m4), len(rec), ptr(rec), ptr(out)))
+    return out[:, 0:3].copy(), out[:, 3:6].copy(), out[:, 6].copy().view(np.uint32)
+
+
 # ---- radiance queries: lupin_hip_pathtrace_rays (include/lupin_hip.h, DESIGN.md 13) ----
 RAY_RECORD_FLOATS = 8
 RAY_RESULT_FLOATS = 4

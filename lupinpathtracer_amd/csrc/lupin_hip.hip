@@ -1836,6 +1836,20 @@ int lupin_hip_dbuf_resize(LupinDoubleBufferedTexture *t, uint32_t width, uint32_
 static const char *const kWideStale = "lupin_hip_scene_update_instances moved this scene's instances and its four-wide hierarchy was not rebuilt: "
                                       "use the binary traversal or create the scene anew";
 
+// The camera's share of get_push_constants (renderer.rs:1426-1493): what camera_ray_of reads.  Every entry point that
+// generates camera rays (pathtrace_impl, the reprojection's primary trace, lupin_hip_camera_probe) fills it here.
+static void set_camera_constants(LupinPushConstants &pc, const LupinCameraParams &cp, const LupinMat3x4 &ct)
+{
+    if (cp.is_orthographic) pc.flags |= LUPIN_FLAG_CAMERA_ORTHO;
+    // Mat3x4::to_mat4 (base.rs:695-705)
+    for (int c = 0; c < 4; c++) { pc.camera_transform.m[c][0] = ct.m[c][0]; pc.camera_transform.m[c][1] = ct.m[c][1]; pc.camera_transform.m[c][2] = ct.m[c][2]; pc.camera_transform.m[c][3] = (c == 3) ? 1.0f : 0.0f; }
+    pc.camera_lens = cp.lens;
+    pc.camera_film = cp.film;
+    pc.camera_aspect = cp.aspect;
+    pc.camera_focus = cp.focus;
+    pc.camera_aperture = cp.aperture;
+}
+
 static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res, const LupinScene *scene,
                           LupinTexture *render_target, uint32_t pathtrace_type, const LupinPathtraceDesc *desc,
                           bool tile_set, uint32_t set_tile_size, uint32_t rank, uint32_t world, int falsecolor_type = -1,
@@ -1858,14 +1872,7 @@ static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res,
     memset(&fp, 0, sizeof(fp));
     // get_push_constants (renderer.rs:1426-1493)
     LupinPushConstants &pc = fp.pc;
-    if (desc->camera_params.is_orthographic) pc.flags |= LUPIN_FLAG_CAMERA_ORTHO;
-    const LupinMat3x4 &ct = desc->camera_transform;   // Mat3x4::to_mat4 (base.rs:695-705)
-    for (int c = 0; c < 4; c++) { pc.camera_transform.m[c][0] = ct.m[c][0]; pc.camera_transform.m[c][1] = ct.m[c][1]; pc.camera_transform.m[c][2] = ct.m[c][2]; pc.camera_transform.m[c][3] = (c == 3) ? 1.0f : 0.0f; }
-    pc.camera_lens = desc->camera_params.lens;
-    pc.camera_film = desc->camera_params.film;
-    pc.camera_aspect = desc->camera_params.aspect;
-    pc.camera_focus = desc->camera_params.focus;
-    pc.camera_aperture = desc->camera_params.aperture;
+    set_camera_constants(pc, desc->camera_params, desc->camera_transform);
     if (scene->envs_empty) pc.flags |= LUPIN_FLAG_ENVS_EMPTY;
     if (scene->lights_empty) pc.flags |= LUPIN_FLAG_LIGHTS_EMPTY;
     if (scene->instances_empty) pc.flags |= LUPIN_FLAG_INSTANCES_EMPTY;
@@ -2489,6 +2496,29 @@ int lupin_hip_surface_probe(LupinContext *ctx, const LupinScene *scene, uint32_t
             hipLaunchKernelGGL(k_surface_probe<decltype(G)::value>, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev, n,
                                in[0].as<float>(), dout);
         });
+    });
+}
+
+int lupin_hip_camera_probe(LupinContext *ctx, uint32_t width, uint32_t height, const LupinCameraParams *camera_params,
+                           const LupinMat4 *camera_transform, uint32_t n, const uint32_t *records, float *out)
+{
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !camera_params || !camera_transform || !records || !out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (width == 0 || height == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "lupin_hip_camera_probe: empty image");
+    if (n == 0) return LUPIN_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    FrameParams fp;
+    memset(&fp, 0, sizeof(fp));
+    LupinMat3x4 ct;
+    for (int c = 0; c < 4; c++) for (int r = 0; r < 3; r++) ct.m[c][r] = camera_transform->m[c][r];
+    set_camera_constants(fp.pc, *camera_params, ct);
+    // the renderer's last row is (0, 0, 0, 1); the probe passes the caller's on, and the ray must not depend on it
+    for (int c = 0; c < 4; c++) fp.pc.camera_transform.m[c][3] = camera_transform->m[c][3];
+    fp.width = width; fp.height = height; fp.reg_w = width; fp.reg_h = height;
+    join_primary(ctx);   // recorded calls run first
+    const size_t in_bytes = (size_t)n * LUPIN_CAMERA_IN_WORDS * 4, out_bytes = (size_t)n * LUPIN_CAMERA_OUT_FLOATS * 4;
+    return run_probe(ctx, "lupin_hip_camera_probe", {{records, in_bytes}}, out, out_bytes, [&](const DeviceBuffer *in, float *dout) {
+        hipLaunchKernelGGL(k_camera_probe, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, ctx->stream, fp, n, in[0].as<uint32_t>(), dout);
     });
 }
 
@@ -3474,13 +3504,8 @@ int lupin_hip_adaptive_reproject(LupinContext *ctx, LupinAdaptiveResources *ares
     FrameParams fp;
     memset(&fp, 0, sizeof(fp));
     LupinPushConstants &pc = fp.pc;
-    if (desc->camera_params.is_orthographic) pc.flags |= LUPIN_FLAG_CAMERA_ORTHO;
     const LupinMat3x4 &ct = desc->camera_transform;
-    for (int c = 0; c < 4; c++) { pc.camera_transform.m[c][0] = ct.m[c][0]; pc.camera_transform.m[c][1] = ct.m[c][1]; pc.camera_transform.m[c][2] = ct.m[c][2]; pc.camera_transform.m[c][3] = (c == 3) ? 1.0f : 0.0f; }
-    pc.camera_lens = desc->camera_params.lens;
-    pc.camera_film = desc->camera_params.film;
-    pc.camera_aspect = desc->camera_params.aspect;
-    pc.camera_focus = desc->camera_params.focus;
+    set_camera_constants(pc, desc->camera_params, ct);   // the aperture travels along unread: the centre ray is a pinhole's
     pc.ray_epsilon = desc->ray_epsilon;
     fp.width = W; fp.height = H; fp.reg_w = W; fp.reg_h = H;
     LupinMat3x4 cam_inv;

@@ -2367,6 +2367,24 @@ __global__ void __launch_bounds__(LP_BLOCK) k_surface_probe(SceneDev sc, uint32_
     for (int k = 0; k < LUPIN_SURFACE_OUT_FLOATS; k++) w[k] = o[k];
 }
 
+// camera_ray (mode 0) and camera_ray_centre (mode 1) over a batch of records (layout: lupin_hip_camera_probe in
+// include/lupin_hip.h): the force-inlined functions k_begin, the shade kernels' path regeneration and the reprojection's
+// primary trace call, on frame parameters the host filled as it does for a render.  Any other mode writes zeros and returns
+// the RNG state unchanged.
+__global__ void __launch_bounds__(LP_BLOCK) k_camera_probe(FrameParams fp, uint32_t n, const uint32_t *__restrict__ in, float *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * LP_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint4 r = reinterpret_cast<const uint4 *>(in)[i];   // gx, gy, RNG state, mode
+    uint32_t rng = r.z;
+    f3 o = splat(0.0f), d = splat(0.0f);
+    if (r.w == LUPIN_CAMERA_RAY) camera_ray(fp, r.x, r.y, rng, o, d);
+    else if (r.w == LUPIN_CAMERA_RAY_CENTRE) camera_ray_centre(fp, r.x, r.y, o, d);
+    float4 *w = reinterpret_cast<float4 *>(out) + (size_t)i * 2;
+    w[0] = make_float4(o.x, o.y, o.z, d.x);
+    w[1] = make_float4(d.y, d.z, __uint_as_float(rng), 0.0f);
+}
+
 // Tile pack / unpack for the multi-GPU gather.  Payload of a rank = its tiles in ascending order (include/lupin_tiles.h),
 // each tile row-major, 8 B per pixel.  One block per tile: the block first sums the pixel counts of the owner's earlier
 // tiles (a few hundred terms at most, strided over the threads), then copies the tile's rows.

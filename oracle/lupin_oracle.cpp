@@ -2422,6 +2422,37 @@ int oracle_camera_rays(const LupinPushConstants *constants, uint32_t width, uint
     return 0;
 }
 
+// The record layout and modes of lupin_hip_camera_probe (include/lupin_hip.h): compute_camera_ray from a given RNG state,
+// the pixel offset drawn first as the entry points do (:236-237); RAY_CENTRE is the same function with a zero offset and a
+// zero aperture, and draws nothing that survives (the state is returned as it came).
+int oracle_camera_probe(const LupinPushConstants *constants, uint32_t width, uint32_t height, uint32_t n, const uint32_t *records, float *out)
+{
+    if (!constants || !records || !out) return -1;
+    for (uint32_t i = 0; i < n; i++)
+    {
+        const uint32_t *r = records + (size_t)i * LUPIN_CAMERA_IN_WORDS;
+        float *o = out + (size_t)i * LUPIN_CAMERA_OUT_FLOATS;
+        for (int k = 0; k < LUPIN_CAMERA_OUT_FLOATS; k++) o[k] = 0.0f;
+        Inv inv;
+        inv.s = nullptr; inv.constants = *constants;
+        inv.MAX_BOUNCES = 0; inv.SAMPLES_PER_PIXEL = 1;
+        inv.RNG_STATE = r[2];
+        uint32_t after = r[2];
+        if (r[3] == LUPIN_CAMERA_RAY || r[3] == LUPIN_CAMERA_RAY_CENTRE)
+        {
+            vec2f pixel_offset = {0.0f, 0.0f};
+            if (r[3] == LUPIN_CAMERA_RAY) { vec2f ro = inv.random_vec2f(); pixel_offset = {ro.x - 0.5f, ro.y - 0.5f}; }
+            else inv.constants.camera_aperture = 0.0f;
+            Ray ray = inv.compute_camera_ray(r[0], r[1], width, height, pixel_offset);
+            if (r[3] == LUPIN_CAMERA_RAY) after = inv.RNG_STATE;
+            o[0] = ray.ori.x; o[1] = ray.ori.y; o[2] = ray.ori.z;
+            o[3] = ray.dir.x; o[4] = ray.dir.y; o[5] = ray.dir.z;
+        }
+        memcpy(&o[6], &after, 4);
+    }
+    return 0;
+}
+
 // RNG stream probe: first `count` random_f32() outputs for (pixel linear index, accum_counter)
 // (pathtracer.wgsl:1563-1600).
 void oracle_rng_stream(uint32_t global_id, uint32_t accum_counter, uint32_t count, float *out)

@@ -58,6 +58,8 @@ def lib():
         h.oracle_surface_probe.argtypes = [C.POINTER(_abi.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         h.oracle_camera_rays.restype = C.c_int
         h.oracle_camera_rays.argtypes = [C.POINTER(_abi.PushConstants), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        h.oracle_camera_probe.restype = C.c_int
+        h.oracle_camera_probe.argtypes = [C.POINTER(_abi.PushConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         h.oracle_float_to_half.restype = C.c_uint16
         h.oracle_float_to_half.argtypes = [C.c_float]
         h.oracle_float_to_half_rtz.restype = C.c_uint16
@@ -239,6 +241,22 @@ def camera_rays(scene, width, height, camera_params, camera_transform, accum_cou
     if lib().oracle_camera_rays(C.byref(pc), width, height, _abi.ptr(ori), _abi.ptr(dir_)) != 0:
         raise RuntimeError("oracle_camera_rays failed")
     return ori, dir_
+
+
+def camera_probe(width, height, camera_params, camera_transform, records):
+    """oracle_camera_probe over (n, 4) uint32 records (layout and modes of lupin_hip_camera_probe, include/lupin_hip.h), with
+    the arguments and the result of api.camera_probe: (ori (n, 3), dir (n, 3), RNG state afterwards (n,) uint32)."""
+    from lupinpathtracer_amd import api
+    pc = _abi.PushConstants()
+    C.memmove(C.byref(pc.camera_transform), api.camera_transform_mat4(camera_transform).ctypes.data, 64)
+    pc.camera_lens, pc.camera_film, pc.camera_aspect = camera_params.lens, camera_params.film, camera_params.aspect
+    pc.camera_focus, pc.camera_aperture = camera_params.focus, camera_params.aperture
+    pc.flags = _abi.FLAG_CAMERA_ORTHO if camera_params.is_orthographic else 0
+    rec = np.ascontiguousarray(records, np.uint32).reshape(-1, 4)
+    out = np.zeros((len(rec), 8), np.float32)
+    if lib().oracle_camera_probe(C.byref(pc), int(width), int(height), len(rec), _abi.ptr(rec), _abi.ptr(out)) != 0:
+        raise RuntimeError("oracle_camera_probe failed")
+    return out[:, 0:3].copy(), out[:, 3:6].copy(), out[:, 6].copy().view(np.uint32)
 
 
 def effective_cpus():
