@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <array>
 #include <optional>
 #include <stdexcept>
@@ -712,6 +713,33 @@ inline std::vector<float> ambient_occlusion(const Device &d, const Scene &scene,
     occlusion_rays(d, scene, OcclusionDesc{OcclusionMode::CosineHemisphere, samples, 0u, ray_epsilon}, n, rec.data(), blocked.data());
     std::vector<float> out(n);
     for (uint64_t i = 0; i < n; i++) out[i] = 1.0f - (float)blocked[i] / (float)samples;
+    return out;
+}
+
+// distance queries (no reference counterpart): the nearest surface point of points in world space.
+// `side` is the side of the REPORTED triangle (sign of dot(p - point, (v1 - v0) x (v2 - v0))), not inside / outside.
+struct DistanceResult   // the twelve words of LUPIN_DISTANCE_RESULT_FLOATS
+{
+    uint32_t found;
+    float distance;
+    float point[3];
+    float u, v;
+    uint32_t instance, tri;
+    float side;
+    uint32_t pad[2];
+};
+static_assert(sizeof(DistanceResult) == 4 * LUPIN_DISTANCE_RESULT_FLOATS, "DistanceResult mirrors the result words");
+// records: n x 4 floats (point | rmax); flags: LUPIN_DISTANCE_DEVICE_POINTERS or 0
+inline void distance_points(const Device &d, const Scene &scene, uint64_t n, const float *records, DistanceResult *out_results, uint32_t flags = 0)
+{
+    check(lupin_hip_distance_points(d.raw(), scene.raw(), flags, n, records, reinterpret_cast<float *>(out_results)));
+}
+// dims[0] x dims[1] x dims[2] distances, x fastest, at origin + (i + 0.5) * spacing; rmax where nothing lies within rmax
+inline std::vector<float> bake_distance_grid(const Device &d, const Scene &scene, const std::array<float, 3> &origin, const std::array<float, 3> &spacing,
+                                             const std::array<uint32_t, 3> &dims, float rmax = std::numeric_limits<float>::infinity(), bool is_signed = false)
+{
+    std::vector<float> out((size_t)dims[0] * dims[1] * dims[2]);
+    check(lupin_hip_bake_distance_grid(d.raw(), scene.raw(), is_signed ? LUPIN_DISTANCE_GRID_SIGNED : 0u, origin.data(), spacing.data(), dims.data(), rmax, out.data()));
     return out;
 }
 

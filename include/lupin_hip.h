@@ -1054,6 +1054,61 @@ typedef struct LupinOcclusionDesc {
 int lupin_hip_occlusion_rays(LupinContext *ctx, const LupinScene *scene, const LupinOcclusionDesc *desc,
                              uint64_t n, const float *records /* n x 8 */, uint32_t *out_blocked /* n */);
 
+/* ---- distance queries (no reference counterpart) ----
+ * "How far is the nearest surface, where is it, and which side of it am I on?" for POINTS: clearances for bake offsets, probe
+ * validity, a distance volume for collision, sphere tracing or leak checks.  A nearest-point traversal of the binary
+ * hierarchy, pruned by the distance from the point to a node's box.
+ *
+ * Record, LUPIN_DISTANCE_RECORD_FLOATS floats:   [0..2] point p (finite)   [3] rmax, the search radius (> 0; +inf or any
+ * value >= FLT_MAX: unbounded, clamped to FLT_MAX)
+ * Over every triangle of every instance, taken in WORLD space (its vertices through the instance's local -> world
+ * transform, the f32 inverse lupin_mat3x4_inverse gives of the world -> local rows: non-uniform scale and shear are
+ * measured as they appear in the world), c* is the point of the surface nearest to p, and  found = |p - c*| < rmax.
+ * Contributing nothing: an instance whose rows have no finite inverse, and a triangle whose world-space cross product
+ * (v1 - v0) x (v2 - v0) has squared length 0 in f32 (zero area).  Material opacity is NOT consulted.  Triangles at equal
+ * distance: either may be reported.  A surface further than about 1.8e19 units away (its squared distance is not a finite
+ * float) is not found.
+ *
+ * Result, LUPIN_DISTANCE_RESULT_FLOATS floats, 48 bytes ("bits": the u32's bits stored in the float's place):
+ *   [0] found (bits: 1 or 0)   [1] distance |p - c*|   [2..4] point c*   [5] u   [6] v   [7] instance (bits)
+ *   [8] tri (bits): the triangle index lupin_hip_trace_rays reports (within the instance's mesh, in the scene's order)
+ *   [9] side: +1.0, -1.0 or 0.0   [10] 0   [11] 0
+ * c* = v0 + (v1 - v0) u + (v2 - v0) v with the triangle's world-space vertices.  Words 1 .. 9 are 0 when nothing was found.
+ * side is the sign of dot(p - c*, n) with n = (v1 - v0) x (v2 - v0) of THE REPORTED TRIANGLE in world space.  It is a
+ * statement about that one triangle.  It is NOT an inside / outside classification: where c* lies on an edge or a vertex
+ * that several triangles share, it is the side of whichever of them was reported, and two of them can disagree.
+ *
+ * lupin_hip_bake_distance_grid fills a regular grid of dims[0] x dims[1] x dims[2] voxels, x fastest:
+ * voxel = ix + dims[0] * (iy + dims[1] * iz), centre, per axis and in this order in f32,
+ *   c = origin + ((float)i + 0.5f) * spacing
+ * out_volume[voxel] = the distance from the centre, or rmax (clamped to FLT_MAX) where nothing lies within rmax.  With
+ * LUPIN_DISTANCE_GRID_SIGNED a found distance is multiplied by side, and where side is 0 the value is 0.  The same
+ * centres given to lupin_hip_distance_points give the same floats.
+ *
+ * Both calls run the calls recorded on the context first (and return their error, if any), then their own launches on the
+ * primary stream, and return when the output is complete.  Large batches run as successive launches of at most 2^30 records
+ * or voxels.  With LUPIN_DISTANCE_DEVICE_POINTERS records and out_results (16-byte aligned) or out_volume (4-byte aligned)
+ * are device memory of the context's device and nothing is copied to or from the host; host arrays go through staging
+ * buffers the context keeps and reuses from call to call.  origin, spacing and dims are host memory always.  Both work on
+ * a scene whose four-wide hierarchy is stale after lupin_hip_scene_update_instances: only the binary hierarchy is read,
+ * and the transforms are the scene's current ones.
+ *
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing computed and the output untouched, for: a NULL argument; an unknown flag (GRID_SIGNED
+ * is unknown to distance_points); a scene of another or of a destroyed context; a record with a non-finite point or an
+ * rmax that is NaN or <= 0; n above 2^38; a non-finite origin; a spacing that is not finite or not positive; a zero
+ * dimension; more than 2^36 voxels; a grid whose last centre is not finite; misaligned device pointers; a hierarchy too
+ * deep for the traversal stack (which holds two words per entry here).  Host records are checked on the host, device
+ * records by a kernel whose count the host reads before the first launch.  n == 0: LUPIN_OK, nothing touched.
+ * Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_DISTANCE_RECORD_FLOATS 4
+#define LUPIN_DISTANCE_RESULT_FLOATS 12
+enum { LUPIN_DISTANCE_DEVICE_POINTERS = 1u, LUPIN_DISTANCE_GRID_SIGNED = 2u };   /* flags */
+int lupin_hip_distance_points(LupinContext *ctx, const LupinScene *scene, uint32_t flags, uint64_t n,
+                              const float *records /* n x 4 */, float *out_results /* n x 12 */);
+int lupin_hip_bake_distance_grid(LupinContext *ctx, const LupinScene *scene, uint32_t flags, const float *origin /* 3 */,
+                                 const float *spacing /* 3 */, const uint32_t *dims /* 3 */, float rmax,
+                                 float *out_volume /* dims[0] * dims[1] * dims[2] */);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

@@ -111,6 +111,11 @@ pub const LUPIN_OCCLUSION_DEVICE_POINTERS: u32 = 1;
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinOcclusionDesc {
     pub mode: u32, pub samples: u32, pub flags: u32, pub ray_epsilon: f32,
 }
+// distance queries (no reference counterpart)
+pub const LUPIN_DISTANCE_RECORD_FLOATS: usize = 4;
+pub const LUPIN_DISTANCE_RESULT_FLOATS: usize = 12;
+pub const LUPIN_DISTANCE_DEVICE_POINTERS: u32 = 1;
+pub const LUPIN_DISTANCE_GRID_SIGNED: u32 = 2;
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -205,6 +210,10 @@ extern "C" {
     // occlusion queries: records n x 8 f32 (origin | RNG bits, unit direction or normal | tmax), out_blocked n counts
     pub fn lupin_hip_occlusion_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinOcclusionDesc, n: u64,
                                     records: *const f32, out_blocked: *mut u32) -> c_int;
+    // distance queries: records n x 4 f32 (point | rmax), out_results n x 12 f32 words; the grid: x fastest, one f32 per voxel
+    pub fn lupin_hip_distance_points(ctx: *mut LupinContext, scene: *const LupinScene, flags: u32, n: u64, records: *const f32, out_results: *mut f32) -> c_int;
+    pub fn lupin_hip_bake_distance_grid(ctx: *mut LupinContext, scene: *const LupinScene, flags: u32, origin: *const f32, spacing: *const f32,
+                                        dims: *const u32, rmax: f32, out_volume: *mut f32) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

@@ -290,3 +290,24 @@ pub fn occlusion_rays(device: &Device, scene: &Scene, records: &[f32], mode: Occ
     check(unsafe { lupin_hip_occlusion_rays(device.raw, scene.raw, &c, n as u64, records.as_ptr(), out.as_mut_ptr()) });
     out
 }
+
+// ---- distance queries (no reference counterpart) ----
+/// The twelve words of a result.  `side` is the side of the reported triangle, not an inside / outside classification.
+#[repr(C)] #[derive(Copy, Clone, Debug, Default)] pub struct DistanceResult {
+    pub found: u32, pub distance: f32, pub point: [f32; 3], pub u: f32, pub v: f32, pub instance: u32, pub tri: u32, pub side: f32, pub pad: [u32; 2],
+}
+/// Per record (4 floats: point | rmax, `f32::INFINITY` = unbounded), the nearest surface point in world space.
+pub fn distance_points(device: &Device, scene: &Scene, records: &[f32]) -> Vec<DistanceResult> {
+    assert!(records.len() % LUPIN_DISTANCE_RECORD_FLOATS == 0);
+    let n = records.len() / LUPIN_DISTANCE_RECORD_FLOATS;
+    let mut out = vec![DistanceResult::default(); n];
+    check(unsafe { lupin_hip_distance_points(device.raw, scene.raw, 0, n as u64, records.as_ptr(), out.as_mut_ptr() as *mut f32) });
+    out
+}
+/// dims[0] x dims[1] x dims[2] distances, x fastest, at `origin + (i + 0.5) * spacing`; `rmax` where nothing lies within it.
+pub fn bake_distance_grid(device: &Device, scene: &Scene, origin: [f32; 3], spacing: [f32; 3], dims: [u32; 3], rmax: f32, signed: bool) -> Vec<f32> {
+    let mut out = vec![0f32; dims[0] as usize * dims[1] as usize * dims[2] as usize];
+    let flags = if signed { LUPIN_DISTANCE_GRID_SIGNED } else { 0 };
+    check(unsafe { lupin_hip_bake_distance_grid(device.raw, scene.raw, flags, origin.as_ptr(), spacing.as_ptr(), dims.as_ptr(), rmax, out.as_mut_ptr()) });
+    out
+}

@@ -1701,3 +1701,95 @@ def ambient_occlusion(ctx, scene, points, normals, radius, samples=64, ray_epsil
     rec = occlusion_records(points + normals * np.float32(surface_offset), normals, radius, rng_seed_for(np.arange(len(points), dtype=np.uint32), counter))
     blocked = occlusion_rays(ctx, scene, rec, OcclusionMode.COSINE_HEMISPHERE, samples, ray_epsilon)
     return np.float32(1.0) - blocked.astype(np.float32) / np.float32(samples)
+
+
+# ---- distance queries: lupin_hip_distance_points, lupin_hip_bake_distance_grid (include/lupin_hip.h) ----
+DISTANCE_RECORD_FLOATS = 4
+DISTANCE_RESULT_FLOATS = 12
+DISTANCE_DEVICE_POINTERS = 1
+DISTANCE_GRID_SIGNED = 2
+# the twelve words of a result, as the header lists them
+DISTANCE_RESULT_DTYPE = np.dtype([("found", np.uint32), ("distance", np.float32), ("point", np.float32, 3), ("u", np.float32), ("v", np.float32),
+                                  ("instance", np.uint32), ("tri", np.uint32), ("side", np.float32), ("pad", np.uint32, 2)])
+assert DISTANCE_RESULT_DTYPE.itemsize == 4 * DISTANCE_RESULT_FLOATS
+
+
+def distance_records(points, rmax=np.inf):
+    """(n, DISTANCE_RECORD_FLOATS) float32 records for distance_points: `points` (n, 3); `rmax` the search radius, a scalar
+    or an (n,) array (inf: unbounded)."""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    rec = np.zeros((len(points), DISTANCE_RECORD_FLOATS), np.float32)
+    rec[:, 0:3] = points
+    rec[:, 3] = np.asarray(rmax, np.float32)
+    return rec
+
+
+def distance_points(ctx, scene, records):
+    """The nearest surface point of every record (see distance_records): an (n,) array of DISTANCE_RESULT_DTYPE -- found,
+    distance, point, the barycentrics u, v, instance, tri (as trace_rays reports it) and side, the sign of dot(p - point, n) for
+    the REPORTED triangle's world-space normal (v1 - v0) x (v2 - v0): not an inside / outside classification.  `records` is
+    an (n, DISTANCE_RECORD_FLOATS) float32 numpy array, or a contiguous float32 torch tensor on the context's device: then
+    torch's current stream is synchronised, the device memory is used in place and an (n, DISTANCE_RESULT_FLOATS) float32
+    tensor of the same words is returned.  Blocks until complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "distance_points needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if hasattr(records, "data_ptr"):   # a torch tensor
+        import torch
+        t = records
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == DISTANCE_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 4) float32 tensor on the context's device")
+        if t.device.index != ctx.device_ordinal:
+            raise ValueError("records are on another device than the context")
+        out = torch.zeros((int(t.shape[0]), DISTANCE_RESULT_FLOATS), dtype=torch.float32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()   # the records (and the zero fill) are written
+        check(lib().lupin_hip_distance_points(ctx.handle, scene.handle, DISTANCE_DEVICE_POINTERS, int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, DISTANCE_RECORD_FLOATS)
+    out = np.zeros((len(rec), DISTANCE_RESULT_FLOATS), np.float32)
+    check(lib().lupin_hip_distance_points(ctx.handle, scene.handle, 0, len(rec), ptr(rec), ptr(out)))
+    return out.view(DISTANCE_RESULT_DTYPE).reshape(-1)
+
+
+def nearest_distance(ctx, scene, points, rmax=np.inf):
+    """(n,) float32: the distance from `points` (n, 3) to the nearest surface; inf where nothing lies within `rmax`."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "nearest_distance needs a GPU context and an uploaded scene; there is no CPU fallback")
+    res = distance_points(ctx, scene, distance_records(points, rmax))
+    return np.where(res["found"] != 0, res["distance"], np.float32(np.inf)).astype(np.float32)
+
+
+def grid_centres(origin, spacing, dims):
+    """The voxel centres of bake_distance_grid, (nz, ny, nx, 3) float32, by the stated f32 expression per axis:
+    origin + (float32(i) + 0.5) * spacing, the product first."""
+    origin, spacing = np.asarray(origin, np.float32).reshape(3), np.asarray(spacing, np.float32).reshape(3)
+    axes = [origin[k] + (np.arange(int(dims[k]), dtype=np.float32) + np.float32(0.5)) * spacing[k] for k in range(3)]
+    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.stack([x, y, z], -1).astype(np.float32)
+
+
+def bake_distance_grid(ctx, scene, origin, spacing, dims, rmax=np.inf, signed=False):
+    """A (nz, ny, nx) float32 volume of distances to the nearest surface at the voxel centres of grid_centres(origin,
+    spacing, dims) (dims = (nx, ny, nz)), computed on the device; `rmax` (clamped to the largest float) where nothing lies
+    within `rmax`.  signed: a found distance is multiplied by distance_points' `side` (0 where side is 0) -- the side of the
+    nearest TRIANGLE, not a true signed distance."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_distance_grid needs a GPU context and an uploaded scene; there is no CPU fallback")
+    o = (C.c_float * 3)(*[float(x) for x in np.asarray(origin, np.float32).reshape(3)])
+    s = (C.c_float * 3)(*[float(x) for x in np.asarray(spacing, np.float32).reshape(3)])
+    nx, ny, nz = (int(d) for d in dims)
+    d = (C.c_uint32 * 3)(nx, ny, nz)
+    out = np.zeros((nz, ny, nx), np.float32)
+    check(lib().lupin_hip_bake_distance_grid(ctx.handle, scene.handle, DISTANCE_GRID_SIGNED if signed else 0, o, s, d, float(np.float32(rmax)), ptr(out)))
+    return out
+
+
+def surface_clearance(ctx, scene, points, normals, offset):
+    """(n,) float32: the distance to the nearest surface from `points` + `offset` * `normals` ((n, 3) each, float32
+    arithmetic; `offset` a scalar or (n,) array) -- what a caller looks at to choose a bake offset locally: a clearance below
+    the offset says that another surface is nearer to the moved point than the one it was moved off."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "surface_clearance needs a GPU context and an uploaded scene; there is no CPU fallback")
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    normals = np.asarray(normals, np.float32).reshape(-1, 3)
+    offset = np.asarray(offset, np.float32).reshape(-1, 1)
+    return nearest_distance(ctx, scene, points + normals * offset)

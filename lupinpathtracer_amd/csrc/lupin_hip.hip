@@ -3,7 +3,8 @@
 // traversal / material / light device functions in lupin_device.hpp, the CPU builders in builders.cpp, the device BLAS
 // builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp, adaptive sampling's in lupin_adaptive.hpp, its
 // reprojection's in lupin_reproject.hpp, the radiance queries' in lupin_rays.hpp, light-probe baking's in lupin_probes.hpp,
-// lightmap baking's in lupin_lightmap.hpp, the occlusion queries' in lupin_occlusion.hpp.
+// lightmap baking's in lupin_lightmap.hpp, the occlusion queries' in lupin_occlusion.hpp, the distance queries' in
+// lupin_distance.hpp.
 //
 // THERE IS NO CPU FALLBACK: without a HIP device every entry point that needs one fails with LUPIN_ERR_NO_DEVICE.
 
@@ -31,6 +32,7 @@
 #include "lupin_probes.hpp"
 #include "lupin_lightmap.hpp"
 #include "lupin_occlusion.hpp"
+#include "lupin_distance.hpp"
 #include "lupin_internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -129,6 +131,10 @@ struct LupinContext
     // and counts), kept from call to call and grown when a call needs more; freed with the context
     DeviceBuffer occ_bad, occ_records, occ_counts;
     size_t occ_records_bytes = 0, occ_counts_bytes = 0;
+    // lupin_hip_distance_points / lupin_hip_bake_distance_grid: the same for the distance queries, and the per-instance
+    // auxiliary array (local -> world rows and c_i) that every call rebuilds from the scene's current rows
+    DeviceBuffer dist_bad, dist_records, dist_results, dist_aux;
+    size_t dist_records_bytes = 0, dist_results_bytes = 0, dist_aux_bytes = 0;
 };
 
 struct LupinPathtraceResources
@@ -2865,6 +2871,204 @@ int lupin_hip_occlusion_rays(LupinContext *ctx, const LupinScene *scene, const L
         });
         HIP_TRY(hipGetLastError());
         if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_cnt, (size_t)recs * 4, hipMemcpyDeviceToHost, st));
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+// ---- distance queries (no reference counterpart; kernels: lupin_distance.hpp) ----
+
+static constexpr uint64_t LP_DISTANCE_MAX_LAUNCH = 1ull << 30;          // records / voxels of one launch: indices fit 32 bits
+static constexpr uint64_t LP_DISTANCE_MAX_STAGED_RECORDS = 1ull << 20;  // host arrays: records of one launch (16 + 48 MB of staging)
+static constexpr uint64_t LP_DISTANCE_MAX_STAGED_VOXELS = 1ull << 24;   // host volume: voxels of one launch (64 MB of staging)
+static constexpr uint64_t LP_DISTANCE_MAX_VOXELS = 1ull << 36;
+
+// c_i of DESIGN.md 20: a float not above 1 / sigma_max of the world -> local rows' 3x3 part, so that c_i * (a distance in the
+// instance's local space) is a lower bound of the world distance.  sigma_max^2 is the largest eigenvalue of R^T R, by the
+// closed form for a symmetric 3x3 matrix in float64; the quotient is shrunk by 1e-9 (far above the closed form's error) and
+// rounded toward zero.  0 for a zero or non-finite sigma: nothing of that instance is pruned by distance.
+static float distance_scale(const InstanceDev &in)
+{
+    const double r[3][3] = {{in.r0.x, in.r0.y, in.r0.z}, {in.r1.x, in.r1.y, in.r1.z}, {in.r2.x, in.r2.y, in.r2.z}};
+    double a[3][3];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) a[i][j] = r[0][i] * r[0][j] + r[1][i] * r[1][j] + r[2][i] * r[2][j];
+    const double p1 = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
+    const double q = (a[0][0] + a[1][1] + a[2][2]) / 3.0;
+    const double p2 = (a[0][0] - q) * (a[0][0] - q) + (a[1][1] - q) * (a[1][1] - q) + (a[2][2] - q) * (a[2][2] - q) + 2.0 * p1;
+    const double p = std::sqrt(p2 / 6.0);
+    double lam = q;
+    if (p > 0.0)
+    {
+        double b[3][3];
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) b[i][j] = (a[i][j] - (i == j ? q : 0.0)) / p;
+        const double det = b[0][0] * (b[1][1] * b[2][2] - b[1][2] * b[2][1]) - b[0][1] * (b[1][0] * b[2][2] - b[1][2] * b[2][0]) +
+                           b[0][2] * (b[1][0] * b[2][1] - b[1][1] * b[2][0]);
+        const double h = std::min(1.0, std::max(-1.0, det / 2.0));
+        lam = q + 2.0 * p * std::cos(std::acos(h) / 3.0);
+    }
+    const double sigma = std::sqrt(lam);
+    if (!(std::isfinite(sigma) && sigma > 0.0)) return 0.0f;
+    const double c = (1.0 / sigma) * (1.0 - 1e-9);
+    float f = (float)c;
+    if ((double)f > c) f = std::nextafterf(f, 0.0f);
+    return std::isfinite(f) ? f : 0.0f;
+}
+
+// What both entry points share once their own arguments are accepted: the recorded calls run, the auxiliary array is built
+// from the scene's current rows and copied, the stack is sized for (reference, key) pairs.
+static int distance_begin(LupinContext *ctx, const LupinScene *scene, TraversalLds *t)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = flush_pending(ctx)) return rc;
+    if (int rc = traversal_lds(ctx, scene, 2u * scene->stack_entries, true, t)) return rc;
+    join_primary(ctx);   // the primary stream waits for the latest of the recorded calls
+    const uint32_t ninst = scene->dev.num_instances;
+    std::vector<float4> aux((size_t)std::max(1u, ninst) * LP_DISTANCE_AUX_WORDS, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (uint32_t i = 0; i < ninst; i++)
+    {
+        const InstanceDev &in = scene->host_instances[i];
+        const float4 rr[3] = {in.r0, in.r1, in.r2};
+        LupinMat3x4 w2l, l2w;
+        for (int r = 0; r < 3; r++) { w2l.m[0][r] = rr[r].x; w2l.m[1][r] = rr[r].y; w2l.m[2][r] = rr[r].z; w2l.m[3][r] = rr[r].w; }
+        lupin_mat3x4_inverse(&w2l, &l2w);   // the TLAS builder's own local -> world: the same floats
+        bool finite = true;
+        for (int r = 0; r < 3; r++)
+        {
+            aux[(size_t)i * LP_DISTANCE_AUX_WORDS + r] = make_float4(l2w.m[0][r], l2w.m[1][r], l2w.m[2][r], l2w.m[3][r]);
+            for (int c = 0; c < 4; c++) finite = finite && std::isfinite(l2w.m[c][r]);
+        }
+        aux[(size_t)i * LP_DISTANCE_AUX_WORDS + 3] = make_float4(finite ? distance_scale(in) : -1.0f, 0.0f, 0.0f, 0.0f);
+    }
+    // every call ends synchronised, so the buffer of the call before is free; the copy is from pageable memory and has left
+    // the vector when hipMemcpyAsync returns
+    HIP_TRY(occlusion_staging(&ctx->dist_aux, &ctx->dist_aux_bytes, aux.size() * sizeof(float4)));
+    HIP_TRY(hipMemcpyAsync(ctx->dist_aux.get(), aux.data(), aux.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    return LUPIN_OK;
+}
+
+int lupin_hip_distance_points(LupinContext *ctx, const LupinScene *scene, uint32_t flags, uint64_t n, const float *records, float *out_results)
+{
+    const char *who = "lupin_hip_distance_points";
+    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !scene || !records || !out_results) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (flags & ~(uint32_t)LUPIN_DISTANCE_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (n > LP_RAYS_MAX_PATHS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n must not exceed 2^38");
+    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    const bool on_device = (flags & LUPIN_DISTANCE_DEVICE_POINTERS) != 0;
+    if (on_device && (((uintptr_t)records & 15u) || ((uintptr_t)out_results & 15u)))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device records and results must be 16-byte aligned");
+    if (n == 0) return LUPIN_OK;
+    if (!on_device)
+        for (uint64_t i = 0; i < n; i++)
+        {
+            const float *r = records + i * LUPIN_DISTANCE_RECORD_FLOATS;
+            if (!distance_record_ok(r[0], r[1], r[2], r[3]))
+                return fail(LUPIN_ERR_INVALID_ARGUMENT, "record " + std::to_string(i) + ": non-finite point, or rmax NaN or not positive");
+        }
+    TraversalLds t;
+    if (int rc = distance_begin(ctx, scene, &t)) return rc;
+    hipStream_t st = ctx->stream;
+
+    if (on_device)
+    {
+        size_t have = ctx->dist_bad.get() ? sizeof(unsigned long long) : 0;
+        HIP_TRY(occlusion_staging(&ctx->dist_bad, &have, sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(ctx->dist_bad.get(), 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_distance_validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, reinterpret_cast<const float4 *>(records),
+                           (unsigned long long)n, ctx->dist_bad.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        unsigned long long count = 0;
+        HIP_TRY(hipMemcpyAsync(&count, ctx->dist_bad.get(), sizeof(count), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (count) return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " record(s): non-finite point, or rmax NaN or not positive");
+    }
+
+    uint64_t chunk = std::min(n, LP_DISTANCE_MAX_LAUNCH);
+    if (!on_device)
+    {
+        chunk = std::min(chunk, LP_DISTANCE_MAX_STAGED_RECORDS);
+        HIP_TRY(occlusion_staging(&ctx->dist_records, &ctx->dist_records_bytes, (size_t)chunk * LUPIN_DISTANCE_RECORD_FLOATS * 4));
+        HIP_TRY(occlusion_staging(&ctx->dist_results, &ctx->dist_results_bytes, (size_t)chunk * LUPIN_DISTANCE_RESULT_FLOATS * 4));
+    }
+    for (uint64_t first = 0; first < n; first += chunk)
+    {
+        const uint32_t recs = (uint32_t)std::min(chunk, n - first);
+        const float *src = records + first * LUPIN_DISTANCE_RECORD_FLOATS;
+        float *dst = out_results + first * LUPIN_DISTANCE_RESULT_FLOATS;
+        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
+        float4 *d_res = reinterpret_cast<float4 *>(dst);
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(ctx->dist_records.get(), src, (size_t)recs * LUPIN_DISTANCE_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
+            d_rec = ctx->dist_records.as<float4>();
+            d_res = ctx->dist_results.as<float4>();
+        }
+        with_bool(t.geo, [&](auto G) {
+            hipLaunchKernelGGL(k_distance<decltype(G)::value>, dim3((recs + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, st, scene->dev, recs, d_rec,
+                               ctx->dist_aux.as<float4>(), d_res, t.stack_words);
+        });
+        HIP_TRY(hipGetLastError());
+        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_res, (size_t)recs * LUPIN_DISTANCE_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+int lupin_hip_bake_distance_grid(LupinContext *ctx, const LupinScene *scene, uint32_t flags, const float *origin, const float *spacing,
+                                 const uint32_t *dims, float rmax, float *out_volume)
+{
+    const char *who = "lupin_hip_bake_distance_grid";
+    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !scene || !origin || !spacing || !dims || !out_volume) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (flags & ~(uint32_t)(LUPIN_DISTANCE_DEVICE_POINTERS | LUPIN_DISTANCE_GRID_SIGNED)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    for (int k = 0; k < 3; k++)
+    {
+        if (!std::isfinite(origin[k])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "origin must be finite");
+        if (!(std::isfinite(spacing[k]) && spacing[k] > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "spacing must be finite and positive");
+        if (dims[k] == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "a dimension is zero");
+        // the last centre, by the kernel's own expression: every centre of the axis lies between the first and this one
+        if (!std::isfinite(origin[k] + ((float)(dims[k] - 1u) + 0.5f) * spacing[k])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid's far corner is not finite");
+    }
+    if (!(rmax > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "rmax must be positive (+inf: unbounded)");
+    const uint64_t slice = (uint64_t)dims[0] * dims[1];   // below 2^64: both factors are below 2^32
+    if (slice > LP_DISTANCE_MAX_VOXELS || dims[2] > LP_DISTANCE_MAX_VOXELS / slice)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid must not exceed 2^36 voxels");
+    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    const bool on_device = (flags & LUPIN_DISTANCE_DEVICE_POINTERS) != 0;
+    if (on_device && ((uintptr_t)out_volume & 3u)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "a device volume must be 4-byte aligned");
+    const uint64_t n = (uint64_t)dims[0] * dims[1] * dims[2];
+    TraversalLds t;
+    if (int rc = distance_begin(ctx, scene, &t)) return rc;
+    hipStream_t st = ctx->stream;
+    DistanceGrid g;
+    g.ox = origin[0]; g.oy = origin[1]; g.oz = origin[2];
+    g.sx = spacing[0]; g.sy = spacing[1]; g.sz = spacing[2];
+    g.nx = dims[0]; g.ny = dims[1];
+    g.rmax = std::min(rmax, LP_F32_MAX);
+    g.flags = flags;
+    uint64_t chunk = std::min(n, LP_DISTANCE_MAX_LAUNCH);
+    if (!on_device)
+    {
+        chunk = std::min(chunk, LP_DISTANCE_MAX_STAGED_VOXELS);
+        HIP_TRY(occlusion_staging(&ctx->dist_results, &ctx->dist_results_bytes, (size_t)chunk * 4));
+    }
+    for (uint64_t first = 0; first < n; first += chunk)
+    {
+        const uint32_t voxels = (uint32_t)std::min(chunk, n - first);
+        float *dst = out_volume + first;
+        float *d_out = on_device ? dst : ctx->dist_results.as<float>();
+        with_bool(t.geo, [&](auto G) {
+            hipLaunchKernelGGL(k_distance_grid<decltype(G)::value>, dim3((voxels + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, st, scene->dev,
+                               (unsigned long long)first, voxels, g, ctx->dist_aux.as<float4>(), d_out, t.stack_words);
+        });
+        HIP_TRY(hipGetLastError());
+        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, (size_t)voxels * 4, hipMemcpyDeviceToHost, st));
     }
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
