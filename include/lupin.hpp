@@ -716,6 +716,35 @@ inline std::vector<float> ambient_occlusion(const Device &d, const Scene &scene,
     return out;
 }
 
+// transmittance queries (no reference counterpart): occlusion_rays' records and desc; out_sum: per record, the
+// sum over its slots of the product of 1 - opacity over the surfaces at ray_epsilon <= t < tmax (0 once an opacity of 1 is
+// met): the expected result of the integrators' stochastic alpha skip.  The caller divides by samples.
+inline void transmittance_rays(const Device &d, const Scene &scene, const OcclusionDesc &desc, uint64_t n, const float *records, float *out_sum)
+{
+    const LupinOcclusionDesc c{(uint32_t)desc.mode, desc.samples, desc.flags, desc.ray_epsilon};
+    check(lupin_hip_transmittance_rays(d.raw(), scene.raw(), &c, n, records, out_sum));
+}
+// The transmittance between p[i] and q[i] (n x 3 floats each); the segments are lp::visible's.
+inline std::vector<float> transmittance(const Device &d, const Scene &scene, uint64_t n, const float *p, const float *q, float ray_epsilon = 0.001f)
+{
+    std::vector<float> rec(n * LUPIN_OCCLUSION_RECORD_FLOATS, 0.0f);
+    for (uint64_t i = 0; i < n; i++)
+    {
+        const float dx = q[3 * i] - p[3 * i], dy = q[3 * i + 1] - p[3 * i + 1], dz = q[3 * i + 2] - p[3 * i + 2];
+        const float len = std::sqrt((dx * dx + dy * dy) + dz * dz);
+        if (!(len > 2.0f * ray_epsilon)) throw std::invalid_argument("lp::transmittance: a segment is not longer than 2 * ray_epsilon");
+        float *r = &rec[i * LUPIN_OCCLUSION_RECORD_FLOATS];
+        r[0] = p[3 * i]; r[1] = p[3 * i + 1]; r[2] = p[3 * i + 2];
+        r[4] = dx / len; r[5] = dy / len; r[6] = dz / len;
+        r[7] = len - ray_epsilon;
+    }
+    std::vector<float> out(n, 0.0f);
+    OcclusionDesc desc;
+    desc.ray_epsilon = ray_epsilon;
+    transmittance_rays(d, scene, desc, n, rec.data(), out.data());
+    return out;
+}
+
 // distance queries (no reference counterpart): the nearest surface point of points in world space.
 // `side` is the side of the REPORTED triangle (sign of dot(p - point, (v1 - v0) x (v2 - v0))), not inside / outside.
 struct DistanceResult   // the twelve words of LUPIN_DISTANCE_RESULT_FLOATS

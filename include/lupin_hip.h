@@ -1054,6 +1054,40 @@ typedef struct LupinOcclusionDesc {
 int lupin_hip_occlusion_rays(LupinContext *ctx, const LupinScene *scene, const LupinOcclusionDesc *desc,
                              uint64_t n, const float *records /* n x 8 */, uint32_t *out_blocked /* n */);
 
+/* ---- transmittance queries (no reference counterpart) ----
+ * "How much gets through?": opacity-aware visibility for the callers of lupin_hip_occlusion_rays -- alpha-textured leaf
+ * cards, cut-out fences, half-transparent panes.  The records, modes, slots, flags and LupinOcclusionDesc are those of
+ * lupin_hip_occlusion_rays; the traversal does not stop at the first triangle.
+ *
+ * A slot's segment (o, d, ray_epsilon, tmax) starts with T = 1.  Each triangle the traversal tests that is hit at
+ * ray_epsilon <= t < tmax contributes one factor, in the order the traversal meets them:
+ *   - its instance cannot have an opacity other than 1 (material colour alpha == 1, no colour texture on a mesh with
+ *     texcoords, no vertex colours: decided at upload): T = 0 and the query ends; no material is read.
+ *   - otherwise a = texture alpha * material colour alpha * vertex colour alpha at the hit (LUPIN_SURFACE_OPACITY of
+ *     lupin_hip_surface_probe).  If !(a < 1) (this includes NaN): T = 0 and the query ends.  Otherwise
+ *     T = T * (1 - max(a, 0)).
+ * f32, no contraction, one multiplication per accepted triangle.  For a in [0, 1), 1 - a is the probability with which the
+ * integrators' stochastic alpha skip lets a path through that surface, so T is the EXPECTED result of that skip over the
+ * surfaces of one segment.  It is NOT a replay of the integrators' loop: that loop restarts the ray at every skipped surface
+ * with a fresh ray_epsilon and gives up after 128 skips.  Colour is not consulted: a refractive or transparent MATERIAL
+ * TYPE with opacity 1 blocks -- this is alpha, not BSDF transmission.  The visited nodes are those of
+ * lupin_hip_occlusion_rays (slab distance below the constant tmax, binary hierarchy only: it works after
+ * lupin_hip_scene_update_instances), each triangle of a visited leaf is tested once, and T(tmax) never grows with tmax.
+ * On a scene without an alpha-capable instance T == 1 - blocked of lupin_hip_occlusion_rays, bit for bit.
+ *
+ * out_sum[i]: the SUM of T over record i's slots (direction mode: T itself); the caller divides by samples.  The sum's
+ * order is fixed: 64 partial sums p[l] = T[l] + T[l + 64] + ... (ascending, from 0), then for off = 32, 16, 8, 4, 2, 1:
+ * p[l] = p[l] + p[l ^ off]; the result is p[0].  No float atomics: the same records give the same words.
+ *
+ * The call behaves as lupin_hip_occlusion_rays does: recorded calls run first, the work runs on the primary stream, host
+ * arrays go through the context's staging buffers, LUPIN_OCCLUSION_DEVICE_POINTERS takes device memory in place (records
+ * 16-byte, out_sum 4-byte aligned), launches cover whole records, and the same refusals apply (LUPIN_ERR_INVALID_ARGUMENT,
+ * out_sum untouched) with one tighter limit: samples must not exceed 2^20.  With samples > 1 the slots' T go through a
+ * plane of floats the context owns and reuses; launches are sized so that it stays within 2^24 slots (64 MB).
+ * n == 0: LUPIN_OK, nothing touched.  Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+int lupin_hip_transmittance_rays(LupinContext *ctx, const LupinScene *scene, const LupinOcclusionDesc *desc,
+                                 uint64_t n, const float *records /* n x 8 */, float *out_sum /* n */);
+
 /* ---- distance queries (no reference counterpart) ----
  * "How far is the nearest surface, where is it, and which side of it am I on?" for POINTS: clearances for bake offsets, probe
  * validity, a distance volume for collision, sphere tracing or leak checks.  A nearest-point traversal of the binary

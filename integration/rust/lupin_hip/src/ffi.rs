@@ -210,6 +210,7 @@ extern "C" {
     // occlusion queries: records n x 8 f32 (origin | RNG bits, unit direction or normal | tmax), out_blocked n counts
     pub fn lupin_hip_occlusion_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinOcclusionDesc, n: u64,
                                     records: *const f32, out_blocked: *mut u32) -> c_int;
+    pub fn lupin_hip_transmittance_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinOcclusionDesc, n: u64, records: *const f32, out_sum: *mut f32) -> c_int;
     // distance queries: records n x 4 f32 (point | rmax), out_results n x 12 f32 words; the grid: x fastest, one f32 per voxel
     pub fn lupin_hip_distance_points(ctx: *mut LupinContext, scene: *const LupinScene, flags: u32, n: u64, records: *const f32, out_results: *mut f32) -> c_int;
     pub fn lupin_hip_bake_distance_grid(ctx: *mut LupinContext, scene: *const LupinScene, flags: u32, origin: *const f32, spacing: *const f32,

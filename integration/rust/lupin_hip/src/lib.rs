@@ -291,6 +291,17 @@ pub fn occlusion_rays(device: &Device, scene: &Scene, records: &[f32], mode: Occ
     out
 }
 
+/// Transmittance queries: per record of `occlusion_rays`' layout, the sum over its `samples` slots of the product
+/// of `1 - opacity` over the surfaces at `ray_epsilon <= t < tmax` (0 once an opacity of 1 is met).  Divide by `samples`.
+pub fn transmittance_rays(device: &Device, scene: &Scene, records: &[f32], mode: OcclusionMode, samples: u32, ray_epsilon: f32) -> Vec<f32> {
+    assert!(records.len() % LUPIN_OCCLUSION_RECORD_FLOATS == 0);
+    let n = records.len() / LUPIN_OCCLUSION_RECORD_FLOATS;
+    let mut out = vec![0f32; n];
+    let c = LupinOcclusionDesc { mode: mode as u32, samples, flags: 0, ray_epsilon };
+    check(unsafe { lupin_hip_transmittance_rays(device.raw, scene.raw, &c, n as u64, records.as_ptr(), out.as_mut_ptr()) });
+    out
+}
+
 // ---- distance queries (no reference counterpart) ----
 /// The twelve words of a result.  `side` is the side of the reported triangle, not an inside / outside classification.
 #[repr(C)] #[derive(Copy, Clone, Debug, Default)] pub struct DistanceResult {

@@ -254,6 +254,7 @@ SYMBOLS = [
     ("lupin_hip_lightmap_stats", None, [C.POINTER(LightmapStatsC)]),
     ("lupin_hip_bake_probes", C.c_int, [_P, _P, C.POINTER(ProbeDescC), C.c_uint64, _P, _P, _P]),
     ("lupin_hip_occlusion_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),
+    ("lupin_hip_transmittance_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),
     ("lupin_hip_distance_points", C.c_int, [_P, _P, _U32, C.c_uint64, _P, _P]),
     ("lupin_hip_bake_distance_grid", C.c_int, [_P, _P, _U32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_float, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),

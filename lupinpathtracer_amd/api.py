@@ -1687,11 +1687,47 @@ def visible(ctx, scene, p, q, ray_epsilon=0.001):
     return occlusion_rays(ctx, scene, segment_records(p, q, ray_epsilon), OcclusionMode.DIRECTION, 1, ray_epsilon) == 0
 
 
-def ambient_occlusion(ctx, scene, points, normals, radius, samples=64, ray_epsilon=0.001, counter=0, surface_offset=None):
+def transmittance_rays(ctx, scene, records, mode=OcclusionMode.DIRECTION, samples=1, ray_epsilon=0.001):
+    """Per record, the SUM over its `samples` slots of the slot's transmittance T: (n,) float32; divide by
+    `samples` for the mean.  T is the product of 1 - opacity over the surfaces at ray_epsilon <= t < tmax, 0 once a surface
+    of opacity 1 is met: the expected result of the integrators' stochastic alpha skip along the segment.  `records` as
+    occlusion_rays takes them: an (n, OCCLUSION_RECORD_FLOATS) float32 numpy array, or a contiguous float32 torch tensor on
+    the context's device, used in place (a float32 tensor is returned).  Blocks until complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "transmittance_rays needs a GPU context and an uploaded scene; there is no CPU fallback")
+    c = _abi.OcclusionDescC(int(mode), int(samples), 0, float(ray_epsilon))
+    if hasattr(records, "data_ptr"):   # a torch tensor
+        import torch
+        t = records
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == OCCLUSION_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+        if t.device.index != ctx.device_ordinal:
+            raise ValueError("records are on another device than the context")
+        out = torch.zeros((int(t.shape[0]),), dtype=torch.float32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()   # the records (and the zero fill) are written
+        c.flags = OCCLUSION_DEVICE_POINTERS
+        check(lib().lupin_hip_transmittance_rays(ctx.handle, scene.handle, C.byref(c), int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, OCCLUSION_RECORD_FLOATS)
+    out = np.zeros(len(rec), np.float32)
+    check(lib().lupin_hip_transmittance_rays(ctx.handle, scene.handle, C.byref(c), len(rec), ptr(rec), ptr(out)))
+    return out
+
+
+def transmittance(ctx, scene, p, q, ray_epsilon=0.001):
+    """(n,) float32: the transmittance between the points p and q ((n, 3) each); see segment_records and transmittance_rays."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "transmittance needs a GPU context and an uploaded scene; there is no CPU fallback")
+    return transmittance_rays(ctx, scene, segment_records(p, q, ray_epsilon), OcclusionMode.DIRECTION, 1, ray_epsilon)
+
+
+def ambient_occlusion(ctx, scene, points, normals, radius, samples=64, ray_epsilon=0.001, counter=0, surface_offset=None, opacity=False):
     """Ambient occlusion (n,) float32 at `points` (n, 3) with unit `normals` (n, 3): 1 - blocked / samples over `samples`
     cosine-weighted directions per point, each tested up to `radius` (a scalar or (n,) array).  Point i is seeded with
     rng_seed_for(i, counter), as bake_irradiance seeds it.  The origins are the points moved along their normals by
-    `surface_offset` world units (default: LIGHTMAP_OFFSET_FRACTION of the scene's extent, bake_lightmap's default)."""
+    `surface_offset` world units (default: LIGHTMAP_OFFSET_FRACTION of the scene's extent, bake_lightmap's default).
+    opacity=True: the mean transmittance of the same slots instead (transmittance_rays' sum / samples): alpha-textured,
+    cut-out and half-transparent surfaces let through what the integrators let through on average."""
     if ctx is None or scene.handle is None:
         raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "ambient_occlusion needs a GPU context and an uploaded scene; there is no CPU fallback")
     points = np.asarray(points, np.float32).reshape(-1, 3)
@@ -1699,6 +1735,8 @@ def ambient_occlusion(ctx, scene, points, normals, radius, samples=64, ray_epsil
     if surface_offset is None:
         surface_offset = LIGHTMAP_OFFSET_FRACTION * scene_world_extent(scene)
     rec = occlusion_records(points + normals * np.float32(surface_offset), normals, radius, rng_seed_for(np.arange(len(points), dtype=np.uint32), counter))
+    if opacity:
+        return transmittance_rays(ctx, scene, rec, OcclusionMode.COSINE_HEMISPHERE, samples, ray_epsilon) / np.float32(samples)
     blocked = occlusion_rays(ctx, scene, rec, OcclusionMode.COSINE_HEMISPHERE, samples, ray_epsilon)
     return np.float32(1.0) - blocked.astype(np.float32) / np.float32(samples)
 

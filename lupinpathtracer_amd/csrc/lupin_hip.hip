@@ -32,6 +32,7 @@
 #include "lupin_probes.hpp"
 #include "lupin_lightmap.hpp"
 #include "lupin_occlusion.hpp"
+#include "lupin_transmittance.hpp"
 #include "lupin_distance.hpp"
 #include "lupin_internal.hpp"
 
@@ -131,6 +132,10 @@ struct LupinContext
     // and counts), kept from call to call and grown when a call needs more; freed with the context
     DeviceBuffer occ_bad, occ_records, occ_counts;
     size_t occ_records_bytes = 0, occ_counts_bytes = 0;
+    // lupin_hip_transmittance_rays: it shares the three buffers above (a result is four bytes, as a count is) and adds the
+    // per-slot plane of hemisphere mode (one float per slot of a chunk), kept and grown the same way
+    DeviceBuffer trans_plane;
+    size_t trans_plane_bytes = 0;
     // lupin_hip_distance_points / lupin_hip_bake_distance_grid: the same for the distance queries, and the per-instance
     // auxiliary array (local -> world rows and c_i) that every call rebuilds from the scene's current rows
     DeviceBuffer dist_bad, dist_records, dist_results, dist_aux;
@@ -2871,6 +2876,106 @@ int lupin_hip_occlusion_rays(LupinContext *ctx, const LupinScene *scene, const L
         });
         HIP_TRY(hipGetLastError());
         if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_cnt, (size_t)recs * 4, hipMemcpyDeviceToHost, st));
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+// ---- transmittance queries (no reference counterpart; kernels: lupin_transmittance.hpp) ----
+
+static constexpr uint32_t LP_TRANSMITTANCE_MAX_SAMPLES = 1u << 20;
+static constexpr uint64_t LP_TRANSMITTANCE_MAX_PLANE_SLOTS = 1ull << 24;   // slots of one hemisphere launch: the plane stays within 64 MB
+
+int lupin_hip_transmittance_rays(LupinContext *ctx, const LupinScene *scene, const LupinOcclusionDesc *desc, uint64_t n, const float *records,
+                                 float *out_sum)
+{
+    const char *who = "lupin_hip_transmittance_rays";
+    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !scene || !desc || !records || !out_sum) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (desc->mode > LUPIN_OCCLUSION_COSINE_HEMISPHERE) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown mode");
+    if (desc->flags & ~(uint32_t)LUPIN_OCCLUSION_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (desc->samples == 0 || desc->samples > LP_TRANSMITTANCE_MAX_SAMPLES) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^20]");
+    if (desc->mode == LUPIN_OCCLUSION_DIRECTION && desc->samples != 1) return fail(LUPIN_ERR_INVALID_ARGUMENT, "direction mode takes samples == 1");
+    const uint64_t S = desc->samples;
+    if (n > LP_RAYS_MAX_PATHS / S) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n * samples must not exceed 2^38");
+    if (!(std::isfinite(desc->ray_epsilon) && desc->ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
+    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    // (a stale four-wide hierarchy is no obstacle: only the binary one is read)
+    const bool on_device = (desc->flags & LUPIN_OCCLUSION_DEVICE_POINTERS) != 0;
+    if (on_device && (((uintptr_t)records & 15u) || ((uintptr_t)out_sum & 3u)))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device records must be 16-byte aligned, device results 4-byte aligned");
+    if (n == 0) return LUPIN_OK;
+    // the calls recorded so far run first, whatever becomes of this one from here on
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = flush_pending(ctx)) return rc;
+    if (!on_device)
+        for (uint64_t i = 0; i < n; i++)
+        {
+            const float *r = records + i * LUPIN_OCCLUSION_RECORD_FLOATS;
+            if (!occlusion_record_ok(r[0], r[1], r[2], r[4], r[5], r[6], r[7]))
+                return fail(LUPIN_ERR_INVALID_ARGUMENT, "record " + std::to_string(i) + ": non-finite component, direction or normal not of unit length, or tmax NaN or not positive");
+        }
+    TraversalLds t;
+    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
+    join_primary(ctx);   // the primary stream waits for the latest of the recorded calls
+    hipStream_t st = ctx->stream;
+
+    if (on_device)
+    {
+        size_t have = ctx->occ_bad.get() ? sizeof(unsigned long long) : 0;
+        HIP_TRY(occlusion_staging(&ctx->occ_bad, &have, sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(ctx->occ_bad.get(), 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_transmittance_validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, records, (unsigned long long)n,
+                           ctx->occ_bad.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        unsigned long long count = 0;
+        HIP_TRY(hipMemcpyAsync(&count, ctx->occ_bad.get(), sizeof(count), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (count)
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " record(s): non-finite component, direction or normal not of unit length, or tmax NaN or not positive");
+    }
+
+    // whole records per launch; with more than one slot per record the slots go through the plane, which bounds the chunk
+    const bool planed = S > 1;
+    const uint64_t max_slots = planed ? LP_TRANSMITTANCE_MAX_PLANE_SLOTS : LP_OCCLUSION_MAX_LAUNCH_SLOTS;
+    uint64_t chunk_records = std::min(n, std::max<uint64_t>(1, max_slots / S));
+    if (!on_device)
+    {
+        chunk_records = std::min(chunk_records, LP_OCCLUSION_MAX_STAGED_RECORDS);
+        HIP_TRY(occlusion_staging(&ctx->occ_records, &ctx->occ_records_bytes, (size_t)chunk_records * LUPIN_OCCLUSION_RECORD_FLOATS * 4));
+        HIP_TRY(occlusion_staging(&ctx->occ_counts, &ctx->occ_counts_bytes, (size_t)chunk_records * 4));
+    }
+    if (planed) HIP_TRY(occlusion_staging(&ctx->trans_plane, &ctx->trans_plane_bytes, (size_t)(chunk_records * S) * 4));
+    for (uint64_t first = 0; first < n; first += chunk_records)
+    {
+        const uint64_t recs = std::min(chunk_records, n - first);
+        const uint32_t slots = (uint32_t)(recs * S);
+        const float *src = records + first * LUPIN_OCCLUSION_RECORD_FLOATS;
+        float *dst = out_sum + first;
+        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
+        float *d_sum = dst;
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(ctx->occ_records.get(), src, (size_t)recs * LUPIN_OCCLUSION_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
+            d_rec = ctx->occ_records.as<float4>();
+            d_sum = ctx->occ_counts.as<float>();
+        }
+        float *d_slots = planed ? ctx->trans_plane.as<float>() : d_sum;
+        with_bool(t.geo, [&](auto G) {
+            hipLaunchKernelGGL(k_transmittance<decltype(G)::value>, dim3((slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, st, scene->dev, slots, d_rec,
+                               desc->samples, desc->mode, desc->ray_epsilon, d_slots, t.stack_words);
+        });
+        HIP_TRY(hipGetLastError());
+        if (planed)
+        {
+            hipLaunchKernelGGL(k_transmittance_resolve, dim3((uint32_t)((recs + LP_TRANSMITTANCE_RECORDS_PER_BLOCK - 1) / LP_TRANSMITTANCE_RECORDS_PER_BLOCK)),
+                               dim3(LP_BLOCK), 0, st, d_slots, (uint32_t)recs, desc->samples, d_sum);
+            HIP_TRY(hipGetLastError());
+        }
+        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_sum, (size_t)recs * 4, hipMemcpyDeviceToHost, st));
     }
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
