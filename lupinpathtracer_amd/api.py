@@ -1636,13 +1636,12 @@ def occlusion_records(ori, dir_or_normal, tmax=np.inf, rng=0):
     return rec
 
 
-def occlusion_rays(ctx, scene, records, mode=OcclusionMode.DIRECTION, samples=1, ray_epsilon=0.001):
-    """Per record, the number of its `samples` slots whose segment is blocked (some triangle at ray_epsilon <= t < tmax):
-    (n,) uint32.  Geometric visibility: opacity is not consulted.  `records` is an (n, OCCLUSION_RECORD_FLOATS) float32 numpy
-    array (see occlusion_records), or a contiguous float32 torch tensor on the context's device: then torch's current stream
-    is synchronised, the device memory is used in place and an int32 tensor is returned.  Blocks until complete."""
+def _segment_query(name, np_dtype, torch_dtype, ctx, scene, records, mode, samples, ray_epsilon):
+    """What occlusion_rays and transmittance_rays share: lupin_hip_<name> over numpy records (a `np_dtype` array comes back)
+    or over a torch tensor in place (a tensor of torch's dtype named `torch_dtype`)."""
     if ctx is None or scene.handle is None:
-        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "occlusion_rays needs a GPU context and an uploaded scene; there is no CPU fallback")
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), f"{name} needs a GPU context and an uploaded scene; there is no CPU fallback")
+    fn = getattr(lib(), "lupin_hip_" + name)
     c = _abi.OcclusionDescC(int(mode), int(samples), 0, float(ray_epsilon))
     if hasattr(records, "data_ptr"):   # a torch tensor
         import torch
@@ -1651,15 +1650,23 @@ def occlusion_rays(ctx, scene, records, mode=OcclusionMode.DIRECTION, samples=1,
             raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
         if t.device.index != ctx.device_ordinal:
             raise ValueError("records are on another device than the context")
-        out = torch.zeros((int(t.shape[0]),), dtype=torch.int32, device=t.device)
+        out = torch.zeros((int(t.shape[0]),), dtype=getattr(torch, torch_dtype), device=t.device)
         torch.cuda.current_stream(t.device).synchronize()   # the records (and the zero fill) are written
         c.flags = OCCLUSION_DEVICE_POINTERS
-        check(lib().lupin_hip_occlusion_rays(ctx.handle, scene.handle, C.byref(c), int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
+        check(fn(ctx.handle, scene.handle, C.byref(c), int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
     rec = np.ascontiguousarray(records, np.float32).reshape(-1, OCCLUSION_RECORD_FLOATS)
-    out = np.zeros(len(rec), np.uint32)
-    check(lib().lupin_hip_occlusion_rays(ctx.handle, scene.handle, C.byref(c), len(rec), ptr(rec), ptr(out)))
+    out = np.zeros(len(rec), np_dtype)
+    check(fn(ctx.handle, scene.handle, C.byref(c), len(rec), ptr(rec), ptr(out)))
     return out
+
+
+def occlusion_rays(ctx, scene, records, mode=OcclusionMode.DIRECTION, samples=1, ray_epsilon=0.001):
+    """Per record, the number of its `samples` slots whose segment is blocked (some triangle at ray_epsilon <= t < tmax):
+    (n,) uint32.  Geometric visibility: opacity is not consulted.  `records` is an (n, OCCLUSION_RECORD_FLOATS) float32 numpy
+    array (see occlusion_records), or a contiguous float32 torch tensor on the context's device: then torch's current stream
+    is synchronised, the device memory is used in place and an int32 tensor is returned.  Blocks until complete."""
+    return _segment_query("occlusion_rays", np.uint32, "int32", ctx, scene, records, mode, samples, ray_epsilon)
 
 
 def occluded(ctx, scene, ori, dir_, tmax=np.inf, ray_epsilon=0.001):
@@ -1693,25 +1700,7 @@ def transmittance_rays(ctx, scene, records, mode=OcclusionMode.DIRECTION, sample
     of opacity 1 is met: the expected result of the integrators' stochastic alpha skip along the segment.  `records` as
     occlusion_rays takes them: an (n, OCCLUSION_RECORD_FLOATS) float32 numpy array, or a contiguous float32 torch tensor on
     the context's device, used in place (a float32 tensor is returned).  Blocks until complete."""
-    if ctx is None or scene.handle is None:
-        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "transmittance_rays needs a GPU context and an uploaded scene; there is no CPU fallback")
-    c = _abi.OcclusionDescC(int(mode), int(samples), 0, float(ray_epsilon))
-    if hasattr(records, "data_ptr"):   # a torch tensor
-        import torch
-        t = records
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == OCCLUSION_RECORD_FLOATS):
-            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
-        if t.device.index != ctx.device_ordinal:
-            raise ValueError("records are on another device than the context")
-        out = torch.zeros((int(t.shape[0]),), dtype=torch.float32, device=t.device)
-        torch.cuda.current_stream(t.device).synchronize()   # the records (and the zero fill) are written
-        c.flags = OCCLUSION_DEVICE_POINTERS
-        check(lib().lupin_hip_transmittance_rays(ctx.handle, scene.handle, C.byref(c), int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
-        return out
-    rec = np.ascontiguousarray(records, np.float32).reshape(-1, OCCLUSION_RECORD_FLOATS)
-    out = np.zeros(len(rec), np.float32)
-    check(lib().lupin_hip_transmittance_rays(ctx.handle, scene.handle, C.byref(c), len(rec), ptr(rec), ptr(out)))
-    return out
+    return _segment_query("transmittance_rays", np.float32, "float32", ctx, scene, records, mode, samples, ray_epsilon)
 
 
 def transmittance(ctx, scene, p, q, ray_epsilon=0.001):

@@ -10,7 +10,7 @@
 // squared length of zero in f32 is SKIPPED, and so is every triangle of an instance whose rows have no finite inverse.
 // Material opacity is not consulted.
 //
-//   k_distance_validate    device records only: counts the records the host check would refuse
+//   k_validate_records<DistanceRecordRule>   device records only: counts the records the host check would refuse
 //   k_distance<LDSGEO>     one lane per record; three float4 stores per result
 //   k_distance_grid<LDSGEO> one lane per voxel, x fastest: centre = origin + (i + 0.5) * spacing per axis, one float per voxel
 //
@@ -23,26 +23,24 @@ constexpr uint32_t LP_DISTANCE_GRID_SIGNED = 2u;   // LUPIN_DISTANCE_GRID_SIGNED
 constexpr uint32_t LP_DISTANCE_AUX_WORDS = 4u;     // float4 per instance: local -> world rows 0..2, then (c_i, 0, 0, 0)
 
 // What the distance entry points refuse in a record: a non-finite point, an rmax that is NaN or <= 0 (+inf is "unbounded").
-// The host check and k_distance_validate share this function.
+// The host check and DistanceRecordRule share this function.
 __host__ __device__ inline bool distance_record_ok(float px, float py, float pz, float rmax)
 {
     const float s = (px - px) + (py - py) + (pz - pz);   // 0 for finite components, NaN otherwise
     return s == 0.0f && rmax > 0.0f;                     // (NaN > 0 is false)
 }
 
-// one thread per record, one atomic per wave that found something
-__global__ void __launch_bounds__(LP_BLOCK) k_distance_validate(const float4 *__restrict__ records, unsigned long long n, unsigned long long *bad_count)
+struct DistanceRecordRule   // the record format (lupin_rays.hpp says what a Rule is)
 {
-    const unsigned long long i = (unsigned long long)blockIdx.x * LP_BLOCK + threadIdx.x;
-    bool bad = false;
-    if (i < n)
+    static constexpr uint32_t FLOATS = LUPIN_DISTANCE_RECORD_FLOATS;
+    static constexpr const char *NOUN = "record", *WHY = "non-finite point, or rmax NaN or not positive";
+    static bool host_ok(const float *r) { return distance_record_ok(r[0], r[1], r[2], r[3]); }
+    static __device__ bool ok(const float4 *__restrict__ records, unsigned long long i)
     {
         const float4 a = records[i];
-        bad = !distance_record_ok(a.x, a.y, a.z, a.w);
+        return distance_record_ok(a.x, a.y, a.z, a.w);
     }
-    const unsigned long long mask = __ballot(bad);
-    if (mask && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)mask) - 1)) atomicAdd(bad_count, (unsigned long long)__popcll(mask));
-}
+};
 
 // The flag word of a node (WideNode.d.z: bit 0 / 1 = the left / right child's stored box does not bound its triangles), read
 // beside node() so that NodeRegs and every kernel that uses it stay what they were.  0 in a TLAS node.

@@ -128,17 +128,19 @@ struct LupinContext
     int last_lanes = 0;                    // frames in flight the latest pathtrace call could use (reported by lupin_hip_stats_get)
     bool last_wide = false;                // ... and whether it ran the four-wide tracer
     uint32_t last_batch = 0, last_short = 0;   // frames the latest wavefront carried; its first-pass stack entries (0 = one pass)
-    // lupin_hip_occlusion_rays: the bad-record counter of its device check, and the staging of host arrays (one chunk's records
-    // and counts), kept from call to call and grown when a call needs more; freed with the context
-    DeviceBuffer occ_bad, occ_records, occ_counts;
+    // the scene queries' device check of records: its counter of refused records (count_bad_records), made by the first check
+    DeviceBuffer bad_records;
+    // lupin_hip_occlusion_rays: the staging of host arrays (one chunk's records and counts), kept from call to call and grown
+    // when a call needs more (grow_buffer); freed with the context
+    DeviceBuffer occ_records, occ_counts;
     size_t occ_records_bytes = 0, occ_counts_bytes = 0;
-    // lupin_hip_transmittance_rays: it shares the three buffers above (a result is four bytes, as a count is) and adds the
+    // lupin_hip_transmittance_rays: it shares the two buffers above (a result is four bytes, as a count is) and adds the
     // per-slot plane of hemisphere mode (one float per slot of a chunk), kept and grown the same way
     DeviceBuffer trans_plane;
     size_t trans_plane_bytes = 0;
     // lupin_hip_distance_points / lupin_hip_bake_distance_grid: the same for the distance queries, and the per-instance
     // auxiliary array (local -> world rows and c_i) that every call rebuilds from the scene's current rows
-    DeviceBuffer dist_bad, dist_records, dist_results, dist_aux;
+    DeviceBuffer dist_records, dist_results, dist_aux;
     size_t dist_records_bytes = 0, dist_results_bytes = 0, dist_aux_bytes = 0;
 };
 
@@ -2533,8 +2535,105 @@ int lupin_hip_camera_probe(LupinContext *ctx, uint32_t width, uint32_t height, c
     });
 }
 
-// ---- radiance queries (no reference counterpart; kernels: lupin_rays.hpp) ----
+// ---- what the scene queries share (DESIGN.md 5 "The scene queries' host scaffold") ----
+// An entry point reads: query_refuse, the checks of its own arguments, query_refuse_hierarchy, n == 0, query_start, its
+// chunks, query_end.  The order is the contract: the first check that fails decides the error.
+extern "C++" {   // (there are templates among them, and the entry points around them are extern "C")
 
+// the refusals every scene query opens with; `args`: the entry point's own pointers are all there
+static int query_refuse(const LupinContext *ctx, const LupinScene *scene, bool args)
+{
+    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    CTX_ALIVE_TRY(ctx);
+    if (!ctx || !scene || !args) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    return LUPIN_OK;
+}
+// ... and the ones about the scene's hierarchies (a stale four-wide hierarchy is no obstacle to a query that reads only the binary one)
+static int query_refuse_hierarchy(const LupinContext *ctx, const LupinScene *scene, bool reads_wide)
+{
+    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    if (reads_wide && scene->wide_stale && ctx->wide_traversal) return fail(LUPIN_ERR_INVALID_ARGUMENT, kWideStale);
+    return LUPIN_OK;
+}
+// the calls recorded so far run first, whatever becomes of this one from here on
+static int query_flush(LupinContext *ctx)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    return flush_pending(ctx);
+}
+// the LDS plan for a per-lane stack of `stack_entries` entries; the primary stream, the query's own, waits for the latest of the recorded calls
+static int query_plan(LupinContext *ctx, const LupinScene *scene, uint32_t stack_entries, TraversalLds *t)
+{
+    if (int rc = traversal_lds(ctx, scene, stack_entries, true, t)) return rc;
+    join_primary(ctx);
+    return LUPIN_OK;
+}
+// every call ends synchronised
+static int query_end(LupinContext *ctx, const char *who)
+{
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return LUPIN_OK;
+}
+
+// host records: the first one the format's Rule (lupin_rays.hpp) refuses is named
+template <typename Rule>
+static int refuse_bad_host_records(uint64_t n, const float *records)
+{
+    for (uint64_t i = 0; i < n; i++)
+        if (!Rule::host_ok(records + i * Rule::FLOATS))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, std::string(Rule::NOUN) + " " + std::to_string(i) + ": " + Rule::WHY);
+    return LUPIN_OK;
+}
+// device records: `validate` (a k_validate_records<Rule>) counts them into the context's counter; the host waits for the count
+static int count_bad_records(LupinContext *ctx, void (*validate)(const float4 *, unsigned long long, unsigned long long *), const float *records, uint64_t n,
+                             unsigned long long *count)
+{
+    hipStream_t st = ctx->stream;
+    if (!ctx->bad_records.get()) HIP_TRY(DeviceBuffer::make(sizeof(unsigned long long), &ctx->bad_records));
+    HIP_TRY(hipMemsetAsync(ctx->bad_records.get(), 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, reinterpret_cast<const float4 *>(records),
+                       (unsigned long long)n, ctx->bad_records.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(count, ctx->bad_records.get(), sizeof(*count), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LUPIN_OK;
+}
+template <typename Rule>
+static int refuse_bad_device_records(LupinContext *ctx, uint64_t n, const float *records)
+{
+    unsigned long long count = 0;
+    if (int rc = count_bad_records(ctx, k_validate_records<Rule>, records, n, &count)) return rc;
+    if (count) return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " " + Rule::NOUN + "(s): " + Rule::WHY);
+    return LUPIN_OK;
+}
+
+// The start of a query over `n` records of format Rule and a stack of the scene's depth, once the entry point's own
+// arguments are accepted: host records are looked at after the recorded calls have run and before anything is planned,
+// device records once the stream is the query's.  (The distance queries put the same pieces in their own order.)
+template <typename Rule>
+static int query_start(LupinContext *ctx, const LupinScene *scene, bool on_device, uint64_t n, const float *records, TraversalLds *t)
+{
+    if (int rc = query_flush(ctx)) return rc;
+    if (!on_device)
+        if (int rc = refuse_bad_host_records<Rule>(n, records)) return rc;
+    if (int rc = query_plan(ctx, scene, scene->stack_entries, t)) return rc;
+    return on_device ? refuse_bad_device_records<Rule>(ctx, n, records) : LUPIN_OK;
+}
+
+// *buf, a buffer the context keeps from call to call, holds at least `bytes`: kept when it is large enough, replaced otherwise
+// (the stream has finished with the old one: every call ends synchronised)
+static hipError_t grow_buffer(DeviceBuffer *buf, size_t *have, size_t bytes)
+{
+    if (*have >= bytes) return hipSuccess;
+    DeviceBuffer b;
+    const hipError_t e = DeviceBuffer::make(bytes, &b);
+    if (e == hipSuccess) { *buf = std::move(b); *have = bytes; }
+    return e;
+}
+
+// The path queries (radiance queries, probe bakes: DESIGN.md 13, 15).
 // Path state is 312 bytes per slot (ensure_path_buffers: two 128-byte records, 16 + 16 of medium, 4 + 4 of queues, 8 of
 // re-trace tokens, 4 + 4 of sort key and shade order): the default chunk of 4 Mi paths holds 1.3 GB of it.
 static constexpr uint64_t LP_RAYS_DEFAULT_SLOTS = LUPIN_RAYS_DEFAULT_MAX_SLOTS;
@@ -2574,237 +2673,175 @@ static Shape query_chunk_shape(LupinContext *ctx, const LupinScene *scene, uint3
     return sh;
 }
 
-int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const LupinRayQueryDesc *desc, uint64_t n, const float *records,
-                             float *out, float *out_rays)
+// lupin_hip_pathtrace_rays and lupin_hip_bake_probes are twins: records (rays | probes) of format Rule expand into `samples`
+// paths each, chunks of them run the wavefront, a resolve kernel folds a record's paths into `result_floats` floats.  What
+// differs is the descriptor's type, here flattened, and the two launches of a chunk, handed in.
+struct PathQuery
 {
-    const char *who = "lupin_hip_pathtrace_rays";
-    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    CTX_ALIVE_TRY(ctx);
-    if (!ctx || !scene || !desc || !records || !out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
-    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
-    if (desc->pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
-    if (desc->flags & ~(uint32_t)LUPIN_RAYS_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
-    if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
-    if (desc->max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
-    const uint64_t S = desc->samples;
+    const char *who;
+    uint32_t pathtrace_type, flags, samples, max_bounces, max_slots;   // flags: bit 0 = device pointers, for both
+    const LupinAdvancedParams *advanced;
+    uint32_t result_floats;
+};
+struct PathChunk   // all that `launch` sees of the query and of one chunk: device pointers whichever side the caller's arrays are on
+{
+    Lane *ln;
+    Shape sh;
+    uint32_t pathtrace_type, samples, slots, records, iterations;
+    const float4 *d_records;
+    float4 *d_rays, *d_out;   // d_rays: the chunk's first slot, or nullptr
+};
+template <typename Rule, typename Launch>
+static int path_query(LupinContext *ctx, const LupinScene *scene, const PathQuery &q, uint64_t n, const float *records, float *out, float *out_rays,
+                      Launch launch)
+{
+    if (q.pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
+    static_assert(LUPIN_RAYS_DEVICE_POINTERS == LUPIN_PROBES_DEVICE_POINTERS, "one flag word for both twins");
+    if (q.flags & ~(uint32_t)LUPIN_RAYS_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (q.samples == 0 || q.samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
+    if (q.max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
+    const uint64_t S = q.samples;
     if (n > LP_RAYS_MAX_PATHS / S) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n * samples must not exceed 2^38");
-    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
-    if (scene->wide_stale && ctx->wide_traversal) return fail(LUPIN_ERR_INVALID_ARGUMENT, kWideStale);
-    const bool on_device = (desc->flags & LUPIN_RAYS_DEVICE_POINTERS) != 0;
+    if (int rc = query_refuse_hierarchy(ctx, scene, true)) return rc;
+    const bool on_device = (q.flags & LUPIN_RAYS_DEVICE_POINTERS) != 0;
     if (on_device && (((uintptr_t)records | (uintptr_t)out | (uintptr_t)out_rays) & 15u))
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "device pointers must be 16-byte aligned");
     if (n == 0) return LUPIN_OK;
-    // the calls recorded so far run first, whatever becomes of this one from here on
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = flush_pending(ctx)) return rc;
-    if (!on_device)
-        for (uint64_t i = 0; i < n; i++)
-        {
-            const float *r = records + i * LUPIN_RAY_RECORD_FLOATS;
-            uint32_t mode;
-            memcpy(&mode, &r[7], 4);
-            if (!ray_record_ok(r[0], r[1], r[2], r[4], r[5], r[6], mode))
-                return fail(LUPIN_ERR_INVALID_ARGUMENT, "record " + std::to_string(i) + ": non-finite component, direction or normal not of unit length, or unknown mode");
-        }
     TraversalLds t;
-    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
-    join_primary(ctx);   // the primary stream waits for the latest of the recorded calls
+    if (int rc = query_start<Rule>(ctx, scene, on_device, n, records, &t)) return rc;
     Lane *ln = &ctx->lanes[0];   // one lane for every chunk: its stream is the primary stream
     hipStream_t st = ln->stream;
 
-    if (on_device)
-    {
-        DeviceBuffer bad;
-        HIP_TRY(DeviceBuffer::make(sizeof(unsigned long long), &bad));
-        HIP_TRY(hipMemsetAsync(bad.get(), 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_rays_validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, records, (unsigned long long)n,
-                           bad.as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        unsigned long long count = 0;
-        HIP_TRY(hipMemcpyAsync(&count, bad.get(), sizeof(count), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (count)
-            return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " record(s): non-finite component, direction or normal not of unit length, or unknown mode");
-    }
-
-    const uint64_t max_slots = std::min(desc->max_slots ? (uint64_t)desc->max_slots : LP_RAYS_DEFAULT_SLOTS, LP_RAYS_MAX_CHUNK_SLOTS);
+    const uint64_t max_slots = std::min(q.max_slots ? (uint64_t)q.max_slots : LP_RAYS_DEFAULT_SLOTS, LP_RAYS_MAX_CHUNK_SLOTS);
     const uint64_t chunk_records = std::min(n, std::max<uint64_t>(1, max_slots / S));
-    const uint32_t iterations = desc->max_bounces + 1;
+    const uint32_t iterations = q.max_bounces + 1;
     int rc = ensure_path_buffers(ctx, ln, chunk_records * S, iterations);
     if (rc != LUPIN_OK) return rc;
     set_path_layout(ln, ctx->path_records < 0 ? (scene->dev.sort_shade != 0) : ctx->path_records != 0);
 
     // host arrays: one chunk's records, results and first rays at a time through device buffers that live for the call
+    // (the path state beside them is the large allocation, and these are released with the call as they always were)
     DeviceBuffer d_rec, d_out, d_rays;
     if (!on_device)
     {
-        HIP_TRY(DeviceBuffer::make((size_t)chunk_records * LUPIN_RAY_RECORD_FLOATS * 4, &d_rec));
-        HIP_TRY(DeviceBuffer::make((size_t)chunk_records * LUPIN_RAY_RESULT_FLOATS * 4, &d_out));
+        HIP_TRY(DeviceBuffer::make((size_t)chunk_records * Rule::FLOATS * 4, &d_rec));
+        HIP_TRY(DeviceBuffer::make((size_t)chunk_records * q.result_floats * 4, &d_out));
         if (out_rays) HIP_TRY(DeviceBuffer::make((size_t)(chunk_records * S) * LUPIN_RAY_RECORD_FLOATS * 4, &d_rays));
     }
 
-    FrameParams fp = query_frame_params(scene, desc->pathtrace_type, desc->max_bounces, desc->advanced);
+    FrameParams fp = query_frame_params(scene, q.pathtrace_type, q.max_bounces, *q.advanced);
 
     for (uint64_t first = 0; first < n; first += chunk_records)
     {
         const uint64_t recs = std::min(chunk_records, n - first);
         const uint32_t slots = (uint32_t)(recs * S);
-        const Shape sh = query_chunk_shape(ctx, scene, desc->pathtrace_type, t, slots, ln, &fp);
-
-        const float *src = records + first * LUPIN_RAY_RECORD_FLOATS;
-        float *dst = out + first * LUPIN_RAY_RESULT_FLOATS;
+        const float *src = records + first * Rule::FLOATS;
+        float *dst = out + first * q.result_floats;
         float *dst_rays = out_rays ? out_rays + first * S * LUPIN_RAY_RECORD_FLOATS : nullptr;
-        RayBegin rb{reinterpret_cast<const float4 *>(src), desc->samples, reinterpret_cast<float4 *>(dst_rays)};
-        float4 *resolve_to = reinterpret_cast<float4 *>(dst);
+        PathChunk c{ln, query_chunk_shape(ctx, scene, q.pathtrace_type, t, slots, ln, &fp), q.pathtrace_type, q.samples, slots, (uint32_t)recs, iterations,
+                    reinterpret_cast<const float4 *>(src), reinterpret_cast<float4 *>(dst_rays), reinterpret_cast<float4 *>(dst)};
         if (!on_device)
         {
-            HIP_TRY(hipMemcpyAsync(d_rec.get(), src, (size_t)recs * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
-            rb.records = d_rec.as<float4>();
-            rb.out_rays = out_rays ? d_rays.as<float4>() : nullptr;
-            resolve_to = d_out.as<float4>();
+            HIP_TRY(hipMemcpyAsync(d_rec.get(), src, (size_t)recs * Rule::FLOATS * 4, hipMemcpyHostToDevice, st));
+            c.d_records = d_rec.as<float4>();
+            c.d_rays = out_rays ? d_rays.as<float4>() : nullptr;
+            c.d_out = d_out.as<float4>();
         }
         hipLaunchKernelGGL(k_set_params, dim3(1), dim3(1), 0, st, fp, ln->d_fp);
-        HIP_TRY(enqueue_wavefront(ctx, ln, scene, desc->pathtrace_type, slots, sh, iterations, nullptr, &rb));
-        hipLaunchKernelGGL(k_resolve_rays, dim3((uint32_t)((recs + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, ln->pb, (uint32_t)recs, desc->samples, resolve_to);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch(c)) return rc;   // enqueue_wavefront from the chunk's first rays, then the resolve kernel
         if (!on_device)
         {
-            HIP_TRY(hipMemcpyAsync(dst, d_out.get(), (size_t)recs * LUPIN_RAY_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(dst, d_out.get(), (size_t)recs * q.result_floats * 4, hipMemcpyDeviceToHost, st));
             if (out_rays) HIP_TRY(hipMemcpyAsync(dst_rays, d_rays.get(), (size_t)slots * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
         }
     }
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return query_end(ctx, q.who);
+}
+
+// The segment queries (occlusion, transmittance: DESIGN.md 18, 21).
+static constexpr uint64_t LP_OCCLUSION_MAX_LAUNCH_SLOTS = 1ull << 30;    // slots of one launch: slot indices and the grid's threads fit 32 bits
+static constexpr uint64_t LP_OCCLUSION_MAX_STAGED_RECORDS = 1ull << 22;  // host arrays: records of one launch (128 MB of staging)
+static constexpr uint32_t LP_TRANSMITTANCE_MAX_SAMPLES = 1u << 20;
+static constexpr uint64_t LP_TRANSMITTANCE_MAX_PLANE_SLOTS = 1ull << 24;   // slots of one hemisphere launch: the plane stays within 64 MB
+
+// The chunk loop of the two segment queries: whole records per launch, at most `chunk_records` of them, and four bytes of
+// result per record; host arrays go through the context's staging.  launch(records, slots, d_records, d_out) enqueues one
+// chunk's kernels on the primary stream.
+template <typename Launch>
+static int segment_chunks(LupinContext *ctx, const char *who, bool on_device, uint64_t n, uint64_t S, uint64_t chunk_records, const float *records,
+                          void *out, Launch launch)
+{
+    hipStream_t st = ctx->stream;
+    for (uint64_t first = 0; first < n; first += chunk_records)
+    {
+        const uint64_t recs = std::min(chunk_records, n - first);
+        const float *src = records + first * LUPIN_OCCLUSION_RECORD_FLOATS;
+        void *dst = static_cast<uint32_t *>(out) + first;
+        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
+        void *d_out = dst;
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(ctx->occ_records.get(), src, (size_t)recs * LUPIN_OCCLUSION_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
+            d_rec = ctx->occ_records.as<float4>();
+            d_out = ctx->occ_counts.get();
+        }
+        if (int rc = launch((uint32_t)recs, (uint32_t)(recs * S), d_rec, d_out)) return rc;
+        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, (size_t)recs * 4, hipMemcpyDeviceToHost, st));
+    }
+    return query_end(ctx, who);
+}
+// ... and its chunk size: `max_slots` slots per launch, and host arrays within the staging, which this grows
+static int segment_chunk_records(LupinContext *ctx, bool on_device, uint64_t n, uint64_t S, uint64_t max_slots, uint64_t *chunk_records)
+{
+    *chunk_records = std::min(n, std::max<uint64_t>(1, max_slots / S));
+    if (on_device) return LUPIN_OK;
+    *chunk_records = std::min(*chunk_records, LP_OCCLUSION_MAX_STAGED_RECORDS);
+    HIP_TRY(grow_buffer(&ctx->occ_records, &ctx->occ_records_bytes, (size_t)*chunk_records * LUPIN_OCCLUSION_RECORD_FLOATS * 4));
+    HIP_TRY(grow_buffer(&ctx->occ_counts, &ctx->occ_counts_bytes, (size_t)*chunk_records * 4));
     return LUPIN_OK;
 }
 
-// ---- light-probe baking (no reference counterpart; kernels: lupin_probes.hpp) ----
+}   // extern "C++"
+
+// ---- radiance queries and light-probe baking (no reference counterpart; kernels: lupin_rays.hpp, lupin_probes.hpp) ----
+
+int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const LupinRayQueryDesc *desc, uint64_t n, const float *records,
+                             float *out, float *out_rays)
+{
+    if (int rc = query_refuse(ctx, scene, desc && records && out)) return rc;
+    const PathQuery q = {"lupin_hip_pathtrace_rays", desc->pathtrace_type, desc->flags, desc->samples, desc->max_bounces, desc->max_slots, &desc->advanced,
+                         LUPIN_RAY_RESULT_FLOATS};
+    return path_query<RayRecordRule>(ctx, scene, q, n, records, out, out_rays, [ctx, scene](const PathChunk &c) -> int {
+        const RayBegin rb{c.d_records, c.samples, c.d_rays};
+        HIP_TRY(enqueue_wavefront(ctx, c.ln, scene, c.pathtrace_type, c.slots, c.sh, c.iterations, nullptr, &rb));
+        hipLaunchKernelGGL(k_resolve_rays, dim3((c.records + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, c.ln->stream, c.ln->pb, c.records, c.samples, c.d_out);
+        HIP_TRY(hipGetLastError());
+        return LUPIN_OK;
+    });
+}
 
 int lupin_hip_bake_probes(LupinContext *ctx, const LupinScene *scene, const LupinProbeDesc *desc, uint64_t n, const float *probes, float *out_sh,
                           float *out_rays)
 {
-    const char *who = "lupin_hip_bake_probes";
-    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    CTX_ALIVE_TRY(ctx);
-    if (!ctx || !scene || !desc || !probes || !out_sh) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
-    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
-    if (desc->pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
-    if (desc->flags & ~(uint32_t)LUPIN_PROBES_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
-    if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
-    if (desc->max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
-    const uint64_t S = desc->samples;
-    if (n > LP_RAYS_MAX_PATHS / S) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n * samples must not exceed 2^38");
-    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
-    if (scene->wide_stale && ctx->wide_traversal) return fail(LUPIN_ERR_INVALID_ARGUMENT, kWideStale);
-    const bool on_device = (desc->flags & LUPIN_PROBES_DEVICE_POINTERS) != 0;
-    if (on_device && (((uintptr_t)probes | (uintptr_t)out_sh | (uintptr_t)out_rays) & 15u))
-        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device pointers must be 16-byte aligned");
-    if (n == 0) return LUPIN_OK;
-    // the calls recorded so far run first, whatever becomes of this one from here on
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = flush_pending(ctx)) return rc;
-    if (!on_device)
-        for (uint64_t i = 0; i < n; i++)
-        {
-            const float *p = probes + i * LUPIN_PROBE_FLOATS;
-            if (!probe_position_ok(p[0], p[1], p[2])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "probe " + std::to_string(i) + ": non-finite position");
-        }
-    TraversalLds t;
-    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
-    join_primary(ctx);   // the primary stream waits for the latest of the recorded calls
-    Lane *ln = &ctx->lanes[0];   // one lane for every chunk: its stream is the primary stream
-    hipStream_t st = ln->stream;
-
-    if (on_device)
-    {
-        DeviceBuffer bad;
-        HIP_TRY(DeviceBuffer::make(sizeof(unsigned long long), &bad));
-        HIP_TRY(hipMemsetAsync(bad.get(), 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_probes_validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st,
-                           reinterpret_cast<const float4 *>(probes), (unsigned long long)n, bad.as<unsigned long long>());
+    if (int rc = query_refuse(ctx, scene, desc && probes && out_sh)) return rc;
+    const PathQuery q = {"lupin_hip_bake_probes", desc->pathtrace_type, desc->flags, desc->samples, desc->max_bounces, desc->max_slots, &desc->advanced,
+                         LUPIN_PROBE_RESULT_FLOATS};
+    return path_query<ProbeRule>(ctx, scene, q, n, probes, out_sh, out_rays, [ctx, scene](const PathChunk &c) -> int {
+        const ProbeBegin pbg{c.d_records, c.samples, c.d_rays};
+        HIP_TRY(enqueue_wavefront(ctx, c.ln, scene, c.pathtrace_type, c.slots, c.sh, c.iterations, nullptr, nullptr, &pbg));
+        hipLaunchKernelGGL(k_resolve_probes, dim3((c.records + LP_PROBES_PER_BLOCK - 1) / LP_PROBES_PER_BLOCK), dim3(LP_BLOCK), 0, c.ln->stream, c.ln->pb,
+                           c.records, c.d_records, c.samples, c.d_out);
         HIP_TRY(hipGetLastError());
-        unsigned long long count = 0;
-        HIP_TRY(hipMemcpyAsync(&count, bad.get(), sizeof(count), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (count) return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " probe(s): non-finite position");
-    }
-
-    const uint64_t max_slots = std::min(desc->max_slots ? (uint64_t)desc->max_slots : LP_RAYS_DEFAULT_SLOTS, LP_RAYS_MAX_CHUNK_SLOTS);
-    const uint64_t chunk_probes = std::min(n, std::max<uint64_t>(1, max_slots / S));
-    const uint32_t iterations = desc->max_bounces + 1;
-    int rc = ensure_path_buffers(ctx, ln, chunk_probes * S, iterations);
-    if (rc != LUPIN_OK) return rc;
-    set_path_layout(ln, ctx->path_records < 0 ? (scene->dev.sort_shade != 0) : ctx->path_records != 0);
-
-    // host arrays: one chunk's probes, coefficients and first rays at a time through device buffers that live for the call
-    DeviceBuffer d_probes, d_out, d_rays;
-    if (!on_device)
-    {
-        HIP_TRY(DeviceBuffer::make((size_t)chunk_probes * LUPIN_PROBE_FLOATS * 4, &d_probes));
-        HIP_TRY(DeviceBuffer::make((size_t)chunk_probes * LUPIN_PROBE_RESULT_FLOATS * 4, &d_out));
-        if (out_rays) HIP_TRY(DeviceBuffer::make((size_t)(chunk_probes * S) * LUPIN_RAY_RECORD_FLOATS * 4, &d_rays));
-    }
-
-    FrameParams fp = query_frame_params(scene, desc->pathtrace_type, desc->max_bounces, desc->advanced);
-
-    for (uint64_t first = 0; first < n; first += chunk_probes)
-    {
-        const uint64_t count = std::min(chunk_probes, n - first);
-        const uint32_t slots = (uint32_t)(count * S);
-        const Shape sh = query_chunk_shape(ctx, scene, desc->pathtrace_type, t, slots, ln, &fp);
-
-        const float *src = probes + first * LUPIN_PROBE_FLOATS;
-        float *dst = out_sh + first * LUPIN_PROBE_RESULT_FLOATS;
-        float *dst_rays = out_rays ? out_rays + first * S * LUPIN_RAY_RECORD_FLOATS : nullptr;
-        ProbeBegin pbg{reinterpret_cast<const float4 *>(src), desc->samples, reinterpret_cast<float4 *>(dst_rays)};
-        float4 *resolve_to = reinterpret_cast<float4 *>(dst);
-        if (!on_device)
-        {
-            HIP_TRY(hipMemcpyAsync(d_probes.get(), src, (size_t)count * LUPIN_PROBE_FLOATS * 4, hipMemcpyHostToDevice, st));
-            pbg.probes = d_probes.as<float4>();
-            pbg.out_rays = out_rays ? d_rays.as<float4>() : nullptr;
-            resolve_to = d_out.as<float4>();
-        }
-        hipLaunchKernelGGL(k_set_params, dim3(1), dim3(1), 0, st, fp, ln->d_fp);
-        HIP_TRY(enqueue_wavefront(ctx, ln, scene, desc->pathtrace_type, slots, sh, iterations, nullptr, nullptr, &pbg));
-        hipLaunchKernelGGL(k_resolve_probes, dim3((uint32_t)((count + LP_PROBES_PER_BLOCK - 1) / LP_PROBES_PER_BLOCK)), dim3(LP_BLOCK), 0, st, ln->pb,
-                           (uint32_t)count, pbg.probes, desc->samples, resolve_to);
-        HIP_TRY(hipGetLastError());
-        if (!on_device)
-        {
-            HIP_TRY(hipMemcpyAsync(dst, d_out.get(), (size_t)count * LUPIN_PROBE_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
-            if (out_rays) HIP_TRY(hipMemcpyAsync(dst_rays, d_rays.get(), (size_t)slots * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
-        }
-    }
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return LUPIN_OK;
+        return LUPIN_OK;
+    });
 }
 
-// ---- occlusion queries (no reference counterpart; kernels: lupin_occlusion.hpp) ----
-
-static constexpr uint64_t LP_OCCLUSION_MAX_LAUNCH_SLOTS = 1ull << 30;    // slots of one launch: slot indices and the grid's threads fit 32 bits
-static constexpr uint64_t LP_OCCLUSION_MAX_STAGED_RECORDS = 1ull << 22;  // host arrays: records of one launch (128 MB of staging)
-
-// *buf holds at least `bytes`: kept when it is large enough, replaced otherwise (the stream has finished with the old one:
-// every call ends synchronised)
-static hipError_t occlusion_staging(DeviceBuffer *buf, size_t *have, size_t bytes)
-{
-    if (*have >= bytes) return hipSuccess;
-    DeviceBuffer b;
-    const hipError_t e = DeviceBuffer::make(bytes, &b);
-    if (e == hipSuccess) { *buf = std::move(b); *have = bytes; }
-    return e;
-}
+// ---- occlusion and transmittance queries (no reference counterpart; kernels: lupin_occlusion.hpp, lupin_transmittance.hpp) ----
 
 int lupin_hip_occlusion_rays(LupinContext *ctx, const LupinScene *scene, const LupinOcclusionDesc *desc, uint64_t n, const float *records,
                              uint32_t *out_blocked)
 {
-    const char *who = "lupin_hip_occlusion_rays";
-    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    CTX_ALIVE_TRY(ctx);
-    if (!ctx || !scene || !desc || !records || !out_blocked) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
-    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (int rc = query_refuse(ctx, scene, desc && records && out_blocked)) return rc;
     if (desc->mode > LUPIN_OCCLUSION_COSINE_HEMISPHERE) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown mode");
     if (desc->flags & ~(uint32_t)LUPIN_OCCLUSION_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
     if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
@@ -2812,89 +2849,32 @@ int lupin_hip_occlusion_rays(LupinContext *ctx, const LupinScene *scene, const L
     const uint64_t S = desc->samples;
     if (n > LP_RAYS_MAX_PATHS / S) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n * samples must not exceed 2^38");
     if (!(std::isfinite(desc->ray_epsilon) && desc->ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
-    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
-    // (a stale four-wide hierarchy is no obstacle: only the binary one is read)
+    if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
     const bool on_device = (desc->flags & LUPIN_OCCLUSION_DEVICE_POINTERS) != 0;
     if (on_device && (((uintptr_t)records & 15u) || ((uintptr_t)out_blocked & 3u)))
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "device records must be 16-byte aligned, device counts 4-byte aligned");
     if (n == 0) return LUPIN_OK;
-    // the calls recorded so far run first, whatever becomes of this one from here on
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = flush_pending(ctx)) return rc;
-    if (!on_device)
-        for (uint64_t i = 0; i < n; i++)
-        {
-            const float *r = records + i * LUPIN_OCCLUSION_RECORD_FLOATS;
-            if (!occlusion_record_ok(r[0], r[1], r[2], r[4], r[5], r[6], r[7]))
-                return fail(LUPIN_ERR_INVALID_ARGUMENT, "record " + std::to_string(i) + ": non-finite component, direction or normal not of unit length, or tmax NaN or not positive");
-        }
     TraversalLds t;
-    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
-    join_primary(ctx);   // the primary stream waits for the latest of the recorded calls
-    hipStream_t st = ctx->stream;
+    if (int rc = query_start<OcclusionRecordRule>(ctx, scene, on_device, n, records, &t)) return rc;
 
-    if (on_device)
-    {
-        size_t have = ctx->occ_bad.get() ? sizeof(unsigned long long) : 0;
-        HIP_TRY(occlusion_staging(&ctx->occ_bad, &have, sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(ctx->occ_bad.get(), 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_occlusion_validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, records, (unsigned long long)n,
-                           ctx->occ_bad.as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        unsigned long long count = 0;
-        HIP_TRY(hipMemcpyAsync(&count, ctx->occ_bad.get(), sizeof(count), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (count)
-            return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " record(s): non-finite component, direction or normal not of unit length, or tmax NaN or not positive");
-    }
-
-    uint64_t chunk_records = std::min(n, std::max<uint64_t>(1, LP_OCCLUSION_MAX_LAUNCH_SLOTS / S));
-    if (!on_device)
-    {
-        chunk_records = std::min(chunk_records, LP_OCCLUSION_MAX_STAGED_RECORDS);
-        HIP_TRY(occlusion_staging(&ctx->occ_records, &ctx->occ_records_bytes, (size_t)chunk_records * LUPIN_OCCLUSION_RECORD_FLOATS * 4));
-        HIP_TRY(occlusion_staging(&ctx->occ_counts, &ctx->occ_counts_bytes, (size_t)chunk_records * 4));
-    }
-    for (uint64_t first = 0; first < n; first += chunk_records)
-    {
-        const uint64_t recs = std::min(chunk_records, n - first);
-        const uint32_t slots = (uint32_t)(recs * S);
-        const float *src = records + first * LUPIN_OCCLUSION_RECORD_FLOATS;
-        uint32_t *dst = out_blocked + first;
-        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
-        uint32_t *d_cnt = dst;
-        if (!on_device)
-        {
-            HIP_TRY(hipMemcpyAsync(ctx->occ_records.get(), src, (size_t)recs * LUPIN_OCCLUSION_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
-            d_rec = ctx->occ_records.as<float4>();
-            d_cnt = ctx->occ_counts.as<uint32_t>();
-        }
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)recs * 4, st));
+    uint64_t chunk_records;
+    if (int rc = segment_chunk_records(ctx, on_device, n, S, LP_OCCLUSION_MAX_LAUNCH_SLOTS, &chunk_records)) return rc;
+    return segment_chunks(ctx, "lupin_hip_occlusion_rays", on_device, n, S, chunk_records, records, out_blocked,
+                          [&](uint32_t recs, uint32_t slots, const float4 *d_rec, void *d_out) -> int {
+        HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)recs * 4, ctx->stream));
         with_bool(t.geo, [&](auto G) {
-            hipLaunchKernelGGL(k_occlusion<decltype(G)::value>, dim3((slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, st, scene->dev, slots, d_rec,
-                               desc->samples, desc->mode, desc->ray_epsilon, d_cnt, t.stack_words);
+            hipLaunchKernelGGL(k_occlusion<decltype(G)::value>, dim3((slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev, slots,
+                               d_rec, desc->samples, desc->mode, desc->ray_epsilon, static_cast<uint32_t *>(d_out), t.stack_words);
         });
         HIP_TRY(hipGetLastError());
-        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_cnt, (size_t)recs * 4, hipMemcpyDeviceToHost, st));
-    }
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return LUPIN_OK;
+        return LUPIN_OK;
+    });
 }
-
-// ---- transmittance queries (no reference counterpart; kernels: lupin_transmittance.hpp) ----
-
-static constexpr uint32_t LP_TRANSMITTANCE_MAX_SAMPLES = 1u << 20;
-static constexpr uint64_t LP_TRANSMITTANCE_MAX_PLANE_SLOTS = 1ull << 24;   // slots of one hemisphere launch: the plane stays within 64 MB
 
 int lupin_hip_transmittance_rays(LupinContext *ctx, const LupinScene *scene, const LupinOcclusionDesc *desc, uint64_t n, const float *records,
                                  float *out_sum)
 {
-    const char *who = "lupin_hip_transmittance_rays";
-    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    CTX_ALIVE_TRY(ctx);
-    if (!ctx || !scene || !desc || !records || !out_sum) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
-    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (int rc = query_refuse(ctx, scene, desc && records && out_sum)) return rc;
     if (desc->mode > LUPIN_OCCLUSION_COSINE_HEMISPHERE) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown mode");
     if (desc->flags & ~(uint32_t)LUPIN_OCCLUSION_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
     if (desc->samples == 0 || desc->samples > LP_TRANSMITTANCE_MAX_SAMPLES) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^20]");
@@ -2902,84 +2882,35 @@ int lupin_hip_transmittance_rays(LupinContext *ctx, const LupinScene *scene, con
     const uint64_t S = desc->samples;
     if (n > LP_RAYS_MAX_PATHS / S) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n * samples must not exceed 2^38");
     if (!(std::isfinite(desc->ray_epsilon) && desc->ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
-    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
-    // (a stale four-wide hierarchy is no obstacle: only the binary one is read)
+    if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
     const bool on_device = (desc->flags & LUPIN_OCCLUSION_DEVICE_POINTERS) != 0;
     if (on_device && (((uintptr_t)records & 15u) || ((uintptr_t)out_sum & 3u)))
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "device records must be 16-byte aligned, device results 4-byte aligned");
     if (n == 0) return LUPIN_OK;
-    // the calls recorded so far run first, whatever becomes of this one from here on
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = flush_pending(ctx)) return rc;
-    if (!on_device)
-        for (uint64_t i = 0; i < n; i++)
-        {
-            const float *r = records + i * LUPIN_OCCLUSION_RECORD_FLOATS;
-            if (!occlusion_record_ok(r[0], r[1], r[2], r[4], r[5], r[6], r[7]))
-                return fail(LUPIN_ERR_INVALID_ARGUMENT, "record " + std::to_string(i) + ": non-finite component, direction or normal not of unit length, or tmax NaN or not positive");
-        }
     TraversalLds t;
-    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
-    join_primary(ctx);   // the primary stream waits for the latest of the recorded calls
-    hipStream_t st = ctx->stream;
+    if (int rc = query_start<OcclusionRecordRule>(ctx, scene, on_device, n, records, &t)) return rc;
 
-    if (on_device)
-    {
-        size_t have = ctx->occ_bad.get() ? sizeof(unsigned long long) : 0;
-        HIP_TRY(occlusion_staging(&ctx->occ_bad, &have, sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(ctx->occ_bad.get(), 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_transmittance_validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, records, (unsigned long long)n,
-                           ctx->occ_bad.as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        unsigned long long count = 0;
-        HIP_TRY(hipMemcpyAsync(&count, ctx->occ_bad.get(), sizeof(count), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (count)
-            return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " record(s): non-finite component, direction or normal not of unit length, or tmax NaN or not positive");
-    }
-
-    // whole records per launch; with more than one slot per record the slots go through the plane, which bounds the chunk
+    // with more than one slot per record the slots go through the plane, which bounds the chunk
     const bool planed = S > 1;
-    const uint64_t max_slots = planed ? LP_TRANSMITTANCE_MAX_PLANE_SLOTS : LP_OCCLUSION_MAX_LAUNCH_SLOTS;
-    uint64_t chunk_records = std::min(n, std::max<uint64_t>(1, max_slots / S));
-    if (!on_device)
-    {
-        chunk_records = std::min(chunk_records, LP_OCCLUSION_MAX_STAGED_RECORDS);
-        HIP_TRY(occlusion_staging(&ctx->occ_records, &ctx->occ_records_bytes, (size_t)chunk_records * LUPIN_OCCLUSION_RECORD_FLOATS * 4));
-        HIP_TRY(occlusion_staging(&ctx->occ_counts, &ctx->occ_counts_bytes, (size_t)chunk_records * 4));
-    }
-    if (planed) HIP_TRY(occlusion_staging(&ctx->trans_plane, &ctx->trans_plane_bytes, (size_t)(chunk_records * S) * 4));
-    for (uint64_t first = 0; first < n; first += chunk_records)
-    {
-        const uint64_t recs = std::min(chunk_records, n - first);
-        const uint32_t slots = (uint32_t)(recs * S);
-        const float *src = records + first * LUPIN_OCCLUSION_RECORD_FLOATS;
-        float *dst = out_sum + first;
-        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
-        float *d_sum = dst;
-        if (!on_device)
-        {
-            HIP_TRY(hipMemcpyAsync(ctx->occ_records.get(), src, (size_t)recs * LUPIN_OCCLUSION_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
-            d_rec = ctx->occ_records.as<float4>();
-            d_sum = ctx->occ_counts.as<float>();
-        }
-        float *d_slots = planed ? ctx->trans_plane.as<float>() : d_sum;
+    uint64_t chunk_records;
+    if (int rc = segment_chunk_records(ctx, on_device, n, S, planed ? LP_TRANSMITTANCE_MAX_PLANE_SLOTS : LP_OCCLUSION_MAX_LAUNCH_SLOTS, &chunk_records)) return rc;
+    if (planed) HIP_TRY(grow_buffer(&ctx->trans_plane, &ctx->trans_plane_bytes, (size_t)(chunk_records * S) * 4));
+    return segment_chunks(ctx, "lupin_hip_transmittance_rays", on_device, n, S, chunk_records, records, out_sum,
+                          [&](uint32_t recs, uint32_t slots, const float4 *d_rec, void *d_out) -> int {
+        float *d_sum = static_cast<float *>(d_out), *d_slots = planed ? ctx->trans_plane.as<float>() : d_sum;
         with_bool(t.geo, [&](auto G) {
-            hipLaunchKernelGGL(k_transmittance<decltype(G)::value>, dim3((slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, st, scene->dev, slots, d_rec,
-                               desc->samples, desc->mode, desc->ray_epsilon, d_slots, t.stack_words);
+            hipLaunchKernelGGL(k_transmittance<decltype(G)::value>, dim3((slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev,
+                               slots, d_rec, desc->samples, desc->mode, desc->ray_epsilon, d_slots, t.stack_words);
         });
         HIP_TRY(hipGetLastError());
         if (planed)
         {
-            hipLaunchKernelGGL(k_transmittance_resolve, dim3((uint32_t)((recs + LP_TRANSMITTANCE_RECORDS_PER_BLOCK - 1) / LP_TRANSMITTANCE_RECORDS_PER_BLOCK)),
-                               dim3(LP_BLOCK), 0, st, d_slots, (uint32_t)recs, desc->samples, d_sum);
+            hipLaunchKernelGGL(k_transmittance_resolve, dim3((recs + LP_TRANSMITTANCE_RECORDS_PER_BLOCK - 1) / LP_TRANSMITTANCE_RECORDS_PER_BLOCK), dim3(LP_BLOCK), 0,
+                               ctx->stream, d_slots, recs, desc->samples, d_sum);
             HIP_TRY(hipGetLastError());
         }
-        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_sum, (size_t)recs * 4, hipMemcpyDeviceToHost, st));
-    }
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return LUPIN_OK;
+        return LUPIN_OK;
+    });
 }
 
 // ---- distance queries (no reference counterpart; kernels: lupin_distance.hpp) ----
@@ -3020,14 +2951,12 @@ static float distance_scale(const InstanceDev &in)
     return std::isfinite(f) ? f : 0.0f;
 }
 
-// What both entry points share once their own arguments are accepted: the recorded calls run, the auxiliary array is built
-// from the scene's current rows and copied, the stack is sized for (reference, key) pairs.
+// What both entry points share once their own arguments are accepted: the query's start with a stack sized for (reference,
+// key) pairs, then the auxiliary array is built from the scene's current rows and copied.
 static int distance_begin(LupinContext *ctx, const LupinScene *scene, TraversalLds *t)
 {
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = flush_pending(ctx)) return rc;
-    if (int rc = traversal_lds(ctx, scene, 2u * scene->stack_entries, true, t)) return rc;
-    join_primary(ctx);   // the primary stream waits for the latest of the recorded calls
+    if (int rc = query_flush(ctx)) return rc;
+    if (int rc = query_plan(ctx, scene, 2u * scene->stack_entries, t)) return rc;
     const uint32_t ninst = scene->dev.num_instances;
     std::vector<float4> aux((size_t)std::max(1u, ninst) * LP_DISTANCE_AUX_WORDS, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     for (uint32_t i = 0; i < ninst; i++)
@@ -3047,56 +2976,36 @@ static int distance_begin(LupinContext *ctx, const LupinScene *scene, TraversalL
     }
     // every call ends synchronised, so the buffer of the call before is free; the copy is from pageable memory and has left
     // the vector when hipMemcpyAsync returns
-    HIP_TRY(occlusion_staging(&ctx->dist_aux, &ctx->dist_aux_bytes, aux.size() * sizeof(float4)));
+    HIP_TRY(grow_buffer(&ctx->dist_aux, &ctx->dist_aux_bytes, aux.size() * sizeof(float4)));
     HIP_TRY(hipMemcpyAsync(ctx->dist_aux.get(), aux.data(), aux.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
     return LUPIN_OK;
 }
 
 int lupin_hip_distance_points(LupinContext *ctx, const LupinScene *scene, uint32_t flags, uint64_t n, const float *records, float *out_results)
 {
-    const char *who = "lupin_hip_distance_points";
-    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    CTX_ALIVE_TRY(ctx);
-    if (!ctx || !scene || !records || !out_results) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
-    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (int rc = query_refuse(ctx, scene, records && out_results)) return rc;
     if (flags & ~(uint32_t)LUPIN_DISTANCE_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
     if (n > LP_RAYS_MAX_PATHS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n must not exceed 2^38");
-    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
     const bool on_device = (flags & LUPIN_DISTANCE_DEVICE_POINTERS) != 0;
     if (on_device && (((uintptr_t)records & 15u) || ((uintptr_t)out_results & 15u)))
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "device records and results must be 16-byte aligned");
     if (n == 0) return LUPIN_OK;
+    // (host records are looked at before the recorded calls run: query_start's pieces, in this entry point's own order)
     if (!on_device)
-        for (uint64_t i = 0; i < n; i++)
-        {
-            const float *r = records + i * LUPIN_DISTANCE_RECORD_FLOATS;
-            if (!distance_record_ok(r[0], r[1], r[2], r[3]))
-                return fail(LUPIN_ERR_INVALID_ARGUMENT, "record " + std::to_string(i) + ": non-finite point, or rmax NaN or not positive");
-        }
+        if (int rc = refuse_bad_host_records<DistanceRecordRule>(n, records)) return rc;
     TraversalLds t;
     if (int rc = distance_begin(ctx, scene, &t)) return rc;
-    hipStream_t st = ctx->stream;
-
     if (on_device)
-    {
-        size_t have = ctx->dist_bad.get() ? sizeof(unsigned long long) : 0;
-        HIP_TRY(occlusion_staging(&ctx->dist_bad, &have, sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(ctx->dist_bad.get(), 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_distance_validate, dim3((uint32_t)((n + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, reinterpret_cast<const float4 *>(records),
-                           (unsigned long long)n, ctx->dist_bad.as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        unsigned long long count = 0;
-        HIP_TRY(hipMemcpyAsync(&count, ctx->dist_bad.get(), sizeof(count), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (count) return fail(LUPIN_ERR_INVALID_ARGUMENT, std::to_string(count) + " record(s): non-finite point, or rmax NaN or not positive");
-    }
+        if (int rc = refuse_bad_device_records<DistanceRecordRule>(ctx, n, records)) return rc;
+    hipStream_t st = ctx->stream;
 
     uint64_t chunk = std::min(n, LP_DISTANCE_MAX_LAUNCH);
     if (!on_device)
     {
         chunk = std::min(chunk, LP_DISTANCE_MAX_STAGED_RECORDS);
-        HIP_TRY(occlusion_staging(&ctx->dist_records, &ctx->dist_records_bytes, (size_t)chunk * LUPIN_DISTANCE_RECORD_FLOATS * 4));
-        HIP_TRY(occlusion_staging(&ctx->dist_results, &ctx->dist_results_bytes, (size_t)chunk * LUPIN_DISTANCE_RESULT_FLOATS * 4));
+        HIP_TRY(grow_buffer(&ctx->dist_records, &ctx->dist_records_bytes, (size_t)chunk * LUPIN_DISTANCE_RECORD_FLOATS * 4));
+        HIP_TRY(grow_buffer(&ctx->dist_results, &ctx->dist_results_bytes, (size_t)chunk * LUPIN_DISTANCE_RESULT_FLOATS * 4));
     }
     for (uint64_t first = 0; first < n; first += chunk)
     {
@@ -3118,19 +3027,13 @@ int lupin_hip_distance_points(LupinContext *ctx, const LupinScene *scene, uint32
         HIP_TRY(hipGetLastError());
         if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_res, (size_t)recs * LUPIN_DISTANCE_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
     }
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return LUPIN_OK;
+    return query_end(ctx, "lupin_hip_distance_points");
 }
 
 int lupin_hip_bake_distance_grid(LupinContext *ctx, const LupinScene *scene, uint32_t flags, const float *origin, const float *spacing,
                                  const uint32_t *dims, float rmax, float *out_volume)
 {
-    const char *who = "lupin_hip_bake_distance_grid";
-    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    CTX_ALIVE_TRY(ctx);
-    if (!ctx || !scene || !origin || !spacing || !dims || !out_volume) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
-    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (int rc = query_refuse(ctx, scene, origin && spacing && dims && out_volume)) return rc;
     if (flags & ~(uint32_t)(LUPIN_DISTANCE_DEVICE_POINTERS | LUPIN_DISTANCE_GRID_SIGNED)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
     for (int k = 0; k < 3; k++)
     {
@@ -3144,7 +3047,7 @@ int lupin_hip_bake_distance_grid(LupinContext *ctx, const LupinScene *scene, uin
     const uint64_t slice = (uint64_t)dims[0] * dims[1];   // below 2^64: both factors are below 2^32
     if (slice > LP_DISTANCE_MAX_VOXELS || dims[2] > LP_DISTANCE_MAX_VOXELS / slice)
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid must not exceed 2^36 voxels");
-    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
+    if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
     const bool on_device = (flags & LUPIN_DISTANCE_DEVICE_POINTERS) != 0;
     if (on_device && ((uintptr_t)out_volume & 3u)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "a device volume must be 4-byte aligned");
     const uint64_t n = (uint64_t)dims[0] * dims[1] * dims[2];
@@ -3161,7 +3064,7 @@ int lupin_hip_bake_distance_grid(LupinContext *ctx, const LupinScene *scene, uin
     if (!on_device)
     {
         chunk = std::min(chunk, LP_DISTANCE_MAX_STAGED_VOXELS);
-        HIP_TRY(occlusion_staging(&ctx->dist_results, &ctx->dist_results_bytes, (size_t)chunk * 4));
+        HIP_TRY(grow_buffer(&ctx->dist_results, &ctx->dist_results_bytes, (size_t)chunk * 4));
     }
     for (uint64_t first = 0; first < n; first += chunk)
     {
@@ -3175,9 +3078,7 @@ int lupin_hip_bake_distance_grid(LupinContext *ctx, const LupinScene *scene, uin
         HIP_TRY(hipGetLastError());
         if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, (size_t)voxels * 4, hipMemcpyDeviceToHost, st));
     }
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return LUPIN_OK;
+    return query_end(ctx, "lupin_hip_bake_distance_grid");
 }
 
 // ---- lightmap baking (no reference counterpart; kernels: lupin_lightmap.hpp) ----
@@ -3189,10 +3090,7 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
                             uint32_t num_charts, float *out_rgba, float *out_records, uint64_t *out_num_covered)
 {
     const char *who = "lupin_hip_bake_lightmap";
-    if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    CTX_ALIVE_TRY(ctx);
-    if (!ctx || !scene || !desc || !charts || !out_rgba) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
-    if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
+    if (int rc = query_refuse(ctx, scene, desc && charts && out_rgba)) return rc;
     const uint32_t W = desc->width, H = desc->height;
     if (W == 0 || H == 0 || W > LUPIN_LIGHTMAP_MAX_SIZE || H > LUPIN_LIGHTMAP_MAX_SIZE)
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "width and height must be in [1, 16384]");
@@ -3205,8 +3103,7 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
     if (desc->pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
     if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
     if (desc->max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
-    if (!scene->has_sw_bvh) return fail(LUPIN_ERR_NO_SW_BVH, "no software BVH was built for this scene");
-    if (scene->wide_stale && ctx->wide_traversal) return fail(LUPIN_ERR_INVALID_ARGUMENT, kWideStale);
+    if (int rc = query_refuse_hierarchy(ctx, scene, true)) return rc;
     std::vector<LmChartDev> h_charts(num_charts);
     uint64_t total_keys = 0;
     for (uint32_t c = 0; c < num_charts; c++)
@@ -3221,9 +3118,7 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
         total_keys += scene->mesh_tri_count[mesh];
         if (total_keys >= 0xFFFFFFFFull) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the charts hold 2^32 - 1 or more triangles");
     }
-    // the calls recorded so far run first, whatever becomes of this one from here on
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = flush_pending(ctx)) return rc;
+    if (int rc = query_flush(ctx)) return rc;
     join_primary(ctx);
     hipStream_t st = ctx->lanes[0].stream;   // the primary stream, the query's own
     using clk = std::chrono::steady_clock;

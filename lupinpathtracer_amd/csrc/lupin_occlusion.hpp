@@ -9,8 +9,8 @@
 // whose slab distance is below the CONSTANT tmax: the bound never shrinks, so the visited set depends on tmax alone.
 // Material opacity is not consulted: this is geometric visibility.
 //
-//   k_occlusion_validate   device records only: counts the records the host check would refuse (the host reads the count
-//                          before the first launch)
+//   k_validate_records<OcclusionRecordRule>   device records only: counts the records the host check would refuse (the
+//                          host reads the count before the first launch)
 //   k_occlusion<LDSGEO>    one lane per slot: direction (as given, or cosine-weighted about the normal exactly as a mode-1
 //                          radiance query derives it), scene_any_hit, then the lanes of a wave that share a record are
 //                          combined by ballot / popcount and their first lane adds the count with one atomicAdd
@@ -25,25 +25,24 @@ constexpr uint32_t LP_OCCLUSION_DIRECTION = 0u, LP_OCCLUSION_COSINE_HEMISPHERE =
 
 // What lupin_hip_occlusion_rays refuses in a record: what a mode-0 radiance query refuses (a non-finite origin, direction or
 // normal, a squared length further than LP_RAY_UNIT_TOLERANCE from 1), and a tmax that is NaN or <= 0 (+inf is "unbounded").
-// The host check and k_occlusion_validate share this function.
+// The host check and OcclusionRecordRule share this function.
 __host__ __device__ inline bool occlusion_record_ok(float ox, float oy, float oz, float dx, float dy, float dz, float tmax)
 {
     return ray_record_ok(ox, oy, oz, dx, dy, dz, LP_RAY_DIRECTION) && tmax > 0.0f;   // (NaN > 0 is false)
 }
 
-// one thread per record, one atomic per wave that found something
-__global__ void __launch_bounds__(LP_BLOCK) k_occlusion_validate(const float *__restrict__ records, unsigned long long n, unsigned long long *bad_count)
+// the record format (lupin_rays.hpp says what a Rule is); transmittance queries share it
+struct OcclusionRecordRule
 {
-    const unsigned long long i = (unsigned long long)blockIdx.x * LP_BLOCK + threadIdx.x;
-    bool bad = false;
-    if (i < n)
+    static constexpr uint32_t FLOATS = LUPIN_OCCLUSION_RECORD_FLOATS;
+    static constexpr const char *NOUN = "record", *WHY = "non-finite component, direction or normal not of unit length, or tmax NaN or not positive";
+    static bool host_ok(const float *r) { return occlusion_record_ok(r[0], r[1], r[2], r[4], r[5], r[6], r[7]); }
+    static __device__ bool ok(const float4 *__restrict__ records, unsigned long long i)
     {
-        const float4 a = reinterpret_cast<const float4 *>(records)[2 * i], b = reinterpret_cast<const float4 *>(records)[2 * i + 1];
-        bad = !occlusion_record_ok(a.x, a.y, a.z, b.x, b.y, b.z, b.w);
+        const float4 a = records[2 * i], b = records[2 * i + 1];
+        return occlusion_record_ok(a.x, a.y, a.z, b.x, b.y, b.z, b.w);
     }
-    const unsigned long long mask = __ballot(bad);
-    if (mask && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)mask) - 1)) atomicAdd(bad_count, (unsigned long long)__popcll(mask));
-}
+};
 
 // scene_closest's single convergent two-level loop (lupin_device.hpp), with the same per-lane LDS stack, near / far choice
 // (ld <= rd), instance entry arithmetic (the direction is not re-normalised: t stays in world units), slab_dst and tri_dst.

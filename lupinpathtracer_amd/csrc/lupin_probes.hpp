@@ -4,8 +4,8 @@
 // radiance onto the nine real spherical harmonics of bands 0..2.  Probe i expands into `samples` paths, slot = i * samples + s,
 // seeded as a radiance query seeds them.  One chunk of probes runs
 //
-//   k_probes_validate    device positions only: counts the probes the host check would refuse (the host reads the count
-//                        before the first wavefront)
+//   k_validate_records<ProbeRule>   device positions only: counts the probes the host check would refuse (the host reads
+//                        the count before the first wavefront)
 //   k_begin_probes       k_begin_rays for probes: seeding, the sphere sampler, every plane k_begin_rays initialises, the queue
 //                        append per shard; optionally the first ray of every slot as a mode-0 record (out_rays)
 //   (the ordinary iterations, unchanged)
@@ -53,19 +53,17 @@ __host__ __device__ inline bool probe_position_ok(float x, float y, float z)
     return ray_component_finite(x) && ray_component_finite(y) && ray_component_finite(z);
 }
 
-// one thread per probe, one atomic per wave that found something
-__global__ void __launch_bounds__(LP_BLOCK) k_probes_validate(const float4 *__restrict__ probes, unsigned long long n, unsigned long long *bad_count)
+struct ProbeRule   // the probe as a record format (lupin_rays.hpp says what a Rule is)
 {
-    const unsigned long long i = (unsigned long long)blockIdx.x * LP_BLOCK + threadIdx.x;
-    bool bad = false;
-    if (i < n)
+    static constexpr uint32_t FLOATS = LUPIN_PROBE_FLOATS;
+    static constexpr const char *NOUN = "probe", *WHY = "non-finite position";
+    static bool host_ok(const float *p) { return probe_position_ok(p[0], p[1], p[2]); }
+    static __device__ bool ok(const float4 *__restrict__ probes, unsigned long long i)
     {
         const float4 p = probes[i];
-        bad = !probe_position_ok(p.x, p.y, p.z);
+        return probe_position_ok(p.x, p.y, p.z);
     }
-    const unsigned long long mask = __ballot(bad);
-    if (mask && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)mask) - 1)) atomicAdd(bad_count, (unsigned long long)__popcll(mask));
-}
+};
 
 // `probes` and `out_rays` point at the chunk's first probe / first slot; n = the chunk's slots (probes * samples)
 __global__ void __launch_bounds__(LP_BLOCK) k_begin_probes(PathBuffers pb, uint32_t n, const float4 *__restrict__ probes, uint32_t samples,

@@ -4,8 +4,8 @@
 // A record is the ori_rng / dir_meta pair of a path (origin | RNG state, direction or normal | mode); record i expands
 // into `samples` paths, slot = i * samples + s.  One chunk of records runs
 //
-//   k_rays_validate      device records only: counts the records the host check would refuse (the host reads the count
-//                        before the first wavefront)
+//   k_validate_records<RayRecordRule>   device records only: counts the records the host check would refuse (the host
+//                        reads the count before the first wavefront)
 //   k_begin_rays         k_begin for records: seeding, hemisphere sampling, every plane begin_paths initialises, the queue
 //                        append per shard; optionally the first ray of every slot as a mode-0 record (out_rays)
 //   (the ordinary iterations, unchanged: the stage kernels only ever see slots; with fp.spp == 1 path_epilogue never
@@ -23,7 +23,7 @@ constexpr float LP_RAY_UNIT_TOLERANCE = 1e-4f;                              // |
 
 // What lupin_hip_pathtrace_rays refuses in a record: a non-finite origin or direction / normal, a squared length further
 // than LP_RAY_UNIT_TOLERANCE from 1, an unknown mode.  (The RNG word is bits: any pattern is a state.)  The host check
-// and k_rays_validate share this function.
+// and RayRecordRule share this function.
 __host__ __device__ inline bool ray_component_finite(float v)
 {
     uint32_t u;
@@ -40,19 +40,36 @@ __host__ __device__ inline bool ray_record_ok(float ox, float oy, float oz, floa
     return off <= LP_RAY_UNIT_TOLERANCE && off >= -LP_RAY_UNIT_TOLERANCE;   // (an overflowed length is +inf: refused)
 }
 
-// one thread per record, one atomic per wave that found something
-__global__ void __launch_bounds__(LP_BLOCK) k_rays_validate(const float *__restrict__ records, unsigned long long n, unsigned long long *bad_count)
+// A Rule is one record format of a scene query (RayRecordRule here; ProbeRule, OcclusionRecordRule and DistanceRecordRule
+// beside their formats): its size, how a refusal names it, the host's look at one record (host_ok) and the same look on
+// the device (ok).  Device records of every query are checked by this one kernel: one thread per record; a wave that found
+// something adds its count with one atomic.
+template <typename Rule>
+__global__ void __launch_bounds__(LP_BLOCK) k_validate_records(const float4 *__restrict__ records, unsigned long long n, unsigned long long *bad_count)
 {
     const unsigned long long i = (unsigned long long)blockIdx.x * LP_BLOCK + threadIdx.x;
     bool bad = false;
-    if (i < n)
-    {
-        const float4 a = reinterpret_cast<const float4 *>(records)[2 * i], b = reinterpret_cast<const float4 *>(records)[2 * i + 1];
-        bad = !ray_record_ok(a.x, a.y, a.z, b.x, b.y, b.z, __float_as_uint(b.w));
-    }
+    if (i < n) bad = !Rule::ok(records, i);
     const unsigned long long mask = __ballot(bad);
     if (mask && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)mask) - 1)) atomicAdd(bad_count, (unsigned long long)__popcll(mask));
 }
+
+struct RayRecordRule
+{
+    static constexpr uint32_t FLOATS = LUPIN_RAY_RECORD_FLOATS;
+    static constexpr const char *NOUN = "record", *WHY = "non-finite component, direction or normal not of unit length, or unknown mode";
+    static bool host_ok(const float *r)
+    {
+        uint32_t mode;
+        memcpy(&mode, &r[7], 4);
+        return ray_record_ok(r[0], r[1], r[2], r[4], r[5], r[6], mode);
+    }
+    static __device__ bool ok(const float4 *__restrict__ records, unsigned long long i)
+    {
+        const float4 a = records[2 * i], b = records[2 * i + 1];
+        return ray_record_ok(a.x, a.y, a.z, b.x, b.y, b.z, __float_as_uint(b.w));
+    }
+};
 
 // `records` and `out_rays` point at the chunk's first record / first slot; n = the chunk's slots (records * samples)
 __global__ void __launch_bounds__(LP_BLOCK) k_begin_rays(PathBuffers pb, uint32_t n, const float4 *__restrict__ records, uint32_t samples,

@@ -17,7 +17,7 @@
 // a refractive or transparent material type with opacity 1 blocks.  The visited set is scene_any_hit's: the nodes whose slab
 // distance is below the CONSTANT tmax, binary hierarchy only.
 //
-//   k_transmittance_validate   device records only: counts the records occlusion_record_ok refuses
+//   (device records are checked by occlusion's k_validate_records<OcclusionRecordRule>: one rule, one kernel)
 //   k_transmittance<LDSGEO>    one lane per slot: direction exactly as k_occlusion derives it, scene_transmittance, T stored
 //                              to out[slot] (direction mode: the caller's array; hemisphere mode: the context's slot plane)
 //   k_transmittance_resolve    one wave per record: lane l adds slots l, l + 64, ... in ascending order, an xor butterfly
@@ -28,20 +28,6 @@
 #pragma once
 
 #include "lupin_occlusion.hpp"
-
-// device records: occlusion's rule (occlusion_record_ok), one thread per record, one atomic (an integer count) per wave
-__global__ void __launch_bounds__(LP_BLOCK) k_transmittance_validate(const float *__restrict__ records, unsigned long long n, unsigned long long *bad_count)
-{
-    const unsigned long long i = (unsigned long long)blockIdx.x * LP_BLOCK + threadIdx.x;
-    bool bad = false;
-    if (i < n)
-    {
-        const float4 a = reinterpret_cast<const float4 *>(records)[2 * i], b = reinterpret_cast<const float4 *>(records)[2 * i + 1];
-        bad = !occlusion_record_ok(a.x, a.y, a.z, b.x, b.y, b.z, b.w);
-    }
-    const unsigned long long mask = __ballot(bad);
-    if (mask && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)mask) - 1)) atomicAdd(bad_count, (unsigned long long)__popcll(mask));
-}
 
 // scene_any_hit's loop (lupin_occlusion.hpp): the same stack, near / far choice, instance entry arithmetic, slab_dst, tri_dst
 // and constant pruning bound, tracking the current instance and its flags as scene_closest tracks the instance.  At a BLAS

@@ -307,3 +307,29 @@ def test_a_hierarchy_too_deep_for_the_pair_stack_is_refused(gpu_ctx):
     assert e.value.code == INV and "too deep" in str(e.value)
     res = api.distance_points(gpu_ctx, chain_scene(gpu_ctx, 60), api.distance_records([[59.2, 0.2, 1.0], [0.2, 0.2, 0.5]]))
     assert res["tri"].tolist() == [59, 0] and res["distance"].tolist() == [1.0, 0.5]
+
+
+def test_a_refused_call_names_its_records_and_leaves_recorded_frames_intact(gpu_ctx):
+    """Frames recorded and not yet run, then a call refused for its records: host arrays name the first bad index, device
+    arrays count the bad records, the results stay untouched, and the frames are what they are without the call."""
+    from tests import util
+    W, H = 32, 24
+    scene, cams = util.load_scene("cornellbox_builtin", gpu_ctx)
+    rec = api.distance_records([[0, 1, 0], [0.2, 0.5, 0.1], [0.1, 1.5, -0.2], [-0.3, 0.7, 0.2], [0, 0.2, 0]], 2.0)
+    alone = words(api.distance_points(gpu_ctx, scene, rec))
+    bad = rec.copy(); bad[1, 2] = np.inf; bad[4, 3] = -1.0
+    lib = _abi.lib()
+
+    def host_refusal():
+        out = np.full((5, 12), CANARY, np.uint32)
+        assert lib.lupin_hip_distance_points(gpu_ctx.handle, scene.handle, 0, 5, _abi.ptr(bad), _abi.ptr(out)) == INV
+        assert lib.lupin_hip_last_error().decode().startswith("record 1: ") and (out == CANARY).all()
+
+    def device_refusal():
+        rc, out = device_points(gpu_ctx, scene, bad, canary=True)
+        assert rc == INV and lib.lupin_hip_last_error().decode().startswith("2 record(s): ") and (out == CANARY).all()
+
+    plain = util.gpu_accumulate(gpu_ctx, scene, cams[0], W, H, frames=4, spp=1)
+    for refusal in (host_refusal, device_refusal):
+        assert util.f16_words_differ(util.gpu_accumulate(gpu_ctx, scene, cams[0], W, H, frames=4, spp=1, between=refusal), plain) == 0
+    assert np.array_equal(words(api.distance_points(gpu_ctx, scene, rec)), alone)

@@ -400,3 +400,38 @@ def test_frames_around_an_occlusion_call_do_not_notice_it(gpu_ctx):
     assert util.f16_words_differ(chain(3), plain) == 0
     assert util.f16_words_differ(plain, util.oracle_accumulate(scene, cam, W, H, frames=6, spp=2)) == 0
     assert 0 < int(alone.sum()) < 300 * 16
+
+
+# ---- a refused call between recorded frames -----------------------------------------------------------------------
+
+@pytest.mark.parametrize("S", [1, 65])
+def test_a_refused_call_names_its_records_and_leaves_recorded_frames_intact(gpu_ctx, S):
+    """Frames recorded and not yet run, then a call refused for its records: host arrays name the first bad index, device
+    arrays count the bad records, the output stays untouched, and the frames are what they are without the call.  65 slots
+    per record make a record straddle a wave in the combine; that the 65-slot counts are right is property 3's business
+    (test_hemisphere_count_is_the_sum_over_the_radiance_query_first_rays, S = 65 among its cases)."""
+    W, H = 32, 24
+    scene, cams = util.load_scene("cornellbox_builtin", gpu_ctx)
+    mode = MODE.DIRECTION if S == 1 else MODE.COSINE_HEMISPHERE
+    rng = np.random.default_rng(5)
+    nrm = rng.normal(size=(7, 3))
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    rec = api.occlusion_records(rng.uniform(-0.5, 0.5, (7, 3)) + [0.0, 1.0, 0.0], nrm, 0.7, api.rng_seed_for(np.arange(7, dtype=np.uint32), 0))
+    alone = api.occlusion_rays(gpu_ctx, scene, rec, mode, S)
+    bad = rec.copy(); bad[3, 1] = np.nan; bad[5, 7] = 0.0
+    lib = _abi.lib()
+
+    def host_refusal():
+        out = np.full(7, SENTINEL, np.uint32)
+        c = _abi.OcclusionDescC(int(mode), S, 0, 1e-3)
+        assert lib.lupin_hip_occlusion_rays(gpu_ctx.handle, scene.handle, C.byref(c), 7, _abi.ptr(bad), _abi.ptr(out)) == -1
+        assert lib.lupin_hip_last_error().decode().startswith("record 3: ") and np.all(out == SENTINEL)
+
+    def device_refusal():
+        rc, out = device_occlusion(gpu_ctx, scene, bad, mode, S, sentinel=SENTINEL)
+        assert rc == -1 and lib.lupin_hip_last_error().decode().startswith("2 record(s): ") and np.all(out == SENTINEL)
+
+    plain = util.gpu_accumulate(gpu_ctx, scene, cams[0], W, H, frames=4, spp=1)
+    for refusal in (host_refusal, device_refusal):
+        assert util.f16_words_differ(util.gpu_accumulate(gpu_ctx, scene, cams[0], W, H, frames=4, spp=1, between=refusal), plain) == 0
+    assert np.array_equal(api.occlusion_rays(gpu_ctx, scene, rec, mode, S), alone)

@@ -376,3 +376,33 @@ def test_bake_after_update_instances_equals_a_fresh_scene(gpu_ctx):
     fresh = api.bake_probes(gpu_ctx, b, pos, 256, PT.MIS, 8)
     assert int((words(before) != words(fresh)).sum()) > 100      # the move is visible
     assert_same_words(after, fresh, "updated scene against a freshly created moved scene")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [1, 65])
+def test_a_refused_call_names_its_records_and_leaves_recorded_frames_intact(gpu_ctx, S):
+    """Frames recorded and not yet run, then a bake refused for its probes: host arrays name the first bad index, device
+    arrays count the bad probes (the noun is "probe"), `out_sh` stays untouched, and the frames are what they are without
+    the call.  (What 65 samples per probe sum to is checked bit for bit by the tests above: 65 leaves the last lanes of the
+    resolve one sample short.)"""
+    scene, cam, _, _ = rq.cornell(gpu_ctx)
+    probes = probe_records(positions_inside(scene, 7, 31))
+    alone = api.bake_probes(gpu_ctx, scene, probes[:, :3], S, PT.Standard, 4)
+    bad = probes.copy(); bad[3, 1] = np.nan; bad[5, 2] = np.inf
+    lib = _abi.lib()
+
+    def host_refusal():
+        out = np.full((7, 36), -7.0, np.float32)
+        c = _abi.ProbeDescC(int(PT.Standard), 4, S, 0, 0, _abi.AdvancedParamsC(100.0, 0, 0.001))
+        assert lib.lupin_hip_bake_probes(gpu_ctx.handle, scene.handle, C.byref(c), 7, _abi.ptr(bad), _abi.ptr(out), None) == INVALID
+        assert lib.lupin_hip_last_error().decode().startswith("probe 3: ") and np.all(out == -7.0)
+
+    def device_refusal():
+        rc, out, _ = device_bake(gpu_ctx, scene, bad, S, max_bounces=4, sentinel=-7.0)
+        assert rc == INVALID and lib.lupin_hip_last_error().decode().startswith("2 probe(s): ") and np.all(out == -7.0)
+
+    plain = util.gpu_accumulate(gpu_ctx, scene, cam, 32, 24, frames=4, spp=1)
+    for refusal in (host_refusal, device_refusal):
+        assert util.f16_words_differ(util.gpu_accumulate(gpu_ctx, scene, cam, 32, 24, frames=4, spp=1, between=refusal), plain) == 0
+    again = api.bake_probes(gpu_ctx, scene, probes[:, :3], S, PT.Standard, 4)
+    assert np.array_equal(np.asarray(again).view(np.uint32), np.asarray(alone).view(np.uint32))

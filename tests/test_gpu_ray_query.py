@@ -533,3 +533,34 @@ def test_query_after_update_instances_equals_a_fresh_scene(gpu_ctx):
     fresh = api.pathtrace_rays(gpu_ctx, b, rec, desc)
     assert int((words(before) != words(fresh)).sum()) > 100      # the move is visible
     assert_same_words(after, fresh, "updated scene against a freshly created moved scene")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [1, 65])
+def test_a_refused_call_names_its_records_and_leaves_recorded_frames_intact(gpu_ctx, S):
+    """Frames recorded and not yet run, then a query refused for its records: host arrays name the first bad index, device
+    arrays count the bad records, `out` stays untouched, and the frames are what they are without the call.  (What a
+    query returns is checked by the tests above; this one is about the refusal.)"""
+    scene, cam, rec, _ = cornell(gpu_ctx)
+    rec = rec[100:107].copy()
+    if S > 1:
+        rec.view(np.uint32)[:, 7] = int(api.RayMode.COSINE_HEMISPHERE)
+    desc = api.RayQueryDesc(PT.Standard, 4, S)
+    alone = api.pathtrace_rays(gpu_ctx, scene, rec, desc)
+    bad = rec.copy(); bad[3, 1] = np.nan; bad.view(np.uint32)[5, 7] = 2
+    lib = _abi.lib()
+
+    def host_refusal():
+        out = np.full((7, 4), -7.0, np.float32)
+        c = _abi.RayQueryDescC(int(PT.Standard), 4, S, 0, 0, _abi.AdvancedParamsC(100.0, 0, 0.001))
+        assert lib.lupin_hip_pathtrace_rays(gpu_ctx.handle, scene.handle, C.byref(c), 7, _abi.ptr(bad), _abi.ptr(out), None) == -1
+        assert lib.lupin_hip_last_error().decode().startswith("record 3: ") and np.all(out == -7.0)
+
+    def device_refusal():
+        rc, out, _ = device_query(gpu_ctx, scene, bad, desc, sentinel=-7.0)
+        assert rc == -1 and lib.lupin_hip_last_error().decode().startswith("2 record(s): ") and np.all(out == -7.0)
+
+    plain = util.gpu_accumulate(gpu_ctx, scene, cam, 32, 24, frames=4, spp=1)
+    for refusal in (host_refusal, device_refusal):
+        assert util.f16_words_differ(util.gpu_accumulate(gpu_ctx, scene, cam, 32, 24, frames=4, spp=1, between=refusal), plain) == 0
+    assert_same_words(api.pathtrace_rays(gpu_ctx, scene, rec, desc), alone, "the query after the refusals")

@@ -50,8 +50,9 @@ def oracle_accumulate(scene, cam, width, height, frames, spp, max_bounces=8, pty
     return out
 
 
-def gpu_accumulate(ctx, scene, cam, width, height, frames, spp, max_bounces=8, ptype=0, advanced=None, start=0):
-    """The same loop through the C ABI (DoubleBufferedTexture + pathtrace_scene + flip)."""
+def gpu_accumulate(ctx, scene, cam, width, height, frames, spp, max_bounces=8, ptype=0, advanced=None, start=0, between=None):
+    """The same loop through the C ABI (DoubleBufferedTexture + pathtrace_scene + flip).  `between`: called once after the
+    second frame's call, while the frames so far may still be recorded and not run."""
     from lupinpathtracer_amd import api
     res = api.build_pathtrace_resources(ctx, api.BakedPathtraceParams(max_bounces=max_bounces, samples_per_pixel=spp))
     out = api.DoubleBufferedTexture(ctx, width, height)
@@ -60,6 +61,8 @@ def gpu_accumulate(ctx, scene, cam, width, height, frames, spp, max_bounces=8, p
                                  camera_transform=cam.transform, advanced=advanced or api.AdvancedParams())
         api.pathtrace_scene(ctx, res, scene, out.front(), ptype, desc)
         out.flip()
+        if between is not None and k == start + 1:
+            between()
     out.flip()
     return out.front().download()
 
