@@ -21,8 +21,6 @@
 
 namespace {
 
-#define LBVH_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { cleanup(); return lupin_internal_fail(LUPIN_ERR_HIP, hipGetErrorString(e__)); } } while (0)
-
 constexpr int kBlock = 256;
 
 // order-preserving float <-> uint mapping for atomicMin / atomicMax
@@ -150,45 +148,37 @@ int64_t lupin_hip_build_bvh_device(LupinContext *ctx, const float *verts_pos4, u
     if (hipSetDevice(lupin_internal_ctx_device(ctx)) != hipSuccess) return lupin_internal_fail(LUPIN_ERR_HIP, "hipSetDevice");
     hipStream_t st = lupin_internal_ctx_stream(ctx);
 
-    float4 *d_verts = nullptr, *d_centres = nullptr;
-    uint32_t *d_idx = nullptr, *d_idx_out = nullptr, *d_bounds = nullptr, *d_keys = nullptr, *d_vals = nullptr, *d_keys2 = nullptr, *d_vals2 = nullptr;
-    LupinBvhNode *d_nodes = nullptr;
-    void *d_temp = nullptr;
-    auto cleanup = [&]() {
-        void *ptrs[] = {d_verts, d_centres, d_idx, d_idx_out, d_bounds, d_keys, d_vals, d_keys2, d_vals2, d_nodes, d_temp};
-        for (void *p : ptrs) if (p) hipFree(p);
-    };
-    LBVH_TRY(hipMalloc((void **)&d_verts, (size_t)num_verts * 16));
-    LBVH_TRY(hipMalloc((void **)&d_centres, (size_t)n * 16));
-    LBVH_TRY(hipMalloc((void **)&d_idx, (size_t)num_indices * 4));
-    LBVH_TRY(hipMalloc((void **)&d_idx_out, (size_t)num_indices * 4));
-    LBVH_TRY(hipMalloc((void **)&d_bounds, 6 * 4));
-    LBVH_TRY(hipMalloc((void **)&d_keys, (size_t)n * 4));
-    LBVH_TRY(hipMalloc((void **)&d_vals, (size_t)n * 4));
-    LBVH_TRY(hipMalloc((void **)&d_keys2, (size_t)n * 4));
-    LBVH_TRY(hipMalloc((void **)&d_vals2, (size_t)n * 4));
-    LBVH_TRY(hipMalloc((void **)&d_nodes, (size_t)num_nodes * sizeof(LupinBvhNode)));
-    LBVH_TRY(hipMemcpyAsync(d_verts, verts_pos4, (size_t)num_verts * 16, hipMemcpyHostToDevice, st));
-    LBVH_TRY(hipMemcpyAsync(d_idx, indices, (size_t)num_indices * 4, hipMemcpyHostToDevice, st));
+    // scratch of this build, freed when the function returns, by whichever path
+    DeviceArray<float4> d_verts, d_centres;
+    DeviceArray<uint32_t> d_idx, d_idx_out, d_bounds, d_keys, d_vals, d_keys2, d_vals2;
+    DeviceArray<LupinBvhNode> d_nodes;
+    DeviceBuffer d_temp;
+    HIP_TRY(d_verts.alloc(num_verts));
+    HIP_TRY(d_centres.alloc(n));
+    for (auto *a : {&d_idx, &d_idx_out}) HIP_TRY(a->alloc(num_indices));
+    HIP_TRY(d_bounds.alloc(6));
+    for (auto *a : {&d_keys, &d_vals, &d_keys2, &d_vals2}) HIP_TRY(a->alloc(n));
+    HIP_TRY(d_nodes.alloc(num_nodes));
+    HIP_TRY(hipMemcpyAsync(d_verts, verts_pos4, (size_t)num_verts * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_idx, indices, (size_t)num_indices * 4, hipMemcpyHostToDevice, st));
     const uint32_t init_bounds[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-    LBVH_TRY(hipMemcpyAsync(d_bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
 
     const uint32_t tri_blocks = (n + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(k_centre_bounds, dim3(tri_blocks), dim3(kBlock), 0, st, d_verts, d_idx, n, d_centres, d_bounds);
     hipLaunchKernelGGL(k_morton, dim3(tri_blocks), dim3(kBlock), 0, st, d_centres, n, d_bounds, d_keys, d_vals);
     size_t temp_bytes = 0;
-    LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys, d_keys2, d_vals, d_vals2, (int)n, 0, 30, st));
-    LBVH_TRY(hipMalloc(&d_temp, std::max<size_t>(temp_bytes, 16)));
-    LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, d_keys, d_keys2, d_vals, d_vals2, (int)n, 0, 30, st));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys.get(), d_keys2.get(), d_vals.get(), d_vals2.get(), (int)n, 0, 30, st));
+    HIP_TRY(DeviceBuffer::make(std::max<size_t>(temp_bytes, 16), &d_temp));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp.get(), temp_bytes, d_keys.get(), d_keys2.get(), d_vals.get(), d_vals2.get(), (int)n, 0, 30, st));
     const uint64_t leaves = 1ull << depth;
     hipLaunchKernelGGL(k_leaves, dim3((uint32_t)((leaves + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_verts, d_idx, d_vals2, n, depth, d_nodes, d_idx_out);
     for (int level = (int)depth - 1; level >= 0; level--)
         hipLaunchKernelGGL(k_refit_level, dim3((uint32_t)(((1ull << level) + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (uint32_t)level, d_nodes);
-    LBVH_TRY(hipGetLastError());
-    LBVH_TRY(hipMemcpyAsync(out_nodes, d_nodes, (size_t)num_nodes * sizeof(LupinBvhNode), hipMemcpyDeviceToHost, st));
-    LBVH_TRY(hipMemcpyAsync(indices, d_idx_out, (size_t)num_indices * 4, hipMemcpyDeviceToHost, st));
-    LBVH_TRY(hipStreamSynchronize(st));
-    cleanup();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_nodes, d_nodes, (size_t)num_nodes * sizeof(LupinBvhNode), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(indices, d_idx_out, (size_t)num_indices * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return (int64_t)num_nodes;
 }
 

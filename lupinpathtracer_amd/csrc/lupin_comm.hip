@@ -85,14 +85,13 @@ struct LupinComm
     bool owns_comm = true;
     uint32_t rank = 0, world = 1;
     // staging for the gather: [send: capacity px][recv: world * capacity px], 8 B per pixel; grown on demand
-    uint2 *send = nullptr, *recv = nullptr;
+    DeviceArray<uint2> send, recv;
     uint64_t capacity_px = 0;
-    double *scratch = nullptr;      // device words for barrier / all-reduce
+    DeviceArray<double> scratch;    // device words for barrier / all-reduce
     uint32_t scratch_words = 0;
 };
 
 #define COMM_FAIL(code, msg) lupin_internal_fail((code), (msg))
-#define HIP_TRY_C(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return lupin_internal_fail(LUPIN_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); } while (0)
 #define NCCL_TRY(expr) do { ncclResult_t r__ = (expr); if (r__ != ncclSuccess) return lupin_internal_fail(LUPIN_ERR_RCCL, (std::string(#expr) + ": " + (R->GetErrorString ? R->GetErrorString(r__) : "rccl error")).c_str()); } while (0)
 
 static int need_rccl(Rccl **out)
@@ -106,10 +105,10 @@ static int need_rccl(Rccl **out)
 static int ensure_scratch(LupinComm *c, uint32_t words)
 {
     if (words <= c->scratch_words) return LUPIN_OK;
-    HIP_TRY_C(hipSetDevice(lupin_internal_ctx_device(c->ctx)));
-    if (c->scratch) { HIP_TRY_C(hipStreamSynchronize(lupin_internal_ctx_stream(c->ctx))); hipFree(c->scratch); c->scratch = nullptr; }
+    HIP_TRY(hipSetDevice(lupin_internal_ctx_device(c->ctx)));
+    if (c->scratch) { HIP_TRY(hipStreamSynchronize(lupin_internal_ctx_stream(c->ctx))); c->scratch.reset(); c->scratch_words = 0; }
     const uint32_t n = words < 16 ? 16 : words;
-    HIP_TRY_C(hipMalloc((void **)&c->scratch, (size_t)n * sizeof(double)));
+    HIP_TRY(c->scratch.alloc(n));
     c->scratch_words = n;
     return LUPIN_OK;
 }
@@ -129,14 +128,12 @@ static uint64_t gather_capacity(uint32_t w, uint32_t h, uint32_t tile_size, uint
 static int ensure_staging(LupinComm *c, uint64_t capacity_px)
 {
     if (capacity_px <= c->capacity_px) return LUPIN_OK;
-    HIP_TRY_C(hipSetDevice(lupin_internal_ctx_device(c->ctx)));
-    HIP_TRY_C(hipStreamSynchronize(lupin_internal_ctx_stream(c->ctx)));
-    if (c->send) hipFree(c->send);
-    if (c->recv) hipFree(c->recv);
-    c->send = c->recv = nullptr; c->capacity_px = 0;
-    HIP_TRY_C(hipMalloc((void **)&c->send, capacity_px * 8));
-    HIP_TRY_C(hipMalloc((void **)&c->recv, capacity_px * 8 * c->world));
-    HIP_TRY_C(hipMemsetAsync(c->send, 0, capacity_px * 8, lupin_internal_ctx_stream(c->ctx)));   // the padding behind a short payload is gathered too
+    HIP_TRY(hipSetDevice(lupin_internal_ctx_device(c->ctx)));
+    HIP_TRY(hipStreamSynchronize(lupin_internal_ctx_stream(c->ctx)));
+    c->send.reset(); c->recv.reset(); c->capacity_px = 0;
+    HIP_TRY(c->send.alloc(capacity_px));
+    HIP_TRY(c->recv.alloc(capacity_px * c->world));
+    HIP_TRY(hipMemsetAsync(c->send, 0, capacity_px * 8, lupin_internal_ctx_stream(c->ctx)));   // the padding behind a short payload is gathered too
     c->capacity_px = capacity_px;
     return LUPIN_OK;
 }
@@ -159,7 +156,7 @@ int lupin_hip_comm_init_rank(LupinContext *ctx, const uint8_t *id_bytes, uint32_
     if (!ctx || !id_bytes || !out_comm || world == 0 || rank >= world) return COMM_FAIL(LUPIN_ERR_INVALID_ARGUMENT, "bad communicator arguments");
     if (!lupin_internal_ctx_alive(ctx)) return COMM_FAIL(LUPIN_ERR_INVALID_ARGUMENT, "the context of this object has been destroyed");
     Rccl *R; int rc = need_rccl(&R); if (rc) return rc;
-    HIP_TRY_C(hipSetDevice(lupin_internal_ctx_device(ctx)));
+    HIP_TRY(hipSetDevice(lupin_internal_ctx_device(ctx)));
     ncclUniqueId id;
     memcpy(&id, id_bytes, sizeof(id));
     ncclComm_t comm = nullptr;
@@ -211,10 +208,7 @@ void lupin_hip_comm_destroy(LupinComm *c)
     if (lupin_internal_ctx_alive(c->ctx)) lupin_internal_sync_all(c->ctx);   // a destroyed context has drained its streams already
     Rccl *R = rccl();
     if (c->owns_comm && c->comm && R->handle) R->CommDestroy(c->comm);
-    if (c->send) hipFree(c->send);
-    if (c->recv) hipFree(c->recv);
-    if (c->scratch) hipFree(c->scratch);
-    delete c;
+    delete c;   // frees send, recv and scratch: after the synchronisation above
 }
 
 uint32_t lupin_hip_comm_rank(const LupinComm *c) { return c ? c->rank : 0; }
@@ -234,7 +228,7 @@ static int gather_enqueue(Rccl *R, LupinComm *c, LupinTexture *tex, uint32_t til
     }
     if (stage == 1)
     {
-        HIP_TRY_C(hipSetDevice(lupin_internal_ctx_device(ctx)));
+        HIP_TRY(hipSetDevice(lupin_internal_ctx_device(ctx)));
         NCCL_TRY(R->AllGather(c->send, c->recv, (size_t)c->capacity_px * 8, ncclUint8, c->comm, st));
         return LUPIN_OK;
     }
@@ -264,7 +258,7 @@ int lupin_hip_gather_framebuffer_to(LupinComm *c, LupinTexture *tex, uint32_t ti
     if (c->world == 1) return LUPIN_OK;
     LupinContext *ctx = c->ctx;
     hipStream_t st = lupin_internal_ctx_stream(ctx);
-    HIP_TRY_C(hipSetDevice(lupin_internal_ctx_device(ctx)));
+    HIP_TRY(hipSetDevice(lupin_internal_ctx_device(ctx)));
     NCCL_TRY(R->GroupStart());
     if (c->rank == root)
     {
@@ -321,10 +315,10 @@ int lupin_hip_comm_allreduce_f64(LupinComm *c, double *inout, uint32_t n, uint32
     if ((rc = ensure_scratch(c, n))) return rc;
     if ((rc = lupin_internal_sync_all(c->ctx))) return rc;
     hipStream_t st = lupin_internal_ctx_stream(c->ctx);
-    HIP_TRY_C(hipMemcpyAsync(c->scratch, inout, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->scratch, inout, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     NCCL_TRY(R->AllReduce(c->scratch, c->scratch, n, ncclFloat64, op == 0 ? ncclSum : ncclMax, c->comm, st));
-    HIP_TRY_C(hipMemcpyAsync(inout, c->scratch, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY_C(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(inout, c->scratch, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return LUPIN_OK;
 }
 

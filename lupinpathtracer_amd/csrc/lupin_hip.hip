@@ -44,7 +44,6 @@ static inline float host_u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f;
 
 static thread_local std::string g_last_error;
 static int fail(int code, const std::string &msg) { g_last_error = msg; return code; }
-#define HIP_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return fail(LUPIN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
 
 #define LP_MAX_LANES 8
 #define LP_WIDE_WORDS 10   // [0] wide queries, [1] re-traced, [2..9] LUPIN_VERIFY_WIDE: checked, flagged, mismatches among unflagged, raw mismatches, 4 reasons
@@ -56,18 +55,20 @@ static int fail(int code, const std::string &msg) { g_last_error = msg; return c
 struct Lane
 {
     hipStream_t stream = nullptr;
-    PathBuffers pb{};
-    char *hot = nullptr;            // the eight per-bounce fields of the path state: capacity x 128 bytes, planes or records (set_path_layout)
-    char *shadow = nullptr;         // the eight MIS / Direct fields, likewise
-    char *skey = nullptr;           // k_sort_queue's keys, 4 bytes per slot
+    PathBuffers pb{};               // the plain view of the owners below that the kernels get by value
+    // The nine per-slot buffers (bytes per slot: kPathSlotBytes).  HOT: the eight per-bounce fields, capacity x 128 bytes, planes or
+    // records (set_path_layout); SHADOW: the eight MIS / Direct fields, likewise; SKEY: k_sort_queue's keys; the rest: pb's members.
+    enum { HOT, SHADOW, SKEY, VOL0, VOL1, QUEUE0, QUEUE1, RETRACE, SHADE_ORDER, NUM_PATH_BUFFERS };
+    DeviceBuffer path[NUM_PATH_BUFFERS];
+    DeviceArray<uint32_t> counts;   // pb.counts, and pb.cursors / retrace_counts / retrace_cursors carved from it
     uint64_t capacity = 0;          // slots the path buffers hold
     uint32_t counts_capacity = 0;
-    unsigned long long *stat_counters = nullptr;   // per shard: [2s] path bounces, [2s+1] paths
-    unsigned long long *work_counters = nullptr;   // [4 * mode + {nodes, triangles, instances, wide nodes}] of the COUNT kernels (stats mode 2)
-    unsigned long long *wide_counters = nullptr;   // [0] queries the wide tracer took, [1] queries re-traced by the binary tracer
+    DeviceArray<unsigned long long> stat_counters;   // per shard: [2s] path bounces, [2s+1] paths
+    DeviceArray<unsigned long long> work_counters;   // [4 * mode + {nodes, triangles, instances, wide nodes}] of the COUNT kernels (stats mode 2)
+    DeviceArray<unsigned long long> wide_counters;   // [0] queries the wide tracer took, [1] queries re-traced by the binary tracer
     hipEvent_t done = nullptr;      // recorded after the last kernel of the lane's latest call
     bool used = false;
-    FrameParams *d_fp = nullptr;    // this lane's per-call parameters (k_set_params writes, the stage kernels read)
+    DeviceArray<FrameParams> d_fp;  // this lane's per-call parameters (k_set_params writes, the stage kernels read)
     uint64_t pb_generation = 0;     // bumped when the path buffers are reallocated
     // the lane's wavefront (memset + k_begin + all iterations) as a replayable graph
     struct GraphKey
@@ -153,10 +154,11 @@ struct LupinPathtraceResources
 // adaptive sampling's per-pixel and per-block state (lupin_adaptive.hpp)
 struct LupinAdaptiveResources
 {
-    LupinContext *ctx;
-    int device;
-    AdaptiveDev dev;     // device pointers, size and the latest call's parameters
-    uint32_t calls;      // adaptive calls since the latest reset
+    LupinContext *ctx = nullptr;
+    int device = 0;
+    AdaptiveDev dev{};   // device pointers, size and the latest call's parameters: the plain view the kernels get by value
+    DeviceBuffer frames, moments, block_error, block_flags, block_active, block_count, stats;   // own what dev's pointers of the same names point to
+    uint32_t calls = 0;  // adaptive calls since the latest reset
 };
 
 struct LupinDoubleBufferedTexture
@@ -171,7 +173,7 @@ struct LupinScene
     LupinContext *ctx;
     int device = 0;                                 // the context's device ordinal (the scene may outlive the context)
     SceneDev dev{};
-    std::vector<void *> allocations;
+    std::vector<DeviceBuffer> allocations;          // everything `dev` points to
     uint32_t stack_entries = 1;
     // grids of k_extend_persistent per integrator, filled on first use by resident_grid (so `mutable`: a render takes the scene const)
     mutable uint32_t persistent_blocks[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // binary; [1]: sharing the chip with other lanes' stages
@@ -202,9 +204,9 @@ static int upload(LupinScene *sc, const std::vector<T> &host, const T **out)
 {
     *out = nullptr;
     size_t bytes = std::max<size_t>(host.size() * sizeof(T), sizeof(T) > 16 ? sizeof(T) : 16);
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, bytes));
-    sc->allocations.push_back(d);
+    sc->allocations.emplace_back();
+    HIP_TRY(DeviceBuffer::make(bytes, &sc->allocations.back()));
+    void *d = sc->allocations.back().get();
     HIP_TRY(hipMemsetAsync(d, 0, bytes, sc->ctx->stream));
     if (!host.empty()) HIP_TRY(hipMemcpyAsync(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, sc->ctx->stream));
     *out = reinterpret_cast<const T *>(d);
@@ -219,20 +221,20 @@ static hipEvent_t get_event(LupinContext *ctx)
     return e;
 }
 
-// Points the lane's per-bounce fields into its `hot` allocation: planes (neighbouring slots coalesce) or 128-byte records
+// Points the lane's per-bounce fields into its HOT allocation: planes (neighbouring slots coalesce) or 128-byte records
 // (scattered slots cost two sectors per path, not one per field).  See PathField.
 static void set_path_layout(Lane *ln, bool records)
 {
     PathBuffers &pb = ln->pb;
-    char *b = ln->hot;
+    char *b = ln->path[Lane::HOT].as<char>();
     const size_t cap = (size_t)ln->capacity;
-    pb.skey = {ln->skey, 4};   // always a plane: k_sort_queue reads nothing else of a path
+    pb.skey = {ln->path[Lane::SKEY].as<char>(), 4};   // always a plane: k_sort_queue reads nothing else of a path
     if (records)
     {
         const uint32_t st = LP_PATH_RECORD_BYTES;
         pb.ori_rng = {b + 0, st}; pb.dir_meta = {b + 16, st}; pb.hit = {b + 32, st}; pb.hit_tri = {b + 48, st};
         pb.weight = {b + 64, st}; pb.radiance = {b + 80, st}; pb.color = {b + 96, st};
-        char *m = ln->shadow;
+        char *m = ln->path[Lane::SHADOW].as<char>();
         pb.sh_org = {m + 0, st}; pb.sh_d0 = {m + 16, st}; pb.sh_d1 = {m + 32, st}; pb.next_tri = {m + 48, st};
         pb.sh_f0 = {m + 64, st}; pb.sh_f1 = {m + 80, st}; pb.next_hit = {m + 96, st}; pb.sh_hit1 = {m + 112, st};
     }
@@ -240,10 +242,26 @@ static void set_path_layout(Lane *ln, bool records)
     {
         pb.ori_rng = {b, 16}; pb.dir_meta = {b + 16 * cap, 16}; pb.hit = {b + 32 * cap, 16}; pb.weight = {b + 48 * cap, 16};
         pb.radiance = {b + 64 * cap, 16}; pb.color = {b + 80 * cap, 16}; pb.hit_tri = {b + 96 * cap, 4};
-        char *m = ln->shadow;
+        char *m = ln->path[Lane::SHADOW].as<char>();
         pb.sh_org = {m, 16}; pb.sh_d0 = {m + 16 * cap, 16}; pb.sh_d1 = {m + 32 * cap, 16}; pb.sh_f0 = {m + 48 * cap, 16};
         pb.sh_f1 = {m + 64 * cap, 16}; pb.next_hit = {m + 80 * cap, 16}; pb.sh_hit1 = {m + 96 * cap, 16}; pb.next_tri = {m + 112 * cap, 4};
     }
+}
+
+// bytes per slot of Lane::path[k]; re-trace tokens: up to two jobs per slot (shadow rays)
+static constexpr size_t kPathSlotBytes[Lane::NUM_PATH_BUFFERS] = {LP_PATH_RECORD_BYTES, LP_PATH_RECORD_BYTES, 4, 16, 16, 4, 4, 8, 4};
+
+// pb's plain pointers follow their owners (null for an empty owner); the PathFields are set_path_layout's
+static void set_path_views(Lane *ln)
+{
+    PathBuffers &pb = ln->pb;
+    pb.vol0 = ln->path[Lane::VOL0].as<float4>(); pb.vol1 = ln->path[Lane::VOL1].as<float4>();
+    pb.queue[0] = ln->path[Lane::QUEUE0].as<uint32_t>(); pb.queue[1] = ln->path[Lane::QUEUE1].as<uint32_t>();
+    pb.retrace = ln->path[Lane::RETRACE].as<uint32_t>(); pb.shade_order = ln->path[Lane::SHADE_ORDER].as<uint32_t>();
+    // queue counters, then the persistent tracer's hand-out cursors, the re-trace counters and the re-trace cursors (two
+    // per iteration each): one allocation, one clear per call (an empty owner has counts_capacity 0: all four are null)
+    const size_t row = (size_t)ln->counts_capacity * LP_SHARDS;
+    pb.counts = ln->counts; pb.cursors = pb.counts + row; pb.retrace_counts = pb.cursors + 2 * row; pb.retrace_cursors = pb.retrace_counts + 2 * row;
 }
 
 static int ensure_path_buffers(LupinContext *ctx0, Lane *ctx, uint64_t slots, uint32_t iterations)
@@ -254,40 +272,32 @@ static int ensure_path_buffers(LupinContext *ctx0, Lane *ctx, uint64_t slots, ui
     slots = (slots + per_round - 1) / per_round * per_round;
     if (slots > ctx->capacity)
     {
-        PathBuffers &pb = ctx->pb;
-        void **ptrs[] = {(void **)&ctx->hot, (void **)&ctx->shadow, (void **)&ctx->skey, (void **)&pb.vol0, (void **)&pb.vol1, (void **)&pb.queue[0], (void **)&pb.queue[1],
-                         (void **)&pb.retrace, (void **)&pb.shade_order};
-        size_t elem[] = {LP_PATH_RECORD_BYTES, LP_PATH_RECORD_BYTES, 4, 16, 16, 4, 4, 8, 4};   // re-trace tokens: up to two jobs per slot (shadow rays)
-        constexpr int NPTRS = 9;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        // the lane holds nothing until every allocation has succeeded: a failure part-way (hipMalloc returns through
-        // HIP_TRY) must not leave a capacity behind that a later, smaller dispatch would trust
+        // the lane holds nothing until every allocation has succeeded: a failure part-way (make returns through
+        // HIP_TRY) must not leave a capacity behind that a later, smaller dispatch would trust.  All nine are freed before any
+        // is allocated: the peak is the new size, not the old one plus the new
         ctx->capacity = 0;
         ctx->pb_generation++;
-        for (int k = 0; k < NPTRS; k++)
-            if (*ptrs[k]) { hipFree(*ptrs[k]); *ptrs[k] = nullptr; }
-        for (int k = 0; k < NPTRS; k++)
-            HIP_TRY(hipMalloc(ptrs[k], (size_t)slots * elem[k]));
+        for (DeviceBuffer &b : ctx->path) b.reset();
+        set_path_views(ctx);
+        for (int k = 0; k < Lane::NUM_PATH_BUFFERS; k++)
+            HIP_TRY(DeviceBuffer::make((size_t)slots * kPathSlotBytes[k], &ctx->path[k]));
         // touch every page now (a fill runs at several TB/s): otherwise the first wavefront that reaches a slot pays the
         // mapping of its pages inside its kernels -- 1 % of the first full wavefront of eight 4K frames
-        for (int k = 0; k < NPTRS; k++)
-            HIP_TRY(hipMemsetAsync(*ptrs[k], 0, (size_t)slots * elem[k], ctx->stream));
+        for (int k = 0; k < Lane::NUM_PATH_BUFFERS; k++)
+            HIP_TRY(hipMemsetAsync(ctx->path[k].get(), 0, (size_t)slots * kPathSlotBytes[k], ctx->stream));
         ctx->capacity = slots;
+        set_path_views(ctx);
     }
     if (iterations + 2 > ctx->counts_capacity)
     {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         ctx->counts_capacity = 0;
-        if (ctx->pb.counts) hipFree(ctx->pb.counts);
-        ctx->pb.counts = nullptr;
-        ctx->pb.cursors = ctx->pb.retrace_counts = ctx->pb.retrace_cursors = nullptr;
-        // queue counters, then the persistent tracer's hand-out cursors, the re-trace counters and the re-trace cursors (two
-        // per iteration each): one allocation, one clear per call
-        HIP_TRY(hipMalloc((void **)&ctx->pb.counts, LP_COUNTER_ROWS * (size_t)(iterations + 2) * LP_SHARDS * sizeof(uint32_t)));
+        ctx->counts.reset();
+        set_path_views(ctx);
+        HIP_TRY(ctx->counts.alloc(LP_COUNTER_ROWS * (size_t)(iterations + 2) * LP_SHARDS));
         ctx->counts_capacity = iterations + 2;
-        ctx->pb.cursors = ctx->pb.counts + (size_t)ctx->counts_capacity * LP_SHARDS;
-        ctx->pb.retrace_counts = ctx->pb.cursors + 2 * (size_t)ctx->counts_capacity * LP_SHARDS;
-        ctx->pb.retrace_cursors = ctx->pb.retrace_counts + 2 * (size_t)ctx->counts_capacity * LP_SHARDS;
+        set_path_views(ctx);
         ctx->pb_generation++;
     }
     return LUPIN_OK;
@@ -973,13 +983,13 @@ int lupin_hip_create_context(int device_ordinal, LupinContext **out_ctx)
         Lane &ln = ctx->lanes[k];
         e = hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ln.done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipMalloc((void **)&ln.d_fp, LP_MAX_BATCH * sizeof(FrameParams));
-        if (e == hipSuccess) e = hipMalloc((void **)&ln.stat_counters, 2 * LP_SHARDS * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMemsetAsync(ln.stat_counters, 0, 2 * LP_SHARDS * sizeof(unsigned long long), ln.stream);
-        if (e == hipSuccess) e = hipMalloc((void **)&ln.work_counters, LP_WORK_WORDS * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMemsetAsync(ln.work_counters, 0, LP_WORK_WORDS * sizeof(unsigned long long), ln.stream);
-        if (e == hipSuccess) e = hipMalloc((void **)&ln.wide_counters, LP_WIDE_WORDS * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMemsetAsync(ln.wide_counters, 0, LP_WIDE_WORDS * sizeof(unsigned long long), ln.stream);
+        if (e == hipSuccess) e = ln.d_fp.alloc(LP_MAX_BATCH);
+        const std::pair<DeviceArray<unsigned long long> *, size_t> counters[] = {{&ln.stat_counters, 2 * LP_SHARDS}, {&ln.work_counters, LP_WORK_WORDS}, {&ln.wide_counters, LP_WIDE_WORDS}};
+        for (const auto &c : counters)
+        {
+            if (e == hipSuccess) e = c.first->alloc(c.second);
+            if (e == hipSuccess) e = hipMemsetAsync(c.first->get(), 0, c.second * sizeof(unsigned long long), ln.stream);
+        }
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->marker, hipEventDisableTiming);
     if (e != hipSuccess)
@@ -1035,14 +1045,9 @@ void lupin_hip_destroy_context(LupinContext *ctx)
     sync_all(ctx);
     for (int k = 0; k < LP_MAX_LANES; k++)
     {
-        PathBuffers &pb = ctx->lanes[k].pb;
-        void *ptrs[] = {ctx->lanes[k].hot, ctx->lanes[k].shadow, ctx->lanes[k].skey, pb.vol0, pb.vol1, pb.queue[0], pb.queue[1], pb.counts, ctx->lanes[k].stat_counters,
-                        ctx->lanes[k].work_counters, ctx->lanes[k].wide_counters, pb.retrace, pb.shade_order};
-        for (void *p : ptrs) if (p) hipFree(p);
         if (ctx->lanes[k].done) hipEventDestroy(ctx->lanes[k].done);
         if (ctx->lanes[k].graph_exec) hipGraphExecDestroy(ctx->lanes[k].graph_exec);
         if (ctx->lanes[k].graph) hipGraphDestroy(ctx->lanes[k].graph);
-        if (ctx->lanes[k].d_fp) hipFree(ctx->lanes[k].d_fp);
     }
     if (ctx->marker) hipEventDestroy(ctx->marker);
     for (auto &pr : ctx->ev_extend) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
@@ -1050,7 +1055,7 @@ void lupin_hip_destroy_context(LupinContext *ctx)
     for (auto &pr : ctx->ev_total) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     for (auto e : ctx->ev_pool) hipEventDestroy(e);
     for (int k = 0; k < LP_MAX_LANES; k++) if (ctx->lanes[k].stream) hipStreamDestroy(ctx->lanes[k].stream);
-    delete ctx;
+    delete ctx;   // frees every device buffer of the context and its lanes, after the streams are gone: safe only because sync_all above drained them
 }
 
 int lupin_hip_sync(LupinContext *ctx)
@@ -1597,8 +1602,7 @@ void lupin_hip_scene_destroy(LupinScene *scene)
     if (!scene) return;
     hipSetDevice(scene->device);
     if (ctx_alive(scene->ctx)) sync_all(scene->ctx);   // a destroyed context has drained its streams already
-    for (void *p : scene->allocations) hipFree(p);
-    delete scene;
+    delete scene;   // frees its allocations: after the synchronisation above
 }
 
 // Moves the instances in place.  Everything is validated and built in host staging first; device memory is
@@ -1730,6 +1734,15 @@ int64_t lupin_hip_scene_get_tlas(const LupinScene *scene, LupinTlasNode *out_nod
 
 // ---- textures / double buffering ----
 
+// The texture has its f32 shadow: made and cleared on `st` by the first call that needs it, kept afterwards.
+static int ensure_accum32(LupinTexture *tex, hipStream_t st)
+{
+    if (tex->accum32) return LUPIN_OK;
+    HIP_TRY(device_view(&tex->accum32_mem, (size_t)tex->width * tex->height, &tex->accum32));
+    HIP_TRY(hipMemsetAsync(tex->accum32, 0, (size_t)tex->width * tex->height * sizeof(float4), st));
+    return LUPIN_OK;
+}
+
 int lupin_hip_texture_create(LupinContext *ctx, uint32_t width, uint32_t height, LupinTexture **out_tex)
 {
     CTX_ALIVE_TRY(ctx);
@@ -1738,7 +1751,7 @@ int lupin_hip_texture_create(LupinContext *ctx, uint32_t width, uint32_t height,
     LupinTexture *t = new LupinTexture();
     t->ctx = ctx; t->device = ctx->device; t->width = width; t->height = height; t->data = nullptr; t->accum32 = nullptr; t->accum32_valid = false;
     size_t bytes = (size_t)width * height * 4 * sizeof(__half);
-    hipError_t e = hipMalloc((void **)&t->data, bytes);
+    hipError_t e = device_view(&t->data_mem, (size_t)width * height * 4, &t->data);
     if (e != hipSuccess) { delete t; return fail(LUPIN_ERR_OUT_OF_MEMORY, hipGetErrorString(e)); }
     hipMemsetAsync(t->data, 0, bytes, ctx->stream);
     *out_tex = t;
@@ -1749,9 +1762,7 @@ void lupin_hip_texture_destroy(LupinTexture *tex)
     if (!tex) return;
     hipSetDevice(tex->device);
     if (ctx_alive(tex->ctx)) sync_all(tex->ctx);
-    hipFree(tex->data);
-    if (tex->accum32) hipFree(tex->accum32);
-    delete tex;
+    delete tex;   // frees the texels and the f32 shadow: after the synchronisation above
 }
 uint32_t lupin_hip_texture_width(const LupinTexture *tex) { return tex ? tex->width : 0; }
 uint32_t lupin_hip_texture_height(const LupinTexture *tex) { return tex ? tex->height : 0; }
@@ -1822,7 +1833,7 @@ int lupin_hip_dbuf_copy_front_to_back(LupinDoubleBufferedTexture *t)
     b->accum32_valid = false;
     if (f->accum32 && f->accum32_valid)
     {
-        if (!b->accum32) HIP_TRY(hipMalloc((void **)&b->accum32, (size_t)f->width * f->height * 16));
+        if (int rc = ensure_accum32(b, t->ctx->stream)) return rc;
         HIP_TRY(hipMemcpyAsync(b->accum32, f->accum32, (size_t)f->width * f->height * 16, hipMemcpyDeviceToDevice, t->ctx->stream));
         b->accum32_valid = true;
     }
@@ -2026,7 +2037,6 @@ static int flush_pending(LupinContext *ctx)
     const uint32_t n = K * frame_slots;                         // slots of the wavefront
     LupinTexture *render_target = ctx->pending.back().target;    // (f32 accumulation is never batched: K == 1 there)
     const LupinTexture *prev = ctx->pending.front().prev;
-    const uint32_t W = fp.width, H = fp.height;
     LupinAdaptiveResources *adaptive = ctx->pending.front().adaptive;   // (adaptive calls are never batched: K == 1 there)
 
     // Lane choice: consecutive wavefronts alternate over `lanes` streams so that they overlap; per-kernel timing needs them serial.
@@ -2141,11 +2151,7 @@ static int flush_pending(LupinContext *ctx)
     float4 *out32 = nullptr;
     if (ctx->accum_mode == LUPIN_ACCUM_F32)
     {
-        if (!render_target->accum32)
-        {
-            HIP_TRY(hipMalloc((void **)&render_target->accum32, (size_t)W * H * 16));
-            HIP_TRY(hipMemsetAsync(render_target->accum32, 0, (size_t)W * H * 16, st));
-        }
+        if (int rc = ensure_accum32(render_target, st)) return rc;
         out32 = render_target->accum32;
         if (prev && prev->accum32 && prev->accum32_valid) prev32 = prev->accum32;
     }
@@ -2620,17 +2626,6 @@ static int query_start(LupinContext *ctx, const LupinScene *scene, bool on_devic
         if (int rc = refuse_bad_host_records<Rule>(n, records)) return rc;
     if (int rc = query_plan(ctx, scene, scene->stack_entries, t)) return rc;
     return on_device ? refuse_bad_device_records<Rule>(ctx, n, records) : LUPIN_OK;
-}
-
-// *buf, a buffer the context keeps from call to call, holds at least `bytes`: kept when it is large enough, replaced otherwise
-// (the stream has finished with the old one: every call ends synchronised)
-static hipError_t grow_buffer(DeviceBuffer *buf, size_t *have, size_t bytes)
-{
-    if (*have >= bytes) return hipSuccess;
-    DeviceBuffer b;
-    const hipError_t e = DeviceBuffer::make(bytes, &b);
-    if (e == hipSuccess) { *buf = std::move(b); *have = bytes; }
-    return e;
 }
 
 // The path queries (radiance queries, probe bakes: DESIGN.md 13, 15).
@@ -3261,8 +3256,8 @@ int lupin_hip_tonemap_and_fit_aspect(LupinContext *ctx, const LupinTexture *src,
     a.sc_y1 = (uint32_t)std::min<uint64_t>((uint64_t)a.sc_y0 + (uint32_t)a.vp_h, dst_height);
 
     const size_t bytes = (size_t)dst_width * dst_height * 4;
-    uint32_t *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, bytes));
+    DeviceArray<uint32_t> d;   // freed on every return: each path below ends synchronised or failed
+    HIP_TRY(d.alloc((size_t)dst_width * dst_height));
     join_primary(ctx);
     hipError_t e;
     if (desc->clear)   // LoadOp::Clear(0, 0, 0, 1) over the whole attachment
@@ -3280,7 +3275,6 @@ int lupin_hip_tonemap_and_fit_aspect(LupinContext *ctx, const LupinTexture *src,
     }
     if (e == hipSuccess) e = hipMemcpyAsync(dst_rgba8, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    hipFree(d);
     if (e != hipSuccess) return fail(LUPIN_ERR_HIP, hipGetErrorString(e));
     return LUPIN_OK;
 }
@@ -3295,8 +3289,8 @@ struct LupinDenoiseResources
     LupinContext *ctx;
     int device;
     uint32_t width, height;
-    float4 *iv[2];          // (irradiance rgb, variance) ping-pong
-    DenoiseGuide *guide;    // normalised normals + albedo, written by the prep pass
+    DeviceArray<float4> iv[2];          // (irradiance rgb, variance) ping-pong
+    DeviceArray<DenoiseGuide> guide;    // normalised normals + albedo, written by the prep pass
 };
 
 template <bool FINAL>
@@ -3319,14 +3313,12 @@ int lupin_hip_build_denoise_resources(LupinContext *ctx, uint32_t width, uint32_
     HIP_TRY(hipSetDevice(ctx->device));
     LupinDenoiseResources *r = new LupinDenoiseResources();
     r->ctx = ctx; r->device = ctx->device; r->width = width; r->height = height;
-    r->iv[0] = r->iv[1] = nullptr; r->guide = nullptr;
     const size_t px = (size_t)width * height;
-    hipError_t e = hipMalloc((void **)&r->iv[0], px * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc((void **)&r->iv[1], px * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc((void **)&r->guide, px * sizeof(DenoiseGuide));
+    hipError_t e = r->iv[0].alloc(px);
+    if (e == hipSuccess) e = r->iv[1].alloc(px);
+    if (e == hipSuccess) e = r->guide.alloc(px);
     if (e != hipSuccess)
     {
-        hipFree(r->iv[0]); hipFree(r->iv[1]); hipFree(r->guide);
         delete r;
         return fail(LUPIN_ERR_OUT_OF_MEMORY, hipGetErrorString(e));
     }
@@ -3339,8 +3331,7 @@ void lupin_hip_destroy_denoise_resources(LupinDenoiseResources *res)
     if (!res) return;
     hipSetDevice(res->device);
     if (ctx_alive(res->ctx)) sync_all(res->ctx);   // a destroyed context has drained its streams already
-    hipFree(res->iv[0]); hipFree(res->iv[1]); hipFree(res->guide);
-    delete res;
+    delete res;   // frees its buffers: after the synchronisation above
 }
 
 int lupin_hip_denoise(LupinContext *ctx, LupinDenoiseResources *res, const LupinDenoiseDesc *desc)
@@ -3390,13 +3381,6 @@ int lupin_hip_denoise(LupinContext *ctx, LupinDenoiseResources *res, const Lupin
 
 extern "C" {
 
-static void free_adaptive(LupinAdaptiveResources *r)
-{
-    hipFree(r->dev.frames); hipFree(r->dev.moments); hipFree(r->dev.block_error); hipFree(r->dev.block_flags);
-    hipFree(r->dev.block_active); hipFree(r->dev.block_count); hipFree(r->dev.stats);
-    delete r;
-}
-
 static void launch_adaptive_reset(LupinContext *ctx, LupinAdaptiveResources *r)
 {
     const size_t pixels = (size_t)r->dev.width * r->dev.height;   // >= the block count
@@ -3411,22 +3395,21 @@ int lupin_hip_build_adaptive_resources(LupinContext *ctx, uint32_t width, uint32
     if ((uint64_t)width * height > 0xFFFFFFFFull / 2) return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive size too large");
     HIP_TRY(hipSetDevice(ctx->device));
     LupinAdaptiveResources *r = new LupinAdaptiveResources();
-    memset(&r->dev, 0, sizeof(r->dev));
-    r->ctx = ctx; r->device = ctx->device; r->calls = 0;
+    r->ctx = ctx; r->device = ctx->device;
     AdaptiveDev &d = r->dev;
     d.width = width; d.height = height;
     d.blocks_x = (width + LP_AD_BLOCK - 1) / LP_AD_BLOCK; d.blocks_y = (height + LP_AD_BLOCK - 1) / LP_AD_BLOCK;
     const size_t px = (size_t)width * height, nb = (size_t)d.blocks_x * d.blocks_y;
-    hipError_t e = hipMalloc((void **)&d.frames, px * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d.moments, px * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc((void **)&d.block_error, nb * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&d.block_flags, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&d.block_active, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&d.block_count, nb * sizeof(uint2));
-    if (e == hipSuccess) e = hipMalloc((void **)&d.stats, 3 * sizeof(unsigned long long));
+    hipError_t e = device_view(&r->frames, px, &d.frames);
+    if (e == hipSuccess) e = device_view(&r->moments, px, &d.moments);
+    if (e == hipSuccess) e = device_view(&r->block_error, nb, &d.block_error);
+    if (e == hipSuccess) e = device_view(&r->block_flags, nb, &d.block_flags);
+    if (e == hipSuccess) e = device_view(&r->block_active, nb, &d.block_active);
+    if (e == hipSuccess) e = device_view(&r->block_count, nb, &d.block_count);
+    if (e == hipSuccess) e = device_view(&r->stats, 3, &d.stats);
     if (e != hipSuccess)
     {
-        free_adaptive(r);
+        delete r;
         return fail(LUPIN_ERR_OUT_OF_MEMORY, hipGetErrorString(e));
     }
     launch_adaptive_reset(ctx, r);   // primary stream: every adaptive call waits for it (flush_pending)
@@ -3434,7 +3417,7 @@ int lupin_hip_build_adaptive_resources(LupinContext *ctx, uint32_t width, uint32
     if (e != hipSuccess)
     {
         hipStreamSynchronize(ctx->stream);
-        free_adaptive(r);
+        delete r;
         return fail(LUPIN_ERR_HIP, hipGetErrorString(e));
     }
     *out = r;
@@ -3446,7 +3429,7 @@ void lupin_hip_destroy_adaptive_resources(LupinAdaptiveResources *res)
     if (!res) return;
     hipSetDevice(res->device);
     if (ctx_alive(res->ctx)) sync_all(res->ctx);   // a destroyed context has drained its streams already
-    free_adaptive(res);
+    delete res;   // frees its buffers: after the synchronisation above
 }
 
 int lupin_hip_adaptive_reset(LupinContext *ctx, LupinAdaptiveResources *res)
@@ -3526,43 +3509,38 @@ int lupin_hip_adaptive_download(LupinContext *ctx, const LupinAdaptiveResources 
 
 struct LupinReprojectResources
 {
-    LupinContext *ctx;
-    int device;
-    uint32_t width, height;
-    ReprojectVis vis[2];             // [cur] is written by a call's trace; [cur ^ 1] is the previous call's
-    int cur;
-    uint32_t *frames;                // the gather's output, swapped with the adaptive resources' arrays after it
-    float2 *moments;
-    bool prev_valid;
-    LupinPushConstants prev_pc;      // the previous call's camera
-    LupinMat3x4 prev_cam_inv;
+    LupinContext *ctx = nullptr;
+    int device = 0;
+    uint32_t width = 0, height = 0;
+    ReprojectVis vis[2] = {};        // [cur] is written by a call's trace; [cur ^ 1] is the previous call's: the plain views the kernels get
+    DeviceBuffer vis_inst[2], vis_tri[2], vis_uv[2], vis_depth[2];   // own what vis[k]'s pointers point to
+    int cur = 0;
+    DeviceArray<uint32_t> frames;    // the gather's output, swapped with the adaptive resources' arrays after it (swap_gathered)
+    DeviceArray<float2> moments;
+    bool prev_valid = false;
+    LupinPushConstants prev_pc{};    // the previous call's camera
+    LupinMat3x4 prev_cam_inv{};
     // previous local -> world rows of every instance: two pinned staging buffers used in turn (a call never waits for the
     // copy of the call before it) and their device copy, allocated by the first call, grown on demand
-    float4 *h_rows[2], *d_rows;
-    uint32_t rows_capacity;          // instances
-    hipEvent_t rows_copied[2];       // staging buffer k may be rewritten once rows_copied[k] has passed
-    int rows_next;
+    PinnedBuffer h_rows[2];
+    DeviceArray<float4> d_rows;
+    uint32_t rows_capacity = 0;      // instances
+    Event rows_copied[2];            // staging buffer k may be rewritten once rows_copied[k] has passed
+    int rows_next = 0;
     // LUPIN_STATS_KERNEL_TIMING: events before the trace, between trace and gather, after the gather of the latest call
-    hipEvent_t ev[3];
-    bool timed;                      // the latest call recorded them
+    Event ev[3];
+    bool timed = false;              // the latest call recorded them
 };
 
-extern "C" {
-
-static void free_vis(ReprojectVis &v) { hipFree(v.inst); hipFree(v.tri); hipFree(v.uv); hipFree(v.depth); }
-static void free_reproject(LupinReprojectResources *r)
+// The gathered counts and moments become the adaptive state and the old state becomes the next gather's output: the owners
+// trade places and the adaptive kernels' view follows, here and nowhere else.
+static void swap_gathered(LupinAdaptiveResources *ares, LupinReprojectResources *res)
 {
-    free_vis(r->vis[0]); free_vis(r->vis[1]);
-    hipFree(r->frames); hipFree(r->moments); hipFree(r->d_rows);
-    for (int k = 0; k < 2; k++)
-    {
-        if (r->h_rows[k]) hipHostFree(r->h_rows[k]);
-        if (r->rows_copied[k]) hipEventDestroy(r->rows_copied[k]);
-    }
-    for (int k = 0; k < 3; k++)
-        if (r->ev[k]) hipEventDestroy(r->ev[k]);
-    delete r;
+    ares->frames.swap(res->frames); ares->moments.swap(res->moments);
+    ares->dev.frames = ares->frames.as<uint32_t>(); ares->dev.moments = ares->moments.as<float2>();
 }
+
+extern "C" {
 
 int lupin_hip_build_reproject_resources(LupinContext *ctx, uint32_t width, uint32_t height, LupinReprojectResources **out)
 {
@@ -3571,31 +3549,30 @@ int lupin_hip_build_reproject_resources(LupinContext *ctx, uint32_t width, uint3
     if ((uint64_t)width * height > 0xFFFFFFFFull / 2) return fail(LUPIN_ERR_INVALID_ARGUMENT, "reproject size too large");
     HIP_TRY(hipSetDevice(ctx->device));
     LupinReprojectResources *r = new LupinReprojectResources();
-    memset(r, 0, sizeof(*r));
     r->ctx = ctx; r->device = ctx->device; r->width = width; r->height = height;
     const size_t px = (size_t)width * height;
     hipError_t e = hipSuccess;
     for (int k = 0; k < 2 && e == hipSuccess; k++)
     {
         ReprojectVis &v = r->vis[k];
-        e = hipMalloc((void **)&v.inst, px * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&v.tri, px * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&v.uv, px * sizeof(float2));
-        if (e == hipSuccess) e = hipMalloc((void **)&v.depth, px * sizeof(float));
+        e = device_view(&r->vis_inst[k], px, &v.inst);
+        if (e == hipSuccess) e = device_view(&r->vis_tri[k], px, &v.tri);
+        if (e == hipSuccess) e = device_view(&r->vis_uv[k], px, &v.uv);
+        if (e == hipSuccess) e = device_view(&r->vis_depth[k], px, &v.depth);
         // a download before the first call reads misses, not uninitialised memory
         if (e == hipSuccess) e = hipMemsetAsync(v.inst, 0xFF, px * sizeof(uint32_t), ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(v.tri, 0, px * sizeof(uint32_t), ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(v.uv, 0, px * sizeof(float2), ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(v.depth, 0, px * sizeof(float), ctx->stream);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&r->frames, px * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&r->moments, px * sizeof(float2));
-    for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipEventCreateWithFlags(&r->rows_copied[k], hipEventDisableTiming);
-    for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipEventCreate(&r->ev[k]);
+    if (e == hipSuccess) e = r->frames.alloc(px);
+    if (e == hipSuccess) e = r->moments.alloc(px);
+    for (int k = 0; k < 2 && e == hipSuccess; k++) e = r->rows_copied[k].create(hipEventDisableTiming);
+    for (int k = 0; k < 3 && e == hipSuccess; k++) e = r->ev[k].create();
     if (e != hipSuccess)
     {
         hipStreamSynchronize(ctx->stream);
-        free_reproject(r);
+        delete r;
         return fail(LUPIN_ERR_OUT_OF_MEMORY, hipGetErrorString(e));
     }
     *out = r;
@@ -3607,7 +3584,7 @@ void lupin_hip_destroy_reproject_resources(LupinReprojectResources *res)
     if (!res) return;
     hipSetDevice(res->device);
     if (ctx_alive(res->ctx)) sync_all(res->ctx);   // a destroyed context has drained its streams already
-    free_reproject(res);
+    delete res;   // frees its buffers and events: after the synchronisation above
 }
 
 int lupin_hip_reproject_invalidate(LupinContext *ctx, LupinReprojectResources *res)
@@ -3675,22 +3652,17 @@ int lupin_hip_adaptive_reproject(LupinContext *ctx, LupinAdaptiveResources *ares
         // the first call allocates; only a later call with a scene of more instances finds buffers that an earlier call's
         // copy or gather may still read, and waits for them
         if (res->rows_capacity) HIP_TRY(hipStreamSynchronize(st));
-        if (res->d_rows) { hipFree(res->d_rows); res->d_rows = nullptr; }
-        for (int k = 0; k < 2; k++)
-            if (res->h_rows[k]) { hipHostFree(res->h_rows[k]); res->h_rows[k] = nullptr; }
+        res->d_rows.reset();
+        for (PinnedBuffer &h : res->h_rows) h.reset();
         res->rows_capacity = 0;
-        HIP_TRY(hipMalloc((void **)&res->d_rows, (size_t)ninst * 3 * sizeof(float4)));
-        for (int k = 0; k < 2; k++) HIP_TRY(hipHostMalloc((void **)&res->h_rows[k], (size_t)ninst * 3 * sizeof(float4)));
+        HIP_TRY(res->d_rows.alloc((size_t)ninst * 3));
+        for (PinnedBuffer &h : res->h_rows) HIP_TRY(PinnedBuffer::make((size_t)ninst * 3 * sizeof(float4), &h));
         res->rows_capacity = ninst;
     }
     float4 *out32 = nullptr;
     if (ctx->accum_mode == LUPIN_ACCUM_F32)
     {
-        if (!history_out->accum32)
-        {
-            HIP_TRY(hipMalloc((void **)&history_out->accum32, (size_t)W * H * 16));
-            HIP_TRY(hipMemsetAsync(history_out->accum32, 0, (size_t)W * H * 16, st));
-        }
+        if (int rc = ensure_accum32(history_out, st)) return rc;
         out32 = history_out->accum32;
     }
     if (ninst)
@@ -3698,8 +3670,8 @@ int lupin_hip_adaptive_reproject(LupinContext *ctx, LupinAdaptiveResources *ares
         const int k = res->rows_next;
         res->rows_next ^= 1;
         HIP_TRY(hipEventSynchronize(res->rows_copied[k]));   // the copy of the call before the previous one: passed unless three calls are in flight
-        memcpy(res->h_rows[k], rows.data(), rows.size() * sizeof(float4));
-        HIP_TRY(hipMemcpyAsync(res->d_rows, res->h_rows[k], rows.size() * sizeof(float4), hipMemcpyHostToDevice, st));
+        memcpy(res->h_rows[k].get(), rows.data(), rows.size() * sizeof(float4));
+        HIP_TRY(hipMemcpyAsync(res->d_rows, res->h_rows[k].get(), rows.size() * sizeof(float4), hipMemcpyHostToDevice, st));
         HIP_TRY(hipEventRecord(res->rows_copied[k], st));
     }
     res->timed = ctx->timing;
@@ -3746,8 +3718,7 @@ int lupin_hip_adaptive_reproject(LupinContext *ctx, LupinAdaptiveResources *ares
     if (res->timed) hipEventRecord(res->ev[2], st);
 
     // ---- step 3: the gathered counts and moments become the adaptive state; every block active; statistics ----
-    std::swap(ares->dev.frames, res->frames);
-    std::swap(ares->dev.moments, res->moments);
+    swap_gathered(ares, res);
     const AdaptiveDev &ad = ares->dev;
     const uint32_t nblocks = ad.blocks_x * ad.blocks_y;
     HIP_TRY(hipMemsetAsync(ad.stats, 0, 3 * sizeof(unsigned long long), st));

@@ -2,31 +2,53 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
-#include <utility>
+#include <string>
 #include "../../include/lupin_hip.h"
+#include "lupin_owned.hpp"
 
-// A scratch device allocation that lives as long as its holder: hipMalloc in make(), hipFree in the destructor.  Move-only.
-class DeviceBuffer
+// Every allocation of the library has one of these owners (lupin_owned.hpp); only here are the four calls named.
+struct HipStatus { using Error = hipError_t; static constexpr hipError_t success = hipSuccess; };
+struct DeviceMemoryApi : HipStatus
 {
-    void *p_ = nullptr;
+    static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void *p) { hipFree(p); }
+};
+struct PinnedMemoryApi : HipStatus
+{
+    static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes); }
+    static void free(void *p) { hipHostFree(p); }
+};
+using DeviceBuffer = Owned<DeviceMemoryApi>;
+using PinnedBuffer = Owned<PinnedMemoryApi>;
+
+// A DeviceBuffer that knows its element type: it converts to T * where a kernel launch or a copy takes one.
+template <typename T> struct DeviceArray : DeviceBuffer
+{
+    hipError_t alloc(size_t count) { return DeviceBuffer::make(count * sizeof(T), this); }
+    T *get() const { return as<T>(); }
+    operator T *() const { return as<T>(); }
+};
+
+// *owner holds `count` elements of T and *view, the plain pointer of a kernel's argument struct, points to them, or both stay as they were
+template <typename T> static inline hipError_t device_view(DeviceBuffer *owner, size_t count, T **view)
+{
+    const hipError_t e = DeviceBuffer::make(count * sizeof(T), owner);
+    if (e == hipSuccess) *view = owner->as<T>();
+    return e;
+}
+
+// An event whose whole life is inside one function or one resource object.
+class Event
+{
+    hipEvent_t e_ = nullptr;
 
 public:
-    DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer &) = delete;
-    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
-    DeviceBuffer(DeviceBuffer &&o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
-    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { std::swap(p_, o.p_); return *this; }   // o's destructor frees what this held
-    ~DeviceBuffer() { if (p_) hipFree(p_); }
-    // *out holds `bytes` of device memory, or stays as it was if the allocation fails
-    static hipError_t make(size_t bytes, DeviceBuffer *out)
-    {
-        DeviceBuffer b;
-        const hipError_t e = hipMalloc(&b.p_, bytes);
-        if (e == hipSuccess) *out = std::move(b);
-        return e;
-    }
-    void *get() const { return p_; }
-    template <typename T> T *as() const { return static_cast<T *>(p_); }
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e_) hipEventDestroy(e_); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e_, flags); }
+    operator hipEvent_t() const { return e_; }
 };
 
 struct LupinTexture
@@ -34,12 +56,15 @@ struct LupinTexture
     LupinContext *ctx;
     int device;            // the context's device ordinal (valid after the context is gone: a texture may outlive it)
     uint32_t width, height;
+    DeviceBuffer data_mem, accum32_mem;   // own what the two views below point to
     __half *data;          // Rgba16Float, row-major, row 0 = top
-    float4 *accum32;       // f32 shadow (LUPIN_ACCUM_F32), allocated by the first frame rendered into it in that mode
+    float4 *accum32;       // f32 shadow (LUPIN_ACCUM_F32), made by ensure_accum32 for the first frame rendered into it in that mode
     bool accum32_valid;    // the shadow holds the value `data` is the rounded view of
 };
 
 int lupin_internal_fail(int code, const char *msg);          // records the message lupin_hip_last_error() returns
+// the one error macro of the library's HIP calls: returns LUPIN_ERR_HIP with "<expression>: <HIP's error string>"
+#define HIP_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return lupin_internal_fail(LUPIN_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); } while (0)
 bool lupin_internal_ctx_alive(const LupinContext *ctx);       // created by lupin_hip_create_context and not destroyed since
 int lupin_internal_ctx_device(const LupinContext *ctx);
 hipStream_t lupin_internal_ctx_stream(const LupinContext *ctx);   // the primary stream

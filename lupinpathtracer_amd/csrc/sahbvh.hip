@@ -29,8 +29,6 @@
 
 namespace {
 
-#define SAH_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { cleanup(); return lupin_internal_fail(LUPIN_ERR_HIP, hipGetErrorString(e__)); } } while (0)
-
 constexpr int kBlock = 256;
 constexpr int NUM_BINS = 5;
 constexpr uint32_t INACTIVE = 0xFFFFFFFFu;
@@ -360,50 +358,36 @@ int64_t lupin_hip_build_bvh_sah_device(LupinContext *ctx, const float *verts_pos
     hipStream_t st = lupin_internal_ctx_stream(ctx);
     const uint64_t max_nodes = 2ull * n - 1ull;
 
-    float4 *d_verts = nullptr, *d_lo = nullptr, *d_hi = nullptr, *d_cen = nullptr;
-    uint32_t *d_idx = nullptr, *d_idx_out = nullptr, *d_perm[2] = {nullptr, nullptr}, *d_pslot[2] = {nullptr, nullptr}, *d_flags = nullptr, *d_scan = nullptr;
-    uint32_t *d_root = nullptr, *d_cb = nullptr, *d_bins = nullptr, *d_valid = nullptr, *d_valid_scan = nullptr;
-    LupinBvhNode *d_nodes = nullptr;
-    Slot *d_slots[2] = {nullptr, nullptr};
-    SplitDev *d_splits = nullptr;
-    void *d_temp = nullptr;
-    auto cleanup = [&]() {
-        void *ptrs[] = {d_verts, d_lo, d_hi, d_cen, d_idx, d_idx_out, d_perm[0], d_perm[1], d_pslot[0], d_pslot[1], d_flags, d_scan, d_root, d_cb, d_bins, d_valid,
-                        d_valid_scan, d_nodes, d_slots[0], d_slots[1], d_splits, d_temp};
-        for (void *p : ptrs) if (p) hipFree(p);
-    };
+    // scratch of this build, freed when the function returns, by whichever path
+    DeviceArray<float4> d_verts, d_lo, d_hi, d_cen;
+    DeviceArray<uint32_t> d_idx, d_idx_out, d_perm[2], d_pslot[2], d_flags, d_scan, d_root, d_cb, d_bins, d_valid, d_valid_scan;
+    DeviceArray<LupinBvhNode> d_nodes;
+    DeviceArray<Slot> d_slots[2];
+    DeviceArray<SplitDev> d_splits;
+    DeviceBuffer d_temp;
     const size_t slot_cap = (size_t)n + 2;   // a level never has more frontier nodes than triangles
-    SAH_TRY(hipMalloc((void **)&d_verts, (size_t)num_verts * 16));
-    SAH_TRY(hipMalloc((void **)&d_lo, (size_t)n * 16));
-    SAH_TRY(hipMalloc((void **)&d_hi, (size_t)n * 16));
-    SAH_TRY(hipMalloc((void **)&d_cen, (size_t)n * 16));
-    SAH_TRY(hipMalloc((void **)&d_idx, (size_t)num_indices * 4));
-    SAH_TRY(hipMalloc((void **)&d_idx_out, (size_t)num_indices * 4));
-    for (int k = 0; k < 2; k++)
-    {
-        SAH_TRY(hipMalloc((void **)&d_perm[k], (size_t)n * 4));
-        SAH_TRY(hipMalloc((void **)&d_pslot[k], (size_t)n * 4));
-        SAH_TRY(hipMalloc((void **)&d_slots[k], slot_cap * sizeof(Slot)));
-    }
-    SAH_TRY(hipMalloc((void **)&d_flags, ((size_t)n + 1) * 4));
-    SAH_TRY(hipMalloc((void **)&d_scan, ((size_t)n + 1) * 4));
-    SAH_TRY(hipMalloc((void **)&d_root, 6 * 4));
-    SAH_TRY(hipMalloc((void **)&d_cb, slot_cap * 6 * 4));
-    SAH_TRY(hipMalloc((void **)&d_bins, slot_cap * SLOT_BIN_WORDS * 4));
-    SAH_TRY(hipMalloc((void **)&d_valid, (slot_cap + 1) * 4));
-    SAH_TRY(hipMalloc((void **)&d_valid_scan, (slot_cap + 1) * 4));
-    SAH_TRY(hipMalloc((void **)&d_nodes, (size_t)max_nodes * sizeof(LupinBvhNode)));
-    SAH_TRY(hipMalloc((void **)&d_splits, slot_cap * sizeof(SplitDev)));
+    HIP_TRY(d_verts.alloc(num_verts));
+    for (auto *a : {&d_lo, &d_hi, &d_cen}) HIP_TRY(a->alloc(n));
+    for (auto *a : {&d_idx, &d_idx_out}) HIP_TRY(a->alloc(num_indices));
+    for (auto *a : {&d_perm[0], &d_perm[1], &d_pslot[0], &d_pslot[1]}) HIP_TRY(a->alloc(n));
+    for (auto *a : {&d_slots[0], &d_slots[1]}) HIP_TRY(a->alloc(slot_cap));
+    for (auto *a : {&d_flags, &d_scan}) HIP_TRY(a->alloc((size_t)n + 1));
+    HIP_TRY(d_root.alloc(6));
+    HIP_TRY(d_cb.alloc(slot_cap * 6));
+    HIP_TRY(d_bins.alloc(slot_cap * SLOT_BIN_WORDS));
+    for (auto *a : {&d_valid, &d_valid_scan}) HIP_TRY(a->alloc(slot_cap + 1));
+    HIP_TRY(d_nodes.alloc(max_nodes));
+    HIP_TRY(d_splits.alloc(slot_cap));
     size_t temp_bytes = 0, temp2 = 0;
-    SAH_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_flags, d_scan, (int)(n + 1), st));
-    SAH_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp2, d_valid, d_valid_scan, (int)(slot_cap + 1), st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_flags.get(), d_scan.get(), (int)(n + 1), st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp2, d_valid.get(), d_valid_scan.get(), (int)(slot_cap + 1), st));
     temp_bytes = std::max(std::max(temp_bytes, temp2), (size_t)16);
-    SAH_TRY(hipMalloc(&d_temp, temp_bytes));
+    HIP_TRY(DeviceBuffer::make(temp_bytes, &d_temp));
 
-    SAH_TRY(hipMemcpyAsync(d_verts, verts_pos4, (size_t)num_verts * 16, hipMemcpyHostToDevice, st));
-    SAH_TRY(hipMemcpyAsync(d_idx, indices, (size_t)num_indices * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_verts, verts_pos4, (size_t)num_verts * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_idx, indices, (size_t)num_indices * 4, hipMemcpyHostToDevice, st));
     const uint32_t zero_box[6] = {0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u};   // f2ord(0.0f) on both sides
-    SAH_TRY(hipMemcpyAsync(d_root, zero_box, sizeof(zero_box), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_root, zero_box, sizeof(zero_box), hipMemcpyHostToDevice, st));
 
     const uint32_t tri_blocks = (n + kBlock - 1) / kBlock, tri_blocks1 = (n + 1 + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(k_prepare, dim3(tri_blocks), dim3(kBlock), 0, st, d_verts, d_idx, n, d_lo, d_hi, d_cen, d_perm[0], d_pslot[0], d_root);
@@ -421,32 +405,31 @@ int64_t lupin_hip_build_bvh_sah_device(LupinContext *ctx, const float *verts_pos
         hipLaunchKernelGGL(k_bins, dim3(tri_blocks), dim3(kBlock), 0, st, n, d_perm[cur], d_pslot[cur], d_cen, d_lo, d_hi, d_cb, d_bins);
         hipLaunchKernelGGL(k_choose_split, dim3(slot_blocks), dim3(kBlock), 0, st, nslots, d_slots[cur], d_nodes, d_cb, d_bins, d_splits);
         hipLaunchKernelGGL(k_flags, dim3(tri_blocks1), dim3(kBlock), 0, st, n, d_perm[cur], d_pslot[cur], d_cen, d_splits, d_flags);
-        SAH_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_flags, d_scan, (int)(n + 1), st));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp.get(), temp_bytes, d_flags.get(), d_scan.get(), (int)(n + 1), st));
         hipLaunchKernelGGL(k_valid, dim3(slot_blocks1), dim3(kBlock), 0, st, nslots, d_slots[cur], d_scan, d_splits, d_valid);
-        SAH_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_valid, d_valid_scan, (int)(nslots + 1), st));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp.get(), temp_bytes, d_valid.get(), d_valid_scan.get(), (int)(nslots + 1), st));
         uint32_t nvalid = 0;
-        SAH_TRY(hipMemcpyAsync(&nvalid, d_valid_scan + nslots, 4, hipMemcpyDeviceToHost, st));
-        SAH_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(&nvalid, d_valid_scan + nslots, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         if (nvalid == 0) break;
-        if ((uint64_t)num_nodes + 2ull * nvalid > max_nodes) { cleanup(); return lupin_internal_fail(LUPIN_ERR_HIP, "SAH builder produced more nodes than a binary tree can hold"); }
+        if ((uint64_t)num_nodes + 2ull * nvalid > max_nodes) return lupin_internal_fail(LUPIN_ERR_HIP, "SAH builder produced more nodes than a binary tree can hold");
         // the depth of a level is uniform: every slot of this level has the same depth, so either all valid splits push their children or none does
         hipLaunchKernelGGL(k_make_children, dim3(slot_blocks), dim3(kBlock), 0, st, nslots, d_slots[cur], d_splits, d_valid_scan, num_nodes, d_nodes, d_slots[1 - cur], max_depth_to_push);
         hipLaunchKernelGGL(k_scatter, dim3(tri_blocks), dim3(kBlock), 0, st, n, d_perm[cur], d_pslot[cur], d_flags, d_scan, d_slots[cur], d_splits, max_depth_to_push, d_perm[1 - cur], d_pslot[1 - cur]);
         num_nodes += 2u * nvalid;
         // depth of this level = 1 + number of levels done; children join the frontier while depth < BVH_MAX_DEPTH - 1
         Slot first_slot;
-        SAH_TRY(hipMemcpyAsync(&first_slot, d_slots[cur], sizeof(Slot), hipMemcpyDeviceToHost, st));
-        SAH_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(&first_slot, d_slots[cur], sizeof(Slot), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         nslots = first_slot.depth < max_depth_to_push ? 2u * nvalid : 0u;
         cur = 1 - cur;
     }
-    if (num_nodes > out_capacity) { cleanup(); return lupin_internal_fail(LUPIN_ERR_INVALID_ARGUMENT, "node buffer too small (2 * triangles - 1 always suffices)"); }
+    if (num_nodes > out_capacity) return lupin_internal_fail(LUPIN_ERR_INVALID_ARGUMENT, "node buffer too small (2 * triangles - 1 always suffices)");
     hipLaunchKernelGGL(k_reorder_indices, dim3(tri_blocks), dim3(kBlock), 0, st, n, d_perm[cur], d_idx, d_idx_out);
-    SAH_TRY(hipGetLastError());
-    SAH_TRY(hipMemcpyAsync(out_nodes, d_nodes, (size_t)num_nodes * sizeof(LupinBvhNode), hipMemcpyDeviceToHost, st));
-    SAH_TRY(hipMemcpyAsync(indices, d_idx_out, (size_t)num_indices * 4, hipMemcpyDeviceToHost, st));
-    SAH_TRY(hipStreamSynchronize(st));
-    cleanup();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_nodes, d_nodes, (size_t)num_nodes * sizeof(LupinBvhNode), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(indices, d_idx_out, (size_t)num_indices * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return (int64_t)num_nodes;
 }
 

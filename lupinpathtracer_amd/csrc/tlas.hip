@@ -155,8 +155,6 @@ __global__ __launch_bounds__(kMaxBlock) void k_tlas_cluster(LupinTlasNode *nodes
 
 }  // namespace
 
-#define TLAS_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { cleanup(); return lupin_internal_fail(LUPIN_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e__)).c_str()); } } while (0)
-
 extern "C" {
 
 int64_t lupin_hip_build_tlas_device(LupinContext *ctx, const LupinInstance *instances, uint32_t num_instances,
@@ -185,38 +183,31 @@ int64_t lupin_hip_build_tlas_device(LupinContext *ctx, const LupinInstance *inst
     const bool in_lds = n <= lds_slots;
     const uint32_t block = std::min(kMaxBlock, std::max(64u, (n + 63u) / 64u * 64u));
 
-    LupinTlasNode *d_nodes = nullptr;
-    float *d_state = nullptr;
-    uint32_t *d_status = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto cleanup = [&]() {
-        if (d_nodes) hipFree(d_nodes);
-        if (d_state) hipFree(d_state);
-        if (d_status) hipFree(d_status);
-        if (ev0) hipEventDestroy(ev0);
-        if (ev1) hipEventDestroy(ev1);
-    };
+    // scratch of this build, freed when the function returns, by whichever path
+    DeviceArray<LupinTlasNode> d_nodes;
+    DeviceArray<float> d_state;
+    DeviceArray<uint32_t> d_status;
+    Event ev0, ev1;
     const size_t node_bytes = (size_t)n * 2 * sizeof(LupinTlasNode);
-    TLAS_TRY(hipMalloc((void **)&d_nodes, node_bytes));
-    if (!in_lds) TLAS_TRY(hipMalloc((void **)&d_state, (size_t)n * kFields * sizeof(float)));
-    TLAS_TRY(hipMalloc((void **)&d_status, 4 * sizeof(uint32_t)));
-    TLAS_TRY(hipEventCreate(&ev0));
-    TLAS_TRY(hipEventCreate(&ev1));
-    TLAS_TRY(hipMemcpyAsync(d_nodes, tlas.data(), (size_t)n * sizeof(LupinTlasNode), hipMemcpyHostToDevice, st));
-    TLAS_TRY(hipMemsetAsync(d_status, 0xFF, 4 * sizeof(uint32_t), st));   // a kernel that never ran reads as an error
-    TLAS_TRY(hipEventRecord(ev0, st));
+    HIP_TRY(d_nodes.alloc((size_t)n * 2));
+    if (!in_lds) HIP_TRY(d_state.alloc((size_t)n * kFields));
+    HIP_TRY(d_status.alloc(4));
+    HIP_TRY(ev0.create());
+    HIP_TRY(ev1.create());
+    HIP_TRY(hipMemcpyAsync(d_nodes, tlas.data(), (size_t)n * sizeof(LupinTlasNode), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_status, 0xFF, 4 * sizeof(uint32_t), st));   // a kernel that never ran reads as an error
+    HIP_TRY(hipEventRecord(ev0, st));
     const size_t lds = (kRedWords + (in_lds ? (size_t)n * kFields : 0)) * sizeof(float);
     if (in_lds) hipLaunchKernelGGL(k_tlas_cluster<true>, dim3(1), dim3(block), lds, st, d_nodes, n, d_state, d_status);
     else hipLaunchKernelGGL(k_tlas_cluster<false>, dim3(1), dim3(block), lds, st, d_nodes, n, d_state, d_status);
-    TLAS_TRY(hipGetLastError());
-    TLAS_TRY(hipEventRecord(ev1, st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1, st));
     uint32_t status[4] = {0, 0, 0, 0};
-    TLAS_TRY(hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st));
-    if (n > 1) TLAS_TRY(hipMemcpyAsync(tlas.data() + n, d_nodes + n, (size_t)(n - 1) * sizeof(LupinTlasNode), hipMemcpyDeviceToHost, st));
-    TLAS_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st));
+    if (n > 1) HIP_TRY(hipMemcpyAsync(tlas.data() + n, d_nodes + n, (size_t)(n - 1) * sizeof(LupinTlasNode), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     float ms = 0.0f;
-    TLAS_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    cleanup();
+    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
     g_stats.num_instances = n;
     g_stats.scans = (uint64_t)status[1] | ((uint64_t)status[2] << 32);
     g_stats.state_in_lds = in_lds ? 1u : 0u;
