@@ -624,6 +624,23 @@ inline uint64_t bake_lightmap(const Device &d, const Scene &scene, const Lightma
     return covered;
 }
 
+// lightmap denoising (no reference counterpart): an edge-avoiding a-trous filter in atlas space, guided by the
+// records of the bake; `out_rgba` may be `rgba`
+struct LightmapDenoiseDesc
+{
+    uint32_t width = 0, height = 0;
+    uint32_t passes = 5;              // pass i taps at step 2^i
+    uint32_t normal_squarings = 5;    // w_n = max(0, n_p . n_q)^32
+    uint32_t dilate = 0;              // gutter passes after the filter
+    uint32_t flags = 0;               // LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS
+    float max_stretch = 4.0f;
+};
+inline void denoise_lightmap(const Device &d, const LightmapDenoiseDesc &desc, const float *rgba, const float *records, float *out_rgba)
+{
+    const LupinLightmapDenoiseDesc c{desc.width, desc.height, desc.passes, desc.normal_squarings, desc.dilate, desc.flags, desc.max_stretch};
+    check(lupin_hip_denoise_lightmap(d.raw(), &c, rgba, records, out_rgba));
+}
+
 // light-probe baking (no reference counterpart): radiance over the sphere at points in space, as L2 SH
 struct ProbeDesc
 {

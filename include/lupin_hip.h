@@ -949,6 +949,68 @@ typedef struct LupinLightmapStats {
 } LupinLightmapStats;
 void lupin_hip_lightmap_stats(LupinLightmapStats *out);
 
+/* ---- lightmap denoising (no reference counterpart) ----
+ * An edge-avoiding a-trous filter in atlas space for what lupin_hip_bake_lightmap writes: `rgba` is its out_rgba (or several
+ * bakes with different `counter`, averaged by the caller), `records` its out_records.  No scene is needed.  Texel p is
+ * OWNED when its alpha != 0.  Its record gives the world-space surface point x_p (floats 0..2) and the bake normal n_p
+ * (floats 4..6); the record of a texel that is not owned is never read.  Every float operation below is one rounded f32
+ * operation (no contraction, IEEE division and sqrt); sums run dy outer, dx inner.
+ *
+ * 1. Prep.  p is GUIDED when it is owned, x_p and n_p are finite and | ((nx*nx + ny*ny) + nz*nz) - 1 | <= 1e-4 (the
+ *    radiance query's tolerance).  c_p = rgb with non-finite components set to 0.  Luminance l = (0.2126 r + 0.7152 g) +
+ *    0.0722 b.  var_p = max(0, s2 / cnt - (s1 / cnt) * (s1 / cnt)) with s1 = sum l_q, s2 = sum l_q * l_q, cnt the count, over
+ *    the guided texels q of the in-bounds 3 x 3 neighbourhood of a guided p (dy, dx = -1..1).  The footprint f_p = the
+ *    smallest |x_q - x_p|^2 = (ex*ex + ey*ey) + ez*ez, e = x_q - x_p, over the guided 4-neighbours q of p, or 0 without one.
+ *
+ * 2. `passes` passes, ping-pong; pass i = 0, 1, .. has step 2^i.  For a guided p the taps are q = p + (kx, ky) * 2^i with
+ *    kx, ky = -2..2 and h = (1, 4, 6, 4, 1) / 16.  A tap counts only if it is inside the atlas, guided, and, for q != p,
+ *      |x_q - x_p|^2 <= (K_i * (kx*kx + ky*ky)) * f_p,   K_i = (max_stretch * max_stretch) * 4^i
+ *    -- a neighbour in the atlas that is not a neighbour in space (another chart, across a gutter, behind a fold) is further
+ *    away than the texel spacing allows.  Its weight is
+ *      w = ((h_kx * h_ky) * w_n) * exp_neg(-(|l_p - l_q| * s_p)),   s_p = 1 / (4 * sqrt(var_p) + 1e-4),
+ *      w_n = max((n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z, 0) squared normal_squarings times (the exponent 2^k),
+ *    exp_neg being the f32 exponential of lupin_hip_denoise, l of the pass's input.  Then
+ *      c'_p = (sum w * c_q) / sum w per channel,   var'_p = (sum (w * w) * var_q) / ((sum w) * (sum w)).
+ *    The centre tap always counts, so sum w > 0.  A texel that is not guided keeps c_p through every pass.
+ *
+ * 3. out_rgba: on owned texels rgb of the last pass and the input's alpha.  On the others, with dilate == 0, the input texel
+ *    as it is; with dilate > 0, zeros, then `dilate` gutter passes exactly as lupin_hip_bake_lightmap's, in which the owned
+ *    texels count as filled and nothing else does (whatever the bake's own gutter passes left there does not survive); a
+ *    filled gutter texel has alpha 0.  out_rgba may be the same memory as rgba.
+ *
+ * Ordering as lupin_hip_bake_lightmap: recorded calls run first (their error is returned), the call returns when out_rgba
+ * is complete, frames before and after are unchanged.  LUPIN_ERR_INVALID_ARGUMENT with out_rgba untouched for: a NULL
+ * argument; width or height 0 or above LUPIN_LIGHTMAP_MAX_SIZE; passes 0 or above LUPIN_LIGHTMAP_DENOISE_MAX_PASSES;
+ * normal_squarings above LUPIN_LIGHTMAP_DENOISE_MAX_SQUARINGS; dilate above LUPIN_LIGHTMAP_MAX_DILATE; an unknown flag;
+ * max_stretch not finite or not positive; a destroyed context; with LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS a pointer that
+ * is not 16-byte aligned.  LUPIN_ERR_OUT_OF_MEMORY when the scratch (60 bytes per texel, 2 more with gutter passes, 48 more for
+ * host arrays) cannot be allocated.  Without a HIP device: LUPIN_ERR_NO_DEVICE.
+ * With LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS all three pointers are device memory of the context's device and nothing
+ * crosses the bus; otherwise they are host arrays.  The scratch stays with the context from call to call. */
+#define LUPIN_LIGHTMAP_DENOISE_MAX_PASSES 8u
+#define LUPIN_LIGHTMAP_DENOISE_MAX_SQUARINGS 7u
+enum { LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS = 1u };                   /* desc.flags */
+typedef struct LupinLightmapDenoiseDesc {
+    uint32_t width;                 /* atlas texels, 1 .. LUPIN_LIGHTMAP_MAX_SIZE */
+    uint32_t height;
+    uint32_t passes;                /* 1 .. LUPIN_LIGHTMAP_DENOISE_MAX_PASSES; pass i taps at step 2^i */
+    uint32_t normal_squarings;      /* 0 .. 7: w_n = max(0, n_p . n_q)^(2^k) */
+    uint32_t dilate;                /* 0 .. LUPIN_LIGHTMAP_MAX_DILATE gutter passes after the filter */
+    uint32_t flags;
+    float max_stretch;              /* finite, > 0 */
+} LupinLightmapDenoiseDesc;
+int lupin_hip_denoise_lightmap(LupinContext *ctx, const LupinLightmapDenoiseDesc *desc, const float *rgba /* H*W*4 */,
+                               const float *records /* H*W*8 */, float *out_rgba /* H*W*4 */);
+/* The calling thread's latest successful lupin_hip_denoise_lightmap: device-event milliseconds of its kernels (pass_ms[i]
+ * for i < passes, zeros beyond; dilate_ms: all gutter passes) and host-clock milliseconds of the call after its refusals. */
+typedef struct LupinLightmapDenoiseStats {
+    float prep_ms;
+    float pass_ms[8];
+    float dilate_ms;
+    float call_ms;
+} LupinLightmapDenoiseStats;
+void lupin_hip_lightmap_denoise_stats(LupinLightmapDenoiseStats *out);
+
 /* ---- light-probe baking (no reference counterpart) ----
  * The radiance arriving at points in space from every direction, projected onto the nine real spherical harmonics of bands
  * 0..2: what lights everything a lightmap cannot cover.  Every probe is path-traced along `samples` uniformly distributed

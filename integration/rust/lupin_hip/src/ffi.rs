@@ -95,6 +95,16 @@ pub const LUPIN_LIGHTMAP_SMOOTH_NORMALS: u32 = 1;
 #[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinLightmapStats {
     pub covered_texels: u64, pub keys: u32, pub raster_ms: f32, pub compact_ms: f32, pub trace_ms: f32, pub scatter_dilate_ms: f32, pub download_ms: f32,
 }
+// lightmap denoising (no reference counterpart)
+pub const LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS: u32 = 1;
+pub const LUPIN_LIGHTMAP_DENOISE_MAX_PASSES: u32 = 8;
+pub const LUPIN_LIGHTMAP_DENOISE_MAX_SQUARINGS: u32 = 7;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmapDenoiseDesc {
+    pub width: u32, pub height: u32, pub passes: u32, pub normal_squarings: u32, pub dilate: u32, pub flags: u32, pub max_stretch: f32,
+}
+#[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinLightmapDenoiseStats {
+    pub prep_ms: f32, pub pass_ms: [f32; 8], pub dilate_ms: f32, pub call_ms: f32,
+}
 // light-probe baking (no reference counterpart)
 pub const LUPIN_PROBE_FLOATS: usize = 4;
 pub const LUPIN_PROBE_SH_COEFFS: usize = 9;
@@ -204,6 +214,10 @@ extern "C" {
                                    charts: *const LupinLightmapChart, num_charts: u32, out_rgba: *mut f32, out_records: *mut f32,
                                    out_num_covered: *mut u64) -> c_int;
     pub fn lupin_hip_lightmap_stats(out: *mut LupinLightmapStats);
+    // lightmap denoising: rgba and out_rgba height x width x 4 f32 (they may be the same), records height x width x 8
+    pub fn lupin_hip_denoise_lightmap(ctx: *mut LupinContext, desc: *const LupinLightmapDenoiseDesc, rgba: *const f32, records: *const f32,
+                                      out_rgba: *mut f32) -> c_int;
+    pub fn lupin_hip_lightmap_denoise_stats(out: *mut LupinLightmapDenoiseStats);
     // light-probe baking: probes n x 4 f32 (position | RNG word), out_sh n x 9 x 4 (r, g, b, w per L2 SH coefficient), out_rays null or n * samples x 8
     pub fn lupin_hip_bake_probes(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinProbeDesc, n: u64,
                                  probes: *const f32, out_sh: *mut f32, out_rays: *mut f32) -> c_int;

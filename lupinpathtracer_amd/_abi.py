@@ -170,6 +170,15 @@ class LightmapStatsC(C.Structure):   # LupinLightmapStats
                 ("trace_ms", C.c_float), ("scatter_dilate_ms", C.c_float), ("download_ms", C.c_float)]
 
 
+class LightmapDenoiseDescC(C.Structure):   # LupinLightmapDenoiseDesc
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("passes", C.c_uint32), ("normal_squarings", C.c_uint32),
+                ("dilate", C.c_uint32), ("flags", C.c_uint32), ("max_stretch", C.c_float)]
+
+
+class LightmapDenoiseStatsC(C.Structure):   # LupinLightmapDenoiseStats
+    _fields_ = [("prep_ms", C.c_float), ("pass_ms", C.c_float * 8), ("dilate_ms", C.c_float), ("call_ms", C.c_float)]
+
+
 class ProbeDescC(C.Structure):   # LupinProbeDesc
     _fields_ = [("pathtrace_type", C.c_uint32), ("max_bounces", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32),
                 ("max_slots", C.c_uint32), ("advanced", AdvancedParamsC)]
@@ -252,6 +261,8 @@ SYMBOLS = [
     ("lupin_hip_pathtrace_rays", C.c_int, [_P, _P, C.POINTER(RayQueryDescC), C.c_uint64, _P, _P, _P]),
     ("lupin_hip_bake_lightmap", C.c_int, [_P, _P, C.POINTER(LightmapDescC), C.POINTER(LightmapChartC), _U32, _P, _P, C.POINTER(C.c_uint64)]),
     ("lupin_hip_lightmap_stats", None, [C.POINTER(LightmapStatsC)]),
+    ("lupin_hip_denoise_lightmap", C.c_int, [_P, C.POINTER(LightmapDenoiseDescC), _P, _P, _P]),
+    ("lupin_hip_lightmap_denoise_stats", None, [C.POINTER(LightmapDenoiseStatsC)]),
     ("lupin_hip_bake_probes", C.c_int, [_P, _P, C.POINTER(ProbeDescC), C.c_uint64, _P, _P, _P]),
     ("lupin_hip_occlusion_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),
     ("lupin_hip_transmittance_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),

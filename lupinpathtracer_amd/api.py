@@ -1524,7 +1524,7 @@ def lightmap_stats():
 
 
 def bake_lightmap(ctx, scene, charts, width, height, samples=64, pathtrace_type=PathtraceType.Standard, max_bounces=8, advanced=None,
-                  counter=0, max_slots=0, smooth_normals=False, dilate=0, surface_offset=None, want_records=False):
+                  counter=0, max_slots=0, smooth_normals=False, dilate=0, surface_offset=None, want_records=False, denoise=False):
     """The scene's irradiance as a lightmap: (height, width, 4) float32, rgb = pi * the mean radiance over `samples`
     cosine-weighted paths from the surface point under each texel centre, alpha 1 on rasterised texels and 0 elsewhere
     (gutter texels filled by `dilate` passes keep alpha 0).  Row 0 is v in [0, 1 / height): no flip.
@@ -1535,9 +1535,16 @@ def bake_lightmap(ctx, scene, charts, width, height, samples=64, pathtrace_type=
     surface_offset (world units along the geometric normal) defaults to LIGHTMAP_OFFSET_FRACTION = 1e-4 times the
     largest world extent of the scene, taken from the instances' model boxes (scene_world_extent), and to 1e-4 for a scene
     without extent.  With want_records also the (height, width, 8) ray records of the owned texels (zeros elsewhere).
+    denoise: the atlas is baked without gutter passes, filtered by denoise_lightmap with its defaults, and the `dilate`
+    gutter passes run after the filter, from the filtered texels.
     Blocks until the result is complete."""
     if ctx is None or scene.handle is None:
         raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_lightmap needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if denoise:
+        noisy, rec = bake_lightmap(ctx, scene, charts, width, height, samples, pathtrace_type, max_bounces, advanced, counter, max_slots,
+                                   smooth_normals, 0, surface_offset, True)
+        out = denoise_lightmap(ctx, noisy, rec, dilate=dilate)
+        return (out, rec) if want_records else out
     if surface_offset is None:
         surface_offset = LIGHTMAP_OFFSET_FRACTION * (scene_world_extent(scene) or 1.0)
     adv = advanced or AdvancedParams()
@@ -1552,6 +1559,59 @@ def bake_lightmap(ctx, scene, charts, width, height, samples=64, pathtrace_type=
     rec = np.zeros((int(height), int(width), RAY_RECORD_FLOATS) if shape_ok else (1, 1, RAY_RECORD_FLOATS), np.float32) if want_records else None
     check(lib().lupin_hip_bake_lightmap(ctx.handle, scene.handle, C.byref(d), c_charts, len(items), ptr(out), ptr(rec), None))
     return (out, rec) if want_records else out
+
+
+# ---- lightmap denoising: lupin_hip_denoise_lightmap (include/lupin_hip.h) ----
+LIGHTMAP_DENOISE_DEVICE_POINTERS = 1
+LIGHTMAP_DENOISE_MAX_PASSES = 8
+LIGHTMAP_DENOISE_MAX_SQUARINGS = 7
+
+
+def denoise_lightmap(ctx, rgba, records, passes=5, normal_squarings=5, max_stretch=4.0, dilate=0):
+    """A baked lightmap, filtered in atlas space: (height, width, 4) float32.  `rgba` (height, width, 4) and `records`
+    (height, width, RAY_RECORD_FLOATS) are what bake_lightmap(..., want_records=True) returns (or several bakes with
+    different `counter`, averaged).  An edge-avoiding a-trous filter of `passes` 5 x 5 passes at steps 1, 2, 4, ..: a tap
+    counts only if its surface point is as near in space as it is in the atlas (within max_stretch times the texel's own
+    footprint per texel of distance), weighted by max(0, n_p . n_q)^(2^normal_squarings) and by the luminance difference
+    against the local deviation.  Charts, gutters and folds are never filtered across.  Alpha is the input's; texels of
+    alpha 0 are returned as they came, or with dilate > 0 refilled from the filtered texels by that many gutter passes.
+    numpy arrays, or contiguous float32 torch tensors on the context's device: then torch's current stream is synchronised,
+    the tensors' device memory is used in place and a tensor is returned.  Blocks until the result is complete."""
+    if ctx is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "denoise_lightmap needs a GPU context; there is no CPU fallback")
+    if hasattr(rgba, "data_ptr") or hasattr(records, "data_ptr"):   # torch tensors
+        import torch
+        for t, last in ((rgba, 4), (records, RAY_RECORD_FLOATS)):
+            if not (hasattr(t, "data_ptr") and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == last):
+                raise ValueError("rgba and records must be contiguous (height, width, 4) and (height, width, 8) float32 tensors on the context's device")
+            if t.device.index != ctx.device_ordinal:
+                raise ValueError("rgba and records are on another device than the context")
+        if tuple(rgba.shape[:2]) != tuple(records.shape[:2]):
+            raise ValueError("rgba and records differ in height or width")
+        h, w = int(rgba.shape[0]), int(rgba.shape[1])
+        out = torch.zeros((h, w, 4), dtype=torch.float32, device=rgba.device)
+        torch.cuda.current_stream(rgba.device).synchronize()   # the inputs (and the zero fill) are written
+        d = _abi.LightmapDenoiseDescC(w, h, int(passes), int(normal_squarings), int(dilate), LIGHTMAP_DENOISE_DEVICE_POINTERS, float(max_stretch))
+        check(lib().lupin_hip_denoise_lightmap(ctx.handle, C.byref(d), C.c_void_p(rgba.data_ptr()), C.c_void_p(records.data_ptr()),
+                                               C.c_void_p(out.data_ptr())))
+        return out
+    rgba = np.ascontiguousarray(rgba, np.float32)
+    records = np.ascontiguousarray(records, np.float32)
+    if rgba.ndim != 3 or rgba.shape[2] != 4 or records.shape != rgba.shape[:2] + (RAY_RECORD_FLOATS,):
+        raise ValueError("rgba must be (height, width, 4) and records (height, width, 8)")
+    h, w = rgba.shape[:2]
+    d = _abi.LightmapDenoiseDescC(w, h, int(passes), int(normal_squarings), int(dilate), 0, float(max_stretch))
+    out = np.zeros((h, w, 4), np.float32)
+    check(lib().lupin_hip_denoise_lightmap(ctx.handle, C.byref(d), ptr(rgba), ptr(records), ptr(out)))
+    return out
+
+
+def lightmap_denoise_stats():
+    """The calling thread's latest successful denoise_lightmap: device-event ms of the prep pass, of each filter pass and of
+    the gutter passes together, host-clock ms of the call."""
+    s = _abi.LightmapDenoiseStatsC()
+    lib().lupin_hip_lightmap_denoise_stats(C.byref(s))
+    return {"prep_ms": float(s.prep_ms), "pass_ms": [float(v) for v in s.pass_ms], "dilate_ms": float(s.dilate_ms), "call_ms": float(s.call_ms)}
 
 
 # ---- light-probe baking: lupin_hip_bake_probes (include/lupin_hip.h, DESIGN.md 15) ----

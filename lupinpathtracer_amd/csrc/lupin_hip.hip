@@ -31,6 +31,7 @@
 #include "lupin_rays.hpp"
 #include "lupin_probes.hpp"
 #include "lupin_lightmap.hpp"
+#include "lupin_lightmap_denoise.hpp"
 #include "lupin_occlusion.hpp"
 #include "lupin_transmittance.hpp"
 #include "lupin_distance.hpp"
@@ -143,6 +144,12 @@ struct LupinContext
     // auxiliary array (local -> world rows and c_i) that every call rebuilds from the scene's current rows
     DeviceBuffer dist_records, dist_results, dist_aux;
     size_t dist_records_bytes = 0, dist_results_bytes = 0, dist_aux_bytes = 0;
+    // lupin_hip_denoise_lightmap: the staging of host arrays (rgba, which is also where the result lands, and records) and the
+    // filter's scratch (two (irradiance, variance) planes, the two guide planes, the footprint, two `filled` planes for
+    // the gutter passes), kept and grown the same way
+    enum { LMD_RGBA, LMD_RECORDS, LMD_IV0, LMD_IV1, LMD_G0, LMD_G1, LMD_FOOT, LMD_FILLED0, LMD_FILLED1, LMD_BUFFERS };
+    DeviceBuffer lmd[LMD_BUFFERS];
+    size_t lmd_bytes[LMD_BUFFERS] = {};
 };
 
 struct LupinPathtraceResources
@@ -2547,11 +2554,16 @@ int lupin_hip_camera_probe(LupinContext *ctx, uint32_t width, uint32_t height, c
 extern "C++" {   // (there are templates among them, and the entry points around them are extern "C")
 
 // the refusals every scene query opens with; `args`: the entry point's own pointers are all there
-static int query_refuse(const LupinContext *ctx, const LupinScene *scene, bool args)
+static int query_refuse_context(const LupinContext *ctx, bool args)   // (the part that needs no scene: lupin_hip_denoise_lightmap has none)
 {
     if (!ctx_alive(ctx) && lupin_hip_device_count() <= 0) return fail(LUPIN_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
     CTX_ALIVE_TRY(ctx);
-    if (!ctx || !scene || !args) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (!ctx || !args) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    return LUPIN_OK;
+}
+static int query_refuse(const LupinContext *ctx, const LupinScene *scene, bool args)
+{
+    if (int rc = query_refuse_context(ctx, scene && args)) return rc;
     if (scene->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the scene belongs to another context, or to one that has been destroyed");
     return LUPIN_OK;
 }
@@ -3204,6 +3216,107 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
     stats.download_ms = ms_since(t0);
     if (out_num_covered) *out_num_covered = n;
     g_lightmap_stats = stats;
+    return LUPIN_OK;
+}
+
+// ---- lightmap denoising (no reference counterpart; kernels and rule: lupin_lightmap_denoise.hpp) ----
+
+static thread_local LupinLightmapDenoiseStats g_lightmap_denoise_stats = {0.0f, {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 0.0f, 0.0f};
+void lupin_hip_lightmap_denoise_stats(LupinLightmapDenoiseStats *out) { if (out) *out = g_lightmap_denoise_stats; }
+
+// the launch shape of the filter's kernels: one thread per texel in 16 x 16 blocks, as lupin_hip_denoise
+static dim3 lmd_grid(uint32_t W, uint32_t H) { return dim3((W + LP_DN_BX - 1) / LP_DN_BX, (H + LP_DN_BY - 1) / LP_DN_BY); }
+
+int lupin_hip_denoise_lightmap(LupinContext *ctx, const LupinLightmapDenoiseDesc *desc, const float *rgba, const float *records, float *out_rgba)
+{
+    const char *who = "lupin_hip_denoise_lightmap";
+    if (int rc = query_refuse_context(ctx, desc && rgba && records && out_rgba)) return rc;
+    const uint32_t W = desc->width, H = desc->height;
+    if (W == 0 || H == 0 || W > LUPIN_LIGHTMAP_MAX_SIZE || H > LUPIN_LIGHTMAP_MAX_SIZE)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "width and height must be in [1, 16384]");
+    if (desc->passes == 0 || desc->passes > LUPIN_LIGHTMAP_DENOISE_MAX_PASSES) return fail(LUPIN_ERR_INVALID_ARGUMENT, "passes must be in [1, 8]");
+    if (desc->normal_squarings > LUPIN_LIGHTMAP_DENOISE_MAX_SQUARINGS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "normal_squarings must be <= 7");
+    if (desc->dilate > LUPIN_LIGHTMAP_MAX_DILATE) return fail(LUPIN_ERR_INVALID_ARGUMENT, "dilate must be <= 64");
+    if (desc->flags & ~(uint32_t)LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (!(std::isfinite(desc->max_stretch) && desc->max_stretch > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_stretch must be finite and positive");
+    const bool on_device = (desc->flags & LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS) != 0;
+    if (on_device && (((uintptr_t)rgba | (uintptr_t)records | (uintptr_t)out_rgba) & 15u))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device pointers must be 16-byte aligned");
+    if (int rc = query_flush(ctx)) return rc;
+    join_primary(ctx);
+    hipStream_t st = ctx->stream;   // the primary stream
+    const auto t_call = std::chrono::steady_clock::now();
+
+    const size_t texels = (size_t)W * H;   // <= 2^28
+    const uint32_t passes = desc->passes, dilate = desc->dilate;
+    size_t want[LupinContext::LMD_BUFFERS] = {};
+    if (!on_device) { want[LupinContext::LMD_RGBA] = texels * 16; want[LupinContext::LMD_RECORDS] = texels * LUPIN_RAY_RECORD_FLOATS * 4; }
+    want[LupinContext::LMD_IV0] = want[LupinContext::LMD_IV1] = want[LupinContext::LMD_G0] = texels * 16;
+    want[LupinContext::LMD_G1] = texels * 8;
+    want[LupinContext::LMD_FOOT] = texels * 4;
+    if (dilate) want[LupinContext::LMD_FILLED0] = want[LupinContext::LMD_FILLED1] = texels;
+    for (int k = 0; k < LupinContext::LMD_BUFFERS; k++)
+        if (grow_buffer(&ctx->lmd[k], &ctx->lmd_bytes[k], want[k]) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            return fail(LUPIN_ERR_OUT_OF_MEMORY, std::string(who) + ": no device memory for the filter's scratch");
+        }
+    const float4 *d_rgba = reinterpret_cast<const float4 *>(rgba), *d_records = reinterpret_cast<const float4 *>(records);
+    float4 *d_out = reinterpret_cast<float4 *>(out_rgba);
+    if (!on_device)
+    {
+        HIP_TRY(hipMemcpyAsync(ctx->lmd[LupinContext::LMD_RGBA].get(), rgba, texels * 16, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->lmd[LupinContext::LMD_RECORDS].get(), records, texels * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
+        d_rgba = d_out = ctx->lmd[LupinContext::LMD_RGBA].as<float4>();   // the result lands where the input was: the filter may work in place
+        d_records = ctx->lmd[LupinContext::LMD_RECORDS].as<float4>();
+    }
+    float4 *iv[2] = {ctx->lmd[LupinContext::LMD_IV0].as<float4>(), ctx->lmd[LupinContext::LMD_IV1].as<float4>()};
+    uint8_t *filled[2] = {ctx->lmd[LupinContext::LMD_FILLED0].as<uint8_t>(), ctx->lmd[LupinContext::LMD_FILLED1].as<uint8_t>()};
+    const float4 *g0 = ctx->lmd[LupinContext::LMD_G0].as<float4>();
+    const float2 *g1 = ctx->lmd[LupinContext::LMD_G1].as<float2>();
+    const float *foot = ctx->lmd[LupinContext::LMD_FOOT].as<float>();
+
+    // events around the prep pass, every filter pass and the gutter passes together: passes + 3 of them
+    hipEvent_t ev[LUPIN_LIGHTMAP_DENOISE_MAX_PASSES + 3];
+    const uint32_t num_ev = passes + 3;
+    for (uint32_t k = 0; k < num_ev; k++) ev[k] = get_event(ctx);
+    struct Return { LupinContext *c; hipEvent_t *e; uint32_t n; ~Return() { for (uint32_t k = 0; k < n; k++) c->ev_pool.push_back(e[k]); } } give_back{ctx, ev, num_ev};
+    HIP_TRY(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(k_lmd_prep, lmd_grid(W, H), dim3(LP_DN_BX, LP_DN_BY), 0, st, d_rgba, d_records, iv[0], const_cast<float4 *>(g0), const_cast<float2 *>(g1),
+                       const_cast<float *>(foot), W, H);
+    HIP_TRY(hipEventRecord(ev[1], st));
+    const float stretch2 = desc->max_stretch * desc->max_stretch;
+    for (uint32_t i = 0; i < passes; i++)
+    {
+        const int step = 1 << i;
+        const float stretch = stretch2 * (float)(step * step);   // K_i
+        const float4 *src = iv[i & 1];
+        float4 *other = iv[(i + 1) & 1];
+        auto launch = [&](auto kernel, float4 *dst, float4 *out, uint8_t *out_filled) {
+            hipLaunchKernelGGL(kernel, lmd_grid(W, H), dim3(LP_DN_BX, LP_DN_BY), 0, st, src, dst, g0, g1, foot, d_rgba, out, out_filled, W, H, step, stretch,
+                               desc->normal_squarings);
+        };
+        if (i + 1 < passes) launch(k_lmd_pass<false, false>, other, nullptr, nullptr);
+        else if (dilate) launch(k_lmd_pass<true, true>, nullptr, other, filled[0]);   // the gutter passes start from the other plane
+        else launch(k_lmd_pass<true, false>, nullptr, d_out, nullptr);
+        HIP_TRY(hipEventRecord(ev[2 + i], st));
+    }
+    // the gutter passes ping-pong between the two (irradiance, variance) planes, which the filter no longer needs; the last lands in the output
+    const uint32_t texel_blocks = (uint32_t)((texels + LP_BLOCK - 1) / LP_BLOCK);
+    for (uint32_t pass = 0, cur = passes & 1; pass < dilate; pass++, cur ^= 1)
+        hipLaunchKernelGGL(k_lm_dilate, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, W, H, (const float4 *)iv[cur], (const uint8_t *)filled[pass & 1],
+                           pass + 1 < dilate ? iv[cur ^ 1] : d_out, filled[(pass & 1) ^ 1]);
+    HIP_TRY(hipEventRecord(ev[2 + passes], st));
+    HIP_TRY(hipGetLastError());
+    if (!on_device) HIP_TRY(hipMemcpyAsync(out_rgba, d_out, texels * 16, hipMemcpyDeviceToHost, st));
+    if (int rc = query_end(ctx, who)) return rc;
+
+    LupinLightmapDenoiseStats stats = {0.0f, {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 0.0f, 0.0f};
+    HIP_TRY(hipEventElapsedTime(&stats.prep_ms, ev[0], ev[1]));
+    for (uint32_t i = 0; i < passes; i++) HIP_TRY(hipEventElapsedTime(&stats.pass_ms[i], ev[1 + i], ev[2 + i]));
+    HIP_TRY(hipEventElapsedTime(&stats.dilate_ms, ev[1 + passes], ev[2 + passes]));
+    stats.call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    g_lightmap_denoise_stats = stats;
     return LUPIN_OK;
 }
 

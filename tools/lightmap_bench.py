@@ -12,7 +12,10 @@ atlas size, medians of `runs` calls after `warmup`:
                                 each phase ends synchronised); other_share = everything but the trace / the whole call
   bake_mpaths_per_s             covered texels * samples / the whole call;  trace_mpaths_per_s: / the trace alone
   query_mpaths_per_s            api.pathtrace_rays on the same records from host arrays, the same number of paths
-  baseline (first size only, once)   the nearest equivalent without this entry point: the records built on the host by
+  denoise                       lupin_hip_denoise_lightmap (defaults, `dilate` gutter passes) on that atlas baked without gutter
+                                passes: prep_ms, pass_ms per pass, dilate_ms (device events; lupin_hip_lightmap_denoise_stats),
+                                their sum kernels_ms and its share of trace_ms, the call from host arrays (host clock)
+  baseline (first size only, once)  the nearest equivalent without this entry point: the records built on the host by
                                 tests/lightmap_ref.py (host_records_ms), then api.bake_irradiance-style tracing of them (query)
 """
 import argparse
@@ -78,7 +81,29 @@ def main():
                "other_share": round(other / (other + med["trace_ms"]), 4),
                "bake_mpaths_per_s": round(paths / call_ms / 1e3, 2), "trace_mpaths_per_s": round(paths / med["trace_ms"] / 1e3, 2),
                "mean_irradiance": round(float(out[..., :3][out[..., 3] == 1].astype(np.float64).mean()), 5)}
-        _, rec = api.bake_lightmap(ctx, scene, [chart], size, size, samples=1, surface_offset=offset, want_records=True)
+        # the denoise leg: the same bake without gutter passes and with its records, then lupin_hip_denoise_lightmap on them
+        noisy, rec = api.bake_lightmap(ctx, scene, [chart], size, size, samples=args.samples, max_bounces=args.bounces, surface_offset=offset,
+                                       want_records=True)
+        dn_whole, dn = [], []
+        for r in range(args.warmup + args.runs):
+            t0 = time.perf_counter()
+            filtered = api.denoise_lightmap(ctx, noisy, rec, dilate=args.dilate)
+            ms = (time.perf_counter() - t0) * 1e3
+            if r >= args.warmup:
+                dn_whole.append(ms)
+                dn.append(api.lightmap_denoise_stats())
+        passes = 5
+        pass_ms = [statistics.median(d["pass_ms"][i] for d in dn) for i in range(passes)]
+        prep_ms, dilate_ms = statistics.median(d["prep_ms"] for d in dn), statistics.median(d["dilate_ms"] for d in dn)
+        kernels_ms = prep_ms + sum(pass_ms) + dilate_ms
+        row["denoise"] = {"passes": passes, "normal_squarings": 5, "max_stretch": 4.0, "dilate": args.dilate,
+                          "call_ms_host_arrays": round(statistics.median(dn_whole), 3),       # with 48 bytes per texel up and 16 down
+                          "library_call_ms": round(statistics.median(d["call_ms"] for d in dn), 3),
+                          "prep_ms": round(prep_ms, 4), "pass_ms": [round(v, 4) for v in pass_ms], "dilate_ms": round(dilate_ms, 4),
+                          "kernels_ms": round(kernels_ms, 4), "kernels_over_trace": round(kernels_ms / med["trace_ms"], 6),
+                          "pass_ns_per_texel": [round(v * 1e6 / (size * size), 4) for v in pass_ms],
+                          "mean_irradiance_filtered": round(float(filtered[..., :3][filtered[..., 3] == 1].astype(np.float64).mean()), 5),
+                          "mean_irradiance_noisy": round(float(noisy[..., :3][noisy[..., 3] == 1].astype(np.float64).mean()), 5)}
         rec = rec[rec.view(np.uint32)[..., 7] == 1]
         desc = api.RayQueryDesc(api.PathtraceType.Standard, args.bounces, args.samples)
         q = []
