@@ -205,7 +205,7 @@ void lupin_hip_comm_destroy(LupinComm *c)
 {
     if (!c) return;
     hipSetDevice(c->device);
-    if (lupin_internal_ctx_alive(c->ctx)) lupin_internal_sync_all(c->ctx);   // a destroyed context has drained its streams already
+    if (lupin_internal_ctx_alive(c->ctx)) (void)lupin_internal_sync_all(c->ctx);   // a destroyed context has drained its streams already; a batch that fails here is dropped
     Rccl *R = rccl();
     if (c->owns_comm && c->comm && R->handle) R->CommDestroy(c->comm);
     delete c;   // frees send, recv and scratch: after the synchronisation above

@@ -126,7 +126,6 @@ struct LupinContext
     uint32_t pending_type = 0;
     uint32_t batch_frames = 0;             // LUPIN_BATCH=1..16: calls per wavefront (1 = every call is its own wavefront); 0 = by dispatch size,
                                            // see frames_per_wavefront()
-    bool in_flush = false;
     int last_lanes = 0;                    // frames in flight the latest pathtrace call could use (reported by lupin_hip_stats_get)
     bool last_wide = false;                // ... and whether it ran the four-wide tracer
     uint32_t last_batch = 0, last_short = 0;   // frames the latest wavefront carried; its first-pass stack entries (0 = one pass)
@@ -686,6 +685,19 @@ static void plan_tracers(LupinContext *ctx, const LupinScene *scene, uint32_t ty
     });
 }
 
+// The launch shape of a wavefront of `n` slots on lane `ln`: every shard gets the same number of blocks, block b serves shard
+// b % LP_SHARDS (the lane's shard capacity follows from it), then the tracers.
+static Shape plan_wavefront(LupinContext *ctx, Lane *ln, const LupinScene *scene, uint32_t type, bool chip_to_itself, const TraversalLds &t, uint32_t n)
+{
+    const uint32_t blocks_needed = (n + LP_BLOCK - 1) / LP_BLOCK;
+    const uint32_t blocks_per_shard = (blocks_needed + LP_SHARDS - 1) / LP_SHARDS;
+    ln->pb.shard_cap = blocks_per_shard * LP_BLOCK;
+    Shape sh;
+    sh.blocks = blocks_per_shard * LP_SHARDS;
+    plan_tracers(ctx, scene, type, chip_to_itself, t, &sh);
+    return sh;
+}
+
 // the tracing stage of MODE 0 (closest hits of the integrator loop) or 1 (recorded shadow rays) on the persistent tracer
 template <int TYPE, int MODE>
 static void launch_persistent_tracer(LupinContext *ctx, Lane *ln, const LupinScene *scene, const Shape &sh, uint32_t iter)
@@ -873,22 +885,80 @@ static hipError_t enqueue_wavefront(LupinContext *ctx, Lane *ln, const LupinScen
     return hipSuccess;
 }
 
+// The wavefront as a replayed graph (LUPIN_GRAPH=1).  Everything between k_set_params and the resolve depends on the call only through
+// *d_fp, so it is captured once per (scene, dispatch size, integrator, buffers) and replayed: one graph launch instead of 2-4 per iteration.
+static int replay_wavefront(LupinContext *ctx, Lane *ln, const LupinScene *scene, uint32_t pathtrace_type, uint32_t n, const Shape &sh, uint32_t iterations)
+{
+    hipStream_t st = ln->stream;
+    Lane::GraphKey key;
+    key.scene_id = scene->id; key.pb_generation = ln->pb_generation; key.n = n; key.blocks = sh.blocks; key.type = pathtrace_type;
+    key.iterations = iterations; key.stack_words = sh.binary.stack_words; key.lds = (uint32_t)sh.binary.lds; key.pblocks = sh.binary.blocks;
+    key.persistent = ctx->persistent_extend;
+    key.persistent_shadow = ctx->persistent_shadow ? 1 : 0; key.lds_geometry = sh.lds_geo ? 1 : 0;
+    const TracerGrid &first_pass = sh.wide.blocks ? sh.wide : sh.shrt;   // at most one of the two runs
+    key.wide_blocks = first_pass.blocks; key.wide_stack_words = first_pass.stack_words;
+    const bool have = ln->graph_exec && key == ln->graph_key;
+    if (!have && ln->graph_exec && !(key == ln->seen_key))
+    {
+        // the lane holds a graph of another shape and this one is new (shapes alternate, e.g. edge tiles): capturing
+        // costs about a millisecond, so launch directly and re-capture only if the shape repeats
+        ln->seen_key = key;
+        HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations));
+        return LUPIN_OK;
+    }
+    if (!have)
+    {
+        if (ln->graph_exec) { hipGraphExecDestroy(ln->graph_exec); ln->graph_exec = nullptr; }
+        if (ln->graph) { hipGraphDestroy(ln->graph); ln->graph = nullptr; }
+        HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        hipError_t ce = enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations);
+        hipError_t ee = hipStreamEndCapture(st, &ln->graph);
+        if (ce != hipSuccess || ee != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(ce != hipSuccess ? ce : ee));
+        HIP_TRY(hipGraphInstantiate(&ln->graph_exec, ln->graph, nullptr, nullptr, 0));
+        ln->graph_key = key;
+    }
+    else ctx->extend_launches += iterations;
+    ln->seen_key = key;
+    HIP_TRY(hipGraphLaunch(ln->graph_exec, st));
+    return LUPIN_OK;
+}
+
+// Lane `ln` waits for everything enqueued so far on the primary stream (texture uploads and copies, an adaptive reset;
+// lane 0 is that stream) and on the lane of the wavefront before (its resolve, an adaptive call's update).
+static int order_lane(LupinContext *ctx, Lane *ln)
+{
+    const int w = (int)(ln - ctx->lanes);
+    if (w != 0)
+    {
+        HIP_TRY(hipEventRecord(ctx->marker, ctx->stream));
+        HIP_TRY(hipStreamWaitEvent(ln->stream, ctx->marker, 0));
+    }
+    if (ctx->last_lane >= 0 && ctx->last_lane != w)
+        HIP_TRY(hipStreamWaitEvent(ln->stream, ctx->lanes[ctx->last_lane].done, 0));
+    return LUPIN_OK;
+}
+
 static int flush_pending(LupinContext *ctx);
 
+// The gate (DESIGN 5 "Recorded frames run first"): every reader / writer of a texture on the primary stream comes through here, or
+// through sync_all, before any work of its own.  The recorded calls run; if they fail, their code is the caller's and their message stays.
 // The resolves form a chain (each waits for the previous call's), so the latest call's event covers all lanes' texture writes.
-// Every reader / writer of a texture on the primary stream comes through here (or through sync_all): recorded calls run first.
-static void join_primary(LupinContext *ctx)
+static int join_primary(LupinContext *ctx)
 {
-    flush_pending(ctx);
+    if (int rc = flush_pending(ctx)) return rc;
     if (ctx->last_lane > 0) hipStreamWaitEvent(ctx->stream, ctx->lanes[ctx->last_lane].done, 0);
+    return LUPIN_OK;
 }
-static hipError_t sync_all(LupinContext *ctx)
+// ... and the host waits for every lane.  The lanes are drained even when the batch failed: teardown frees what they may use.
+static int sync_all(LupinContext *ctx)
 {
-    if (flush_pending(ctx) != LUPIN_OK) return hipErrorUnknown;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < LP_MAX_LANES && e == hipSuccess; k++)
-        if (ctx->lanes[k].stream) e = hipStreamSynchronize(ctx->lanes[k].stream);
-    return e;
+    int rc = flush_pending(ctx);
+    for (int k = 0; k < LP_MAX_LANES; k++)
+    {
+        hipError_t e = ctx->lanes[k].stream ? hipStreamSynchronize(ctx->lanes[k].stream) : hipSuccess;
+        if (e != hipSuccess && rc == LUPIN_OK) rc = fail(LUPIN_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
+    return rc;
 }
 
 // "Records in, launch, records out" on the primary stream, in scratch buffers that live for the call.  `launch` gets the
@@ -927,8 +997,7 @@ static bool ctx_alive(const LupinContext *ctx)
 
 bool lupin_internal_ctx_alive(const LupinContext *ctx) { return ctx_alive(ctx); }
 int lupin_internal_fail(int code, const char *msg) { return fail(code, msg); }
-void lupin_internal_join_primary(LupinContext *ctx) { join_primary(ctx); }
-int lupin_internal_sync_all(LupinContext *ctx) { HIP_TRY(hipSetDevice(ctx->device)); HIP_TRY(sync_all(ctx)); return LUPIN_OK; }
+int lupin_internal_sync_all(LupinContext *ctx) { HIP_TRY(hipSetDevice(ctx->device)); return sync_all(ctx); }
 // pack / unpack launches on the primary stream, ordered after every frame enqueued so far (see k_tiles_copy for `mode`)
 int lupin_internal_tiles_copy(LupinContext *ctx, const LupinTexture *tex, void *packed, uint32_t tile_size, uint32_t rank, uint32_t world,
                               uint64_t capacity_px, int mode)
@@ -937,7 +1006,7 @@ int lupin_internal_tiles_copy(LupinContext *ctx, const LupinTexture *tex, void *
     const uint32_t tpx = tile_size * LUPIN_WORKGROUP_SIZE;
     const uint32_t ntx = (tex->width - 1) / tpx + 1, nty = (tex->height - 1) / tpx + 1;
     const uint32_t blocks = mode == 2 ? ntx * nty : lupin_owned_tile_count(ntx * nty, rank, world);
-    join_primary(ctx);
+    if (int rc = join_primary(ctx)) return rc;
     // unpacked texels also refresh a valid f32 accumulator (widened: another rank's tile arrives as f16), so that
     // lupin_hip_texture_download_rgba32f and the next frame's blend see the gathered frame, not stale or zero words
     float4 *shadow = (mode != 0 && tex->accum32 && tex->accum32_valid) ? tex->accum32 : nullptr;
@@ -1049,7 +1118,7 @@ void lupin_hip_destroy_context(LupinContext *ctx)
         if (!g_live_contexts.erase(ctx)) return;   // not ours, or destroyed already
     }
     hipSetDevice(ctx->device);
-    sync_all(ctx);
+    (void)sync_all(ctx);   // nobody to tell: a batch that fails at teardown is dropped (DESIGN 5 "Teardown order"); the lanes are drained all the same
     for (int k = 0; k < LP_MAX_LANES; k++)
     {
         if (ctx->lanes[k].done) hipEventDestroy(ctx->lanes[k].done);
@@ -1070,14 +1139,13 @@ int lupin_hip_sync(LupinContext *ctx)
     CTX_ALIVE_TRY(ctx);
     if (!ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ctx is null");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(sync_all(ctx));
-    return LUPIN_OK;
+    return sync_all(ctx);
 }
 
 int lupin_hip_set_f16_store_rounding(LupinContext *ctx, int mode)
 {
     CTX_ALIVE_TRY(ctx);
-    if (ctx) { int frc = flush_pending(ctx); if (frc != LUPIN_OK) return frc; }   // calls recorded so far ran under the old setting
+    if (int rc = flush_pending(ctx)) return rc;   // calls recorded so far ran under the old setting
     if (!ctx || (mode != 0 && mode != 1)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "mode must be 0 (toward zero) or 1 (nearest even)");
     ctx->store_rounding = mode;
     return LUPIN_OK;
@@ -1097,8 +1165,7 @@ int lupin_hip_set_batch_frames(LupinContext *ctx, uint32_t frames)
 {
     CTX_ALIVE_TRY(ctx);
     if (!ctx || frames > LP_MAX_BATCH) return fail(LUPIN_ERR_INVALID_ARGUMENT, "frames per wavefront must be in [1, 16] (0: chosen by dispatch size)");
-    int frc = flush_pending(ctx);
-    if (frc != LUPIN_OK) return frc;
+    if (int rc = flush_pending(ctx)) return rc;   // calls recorded so far ran under the old setting
     ctx->batch_frames = frames;
     return LUPIN_OK;
 }
@@ -1106,7 +1173,7 @@ int lupin_hip_set_batch_frames(LupinContext *ctx, uint32_t frames)
 int lupin_hip_set_traversal(LupinContext *ctx, int mode)
 {
     CTX_ALIVE_TRY(ctx);
-    if (ctx) { int frc = flush_pending(ctx); if (frc != LUPIN_OK) return frc; }   // calls recorded so far ran under the old setting
+    if (int rc = flush_pending(ctx)) return rc;   // calls recorded so far ran under the old setting
     if (!ctx || (mode != LUPIN_TRAVERSAL_WIDE && mode != LUPIN_TRAVERSAL_BINARY)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown traversal mode");
     ctx->wide_traversal = mode == LUPIN_TRAVERSAL_WIDE;
     return LUPIN_OK;
@@ -1115,7 +1182,7 @@ int lupin_hip_set_traversal(LupinContext *ctx, int mode)
 int lupin_hip_set_accumulation_mode(LupinContext *ctx, int mode)
 {
     CTX_ALIVE_TRY(ctx);
-    if (ctx) { int frc = flush_pending(ctx); if (frc != LUPIN_OK) return frc; }   // calls recorded so far ran under the old setting
+    if (int rc = flush_pending(ctx)) return rc;   // calls recorded so far ran under the old setting
     if (!ctx || (mode != LUPIN_ACCUM_F16_RUNNING_AVERAGE && mode != LUPIN_ACCUM_F32)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown accumulation mode");
     ctx->accum_mode = mode;
     return LUPIN_OK;
@@ -1608,7 +1675,7 @@ void lupin_hip_scene_destroy(LupinScene *scene)
 {
     if (!scene) return;
     hipSetDevice(scene->device);
-    if (ctx_alive(scene->ctx)) sync_all(scene->ctx);   // a destroyed context has drained its streams already
+    if (ctx_alive(scene->ctx)) (void)sync_all(scene->ctx);   // a destroyed context has drained its streams already; a batch that fails here is dropped
     delete scene;   // frees its allocations: after the synchronisation above
 }
 
@@ -1626,8 +1693,7 @@ int lupin_hip_scene_update_instances(LupinScene *scene, const LupinMat4x3 *trans
     if (num_instances != n) return fail(LUPIN_ERR_INVALID_ARGUMENT, "update_instances: the instance count cannot change (" + std::to_string(num_instances) + " transforms for " + std::to_string(n) + " instances)");
     if (n == 0) return LUPIN_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    // calls recorded so far render the old transforms; their failure is this call's (not dropped as join_primary drops it)
-    { int frc = flush_pending(ctx); if (frc != LUPIN_OK) return frc; }
+    if (int rc = flush_pending(ctx)) return rc;   // calls recorded so far render the old transforms
 
     // ---- staging: instance records, TLAS, child pairs, light bounds ----
     std::vector<LupinInstance> inst(n);
@@ -1768,7 +1834,7 @@ void lupin_hip_texture_destroy(LupinTexture *tex)
 {
     if (!tex) return;
     hipSetDevice(tex->device);
-    if (ctx_alive(tex->ctx)) sync_all(tex->ctx);
+    if (ctx_alive(tex->ctx)) (void)sync_all(tex->ctx);   // a destroyed context has drained its streams already; a batch that fails here is dropped
     delete tex;   // frees the texels and the f32 shadow: after the synchronisation above
 }
 uint32_t lupin_hip_texture_width(const LupinTexture *tex) { return tex ? tex->width : 0; }
@@ -1780,7 +1846,7 @@ int lupin_hip_texture_upload_rgba16f(LupinTexture *tex, const uint16_t *pixels)
     if (!tex || !pixels) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
     CTX_ALIVE_TRY(tex->ctx);
     HIP_TRY(hipSetDevice(tex->ctx->device));
-    join_primary(tex->ctx);
+    if (int rc = join_primary(tex->ctx)) return rc;
     HIP_TRY(hipMemcpyAsync(tex->data, pixels, (size_t)tex->width * tex->height * 8, hipMemcpyHostToDevice, tex->ctx->stream));
     HIP_TRY(hipStreamSynchronize(tex->ctx->stream));
     tex->accum32_valid = false;   // the f16 texels are now the only truth
@@ -1792,7 +1858,7 @@ int lupin_hip_texture_download_rgba32f(const LupinTexture *tex, float *out_pixel
     if (!tex->accum32 || !tex->accum32_valid) return fail(LUPIN_ERR_INVALID_ARGUMENT, "texture has no f32 accumulator (render into it with LUPIN_ACCUM_F32 first)");
     CTX_ALIVE_TRY(tex->ctx);
     HIP_TRY(hipSetDevice(tex->ctx->device));
-    join_primary(tex->ctx);
+    if (int rc = join_primary(tex->ctx)) return rc;
     HIP_TRY(hipMemcpyAsync(out_pixels, tex->accum32, (size_t)tex->width * tex->height * 16, hipMemcpyDeviceToHost, tex->ctx->stream));
     HIP_TRY(hipStreamSynchronize(tex->ctx->stream));
     return LUPIN_OK;
@@ -1802,7 +1868,7 @@ int lupin_hip_texture_download_rgba16f(const LupinTexture *tex, uint16_t *out_pi
     if (!tex || !out_pixels) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
     CTX_ALIVE_TRY(tex->ctx);
     HIP_TRY(hipSetDevice(tex->ctx->device));
-    join_primary(tex->ctx);
+    if (int rc = join_primary(tex->ctx)) return rc;
     HIP_TRY(hipMemcpyAsync(out_pixels, tex->data, (size_t)tex->width * tex->height * 8, hipMemcpyDeviceToHost, tex->ctx->stream));
     HIP_TRY(hipStreamSynchronize(tex->ctx->stream));
     return LUPIN_OK;
@@ -1835,7 +1901,7 @@ int lupin_hip_dbuf_copy_front_to_back(LupinDoubleBufferedTexture *t)
     LupinTexture *f = t->tex[t->front_idx], *b = t->tex[t->back_idx];
     CTX_ALIVE_TRY(t->ctx);
     HIP_TRY(hipSetDevice(t->ctx->device));
-    join_primary(t->ctx);
+    if (int rc = join_primary(t->ctx)) return rc;
     HIP_TRY(hipMemcpyAsync(b->data, f->data, (size_t)f->width * f->height * 8, hipMemcpyDeviceToDevice, t->ctx->stream));
     b->accum32_valid = false;
     if (f->accum32 && f->accum32_valid)
@@ -1880,6 +1946,13 @@ static void set_camera_constants(LupinPushConstants &pc, const LupinCameraParams
     pc.camera_focus = cp.focus;
     pc.camera_aperture = cp.aperture;
 }
+// ... and the scene's share: what an integrator may skip.  (The reprojection's primary trace shades nothing and sets none.)
+static void set_scene_constants(LupinPushConstants &pc, const LupinScene *scene)
+{
+    if (scene->envs_empty) pc.flags |= LUPIN_FLAG_ENVS_EMPTY;
+    if (scene->lights_empty) pc.flags |= LUPIN_FLAG_LIGHTS_EMPTY;
+    if (scene->instances_empty) pc.flags |= LUPIN_FLAG_INSTANCES_EMPTY;
+}
 
 static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res, const LupinScene *scene,
                           LupinTexture *render_target, uint32_t pathtrace_type, const LupinPathtraceDesc *desc,
@@ -1904,10 +1977,8 @@ static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res,
     // get_push_constants (renderer.rs:1426-1493)
     LupinPushConstants &pc = fp.pc;
     set_camera_constants(pc, desc->camera_params, desc->camera_transform);
-    if (scene->envs_empty) pc.flags |= LUPIN_FLAG_ENVS_EMPTY;
-    if (scene->lights_empty) pc.flags |= LUPIN_FLAG_LIGHTS_EMPTY;
-    if (scene->instances_empty) pc.flags |= LUPIN_FLAG_INSTANCES_EMPTY;
-    if (debug)   // get_push_constants (renderer.rs:1430-1454)
+    set_scene_constants(pc, scene);
+    if (debug)  // get_push_constants (renderer.rs:1430-1454)
     {
         pc.flags |= debug->viz_type == LUPIN_DEBUG_VIZ_BVH_AABB_CHECKS ? LUPIN_FLAG_DEBUG_AABB_CHECKS
                   : debug->viz_type == LUPIN_DEBUG_VIZ_BVH_TRI_CHECKS ? LUPIN_FLAG_DEBUG_TRI_CHECKS : LUPIN_FLAG_DEBUG_NUM_BOUNCES;
@@ -1973,8 +2044,8 @@ static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res,
         TraversalLds t;
         if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
         const __half *pv = prev ? prev->data : (const __half *)nullptr;
+        if (int rc = join_primary(ctx)) return rc;
         render_target->accum32_valid = false;
-        join_primary(ctx);
         with_bool(t.geo, [&](auto G) {
             constexpr bool LDSGEO = decltype(G)::value;
             if (debug) hipLaunchKernelGGL(k_debug<LDSGEO>, dim3(fblocks), dim3(LP_BLOCK), t.lds, ctx->stream, scene->dev, fp, n, pv, render_target->data, t.stack_words);
@@ -1990,8 +2061,7 @@ static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res,
     if (adaptive)
     {
         // one frame per wavefront: the next call's first rays read the mask this call's update writes
-        int rc = flush_pending(ctx);
-        if (rc != LUPIN_OK) return rc;
+        if (int rc = flush_pending(ctx)) return rc;
         ctx->pending.push_back({fp, render_target, prev, adaptive});
         ctx->pending_scene = scene;
         ctx->pending_type = pathtrace_type;
@@ -2015,10 +2085,7 @@ static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res,
         const bool joins = batchable && ctx->pending_scene == scene && ctx->pending_type == pathtrace_type && memcmp(&a, &b, sizeof(a)) == 0 &&
                            (fp.pc.accum_counter == 0 || prev == ctx->pending.back().target) && ctx->pending.size() < max_frames;
         if (!joins)
-        {
-            int rc = flush_pending(ctx);
-            if (rc != LUPIN_OK) return rc;
-        }
+            if (int rc = flush_pending(ctx)) return rc;
     }
     ctx->pending.push_back({fp, render_target, prev});
     ctx->pending_scene = scene;
@@ -2031,9 +2098,9 @@ static int pathtrace_impl(LupinContext *ctx, const LupinPathtraceResources *res,
 // blends per pixel in call order.  Errors of a deferred call surface here, i.e. at the call that needed its result.
 static int flush_pending(LupinContext *ctx)
 {
-    if (ctx->pending.empty() || ctx->in_flush) return LUPIN_OK;
-    ctx->in_flush = true;
-    struct Done { LupinContext *c; ~Done() { c->pending.clear(); c->pending_scene = nullptr; c->in_flush = false; } } done{ctx};
+    if (ctx->pending.empty()) return LUPIN_OK;
+    // run or refused, the batch is gone when this returns (nothing called from here comes back into it)
+    struct Done { LupinContext *c; ~Done() { c->pending.clear(); c->pending_scene = nullptr; } } done{ctx};
     HIP_TRY(hipSetDevice(ctx->device));
     const LupinScene *scene = ctx->pending_scene;
     const uint32_t pathtrace_type = ctx->pending_type;
@@ -2062,25 +2129,16 @@ static int flush_pending(LupinContext *ctx)
     hipStream_t st = ln->stream;
 
     const uint32_t iterations = fp.spp * (fp.max_bounces + 1);
-    int rc = ensure_path_buffers(ctx, ln, n, iterations);
-    if (rc != LUPIN_OK) return rc;
+    if (int rc = ensure_path_buffers(ctx, ln, n, iterations)) return rc;
     // scenes whose queues get sorted by material read the path state at scattered slots: records; otherwise planes
     set_path_layout(ln, ctx->path_records < 0 ? (scene->dev.sort_shade != 0) : ctx->path_records != 0);
-
-    // grid: every shard gets the same number of blocks, block b serves shard b % LP_SHARDS
-    const uint32_t blocks_needed = (n + LP_BLOCK - 1) / LP_BLOCK;
-    const uint32_t blocks_per_shard = (blocks_needed + LP_SHARDS - 1) / LP_SHARDS;
-    const uint32_t blocks = blocks_per_shard * LP_SHARDS;
-    ln->pb.shard_cap = blocks_per_shard * LP_BLOCK;
     TraversalLds t;
-    if (int trc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return trc;
+    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
 
     hipEvent_t t0 = nullptr, t1 = nullptr;
     if (ctx->timing) { t0 = get_event(ctx); t1 = get_event(ctx); hipEventRecord(t0, st); }
 
-    Shape sh;
-    sh.blocks = blocks;
-    plan_tracers(ctx, scene, pathtrace_type, chip_to_itself, t, &sh);
+    const Shape sh = plan_wavefront(ctx, ln, scene, pathtrace_type, chip_to_itself, t, n);
     ctx->last_lanes = lanes;
     ctx->last_wide = sh.wide.blocks != 0;
     ctx->last_batch = K;
@@ -2096,64 +2154,19 @@ static int flush_pending(LupinContext *ctx)
         // k_begin_adaptive reads the counts and the mask that the previous adaptive call's update wrote (on its lane, before
         // its `done`; the resolves chain every call after the one before) and that a reset wrote on the primary stream.
         // Consecutive one-frame wavefronts change lanes, so wait for both before the first rays.  No graph: launched directly.
-        if (w != 0)
-        {
-            HIP_TRY(hipEventRecord(ctx->marker, ctx->stream));
-            HIP_TRY(hipStreamWaitEvent(st, ctx->marker, 0));
-        }
-        if (ctx->last_lane >= 0 && ctx->last_lane != w)
-            HIP_TRY(hipStreamWaitEvent(st, ctx->lanes[ctx->last_lane].done, 0));
+        if (int rc = order_lane(ctx, ln)) return rc;
         HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations, &adaptive->dev));
     }
     else if (ctx->use_graph && !ctx->timing && !ctx->counting && !ctx->verify_wide)
     {
-        // Everything between k_set_params and the resolve depends on the call only through *d_fp, so it is captured once per
-        // (scene, dispatch size, integrator, buffers) and replayed: one graph launch instead of 2-4 launches per iteration.
-        Lane::GraphKey key;
-        key.scene_id = scene->id; key.pb_generation = ln->pb_generation; key.n = n; key.blocks = blocks; key.type = pathtrace_type;
-        key.iterations = iterations; key.stack_words = sh.binary.stack_words; key.lds = (uint32_t)sh.binary.lds; key.pblocks = sh.binary.blocks;
-        key.persistent = ctx->persistent_extend;
-        key.persistent_shadow = ctx->persistent_shadow ? 1 : 0; key.lds_geometry = sh.lds_geo ? 1 : 0;
-        const TracerGrid &first_pass = sh.wide.blocks ? sh.wide : sh.shrt;   // at most one of the two runs
-        key.wide_blocks = first_pass.blocks; key.wide_stack_words = first_pass.stack_words;
-        const bool have = ln->graph_exec && key == ln->graph_key;
-        if (!have && ln->graph_exec && !(key == ln->seen_key))
-        {
-            // the lane holds a graph of another shape and this one is new (shapes alternate, e.g. edge tiles): capturing
-            // costs about a millisecond, so launch directly and re-capture only if the shape repeats
-            ln->seen_key = key;
-            HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations));
-        }
-        else
-        {
-            if (!have)
-            {
-                if (ln->graph_exec) { hipGraphExecDestroy(ln->graph_exec); ln->graph_exec = nullptr; }
-                if (ln->graph) { hipGraphDestroy(ln->graph); ln->graph = nullptr; }
-                HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                hipError_t ce = enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations);
-                hipError_t ee = hipStreamEndCapture(st, &ln->graph);
-                if (ce != hipSuccess || ee != hipSuccess) return fail(LUPIN_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(ce != hipSuccess ? ce : ee));
-                HIP_TRY(hipGraphInstantiate(&ln->graph_exec, ln->graph, nullptr, nullptr, 0));
-                ln->graph_key = key;
-            }
-            else ctx->extend_launches += iterations;
-            ln->seen_key = key;
-            HIP_TRY(hipGraphLaunch(ln->graph_exec, st));
-        }
+        if (int rc = replay_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations)) return rc;
     }
     else
         HIP_TRY(enqueue_wavefront(ctx, ln, scene, pathtrace_type, n, sh, iterations));
     // The frames meet here: the resolve reads prev_frame and overwrites render_target, so it is ordered after everything
     // enqueued so far on the other lane (the previous call's resolve) and, for lane 1, on the primary stream (texture
     // uploads / copies).  The path state itself is private to the lane.
-    if (w != 0)
-    {
-        HIP_TRY(hipEventRecord(ctx->marker, ctx->stream));
-        HIP_TRY(hipStreamWaitEvent(st, ctx->marker, 0));
-    }
-    if (ctx->last_lane >= 0 && ctx->last_lane != w)
-        HIP_TRY(hipStreamWaitEvent(st, ctx->lanes[ctx->last_lane].done, 0));
+    if (int rc = order_lane(ctx, ln)) return rc;
     const float4 *prev32 = nullptr;
     float4 *out32 = nullptr;
     if (ctx->accum_mode == LUPIN_ACCUM_F32)
@@ -2231,7 +2244,7 @@ int lupin_hip_stats_reset(LupinContext *ctx, int enable_kernel_timing)
     CTX_ALIVE_TRY(ctx);
     if (!ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ctx is null");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(sync_all(ctx));
+    if (int rc = sync_all(ctx)) return rc;
     for (int k = 0; k < ctx->num_lanes; k++)
         HIP_TRY(hipMemsetAsync(ctx->lanes[k].stat_counters, 0, 2 * LP_SHARDS * sizeof(unsigned long long), ctx->lanes[k].stream));
     // extend/shade pairs share their middle event: recycle each event once
@@ -2257,7 +2270,7 @@ int lupin_hip_stats_get(LupinContext *ctx, LupinStats *out)
     CTX_ALIVE_TRY(ctx);
     if (!ctx || !out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(sync_all(ctx));
+    if (int rc = sync_all(ctx)) return rc;
     std::vector<unsigned long long> c(2 * LP_SHARDS, 0ull);
     memset(out, 0, sizeof(*out));
     for (int l = 0; l < ctx->num_lanes; l++)
@@ -2303,7 +2316,7 @@ int lupin_hip_measure_copy_bandwidth(LupinContext *ctx, uint64_t bytes, uint32_t
     CTX_ALIVE_TRY(ctx);
     if (!ctx || !out_gb_per_s || bytes < 16 || reps == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "bad copy-bandwidth arguments");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(sync_all(ctx));
+    if (int rc = sync_all(ctx)) return rc;
     const size_t n = bytes / 16;
     DeviceBuffer da, db;
     hipError_t e = DeviceBuffer::make(n * 16, &da);
@@ -2477,7 +2490,7 @@ int lupin_hip_light_probe(LupinContext *ctx, const LupinScene *scene, uint32_t n
     HIP_TRY(hipSetDevice(ctx->device));
     TraversalLds t;
     if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
-    join_primary(ctx);   // recorded calls run first
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
     const size_t in_bytes = (size_t)n * LUPIN_LIGHT_IN_FLOATS * 4, out_bytes = (size_t)n * LUPIN_LIGHT_OUT_FLOATS * 4;
     return run_probe(ctx, "lupin_hip_light_probe", {{records, in_bytes}}, out, out_bytes, [&](const DeviceBuffer *in, float *dout) {
         with_bool(t.geo, [&](auto G) {
@@ -2515,7 +2528,7 @@ int lupin_hip_surface_probe(LupinContext *ctx, const LupinScene *scene, uint32_t
     HIP_TRY(hipSetDevice(ctx->device));
     TraversalLds t;   // the staged geometry, if any: this kernel never traverses
     if (int rc = traversal_lds(ctx, scene, 0, true, &t)) return rc;
-    join_primary(ctx);   // recorded calls run first
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
     const size_t in_bytes = (size_t)n * LUPIN_SURFACE_IN_FLOATS * 4, out_bytes = (size_t)n * LUPIN_SURFACE_OUT_FLOATS * 4;
     return run_probe(ctx, "lupin_hip_surface_probe", {{records, in_bytes}}, out, out_bytes, [&](const DeviceBuffer *in, float *dout) {
         with_bool(t.geo, [&](auto G) {
@@ -2541,7 +2554,7 @@ int lupin_hip_camera_probe(LupinContext *ctx, uint32_t width, uint32_t height, c
     // the renderer's last row is (0, 0, 0, 1); the probe passes the caller's on, and the ray must not depend on it
     for (int c = 0; c < 4; c++) fp.pc.camera_transform.m[c][3] = camera_transform->m[c][3];
     fp.width = width; fp.height = height; fp.reg_w = width; fp.reg_h = height;
-    join_primary(ctx);   // recorded calls run first
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
     const size_t in_bytes = (size_t)n * LUPIN_CAMERA_IN_WORDS * 4, out_bytes = (size_t)n * LUPIN_CAMERA_OUT_FLOATS * 4;
     return run_probe(ctx, "lupin_hip_camera_probe", {{records, in_bytes}}, out, out_bytes, [&](const DeviceBuffer *in, float *dout) {
         hipLaunchKernelGGL(k_camera_probe, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, ctx->stream, fp, n, in[0].as<uint32_t>(), dout);
@@ -2580,12 +2593,11 @@ static int query_flush(LupinContext *ctx)
     HIP_TRY(hipSetDevice(ctx->device));
     return flush_pending(ctx);
 }
-// the LDS plan for a per-lane stack of `stack_entries` entries; the primary stream, the query's own, waits for the latest of the recorded calls
+// the LDS plan for a per-lane stack of `stack_entries` entries; then the gate: the primary stream, the query's own, waits for the latest of the recorded calls
 static int query_plan(LupinContext *ctx, const LupinScene *scene, uint32_t stack_entries, TraversalLds *t)
 {
     if (int rc = traversal_lds(ctx, scene, stack_entries, true, t)) return rc;
-    join_primary(ctx);
-    return LUPIN_OK;
+    return join_primary(ctx);
 }
 // every call ends synchronised
 static int query_end(LupinContext *ctx, const char *who)
@@ -2653,9 +2665,7 @@ static FrameParams query_frame_params(const LupinScene *scene, uint32_t pathtrac
     FrameParams fp;
     memset(&fp, 0, sizeof(fp));
     LupinPushConstants &pc = fp.pc;
-    if (scene->envs_empty) pc.flags |= LUPIN_FLAG_ENVS_EMPTY;
-    if (scene->lights_empty) pc.flags |= LUPIN_FLAG_LIGHTS_EMPTY;
-    if (scene->instances_empty) pc.flags |= LUPIN_FLAG_INSTANCES_EMPTY;
+    set_scene_constants(pc, scene);
     pc.pathtrace_type = pathtrace_type;
     pc.max_radiance = advanced.max_radiance;
     pc.rng_seed = advanced.rng_seed;
@@ -2671,13 +2681,7 @@ static Shape query_chunk_shape(LupinContext *ctx, const LupinScene *scene, uint3
                                FrameParams *fp)
 {
     fp->width = fp->reg_w = fp->frame_slots = slots;
-    const uint32_t blocks_needed = (slots + LP_BLOCK - 1) / LP_BLOCK;
-    const uint32_t blocks_per_shard = (blocks_needed + LP_SHARDS - 1) / LP_SHARDS;
-    ln->pb.shard_cap = blocks_per_shard * LP_BLOCK;
-    Shape sh;
-    sh.blocks = blocks_per_shard * LP_SHARDS;
-    plan_tracers(ctx, scene, pathtrace_type, true, t, &sh);
-    return sh;
+    return plan_wavefront(ctx, ln, scene, pathtrace_type, true, t, slots);
 }
 
 // lupin_hip_pathtrace_rays and lupin_hip_bake_probes are twins: records (rays | probes) of format Rule expand into `samples`
@@ -3125,8 +3129,8 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
         total_keys += scene->mesh_tri_count[mesh];
         if (total_keys >= 0xFFFFFFFFull) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the charts hold 2^32 - 1 or more triangles");
     }
-    if (int rc = query_flush(ctx)) return rc;
-    join_primary(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
     hipStream_t st = ctx->lanes[0].stream;   // the primary stream, the query's own
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t0) { return std::chrono::duration<float, std::milli>(clk::now() - t0).count(); };
@@ -3242,8 +3246,8 @@ int lupin_hip_denoise_lightmap(LupinContext *ctx, const LupinLightmapDenoiseDesc
     const bool on_device = (desc->flags & LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS) != 0;
     if (on_device && (((uintptr_t)rgba | (uintptr_t)records | (uintptr_t)out_rgba) & 15u))
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "device pointers must be 16-byte aligned");
-    if (int rc = query_flush(ctx)) return rc;
-    join_primary(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
     hipStream_t st = ctx->stream;   // the primary stream
     const auto t_call = std::chrono::steady_clock::now();
 
@@ -3371,7 +3375,7 @@ int lupin_hip_tonemap_and_fit_aspect(LupinContext *ctx, const LupinTexture *src,
     const size_t bytes = (size_t)dst_width * dst_height * 4;
     DeviceArray<uint32_t> d;   // freed on every return: each path below ends synchronised or failed
     HIP_TRY(d.alloc((size_t)dst_width * dst_height));
-    join_primary(ctx);
+    if (int rc = join_primary(ctx)) return rc;
     hipError_t e;
     if (desc->clear)   // LoadOp::Clear(0, 0, 0, 1) over the whole attachment
     {
@@ -3443,7 +3447,7 @@ void lupin_hip_destroy_denoise_resources(LupinDenoiseResources *res)
 {
     if (!res) return;
     hipSetDevice(res->device);
-    if (ctx_alive(res->ctx)) sync_all(res->ctx);   // a destroyed context has drained its streams already
+    if (ctx_alive(res->ctx)) (void)sync_all(res->ctx);   // a destroyed context has drained its streams already; a batch that fails here is dropped
     delete res;   // frees its buffers: after the synchronisation above
 }
 
@@ -3464,9 +3468,7 @@ int lupin_hip_denoise(LupinContext *ctx, LupinDenoiseResources *res, const Lupin
     }
     HIP_TRY(hipSetDevice(ctx->device));
     // the inputs may be targets of recorded pathtrace calls: run them, then order the filter after every frame in flight
-    int frc = flush_pending(ctx);
-    if (frc != LUPIN_OK) return frc;
-    join_primary(ctx);
+    if (int rc = join_primary(ctx)) return rc;
     const uint32_t W = res->width, H = res->height;
     const dim3 block(LP_DN_BX, LP_DN_BY), grid((W + LP_DN_BX - 1) / LP_DN_BX, (H + LP_DN_BY - 1) / LP_DN_BY);
     const uint2 *color = (const uint2 *)desc->pathtrace_output->data;
@@ -3541,7 +3543,7 @@ void lupin_hip_destroy_adaptive_resources(LupinAdaptiveResources *res)
 {
     if (!res) return;
     hipSetDevice(res->device);
-    if (ctx_alive(res->ctx)) sync_all(res->ctx);   // a destroyed context has drained its streams already
+    if (ctx_alive(res->ctx)) (void)sync_all(res->ctx);   // a destroyed context has drained its streams already; a batch that fails here is dropped
     delete res;   // frees its buffers: after the synchronisation above
 }
 
@@ -3551,7 +3553,7 @@ int lupin_hip_adaptive_reset(LupinContext *ctx, LupinAdaptiveResources *res)
     if (!res) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
     if (res->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive resources of another context");
     HIP_TRY(hipSetDevice(ctx->device));
-    join_primary(ctx);   // after every frame enqueued so far (the latest adaptive call's update among them)
+    if (int rc = join_primary(ctx)) return rc;   // after every frame enqueued so far (the latest adaptive call's update among them)
     launch_adaptive_reset(ctx, res);
     HIP_TRY(hipGetLastError());
     return LUPIN_OK;
@@ -3587,7 +3589,7 @@ int lupin_hip_adaptive_stats(LupinContext *ctx, const LupinAdaptiveResources *ar
     if (!ares || !out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
     if (ares->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive resources of another context");
     HIP_TRY(hipSetDevice(ctx->device));
-    join_primary(ctx);
+    if (int rc = join_primary(ctx)) return rc;
     unsigned long long s[3];
     HIP_TRY(hipMemcpyAsync(s, ares->dev.stats, sizeof(s), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -3605,7 +3607,7 @@ int lupin_hip_adaptive_download(LupinContext *ctx, const LupinAdaptiveResources 
     if (!ares) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
     if (ares->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "adaptive resources of another context");
     HIP_TRY(hipSetDevice(ctx->device));
-    join_primary(ctx);
+    if (int rc = join_primary(ctx)) return rc;
     const AdaptiveDev &d = ares->dev;
     const size_t px = (size_t)d.width * d.height, nb = (size_t)d.blocks_x * d.blocks_y;
     if (frames) HIP_TRY(hipMemcpyAsync(frames, d.frames, px * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -3696,7 +3698,7 @@ void lupin_hip_destroy_reproject_resources(LupinReprojectResources *res)
 {
     if (!res) return;
     hipSetDevice(res->device);
-    if (ctx_alive(res->ctx)) sync_all(res->ctx);   // a destroyed context has drained its streams already
+    if (ctx_alive(res->ctx)) (void)sync_all(res->ctx);   // a destroyed context has drained its streams already; a batch that fails here is dropped
     delete res;   // frees its buffers and events: after the synchronisation above
 }
 
@@ -3756,9 +3758,7 @@ int lupin_hip_adaptive_reproject(LupinContext *ctx, LupinAdaptiveResources *ares
     TraversalLds t;
     if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
     // history_in may be the target of recorded pathtrace calls: run them, then order the work after every frame in flight
-    int frc = flush_pending(ctx);
-    if (frc != LUPIN_OK) return frc;
-    join_primary(ctx);
+    if (int rc = join_primary(ctx)) return rc;
     hipStream_t st = ctx->stream;
     if (ninst > res->rows_capacity)
     {
@@ -3867,7 +3867,7 @@ int lupin_hip_reproject_download(LupinContext *ctx, const LupinReprojectResource
     if (res->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "reproject resources of another context");
     if (which != 0 && which != 1) return fail(LUPIN_ERR_INVALID_ARGUMENT, "which: 0 = current, 1 = previous");
     HIP_TRY(hipSetDevice(ctx->device));
-    join_primary(ctx);
+    if (int rc = join_primary(ctx)) return rc;
     // after a call the buffer its trace wrote is vis[cur ^ 1] (the roles were swapped): that is the current view's
     const ReprojectVis &v = res->vis[res->cur ^ 1 ^ which];
     const size_t px = (size_t)res->width * res->height;

@@ -68,8 +68,7 @@ int lupin_internal_fail(int code, const char *msg);          // records the mess
 bool lupin_internal_ctx_alive(const LupinContext *ctx);       // created by lupin_hip_create_context and not destroyed since
 int lupin_internal_ctx_device(const LupinContext *ctx);
 hipStream_t lupin_internal_ctx_stream(const LupinContext *ctx);   // the primary stream
-void lupin_internal_join_primary(LupinContext *ctx);         // primary stream waits for the frames enqueued so far
-int lupin_internal_sync_all(LupinContext *ctx);              // host waits for every lane
+int lupin_internal_sync_all(LupinContext *ctx);              // recorded calls run (their error is returned, message in place), host waits for every lane
 int lupin_internal_tiles_copy(LupinContext *ctx, const LupinTexture *tex, void *packed, uint32_t tile_size, uint32_t rank, uint32_t world,
                               uint64_t capacity_px, int mode);   // k_tiles_copy on the primary stream
 // the two ends of build_tlas that lupin_build_tlas and the device builder share (builders.cpp)

@@ -461,9 +461,8 @@ def chain_bvh(verts, indices):
     return nodes, tris.reshape(-1).copy()
 
 
-@pytest.mark.gpu
-def test_a_tree_too_deep_is_refused_as_a_render_refuses_it(gpu_ctx):
-    """200 triangles in a chain of depth 200: more stack than a block's LDS holds.  The query gives the render's error."""
+def deep_chain_scene(ctx):
+    """200 triangles in a chain of depth 200: more stack than a block's LDS holds, so every traversal of it is refused."""
     cpu = api.SceneCPU()
     m = api.default_material()
     m["color"] = (0.5, 0.5, 0.5, 1.0)
@@ -476,7 +475,13 @@ def test_a_tree_too_deep_is_refused_as_a_render_refuses_it(gpu_ctx):
     cpu.indices_array.append(np.arange(3 * T, dtype=np.uint32))
     cpu.mesh_infos = np.array([api.default_mesh_info()], _abi.MESH_INFO_DTYPE)
     cpu.instances = np.array([api.default_instance()], _abi.INSTANCE_DTYPE)
-    scene = api.build_accel_structures_and_upload(gpu_ctx, cpu, [], [], True, blas_builder=chain_bvh)
+    return api.build_accel_structures_and_upload(ctx, cpu, [], [], True, blas_builder=chain_bvh)
+
+
+@pytest.mark.gpu
+def test_a_tree_too_deep_is_refused_as_a_render_refuses_it(gpu_ctx):
+    """The query gives the render's error, and so does the call that runs a batch the render was only recorded into."""
+    scene = deep_chain_scene(gpu_ctx)
     rec = api.ray_records([[0.2, 0.2, 1.0]], [[0, 0, -1.0]])
     with pytest.raises(api.LupinError) as query:
         api.pathtrace_rays(gpu_ctx, scene, rec)
@@ -490,6 +495,12 @@ def test_a_tree_too_deep_is_refused_as_a_render_refuses_it(gpu_ctx):
         gpu_ctx.set_batch_frames(0)
     assert query.value.code == render.value.code == -1
     assert "too deep" in str(query.value) and str(query.value) == str(render.value)
+    # default batching: the render is recorded and returns; its error is reported by the call that runs the batch
+    api.pathtrace_scene(gpu_ctx, res, scene, target, PT.Standard, api.PathtraceDesc())
+    with pytest.raises(api.LupinError) as sync:
+        gpu_ctx.sync()
+    assert sync.value.code == query.value.code and str(sync.value) == str(query.value)
+    gpu_ctx.sync()                        # the batch was dropped with its error
 
 
 @pytest.mark.gpu
