@@ -789,6 +789,45 @@ inline std::vector<float> bake_distance_grid(const Device &d, const Scene &scene
     return out;
 }
 
+// irradiance volume lookup (no reference counterpart): irradiance at (point, normal) from a regular grid of
+// bake_probes' coefficients -- trilinear over the cell's eight probes, less the probes marked invalid and the probes the
+// scene hides from the point; lupin_hip.h states the arithmetic.
+struct ProbeGridDesc
+{
+    std::array<float, 3> origin{{0.0f, 0.0f, 0.0f}}, spacing{{1.0f, 1.0f, 1.0f}};
+    std::array<uint32_t, 3> dims{{1u, 1u, 1u}};
+    uint32_t flags = LUPIN_PROBE_GRID_VISIBILITY | LUPIN_PROBE_GRID_BACKFACE;   // | LUPIN_PROBE_GRID_DEVICE_POINTERS
+    float ray_epsilon = 0.001f;
+    float normal_bias = 0.0f;   // world units; the Python mirror's default is 1e-4 of the scene's extent
+};
+// the probe positions in index order (x fastest), n x 3 floats: origin + (float)i * spacing per axis
+inline std::vector<float> probe_grid_positions(const std::array<float, 3> &origin, const std::array<float, 3> &spacing, const std::array<uint32_t, 3> &dims)
+{
+    std::vector<float> out;
+    out.reserve((size_t)dims[0] * dims[1] * dims[2] * 3);
+    for (uint32_t iz = 0; iz < dims[2]; iz++)
+        for (uint32_t iy = 0; iy < dims[1]; iy++)
+            for (uint32_t ix = 0; ix < dims[0]; ix++)
+            {
+                const float px = (float)ix * spacing[0], py = (float)iy * spacing[1], pz = (float)iz * spacing[2];   // the product first
+                out.push_back(origin[0] + px);
+                out.push_back(origin[1] + py);
+                out.push_back(origin[2] + pz);
+            }
+    return out;
+}
+// sh: P x 9 x 4 floats; valid: nullptr or P bytes; records: n x 8 floats (point | -, unit normal | -); out: n x (r, g, b, w)
+inline void sample_probe_grid(const Device &d, const Scene &scene, const ProbeGridDesc &desc, const float *sh, const uint8_t *valid, uint64_t n,
+                              const float *records, float *out)
+{
+    LupinProbeGridDesc c;
+    for (int k = 0; k < 3; k++) { c.origin[k] = desc.origin[k]; c.spacing[k] = desc.spacing[k]; c.dims[k] = desc.dims[k]; }
+    c.flags = desc.flags;
+    c.ray_epsilon = desc.ray_epsilon;
+    c.normal_bias = desc.normal_bias;
+    check(lupin_hip_sample_probe_grid(d.raw(), scene.raw(), &c, sh, valid, n, records, out));
+}
+
 }  // namespace lp
 
 namespace lpl {

@@ -1207,6 +1207,76 @@ int lupin_hip_bake_distance_grid(LupinContext *ctx, const LupinScene *scene, uin
                                  const float *spacing /* 3 */, const uint32_t *dims /* 3 */, float rmax,
                                  float *out_volume /* dims[0] * dims[1] * dims[2] */);
 
+/* ---- irradiance volume lookup (no reference counterpart) ----
+ * "What light arrives at this point with this normal?" from a regular grid of baked probes: what lights everything a
+ * lightmap does not cover.  The consumer of lupin_hip_bake_probes: per shading point the cell, the trilinear weights of its
+ * eight probes, the probes the caller marked invalid and the probes behind a wall dropped, the clamped cosine's irradiance
+ * at the normal, and the normalisation, in one kernel.  Every float operation below is one rounded f32 operation (no
+ * contraction; division and square root correctly rounded), in the order written.
+ *
+ * Probes.  Probe (ix, iy, iz) has index ix + dims[0] * (iy + dims[1] * iz); its position is, per axis,
+ *   origin + (float)i * spacing        (the product first)
+ * These are probe POSITIONS, not voxel centres: there is no + 0.5.  sh is P x LUPIN_PROBE_SH_COEFFS x 4 floats, P =
+ * dims[0] * dims[1] * dims[2]: lupin_hip_bake_probes' out_sh for those positions in index order (the w channel is not read).
+ * valid is NULL or P bytes; a zero byte marks a probe that must not be used.
+ *
+ * Record, LUPIN_PROBE_GRID_RECORD_FLOATS floats:   [0..2] point p   [4..6] unit normal nrm   [3], [7] ignored
+ *
+ * 1. o = p + nrm * normal_bias (the product first), per axis.
+ * 2. Per axis k:   g = (o_k - origin_k) / spacing_k;   g = min(max(g, 0.0f), (float)(dims_k - 1));
+ *    i_k = dims_k > 1 ? min((uint32_t)g, dims_k - 2) : 0;   f_k = g - (float)i_k.   A point outside the grid is clamped onto
+ *    it; an axis with dims_k == 1 has f_k == 0 and ignores that coordinate.
+ * 3. Yj(nrm), j = 0 .. 8, by the nine expressions of the light-probe section above;  B_j = A_j * Yj(nrm) with the clamped
+ *    cosine's band factors A_0 = 3.14159265f (pi), A_1 = A_2 = A_3 = 2.09439510f (2 pi / 3), A_4 = .. = A_8 = 0.78539816f (pi / 4).
+ * 4. The corners c = 0 .. 7 in ascending order; bit 0 of c selects ix + 1, bit 1 iy + 1, bit 2 iz + 1.  acc = (+0, +0, +0, +0).
+ *    For each corner:
+ *      t = (wx * wy) * wz with w = bit ? f : 1.0f - f.  If t == 0 the corner contributes nothing and casts no ray.
+ *      If valid is given and valid[index] == 0 the corner is skipped.
+ *      With q the probe's position:  d = q - o;  len = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z);  dir = d / len per axis; where
+ *      len == 0, dir = nrm.
+ *      LUPIN_PROBE_GRID_BACKFACE:  b = (((dir.x*nrm.x + dir.y*nrm.y) + dir.z*nrm.z) + 1.0f) * 0.5f;  t = t * (b * b + 0.2f):
+ *      probes the surface faces away from count for less, never for nothing.
+ *      LUPIN_PROBE_GRID_VISIBILITY:  if len > 2.0f * ray_epsilon, the corner is skipped when the segment (o, dir,
+ *      ray_epsilon, tmax = len - ray_epsilon) is BLOCKED in the sense of lupin_hip_occlusion_rays: the same traversal of the
+ *      binary hierarchy, material opacity not consulted.  A shorter segment is visible.
+ *      E[ch] = sum over j ascending, from +0, of B_j * sh[index][j][ch], for ch in r, g, b.
+ *      acc.rgb = acc.rgb + t * E;  acc.w = acc.w + t.
+ *    A skipped corner is not added at all (0 * E is not added either: a NaN coefficient of a skipped probe stays out).
+ * 5. out = acc.w > 0 ? (acc.r / acc.w, acc.g / acc.w, acc.b / acc.w, acc.w) : (0, 0, 0, 0).
+ * out (n x LUPIN_PROBE_GRID_RESULT_FLOATS): irradiance r, g, b and the weight w that survived.  w == 0 means "no probe of this
+ * cell may be used"; the fallback is the caller's.  The coefficients are NOT inspected: a NaN or infinite coefficient of a
+ * probe that is used reaches the output.
+ *
+ * The call behaves as the other scene queries do: the calls recorded on the context run first (and their error, if any, is
+ * returned), the work runs on the primary stream, host arrays (sh, valid, records, out) go through staging buffers the
+ * context keeps and reuses, launches cover at most 2^27 records, and the call returns when out is complete; frames rendered
+ * before and after are what they would be without the call.  With LUPIN_PROBE_GRID_DEVICE_POINTERS sh, records and out are
+ * device memory of the context's device, 16-byte aligned, valid is device memory of any alignment, and nothing is copied.
+ * It works on a scene whose four-wide hierarchy is stale after lupin_hip_scene_update_instances.  Without
+ * LUPIN_PROBE_GRID_VISIBILITY the scene's geometry is not read and no traversal stack is reserved.
+ *
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing traced and out untouched, for: a NULL ctx, scene, desc, sh, records or out; an unknown
+ * flag; a non-finite origin; a spacing that is not finite or not positive; a zero dim; more than 2^31 probes; a last probe
+ * position that is not finite; a ray_epsilon or normal_bias that is not finite or is negative; n above 2^38; a record with a
+ * non-finite point or normal; a normal whose squared length is further than 1e-4 from 1; misaligned device pointers; a scene
+ * of another or of a destroyed context; with LUPIN_PROBE_GRID_VISIBILITY, a hierarchy too deep for the traversal stack.  Host
+ * records are checked on the host, device records by a kernel whose count the host reads before the first launch.
+ * n == 0: LUPIN_OK, nothing touched.  Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_PROBE_GRID_RECORD_FLOATS 8
+#define LUPIN_PROBE_GRID_RESULT_FLOATS 4
+enum { LUPIN_PROBE_GRID_DEVICE_POINTERS = 1u, LUPIN_PROBE_GRID_VISIBILITY = 2u, LUPIN_PROBE_GRID_BACKFACE = 4u };   /* desc.flags */
+typedef struct LupinProbeGridDesc {
+    float    origin[3];      /* position of probe (0,0,0); finite */
+    float    spacing[3];     /* finite, > 0 (also on an axis whose dim is 1) */
+    uint32_t dims[3];        /* >= 1 each; product <= 2^31 */
+    uint32_t flags;
+    float    ray_epsilon;    /* finite, >= 0; VISIBILITY only */
+    float    normal_bias;    /* finite, >= 0; world units the point is moved along its normal before anything else */
+} LupinProbeGridDesc;
+int lupin_hip_sample_probe_grid(LupinContext *ctx, const LupinScene *scene, const LupinProbeGridDesc *desc,
+                                const float *sh /* P x 9 x 4, bake_probes' out_sh */, const uint8_t *valid /* NULL or P */,
+                                uint64_t n, const float *records /* n x 8 */, float *out /* n x 4 */);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

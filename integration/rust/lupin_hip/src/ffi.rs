@@ -126,6 +126,15 @@ pub const LUPIN_DISTANCE_RECORD_FLOATS: usize = 4;
 pub const LUPIN_DISTANCE_RESULT_FLOATS: usize = 12;
 pub const LUPIN_DISTANCE_DEVICE_POINTERS: u32 = 1;
 pub const LUPIN_DISTANCE_GRID_SIGNED: u32 = 2;
+// irradiance volume lookup (no reference counterpart)
+pub const LUPIN_PROBE_GRID_RECORD_FLOATS: usize = 8;
+pub const LUPIN_PROBE_GRID_RESULT_FLOATS: usize = 4;
+pub const LUPIN_PROBE_GRID_DEVICE_POINTERS: u32 = 1;
+pub const LUPIN_PROBE_GRID_VISIBILITY: u32 = 2;
+pub const LUPIN_PROBE_GRID_BACKFACE: u32 = 4;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinProbeGridDesc {
+    pub origin: [f32; 3], pub spacing: [f32; 3], pub dims: [u32; 3], pub flags: u32, pub ray_epsilon: f32, pub normal_bias: f32,
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -229,6 +238,9 @@ extern "C" {
     pub fn lupin_hip_distance_points(ctx: *mut LupinContext, scene: *const LupinScene, flags: u32, n: u64, records: *const f32, out_results: *mut f32) -> c_int;
     pub fn lupin_hip_bake_distance_grid(ctx: *mut LupinContext, scene: *const LupinScene, flags: u32, origin: *const f32, spacing: *const f32,
                                         dims: *const u32, rmax: f32, out_volume: *mut f32) -> c_int;
+    // irradiance volume lookup: sh P x 9 x 4 f32 (bake_probes' out_sh), valid null or P bytes, records n x 8 f32 (point | -, unit normal | -), out n x 4
+    pub fn lupin_hip_sample_probe_grid(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinProbeGridDesc, sh: *const f32,
+                                       valid: *const u8, n: u64, records: *const f32, out: *mut f32) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

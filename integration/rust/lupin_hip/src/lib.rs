@@ -322,3 +322,23 @@ pub fn bake_distance_grid(device: &Device, scene: &Scene, origin: [f32; 3], spac
     check(unsafe { lupin_hip_bake_distance_grid(device.raw, scene.raw, flags, origin.as_ptr(), spacing.as_ptr(), dims.as_ptr(), rmax, out.as_mut_ptr()) });
     out
 }
+
+// ---- irradiance volume lookup (no reference counterpart) ----
+/// Irradiance `(r, g, b, w)` per record (8 floats: point | -, unit normal | -) from a regular grid of `bake_probes` coefficients
+/// (`sh`: P x 9 x 4, probe `(ix, iy, iz)` at `origin + i * spacing`, index `ix + dims[0] * (iy + dims[1] * iz)`): trilinear over the
+/// cell's eight probes, less the probes with a zero byte in `valid` and, with `visibility`, the probes the scene hides from the
+/// point.  `w == 0`: no probe of the cell may be used.  The point is first moved along its normal by `normal_bias` world units.
+#[allow(clippy::too_many_arguments)]
+pub fn sample_probe_grid(device: &Device, scene: &Scene, origin: [f32; 3], spacing: [f32; 3], dims: [u32; 3], sh: &[f32], valid: Option<&[u8]>,
+                         records: &[f32], visibility: bool, backface: bool, ray_epsilon: f32, normal_bias: f32) -> Vec<f32> {
+    let probes = dims[0] as usize * dims[1] as usize * dims[2] as usize;
+    assert!(sh.len() == probes * 36 && valid.map_or(true, |v| v.len() == probes));
+    assert!(records.len() % LUPIN_PROBE_GRID_RECORD_FLOATS == 0);
+    let n = records.len() / LUPIN_PROBE_GRID_RECORD_FLOATS;
+    let mut out = vec![0f32; n * LUPIN_PROBE_GRID_RESULT_FLOATS];
+    let flags = if visibility { LUPIN_PROBE_GRID_VISIBILITY } else { 0 } | if backface { LUPIN_PROBE_GRID_BACKFACE } else { 0 };
+    let c = LupinProbeGridDesc { origin, spacing, dims, flags, ray_epsilon, normal_bias };
+    check(unsafe { lupin_hip_sample_probe_grid(device.raw, scene.raw, &c, sh.as_ptr(), valid.map_or(std::ptr::null(), |v| v.as_ptr()), n as u64,
+                                               records.as_ptr(), out.as_mut_ptr()) });
+    out
+}

@@ -188,6 +188,11 @@ class OcclusionDescC(C.Structure):   # LupinOcclusionDesc
     _fields_ = [("mode", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32), ("ray_epsilon", C.c_float)]
 
 
+class ProbeGridDescC(C.Structure):   # LupinProbeGridDesc
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_uint32 * 3), ("flags", C.c_uint32),
+                ("ray_epsilon", C.c_float), ("normal_bias", C.c_float)]
+
+
 class TlasBuildStatsC(C.Structure):   # LupinTlasBuildStats
     _fields_ = [("num_instances", C.c_uint32), ("state_in_lds", C.c_uint32), ("scans", C.c_uint64), ("kernel_ms", C.c_float)]
 
@@ -268,6 +273,7 @@ SYMBOLS = [
     ("lupin_hip_transmittance_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),
     ("lupin_hip_distance_points", C.c_int, [_P, _P, _U32, C.c_uint64, _P, _P]),
     ("lupin_hip_bake_distance_grid", C.c_int, [_P, _P, _U32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_float, _P]),
+    ("lupin_hip_sample_probe_grid", C.c_int, [_P, _P, C.POINTER(ProbeGridDescC), _P, _P, C.c_uint64, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),

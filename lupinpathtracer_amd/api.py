@@ -1880,3 +1880,104 @@ def surface_clearance(ctx, scene, points, normals, offset):
     normals = np.asarray(normals, np.float32).reshape(-1, 3)
     offset = np.asarray(offset, np.float32).reshape(-1, 1)
     return nearest_distance(ctx, scene, points + normals * offset)
+
+
+# ---- irradiance volume lookup: lupin_hip_sample_probe_grid (include/lupin_hip.h) ----
+PROBE_GRID_RECORD_FLOATS = 8
+PROBE_GRID_RESULT_FLOATS = 4
+PROBE_GRID_DEVICE_POINTERS = 1
+PROBE_GRID_VISIBILITY = 2
+PROBE_GRID_BACKFACE = 4
+
+
+def probe_grid_positions(origin, spacing, dims):
+    """The probe positions of a grid, (P, 3) float32 in index order (x fastest: probe (ix, iy, iz) has index
+    ix + nx * (iy + ny * iz)), by the stated f32 expression per axis: origin + float32(i) * spacing, the product first.
+    Probe positions, not voxel centres: there is no + 0.5."""
+    origin, spacing = np.asarray(origin, np.float32).reshape(3), np.asarray(spacing, np.float32).reshape(3)
+    axes = [origin[k] + np.arange(int(dims[k]), dtype=np.float32) * spacing[k] for k in range(3)]
+    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.stack([x, y, z], -1).astype(np.float32).reshape(-1, 3)
+
+
+def bake_probe_grid(ctx, scene, origin, spacing, dims, **bake_probes_kwargs):
+    """(positions (P, 3), sh (P, 9, 4)) float32: one bake_probes call at probe_grid_positions(origin, spacing, dims), with
+    bake_probes' keyword arguments.  No validity judgement is made: which probes may be used (inside geometry, too close
+    to a wall) is the caller's, with occlusion_rays and distance_points to decide it by."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_probe_grid needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if bake_probes_kwargs.get("want_rays"):
+        raise ValueError("bake_probe_grid returns positions and coefficients only; call bake_probes for the first rays")
+    pos = probe_grid_positions(origin, spacing, dims)
+    return pos, bake_probes(ctx, scene, pos, **bake_probes_kwargs)
+
+
+def probe_grid_records(points, normals):
+    """(n, PROBE_GRID_RECORD_FLOATS) float32 records for sample_probe_grid: `points` (n, 3) and unit `normals` (n, 3)."""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    rec = np.zeros((len(points), PROBE_GRID_RECORD_FLOATS), np.float32)
+    rec[:, 0:3] = points
+    rec[:, 4:7] = np.asarray(normals, np.float32).reshape(-1, 3)
+    return rec
+
+
+def sample_probe_grid(ctx, scene, origin, spacing, dims, sh, points_or_records, normals=None, valid=None, visibility=True, backface=True,
+                      ray_epsilon=0.001, normal_bias=None):
+    """Irradiance from a grid of baked probes: (n, 4) float32, (r, g, b, w) per shading point -- the trilinear blend of the
+    cell's eight probes' sh_irradiance at the normal, over the probes that may be used, and the weight w that survived
+    (w == 0: none of the cell's probes may be used, r = g = b = 0; the fallback is the caller's).  `sh` is (P, 9, 4), what
+    bake_probe_grid returns; `valid` None or (P,) with zeros at the probes not to use; visibility drops the probes the
+    scene's geometry hides from the point (light does not leak through walls), backface weighs down the probes behind the
+    surface.  The point is first moved along its normal by `normal_bias` world units (None: LIGHTMAP_OFFSET_FRACTION of the
+    scene's extent, ambient_occlusion's default).  `points_or_records` is (n, 3) points with `normals` (n, 3), or (n, 8)
+    records (see probe_grid_records).  With a contiguous float32 torch tensor on the context's device for `sh` and for the
+    records, torch's current stream is synchronised, the device memory is used in place (`valid`, if given, a uint8 or bool
+    tensor there) and a tensor is returned.  Blocks until complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "sample_probe_grid needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if normal_bias is None:
+        normal_bias = LIGHTMAP_OFFSET_FRACTION * scene_world_extent(scene)
+    nx, ny, nz = (int(d) for d in dims)
+    P = nx * ny * nz
+    flags = (PROBE_GRID_VISIBILITY if visibility else 0) | (PROBE_GRID_BACKFACE if backface else 0)
+    c = _abi.ProbeGridDescC((C.c_float * 3)(*[float(x) for x in np.asarray(origin, np.float32).reshape(3)]),
+                            (C.c_float * 3)(*[float(x) for x in np.asarray(spacing, np.float32).reshape(3)]),
+                            (C.c_uint32 * 3)(nx, ny, nz), flags, float(ray_epsilon), float(np.float32(normal_bias)))
+    fn = lib().lupin_hip_sample_probe_grid
+    if hasattr(points_or_records, "data_ptr") or hasattr(sh, "data_ptr"):   # torch tensors
+        import torch
+        t = points_or_records
+        if not (hasattr(t, "data_ptr") and hasattr(sh, "data_ptr")):
+            raise ValueError("sh and records must both be torch tensors, or neither")
+        if normals is not None:
+            raise ValueError("tensor records carry their normals: (n, 8)")
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == PROBE_GRID_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+        if not (sh.is_cuda and sh.dtype == torch.float32 and sh.is_contiguous() and tuple(sh.shape) == (P, PROBE_SH_COEFFS, 4)):
+            raise ValueError("sh must be a contiguous (P, 9, 4) float32 tensor on the context's device")
+        if valid is not None and not (hasattr(valid, "data_ptr") and valid.is_cuda and valid.dtype in (torch.uint8, torch.bool) and
+                                      valid.is_contiguous() and valid.numel() == P):
+            raise ValueError("valid must be a contiguous uint8 or bool tensor of P elements on the context's device")
+        if any(x.device.index != ctx.device_ordinal for x in (t, sh) + (() if valid is None else (valid,))):
+            raise ValueError("a tensor is on another device than the context")
+        out = torch.zeros((int(t.shape[0]), PROBE_GRID_RESULT_FLOATS), dtype=torch.float32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()   # the inputs (and the zero fill) are written
+        c.flags |= PROBE_GRID_DEVICE_POINTERS
+        check(fn(ctx.handle, scene.handle, C.byref(c), C.c_void_p(sh.data_ptr()), None if valid is None else C.c_void_p(valid.data_ptr()),
+                 int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+    if normals is not None:
+        rec = probe_grid_records(points_or_records, normals)
+    else:
+        rec = np.ascontiguousarray(points_or_records, np.float32).reshape(-1, PROBE_GRID_RECORD_FLOATS)
+    sh = np.ascontiguousarray(sh, np.float32)
+    if sh.shape != (P, PROBE_SH_COEFFS, 4):
+        raise ValueError(f"sh must be ({P}, 9, 4) for dims {(nx, ny, nz)}")
+    v = None
+    if valid is not None:
+        v = np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, np.uint8)
+        if v.shape != (P,):
+            raise ValueError(f"valid must have {P} elements for dims {(nx, ny, nz)}")
+    out = np.zeros((len(rec), PROBE_GRID_RESULT_FLOATS), np.float32)
+    check(fn(ctx.handle, scene.handle, C.byref(c), ptr(sh), ptr(v), len(rec), ptr(rec), ptr(out)))
+    return out

@@ -35,6 +35,7 @@
 #include "lupin_occlusion.hpp"
 #include "lupin_transmittance.hpp"
 #include "lupin_distance.hpp"
+#include "lupin_probe_grid.hpp"
 #include "lupin_internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -143,6 +144,10 @@ struct LupinContext
     // auxiliary array (local -> world rows and c_i) that every call rebuilds from the scene's current rows
     DeviceBuffer dist_records, dist_results, dist_aux;
     size_t dist_records_bytes = 0, dist_results_bytes = 0, dist_aux_bytes = 0;
+    // lupin_hip_sample_probe_grid: the staging of host arrays (the grid's coefficients and validity bytes, one chunk's
+    // records and results), kept and grown the same way
+    DeviceBuffer grid_sh, grid_valid, grid_records, grid_results;
+    size_t grid_sh_bytes = 0, grid_valid_bytes = 0, grid_records_bytes = 0, grid_results_bytes = 0;
     // lupin_hip_denoise_lightmap: the staging of host arrays (rgba, which is also where the result lands, and records) and the
     // filter's scratch (two (irradiance, variance) planes, the two guide planes, the footprint, two `filled` planes for
     // the gutter passes), kept and grown the same way
@@ -3090,6 +3095,104 @@ int lupin_hip_bake_distance_grid(LupinContext *ctx, const LupinScene *scene, uin
         if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, (size_t)voxels * 4, hipMemcpyDeviceToHost, st));
     }
     return query_end(ctx, "lupin_hip_bake_distance_grid");
+}
+
+// ---- irradiance volume lookup (no reference counterpart; kernel: lupin_probe_grid.hpp) ----
+
+static constexpr uint64_t LP_PROBE_GRID_MAX_LAUNCH = 1ull << 27;          // records of one launch: eight lanes each, and the lane index fits 32 bits
+static constexpr uint64_t LP_PROBE_GRID_MAX_STAGED_RECORDS = 1ull << 20;  // host arrays: records of one launch (32 + 16 MB of staging)
+static constexpr uint64_t LP_PROBE_GRID_MAX_PROBES = 1ull << 31;
+
+int lupin_hip_sample_probe_grid(LupinContext *ctx, const LupinScene *scene, const LupinProbeGridDesc *desc, const float *sh, const uint8_t *valid,
+                                uint64_t n, const float *records, float *out)
+{
+    if (int rc = query_refuse(ctx, scene, desc && sh && records && out)) return rc;
+    constexpr uint32_t known = LUPIN_PROBE_GRID_DEVICE_POINTERS | LUPIN_PROBE_GRID_VISIBILITY | LUPIN_PROBE_GRID_BACKFACE;
+    if (desc->flags & ~known) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    for (int k = 0; k < 3; k++)
+    {
+        if (!std::isfinite(desc->origin[k])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "origin must be finite");
+        if (!(std::isfinite(desc->spacing[k]) && desc->spacing[k] > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "spacing must be finite and positive");
+        if (desc->dims[k] == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "a dimension is zero");
+    }
+    const uint64_t slice = (uint64_t)desc->dims[0] * desc->dims[1];   // below 2^64: both factors are below 2^32
+    if (slice > LP_PROBE_GRID_MAX_PROBES || desc->dims[2] > LP_PROBE_GRID_MAX_PROBES / slice)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid must not exceed 2^31 probes");
+    for (int k = 0; k < 3; k++)   // the last probe, by the kernel's own expression: every probe of the axis lies between the first and this one
+        if (!std::isfinite(desc->origin[k] + (float)(desc->dims[k] - 1u) * desc->spacing[k]))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid's last probe position is not finite");
+    if (!(std::isfinite(desc->ray_epsilon) && desc->ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
+    if (!(std::isfinite(desc->normal_bias) && desc->normal_bias >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "normal_bias must be finite and not negative");
+    if (n > LP_RAYS_MAX_PATHS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n must not exceed 2^38");
+    const bool vis = (desc->flags & LUPIN_PROBE_GRID_VISIBILITY) != 0;
+    if (vis)
+        if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
+    const bool on_device = (desc->flags & LUPIN_PROBE_GRID_DEVICE_POINTERS) != 0;
+    if (on_device && (((uintptr_t)sh | (uintptr_t)records | (uintptr_t)out) & 15u))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device coefficients, records and results must be 16-byte aligned");
+    if (n == 0) return LUPIN_OK;
+    // query_start's pieces with this query's own stack: none at all without visibility, where the scene is not read
+    if (int rc = query_flush(ctx)) return rc;
+    if (!on_device)
+        if (int rc = refuse_bad_host_records<ProbeGridRecordRule>(n, records)) return rc;
+    TraversalLds t;
+    if (int rc = traversal_lds(ctx, scene, vis ? scene->stack_entries : 0u, vis, &t)) return rc;
+    if (int rc = join_primary(ctx)) return rc;
+    if (on_device)
+        if (int rc = refuse_bad_device_records<ProbeGridRecordRule>(ctx, n, records)) return rc;
+    hipStream_t st = ctx->stream;
+
+    const uint64_t probes = slice * desc->dims[2];
+    ProbeGridDev g;
+    g.ox = desc->origin[0]; g.oy = desc->origin[1]; g.oz = desc->origin[2];
+    g.sx = desc->spacing[0]; g.sy = desc->spacing[1]; g.sz = desc->spacing[2];
+    g.nx = desc->dims[0]; g.ny = desc->dims[1]; g.nz = desc->dims[2];
+    g.flags = desc->flags;
+    g.eps = desc->ray_epsilon; g.bias = desc->normal_bias;
+
+    uint64_t chunk = std::min(n, LP_PROBE_GRID_MAX_LAUNCH);
+    const float4 *d_sh = reinterpret_cast<const float4 *>(sh);
+    const uint8_t *d_valid = valid;
+    if (!on_device)
+    {
+        chunk = std::min(chunk, LP_PROBE_GRID_MAX_STAGED_RECORDS);
+        const size_t sh_bytes = (size_t)probes * LUPIN_PROBE_RESULT_FLOATS * 4;
+        HIP_TRY(grow_buffer(&ctx->grid_sh, &ctx->grid_sh_bytes, sh_bytes));
+        HIP_TRY(grow_buffer(&ctx->grid_records, &ctx->grid_records_bytes, (size_t)chunk * LUPIN_PROBE_GRID_RECORD_FLOATS * 4));
+        HIP_TRY(grow_buffer(&ctx->grid_results, &ctx->grid_results_bytes, (size_t)chunk * LUPIN_PROBE_GRID_RESULT_FLOATS * 4));
+        HIP_TRY(hipMemcpyAsync(ctx->grid_sh.get(), sh, sh_bytes, hipMemcpyHostToDevice, st));
+        d_sh = ctx->grid_sh.as<float4>();
+        if (valid)
+        {
+            HIP_TRY(grow_buffer(&ctx->grid_valid, &ctx->grid_valid_bytes, (size_t)probes));
+            HIP_TRY(hipMemcpyAsync(ctx->grid_valid.get(), valid, (size_t)probes, hipMemcpyHostToDevice, st));
+            d_valid = ctx->grid_valid.as<uint8_t>();
+        }
+    }
+    for (uint64_t first = 0; first < n; first += chunk)
+    {
+        const uint32_t recs = (uint32_t)std::min(chunk, n - first);
+        const float *src = records + first * LUPIN_PROBE_GRID_RECORD_FLOATS;
+        float *dst = out + first * LUPIN_PROBE_GRID_RESULT_FLOATS;
+        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
+        float4 *d_res = reinterpret_cast<float4 *>(dst);
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(ctx->grid_records.get(), src, (size_t)recs * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
+            d_rec = ctx->grid_records.as<float4>();
+            d_res = ctx->grid_results.as<float4>();
+        }
+        const dim3 grid((recs + LP_PROBE_GRID_RECORDS_PER_BLOCK - 1) / LP_PROBE_GRID_RECORDS_PER_BLOCK);
+        with_bool(t.geo, [&](auto G) {
+            with_bool(vis, [&](auto V) {
+                hipLaunchKernelGGL((k_probe_grid<decltype(G)::value, decltype(V)::value>), grid, dim3(LP_BLOCK), t.lds, st, scene->dev, recs, g, d_sh,
+                                   d_valid, d_rec, d_res, t.stack_words);
+            });
+        });
+        HIP_TRY(hipGetLastError());
+        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_res, (size_t)recs * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    }
+    return query_end(ctx, "lupin_hip_sample_probe_grid");
 }
 
 // ---- lightmap baking (no reference counterpart; kernels: lupin_lightmap.hpp) ----
