@@ -210,6 +210,86 @@ def true_density(scene: RefScene, pos, dirs, slot_prob=None, chunk=4_000_000):
     return out / max(scene.n, 1)
 
 
+# ---- the sampler for given draws ------------------------------------------------------------------------------------------
+
+PICK_ULPS = 8.0 * 2.0 ** -24     # rnd * n is one f32 product of exact numbers: a relative rounding of 2^-24, taken eight times
+
+
+def attach_tables(scene: RefScene, alias_tables, env_alias_tables):
+    """Hand the sampler the alias bins the scene was uploaded with (api.build_lights' tables: data, in light / environment
+    order).  The thresholds and the draws are f32 numbers, so `rnd >= threshold` is an exact comparison."""
+    for light, t in zip(scene.lights, alias_tables):
+        light.bins = t
+    for env, t in zip(scene.envs, env_alias_tables):
+        env.bins = t
+
+
+def _pick(r, n):
+    """random_u32_range_unsafe for a drawn r: min(u32(r * n), n - 1), and its margin (> 1: no f32 rounding changes it)."""
+    x = r * float(n)
+    k = np.minimum(np.floor(x).astype(np.int64), n - 1)
+    near = np.abs(x - np.round(x))
+    with np.errstate(divide="ignore"):
+        margin = np.where((np.round(x) >= 1) & (np.round(x) <= n - 1), near / (PICK_ULPS * np.maximum(x, 1.0)), np.inf)
+    return k, margin
+
+
+def _alias(bins, state, random_f32):
+    n = len(bins)
+    state, r = random_f32(state)
+    k, margin = _pick(r, n)
+    state, r2 = random_f32(state)
+    thr = np.asarray(bins["alias_threshold"], np.float64)[k]
+    return np.where(r2 >= thr, np.asarray(bins["alias"], np.int64)[k], k), state, margin
+
+
+def sample(scene: RefScene, pos, rng_state):
+    """sample_lights (pathtracer.wgsl:2468-2514, :2610-2638, :1675-1679) for the draws that follow rng_state, per query: the
+    pick among mesh lights and environments, the alias pick of a slot, the point on the slot's triangle (the triangle the
+    sampler reads: tris_world), the uniform sphere (not turned by the environment's transform) or the alias pick of a texel
+    and its centre.  Returns (direction (Q, 3), RNG state afterwards (Q,) uint64, margin (Q,)): the margin is the smallest
+    distance of a rnd * n to an integer in units of its f32 rounding; above 1 every pick is certain.  Needs attach_tables."""
+    from tests.camera_ref import random_f32
+    pos = np.asarray(pos, np.float64).reshape(-1, 3)
+    state = np.asarray(rng_state, np.uint64).copy()
+    Q = len(pos)
+    out, margin = np.zeros((Q, 3)), np.full(Q, np.inf)
+    nl, n = len(scene.lights), scene.n
+    if n == 0:
+        return out, state, margin
+    state, r = random_f32(state)
+    which, margin = _pick(r, n)
+    for li in range(n):
+        sel = np.nonzero(which == li)[0]
+        if not len(sel):
+            continue
+        if li < nl:
+            light = scene.lights[li]
+            slot, st, m = _alias(light.bins, state[sel], random_f32)
+            st, r0 = random_f32(st)
+            st, r1 = random_f32(st)
+            u, v = 1.0 - np.sqrt(r0), r1 * np.sqrt(r0)
+            t = light.tris_world[slot]
+            p = t[:, 0] * (1.0 - u - v)[:, None] + t[:, 1] * u[:, None] + t[:, 2] * v[:, None]
+            d = p - pos[sel]
+            out[sel] = d / np.linalg.norm(d, axis=-1, keepdims=True)
+        else:
+            env = scene.envs[li - nl]
+            if env.weights is None:
+                st, r0 = random_f32(state[sel])
+                st, r1 = random_f32(st)
+                z = 2.0 * r1 - 1.0
+                rr = np.sqrt(np.clip(1.0 - z * z, 0.0, 1.0))
+                out[sel] = np.stack([rr * np.cos(2.0 * math.pi * r0), rr * np.sin(2.0 * math.pi * r0), z], -1)
+                m = np.full(len(sel), np.inf)
+            else:
+                texel, st, m = _alias(env.bins, state[sel], random_f32)
+                out[sel] = env_texel_to_dir(env, texel)
+        state[sel] = st
+        margin[sel] = np.minimum(margin[sel], m)
+    return out, state, margin
+
+
 # ---- solid angles -------------------------------------------------------------------------------------------------------
 
 def solid_angle(pos, tris):
