@@ -828,6 +828,46 @@ inline void sample_probe_grid(const Device &d, const Scene &scene, const ProbeGr
     check(lupin_hip_sample_probe_grid(d.raw(), scene.raw(), &c, sh, valid, n, records, out));
 }
 
+// probe depth maps (no reference counterpart): per probe an octahedral map of the mean and mean square of the
+// distance to the nearest surface, and the irradiance volume lookup that takes a corner's visibility from those maps
+// instead of the scene; lupin_hip.h states the arithmetic.
+struct ProbeDepthDesc
+{
+    uint32_t resolution = 16;     // R: interior texels per side, 2 .. 64
+    uint32_t subsamples = 4;      // K: 1, 2, 4 or 8; K * K rays per texel
+    uint32_t flags = 0;           // LUPIN_PROBE_DEPTH_DEVICE_POINTERS
+    uint32_t max_slots = 0;       // rays per launch; 0 = the library's default
+    float ray_epsilon = 0.001f;
+    float max_distance = 1.0f;    // the cap; for a grid, 1.5 |spacing| is the Python mirror's default
+};
+// positions: n x 4 floats ([3] ignored); out_depth: n x (R + 2) x (R + 2) x 2; out_stats: nullptr or n x 4 words
+inline void bake_probe_depth(const Device &d, const Scene &scene, const ProbeDepthDesc &desc, uint64_t n, const float *positions, float *out_depth,
+                             uint32_t *out_stats = nullptr)
+{
+    LupinProbeDepthDesc c;
+    c.resolution = desc.resolution;
+    c.subsamples = desc.subsamples;
+    c.flags = desc.flags;
+    c.max_slots = desc.max_slots;
+    c.ray_epsilon = desc.ray_epsilon;
+    c.max_distance = desc.max_distance;
+    check(lupin_hip_bake_probe_depth(d.raw(), scene.raw(), &c, n, positions, out_depth, out_stats));
+}
+// desc.flags: LUPIN_PROBE_GRID_BACKFACE | LUPIN_PROBE_GRID_DEVICE_POINTERS (LUPIN_PROBE_GRID_VISIBILITY, ProbeGridDesc's default, is
+// refused: clear it); depth: P x (R + 2) x (R + 2) x 2, bake_probe_depth's maps at the grid's positions; max_distance: the bake's
+inline void sample_probe_grid_depth(const Device &d, const Scene &scene, const ProbeGridDesc &desc, uint32_t resolution, float max_distance, const float *sh,
+                                    const float *depth, const uint8_t *valid, uint64_t n, const float *records, float *out)
+{
+    LupinProbeGridDepthDesc c;
+    for (int k = 0; k < 3; k++) { c.grid.origin[k] = desc.origin[k]; c.grid.spacing[k] = desc.spacing[k]; c.grid.dims[k] = desc.dims[k]; }
+    c.grid.flags = desc.flags;
+    c.grid.ray_epsilon = desc.ray_epsilon;
+    c.grid.normal_bias = desc.normal_bias;
+    c.resolution = resolution;
+    c.max_distance = max_distance;
+    check(lupin_hip_sample_probe_grid_depth(d.raw(), scene.raw(), &c, sh, depth, valid, n, records, out));
+}
+
 }  // namespace lp
 
 namespace lpl {

@@ -1277,6 +1277,105 @@ int lupin_hip_sample_probe_grid(LupinContext *ctx, const LupinScene *scene, cons
                                 const float *sh /* P x 9 x 4, bake_probes' out_sh */, const uint8_t *valid /* NULL or P */,
                                 uint64_t n, const float *records /* n x 8 */, float *out /* n x 4 */);
 
+/* ---- probe depth maps (no reference counterpart) ----
+ * "What does this probe see, as distances, per direction?"  lupin_hip_bake_probe_depth bakes per probe an octahedral map of
+ * the mean and the mean square of the distance to the nearest surface; lupin_hip_sample_probe_grid_depth is the irradiance
+ * volume lookup above with a corner's any-hit segment replaced by a Chebyshev test against the corner's map, so that a
+ * baked volume needs no scene geometry to be looked up.  Every float operation below is one rounded f32 operation (no
+ * contraction; division and square root correctly rounded), in the order written.  sgn(x) is -1.0f for x < 0 and +1.0f
+ * otherwise (sgn(0) = +1); |x| clears the sign bit.
+ *
+ * BAKE.  R = resolution, K = subsamples.  positions: n x 4 floats, [3] ignored.  Probe i casts R * R * K * K rays; the ray of
+ * texel (tx, ty), sub-sample (sx, sy) is slot ((i * R * R + ty * R + tx) * K * K) + sy * K + sx.
+ * Direction (octahedral decode):
+ *   a = ((float)(tx * K + sx) + 0.5f) / (float)(R * K);   u = 2.0f * a - 1.0f;   v likewise from ty, sy
+ *   z = (1.0f - |u|) - |v|
+ *   if z < 0:  x = (1.0f - |v|) * sgn(u),  y = (1.0f - |u|) * sgn(v);   otherwise  x = u,  y = v
+ *   len = sqrtf((x * x + y * y) + z * z);   w = (x / len, y / len, z / len)
+ * Distance: (hit, dst) is lupin_hip_trace_rays' answer for (position, w, ray_epsilon), bit for bit (the binary hierarchy;
+ * material opacity is not consulted);  d = hit ? min(dst, max_distance) : max_distance.
+ * Reduction: the K * K rays of a texel hold (d, d * d) in sub-sample order s = sy * K + sx.  For offset = K * K / 2, .., 2, 1:
+ * acc[s] = acc[s] + acc[s xor offset], all s at once (a butterfly: every s ends with the same value).  Then
+ *   m1 = acc.x / (float)(K * K),   m2 = acc.y / (float)(K * K)
+ * Layout: out_depth[i] is a row-major (R + 2) x (R + 2) map of (m1, m2); interior texel (tx, ty) sits at (tx + 1, ty + 1).
+ * The one-texel border holds copies, so that plain bilinear filtering is right across the octahedral seams: for border
+ * coordinates (bx, by) in -1 .. R, with clamp to 0 .. R - 1,
+ *   both out of range:     the source is interior texel (R - 1 - clamp(bx), R - 1 - clamp(by))
+ *   only bx out of range:  (clamp(bx), R - 1 - by)
+ *   only by out of range:  (R - 1 - bx, clamp(by))
+ * Stats (out_stats NULL, or n x LUPIN_PROBE_DEPTH_STATS_WORDS words which the call initialises), per probe:
+ *   [0] rays = R * R * K * K     [1] rays that hit anything (before the cap)
+ *   [2] hits on a back face: ((w.x * g.x + w.y * g.y) + w.z * g.z) > 0 with g the hit triangle's geometric normal, the value
+ *       lupin_hip_surface_probe reports in LUPIN_SURFACE_NORMAL mode at [3..5]
+ *   [3] the bits of the smallest d, as an unsigned minimum over the bits
+ * None of the words depends on how the rays were cut into launches.
+ *
+ * The call behaves as the other scene queries do: the calls recorded on the context run first (and their error, if any, is
+ * returned), the work runs on the primary stream, host arrays go through device buffers that live for the call (at most
+ * 1024 probes at a time), a launch covers at most max_slots rays (0: LUPIN_PROBE_DEPTH_DEFAULT_MAX_SLOTS; rounded down to a
+ * multiple of 64, at least 64, at most 2^30), and the call returns when the outputs are complete; frames rendered before and
+ * after are what they would be without the call.  With LUPIN_PROBE_DEPTH_DEVICE_POINTERS positions, out_depth and out_stats
+ * are device memory of the context's device (positions and out_stats 16-byte aligned, out_depth 8-byte aligned) and nothing
+ * is copied.  It works on a scene whose four-wide hierarchy is stale after lupin_hip_scene_update_instances.
+ *
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing traced and the outputs untouched, for: a NULL ctx, scene, desc, positions or out_depth;
+ * an unknown flag; a resolution outside 2 .. 64; subsamples other than 1, 2, 4, 8; a ray_epsilon that is not finite or is
+ * negative; a max_distance that is not finite or not positive; n * R * R * K * K above 2^38; misaligned device pointers; a
+ * scene of another or of a destroyed context; a position with a non-finite coordinate (host positions are checked on the
+ * host, device positions by a kernel whose count the host reads before the first launch); a hierarchy too deep for the
+ * traversal stack.  LUPIN_ERR_NO_SW_BVH for a scene without a software BVH.  n == 0: LUPIN_OK, nothing touched.  Without a
+ * HIP device: LUPIN_ERR_NO_DEVICE.
+ *
+ * LOOKUP.  sh, valid, records, out and steps 1 to 5 are lupin_hip_sample_probe_grid's, word for word, with grid.flags of
+ * LUPIN_PROBE_GRID_DEVICE_POINTERS and LUPIN_PROBE_GRID_BACKFACE (LUPIN_PROBE_GRID_VISIBILITY is refused: the visibility is
+ * the maps'; grid.ray_epsilon is checked and not used).  depth is P x (R + 2) x (R + 2) x 2 floats, the bake's out_depth for
+ * the grid's probe positions in index order, R = resolution; max_distance is the bake's.  In step 4, in the place of the
+ * LUPIN_PROBE_GRID_VISIBILITY clause, for a corner still in use (after the backface factor):
+ *   if len == 0 the corner is visible.  Otherwise, with e = -dir (the probe looks at the point):
+ *   s = (|e.x| + |e.y|) + |e.z|;   px = e.x / s;   py = e.y / s
+ *   if e.z < 0:  (px, py) = ((1.0f - |py|) * sgn(px), (1.0f - |px|) * sgn(py)), both from the old values
+ *   per axis:  a = px * 0.5f;  a = a + 0.5f;  a = a * (float)R;  a = a + 0.5f;  ix = min((uint32_t)a, R);  fx = a - (float)ix
+ *   m00, m10, m01, m11 = texels (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1) of the probe's bordered map; per moment
+ *   top = m00 + fx * (m10 - m00);   bot = m01 + fx * (m11 - m01);   m = top + fy * (bot - top)
+ *   r = min(len, max_distance)
+ *   if r > m1:  x = m2 - m1 * m1;  var = x > 0 ? x : 0.0f;  dd = r - m1;  c = var / (var + dd * dd);  vis = (c * c) * c;
+ *               t = t * vis;  a corner with vis == 0 is skipped like a blocked one (not added at all).
+ * The moments are NOT inspected.  A NaN m1 fails r > m1: the corner counts as visible.  A NaN m2 (with r > m1) gives var = 0,
+ * hence vis = 0 unless dd * dd underflows to 0 as well, where c = 0 / 0 is NaN and reaches the output, as does any NaN that
+ * an infinite moment produces.
+ *
+ * The scene's geometry is never read and no LDS is reserved: a scene without a software BVH, or with a hierarchy too deep
+ * for the stack, is accepted; it still has to belong to the context.  Otherwise the call behaves as
+ * lupin_hip_sample_probe_grid does (host arrays go through device buffers that live for the call).  With
+ * LUPIN_PROBE_GRID_DEVICE_POINTERS depth is device memory, 8-byte aligned.
+ * LUPIN_ERR_INVALID_ARGUMENT, out untouched, for: what lupin_hip_sample_probe_grid refuses without VISIBILITY; a NULL depth;
+ * LUPIN_PROBE_GRID_VISIBILITY; a resolution outside 2 .. 64; a max_distance that is not finite or not positive. */
+#define LUPIN_PROBE_DEPTH_STATS_WORDS 4
+#define LUPIN_PROBE_DEPTH_MIN_RESOLUTION 2
+#define LUPIN_PROBE_DEPTH_MAX_RESOLUTION 64
+#define LUPIN_PROBE_DEPTH_DEFAULT_MAX_SLOTS (1u << 24)
+enum { LUPIN_PROBE_DEPTH_DEVICE_POINTERS = 1u };   /* LupinProbeDepthDesc.flags */
+typedef struct LupinProbeDepthDesc {
+    uint32_t resolution;    /* R: interior texels per side, 2 .. 64 */
+    uint32_t subsamples;    /* K: 1, 2, 4 or 8; K * K rays per texel on a regular sub-grid, no RNG */
+    uint32_t flags;         /* LUPIN_PROBE_DEPTH_DEVICE_POINTERS */
+    uint32_t max_slots;     /* 0 = library default; rays per launch, rounded down to a multiple of 64, at least 64 */
+    float    ray_epsilon;   /* finite, >= 0 */
+    float    max_distance;  /* finite, > 0: distances are capped here, misses count as this */
+} LupinProbeDepthDesc;
+int lupin_hip_bake_probe_depth(LupinContext *ctx, const LupinScene *scene, const LupinProbeDepthDesc *desc, uint64_t n,
+                               const float *positions /* n x 4, [3] ignored */, float *out_depth /* n x (R+2) x (R+2) x 2 */,
+                               uint32_t *out_stats /* NULL or n x 4 */);
+typedef struct LupinProbeGridDepthDesc {
+    LupinProbeGridDesc grid;   /* flags: DEVICE_POINTERS, BACKFACE; VISIBILITY is refused here */
+    uint32_t resolution;       /* R of the maps */
+    float    max_distance;     /* the bake's */
+} LupinProbeGridDepthDesc;
+int lupin_hip_sample_probe_grid_depth(LupinContext *ctx, const LupinScene *scene, const LupinProbeGridDepthDesc *desc,
+                                      const float *sh /* P x 9 x 4 */, const float *depth /* P x (R+2) x (R+2) x 2 */,
+                                      const uint8_t *valid /* NULL or P */, uint64_t n, const float *records /* n x 8 */,
+                                      float *out /* n x 4 */);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

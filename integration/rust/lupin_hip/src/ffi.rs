@@ -135,6 +135,15 @@ pub const LUPIN_PROBE_GRID_BACKFACE: u32 = 4;
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinProbeGridDesc {
     pub origin: [f32; 3], pub spacing: [f32; 3], pub dims: [u32; 3], pub flags: u32, pub ray_epsilon: f32, pub normal_bias: f32,
 }
+// probe depth maps (no reference counterpart)
+pub const LUPIN_PROBE_DEPTH_STATS_WORDS: usize = 4;
+pub const LUPIN_PROBE_DEPTH_DEVICE_POINTERS: u32 = 1;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinProbeDepthDesc {
+    pub resolution: u32, pub subsamples: u32, pub flags: u32, pub max_slots: u32, pub ray_epsilon: f32, pub max_distance: f32,
+}
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinProbeGridDepthDesc {
+    pub grid: LupinProbeGridDesc, pub resolution: u32, pub max_distance: f32,
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -241,6 +250,12 @@ extern "C" {
     // irradiance volume lookup: sh P x 9 x 4 f32 (bake_probes' out_sh), valid null or P bytes, records n x 8 f32 (point | -, unit normal | -), out n x 4
     pub fn lupin_hip_sample_probe_grid(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinProbeGridDesc, sh: *const f32,
                                        valid: *const u8, n: u64, records: *const f32, out: *mut f32) -> c_int;
+    // probe depth maps: positions n x 4 f32, out_depth n x (R + 2) x (R + 2) x 2 f32, out_stats null or n x 4 u32
+    pub fn lupin_hip_bake_probe_depth(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinProbeDepthDesc, n: u64, positions: *const f32,
+                                      out_depth: *mut f32, out_stats: *mut u32) -> c_int;
+    // ... and the lookup that reads them: depth P x (R + 2) x (R + 2) x 2 f32; the rest as lupin_hip_sample_probe_grid
+    pub fn lupin_hip_sample_probe_grid_depth(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinProbeGridDepthDesc, sh: *const f32,
+                                             depth: *const f32, valid: *const u8, n: u64, records: *const f32, out: *mut f32) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

@@ -342,3 +342,38 @@ pub fn sample_probe_grid(device: &Device, scene: &Scene, origin: [f32; 3], spaci
                                                records.as_ptr(), out.as_mut_ptr()) });
     out
 }
+
+// ---- probe depth maps (no reference counterpart) ----
+/// Octahedral distance moments per probe: `(depth, stats)` with `depth` n x (R + 2) x (R + 2) x 2 floats (mean and mean square of the
+/// distance to the nearest surface per texel, capped at `max_distance`, the border repeating the texels across the seams) and
+/// `stats` n x 4 words (rays, hits, hits on a back face, the bits of the smallest distance).  `positions`: n x 4 floats, `[3]` ignored.
+pub fn bake_probe_depth(device: &Device, scene: &Scene, positions: &[f32], resolution: u32, subsamples: u32, ray_epsilon: f32,
+                        max_distance: f32) -> (Vec<f32>, Vec<u32>) {
+    assert!(positions.len() % 4 == 0 && (2..=64).contains(&resolution));
+    let n = positions.len() / 4;
+    let side = resolution as usize + 2;
+    let mut depth = vec![0f32; n * side * side * 2];
+    let mut stats = vec![0u32; n * LUPIN_PROBE_DEPTH_STATS_WORDS];
+    let c = LupinProbeDepthDesc { resolution, subsamples, flags: 0, max_slots: 0, ray_epsilon, max_distance };
+    check(unsafe { lupin_hip_bake_probe_depth(device.raw, scene.raw, &c, n as u64, positions.as_ptr(), depth.as_mut_ptr(), stats.as_mut_ptr()) });
+    (depth, stats)
+}
+
+/// `sample_probe_grid` with a corner's visibility taken from `depth` (`bake_probe_depth` at the grid's probe positions, with the same
+/// `resolution` and `max_distance`) instead of the scene's geometry, which is not read.
+#[allow(clippy::too_many_arguments)]
+pub fn sample_probe_grid_depth(device: &Device, scene: &Scene, origin: [f32; 3], spacing: [f32; 3], dims: [u32; 3], sh: &[f32], depth: &[f32],
+                               resolution: u32, max_distance: f32, valid: Option<&[u8]>, records: &[f32], backface: bool, normal_bias: f32) -> Vec<f32> {
+    let probes = dims[0] as usize * dims[1] as usize * dims[2] as usize;
+    let side = resolution as usize + 2;
+    assert!(sh.len() == probes * 36 && depth.len() == probes * side * side * 2 && valid.map_or(true, |v| v.len() == probes));
+    assert!(records.len() % LUPIN_PROBE_GRID_RECORD_FLOATS == 0);
+    let n = records.len() / LUPIN_PROBE_GRID_RECORD_FLOATS;
+    let mut out = vec![0f32; n * LUPIN_PROBE_GRID_RESULT_FLOATS];
+    let flags = if backface { LUPIN_PROBE_GRID_BACKFACE } else { 0 };
+    let grid = LupinProbeGridDesc { origin, spacing, dims, flags, ray_epsilon: 0.0, normal_bias };
+    let c = LupinProbeGridDepthDesc { grid, resolution, max_distance };
+    check(unsafe { lupin_hip_sample_probe_grid_depth(device.raw, scene.raw, &c, sh.as_ptr(), depth.as_ptr(), valid.map_or(std::ptr::null(), |v| v.as_ptr()),
+                                                     n as u64, records.as_ptr(), out.as_mut_ptr()) });
+    out
+}

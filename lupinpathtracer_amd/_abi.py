@@ -193,6 +193,15 @@ class ProbeGridDescC(C.Structure):   # LupinProbeGridDesc
                 ("ray_epsilon", C.c_float), ("normal_bias", C.c_float)]
 
 
+class ProbeDepthDescC(C.Structure):   # LupinProbeDepthDesc
+    _fields_ = [("resolution", C.c_uint32), ("subsamples", C.c_uint32), ("flags", C.c_uint32), ("max_slots", C.c_uint32),
+                ("ray_epsilon", C.c_float), ("max_distance", C.c_float)]
+
+
+class ProbeGridDepthDescC(C.Structure):   # LupinProbeGridDepthDesc
+    _fields_ = [("grid", ProbeGridDescC), ("resolution", C.c_uint32), ("max_distance", C.c_float)]
+
+
 class TlasBuildStatsC(C.Structure):   # LupinTlasBuildStats
     _fields_ = [("num_instances", C.c_uint32), ("state_in_lds", C.c_uint32), ("scans", C.c_uint64), ("kernel_ms", C.c_float)]
 
@@ -274,6 +283,8 @@ SYMBOLS = [
     ("lupin_hip_distance_points", C.c_int, [_P, _P, _U32, C.c_uint64, _P, _P]),
     ("lupin_hip_bake_distance_grid", C.c_int, [_P, _P, _U32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_float, _P]),
     ("lupin_hip_sample_probe_grid", C.c_int, [_P, _P, C.POINTER(ProbeGridDescC), _P, _P, C.c_uint64, _P, _P]),
+    ("lupin_hip_bake_probe_depth", C.c_int, [_P, _P, C.POINTER(ProbeDepthDescC), C.c_uint64, _P, _P, _P]),
+    ("lupin_hip_sample_probe_grid_depth", C.c_int, [_P, _P, C.POINTER(ProbeGridDepthDescC), _P, _P, _P, C.c_uint64, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),

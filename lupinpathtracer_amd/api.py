@@ -1981,3 +1981,156 @@ def sample_probe_grid(ctx, scene, origin, spacing, dims, sh, points_or_records, 
     out = np.zeros((len(rec), PROBE_GRID_RESULT_FLOATS), np.float32)
     check(fn(ctx.handle, scene.handle, C.byref(c), ptr(sh), ptr(v), len(rec), ptr(rec), ptr(out)))
     return out
+
+
+# ---- probe depth maps: lupin_hip_bake_probe_depth, lupin_hip_sample_probe_grid_depth (include/lupin_hip.h) ----
+PROBE_DEPTH_DEVICE_POINTERS = 1
+PROBE_DEPTH_STATS_WORDS = 4
+PROBE_DEPTH_MIN_RESOLUTION, PROBE_DEPTH_MAX_RESOLUTION = 2, 64
+PROBE_DEPTH_DEFAULT_MAX_SLOTS = 1 << 24
+
+
+@dataclass
+class ProbeDepthDesc:  # LupinProbeDepthDesc
+    resolution: int = 16
+    subsamples: int = 4
+    flags: int = 0
+    max_slots: int = 0       # rays per launch; 0 = the library's default
+    ray_epsilon: float = 0.001
+    max_distance: float = 1.0
+
+
+def _oct_sgn(x):
+    return np.where(x < 0, np.float32(-1.0), np.float32(1.0))   # sgn(0) = +1
+
+
+def oct_decode(uv):
+    """(..., 3) float32 unit vectors from octahedral coordinates `uv` (..., 2) in [-1, 1]^2, by the header's f32 expressions:
+    z = (1 - |u|) - |v|; below the fold (z < 0) x = (1 - |v|) sgn(u), y = (1 - |u|) sgn(v); then the division by the length."""
+    uv = np.asarray(uv, np.float32)
+    u, v = uv[..., 0], uv[..., 1]
+    one = np.float32(1.0)
+    z = (one - np.abs(u)) - np.abs(v)
+    x = np.where(z < 0, (one - np.abs(v)) * _oct_sgn(u), u)
+    y = np.where(z < 0, (one - np.abs(u)) * _oct_sgn(v), v)
+    ln = np.sqrt((x * x + y * y) + z * z)
+    return np.stack([x / ln, y / ln, z / ln], axis=-1)
+
+
+def oct_encode(dirs):
+    """(..., 2) float32 octahedral coordinates in [-1, 1]^2 of the directions `dirs` (..., 3) (any non-zero length), by the
+    header's f32 expressions: the division by the 1-norm, then the fold for z < 0 from the unfolded pair."""
+    e = np.asarray(dirs, np.float32)
+    one = np.float32(1.0)
+    s = (np.abs(e[..., 0]) + np.abs(e[..., 1])) + np.abs(e[..., 2])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        px, py = e[..., 0] / s, e[..., 1] / s
+    fx, fy = (one - np.abs(py)) * _oct_sgn(px), (one - np.abs(px)) * _oct_sgn(py)
+    below = e[..., 2] < 0
+    return np.stack([np.where(below, fx, px), np.where(below, fy, py)], axis=-1)
+
+
+def bake_probe_depth(ctx, scene, positions, resolution=16, subsamples=4, *, max_distance, ray_epsilon=0.001, want_stats=False, max_slots=0):
+    """Octahedral distance moments of the probes at `positions` (n, 3): (n, R + 2, R + 2, 2) float32, texel [ty + 1, tx + 1] the
+    (mean, mean square) over subsamples^2 rays of the distance to the nearest surface in the texel's directions, capped at
+    `max_distance` (a miss counts as max_distance); the one-texel border repeats the texels across the octahedral seams, so
+    that plain bilinear filtering needs no special case.  With want_stats also (n, 4) uint32: rays, hits, hits on a back
+    face, the bits of the smallest distance.  Blocks until complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_probe_depth needs a GPU context and an uploaded scene; there is no CPU fallback")
+    pos = np.asarray(positions, np.float32).reshape(-1, 3)
+    rec = np.zeros((len(pos), 4), np.float32)
+    rec[:, :3] = pos
+    R = int(resolution)
+    c = _abi.ProbeDepthDescC(R, int(subsamples), 0, int(max_slots), float(ray_epsilon), float(np.float32(max_distance)))
+    side = max(R, 0) + 2
+    out = np.zeros((len(pos), side, side, 2), np.float32)
+    stats = np.zeros((len(pos), PROBE_DEPTH_STATS_WORDS), np.uint32) if want_stats else None
+    check(lib().lupin_hip_bake_probe_depth(ctx.handle, scene.handle, C.byref(c), len(pos), ptr(rec), ptr(out), ptr(stats)))
+    return (out, stats) if want_stats else out
+
+
+def probe_grid_depth_max_distance(spacing):
+    """The default cap of a grid's depth maps, float32: 1.5 |spacing|, the longest segment of a cell plus margin."""
+    return np.float32(1.5 * np.linalg.norm(np.asarray(spacing, np.float32).reshape(3).astype(np.float64)))
+
+
+def bake_probe_grid_depth(ctx, scene, origin, spacing, dims, resolution=16, subsamples=4, max_distance=None, **bake_probe_depth_kwargs):
+    """(positions (P, 3), depth (P, R + 2, R + 2, 2), max_distance) -- and the stats with want_stats: one bake_probe_depth call at
+    probe_grid_positions(origin, spacing, dims).  max_distance None: probe_grid_depth_max_distance(spacing).  Hand depth and
+    max_distance to sample_probe_grid_depth."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_probe_grid_depth needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if max_distance is None:
+        max_distance = probe_grid_depth_max_distance(spacing)
+    max_distance = np.float32(max_distance)
+    pos = probe_grid_positions(origin, spacing, dims)
+    got = bake_probe_depth(ctx, scene, pos, resolution, subsamples, max_distance=max_distance, **bake_probe_depth_kwargs)
+    if bake_probe_depth_kwargs.get("want_stats"):
+        return pos, got[0], max_distance, got[1]
+    return pos, got, max_distance
+
+
+def sample_probe_grid_depth(ctx, scene, origin, spacing, dims, sh, depth, points_or_records, normals=None, *, max_distance, valid=None,
+                            backface=True, normal_bias=None):
+    """sample_probe_grid with the visibility taken from baked depth maps instead of the scene: (n, 4) float32 (r, g, b, w).
+    `depth` is (P, R + 2, R + 2, 2), what bake_probe_grid_depth returns, and `max_distance` the bake's.  A corner whose probe
+    sees, in the direction of the point, a mean distance shorter than the point's is weighed by the cube of Chebyshev's
+    bound var / (var + (r - mean)^2); the scene's geometry is not read.  Everything else is sample_probe_grid's, the torch
+    tensor form included (then `depth` is a tensor as well)."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "sample_probe_grid_depth needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if normal_bias is None:
+        normal_bias = LIGHTMAP_OFFSET_FRACTION * scene_world_extent(scene)
+    nx, ny, nz = (int(d) for d in dims)
+    P = nx * ny * nz
+    if len(depth.shape) != 4 or depth.shape[1] != depth.shape[2] or depth.shape[1] < 3:
+        raise ValueError("depth must be (P, R + 2, R + 2, 2)")
+    R = int(depth.shape[1]) - 2
+    grid = _abi.ProbeGridDescC((C.c_float * 3)(*[float(x) for x in np.asarray(origin, np.float32).reshape(3)]),
+                               (C.c_float * 3)(*[float(x) for x in np.asarray(spacing, np.float32).reshape(3)]),
+                               (C.c_uint32 * 3)(nx, ny, nz), PROBE_GRID_BACKFACE if backface else 0, 0.0, float(np.float32(normal_bias)))
+    c = _abi.ProbeGridDepthDescC(grid, R, float(np.float32(max_distance)))
+    fn = lib().lupin_hip_sample_probe_grid_depth
+    if any(hasattr(x, "data_ptr") for x in (points_or_records, sh, depth)):   # torch tensors
+        import torch
+        t = points_or_records
+        if not all(hasattr(x, "data_ptr") for x in (t, sh, depth)):
+            raise ValueError("sh, depth and records must all be torch tensors, or none of them")
+        if normals is not None:
+            raise ValueError("tensor records carry their normals: (n, 8)")
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == PROBE_GRID_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+        if not (sh.is_cuda and sh.dtype == torch.float32 and sh.is_contiguous() and tuple(sh.shape) == (P, PROBE_SH_COEFFS, 4)):
+            raise ValueError("sh must be a contiguous (P, 9, 4) float32 tensor on the context's device")
+        if not (depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous() and tuple(depth.shape) == (P, R + 2, R + 2, 2)):
+            raise ValueError("depth must be a contiguous (P, R + 2, R + 2, 2) float32 tensor on the context's device")
+        if valid is not None and not (hasattr(valid, "data_ptr") and valid.is_cuda and valid.dtype in (torch.uint8, torch.bool) and
+                                      valid.is_contiguous() and valid.numel() == P):
+            raise ValueError("valid must be a contiguous uint8 or bool tensor of P elements on the context's device")
+        if any(x.device.index != ctx.device_ordinal for x in (t, sh, depth) + (() if valid is None else (valid,))):
+            raise ValueError("a tensor is on another device than the context")
+        out = torch.zeros((int(t.shape[0]), PROBE_GRID_RESULT_FLOATS), dtype=torch.float32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()   # the inputs (and the zero fill) are written
+        c.grid.flags |= PROBE_GRID_DEVICE_POINTERS
+        check(fn(ctx.handle, scene.handle, C.byref(c), C.c_void_p(sh.data_ptr()), C.c_void_p(depth.data_ptr()),
+                 None if valid is None else C.c_void_p(valid.data_ptr()), int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+    if normals is not None:
+        rec = probe_grid_records(points_or_records, normals)
+    else:
+        rec = np.ascontiguousarray(points_or_records, np.float32).reshape(-1, PROBE_GRID_RECORD_FLOATS)
+    sh = np.ascontiguousarray(sh, np.float32)
+    if sh.shape != (P, PROBE_SH_COEFFS, 4):
+        raise ValueError(f"sh must be ({P}, 9, 4) for dims {(nx, ny, nz)}")
+    depth = np.ascontiguousarray(depth, np.float32)
+    if depth.shape != (P, R + 2, R + 2, 2):
+        raise ValueError(f"depth must be ({P}, R + 2, R + 2, 2) for dims {(nx, ny, nz)}")
+    v = None
+    if valid is not None:
+        v = np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, np.uint8)
+        if v.shape != (P,):
+            raise ValueError(f"valid must have {P} elements for dims {(nx, ny, nz)}")
+    out = np.zeros((len(rec), PROBE_GRID_RESULT_FLOATS), np.float32)
+    check(fn(ctx.handle, scene.handle, C.byref(c), ptr(sh), ptr(depth), ptr(v), len(rec), ptr(rec), ptr(out)))
+    return out

@@ -36,6 +36,7 @@
 #include "lupin_transmittance.hpp"
 #include "lupin_distance.hpp"
 #include "lupin_probe_grid.hpp"
+#include "lupin_probe_depth.hpp"
 #include "lupin_internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -3193,6 +3194,180 @@ int lupin_hip_sample_probe_grid(LupinContext *ctx, const LupinScene *scene, cons
         if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_res, (size_t)recs * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
     }
     return query_end(ctx, "lupin_hip_sample_probe_grid");
+}
+
+// ---- probe depth maps (no reference counterpart; kernels: lupin_probe_depth.hpp) ----
+
+static constexpr uint64_t LP_PROBE_DEPTH_DEFAULT_SLOTS = LUPIN_PROBE_DEPTH_DEFAULT_MAX_SLOTS;
+static constexpr uint64_t LP_PROBE_DEPTH_MAX_LAUNCH_SLOTS = 1ull << 30;    // slots of one launch: the lane index and the grid's threads fit 32 bits
+static constexpr uint64_t LP_PROBE_DEPTH_MAX_STAGED_PROBES = 1ull << 10;   // host arrays: probes of one batch (at most 34 MB of maps)
+
+static bool probe_depth_resolution_ok(uint32_t R) { return R >= LUPIN_PROBE_DEPTH_MIN_RESOLUTION && R <= LUPIN_PROBE_DEPTH_MAX_RESOLUTION; }
+
+int lupin_hip_bake_probe_depth(LupinContext *ctx, const LupinScene *scene, const LupinProbeDepthDesc *desc, uint64_t n, const float *positions,
+                               float *out_depth, uint32_t *out_stats)
+{
+    if (int rc = query_refuse(ctx, scene, desc && positions && out_depth)) return rc;
+    if (desc->flags & ~(uint32_t)LUPIN_PROBE_DEPTH_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    const uint32_t R = desc->resolution, K = desc->subsamples;
+    if (!probe_depth_resolution_ok(R)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "resolution must be in [2, 64]");
+    if (K != 1 && K != 2 && K != 4 && K != 8) return fail(LUPIN_ERR_INVALID_ARGUMENT, "subsamples must be 1, 2, 4 or 8");
+    if (!(std::isfinite(desc->ray_epsilon) && desc->ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
+    if (!(std::isfinite(desc->max_distance) && desc->max_distance > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_distance must be finite and positive");
+    const uint64_t rays = (uint64_t)R * R * K * K;   // per probe: at most 2^18
+    if (n > LP_RAYS_MAX_PATHS / rays) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n * resolution^2 * subsamples^2 must not exceed 2^38");
+    if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
+    const bool on_device = (desc->flags & LUPIN_PROBE_DEPTH_DEVICE_POINTERS) != 0;
+    if (on_device && (((uintptr_t)positions & 15u) || ((uintptr_t)out_depth & 7u) || ((uintptr_t)out_stats & 15u)))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device positions and stats must be 16-byte aligned, device maps 8-byte aligned");
+    if (n == 0) return LUPIN_OK;
+    TraversalLds t;
+    if (int rc = query_start<ProbeDepthPositionRule>(ctx, scene, on_device, n, positions, &t)) return rc;
+    hipStream_t st = ctx->stream;
+
+    const uint64_t asked = desc->max_slots ? (uint64_t)desc->max_slots : LP_PROBE_DEPTH_DEFAULT_SLOTS;
+    const uint64_t max_slots = std::min(std::max<uint64_t>(asked / 64u * 64u, 64u), LP_PROBE_DEPTH_MAX_LAUNCH_SLOTS);
+    const size_t map_floats = (size_t)(R + 2u) * (R + 2u) * 2u;
+    // host arrays: a batch of probes at a time through device buffers that live for the call; device arrays: one batch
+    const uint64_t batch = on_device ? n : std::min(n, LP_PROBE_DEPTH_MAX_STAGED_PROBES);
+    DeviceBuffer b_pos, b_depth, b_stats;
+    if (!on_device)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)batch * 16, &b_pos));
+        HIP_TRY(DeviceBuffer::make((size_t)batch * map_floats * 4, &b_depth));
+        if (out_stats) HIP_TRY(DeviceBuffer::make((size_t)batch * LUPIN_PROBE_DEPTH_STATS_WORDS * 4, &b_stats));
+    }
+    for (uint64_t p0 = 0; p0 < n; p0 += batch)
+    {
+        const uint64_t probes = std::min(batch, n - p0);
+        const float *src = positions + p0 * 4;
+        float *dst = out_depth + p0 * map_floats;
+        uint32_t *dst_stats = out_stats ? out_stats + p0 * LUPIN_PROBE_DEPTH_STATS_WORDS : nullptr;
+        const float4 *d_pos = reinterpret_cast<const float4 *>(src);
+        float2 *d_depth = reinterpret_cast<float2 *>(dst);
+        uint32_t *d_stats = dst_stats;
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(b_pos.get(), src, (size_t)probes * 16, hipMemcpyHostToDevice, st));
+            d_pos = b_pos.as<float4>();
+            d_depth = b_depth.as<float2>();
+            d_stats = out_stats ? b_stats.as<uint32_t>() : nullptr;
+        }
+        if (d_stats)
+            hipLaunchKernelGGL(k_probe_depth_stats_init, dim3((uint32_t)((probes + LP_BLOCK - 1) / LP_BLOCK)), dim3(LP_BLOCK), 0, st, (uint32_t)probes,
+                               (uint32_t)rays, reinterpret_cast<uint4 *>(d_stats));
+        const uint64_t total = probes * rays;
+        for (uint64_t first = 0; first < total; first += max_slots)
+        {
+            const uint32_t slots = (uint32_t)std::min(max_slots, total - first);
+            with_bool(t.geo, [&](auto G) {
+                with_bool(d_stats != nullptr, [&](auto S) {
+                    hipLaunchKernelGGL((k_probe_depth<decltype(G)::value, decltype(S)::value>), dim3((slots + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), t.lds,
+                                       st, scene->dev, (unsigned long long)first, slots, R, K, desc->ray_epsilon, desc->max_distance, d_pos, d_depth, d_stats,
+                                       t.stack_words);
+                });
+            });
+            HIP_TRY(hipGetLastError());
+        }
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(dst, d_depth, (size_t)probes * map_floats * 4, hipMemcpyDeviceToHost, st));
+            if (out_stats) HIP_TRY(hipMemcpyAsync(dst_stats, d_stats, (size_t)probes * LUPIN_PROBE_DEPTH_STATS_WORDS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));   // (the next batch writes the same buffers; the copies are to pageable memory)
+        }
+    }
+    return query_end(ctx, "lupin_hip_bake_probe_depth");
+}
+
+int lupin_hip_sample_probe_grid_depth(LupinContext *ctx, const LupinScene *scene, const LupinProbeGridDepthDesc *desc, const float *sh, const float *depth,
+                                      const uint8_t *valid, uint64_t n, const float *records, float *out)
+{
+    if (int rc = query_refuse(ctx, scene, desc && sh && depth && records && out)) return rc;
+    const LupinProbeGridDesc &gd = desc->grid;
+    constexpr uint32_t known = LUPIN_PROBE_GRID_DEVICE_POINTERS | LUPIN_PROBE_GRID_BACKFACE;   // the visibility is the maps': VISIBILITY is the other entry point's
+    if (gd.flags & ~known) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag (LUPIN_PROBE_GRID_VISIBILITY belongs to lupin_hip_sample_probe_grid)");
+    for (int k = 0; k < 3; k++)
+    {
+        if (!std::isfinite(gd.origin[k])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "origin must be finite");
+        if (!(std::isfinite(gd.spacing[k]) && gd.spacing[k] > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "spacing must be finite and positive");
+        if (gd.dims[k] == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "a dimension is zero");
+    }
+    const uint64_t slice = (uint64_t)gd.dims[0] * gd.dims[1];   // below 2^64: both factors are below 2^32
+    if (slice > LP_PROBE_GRID_MAX_PROBES || gd.dims[2] > LP_PROBE_GRID_MAX_PROBES / slice)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid must not exceed 2^31 probes");
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(gd.origin[k] + (float)(gd.dims[k] - 1u) * gd.spacing[k]))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid's last probe position is not finite");
+    if (!(std::isfinite(gd.ray_epsilon) && gd.ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
+    if (!(std::isfinite(gd.normal_bias) && gd.normal_bias >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "normal_bias must be finite and not negative");
+    if (!probe_depth_resolution_ok(desc->resolution)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "resolution must be in [2, 64]");
+    if (!(std::isfinite(desc->max_distance) && desc->max_distance > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_distance must be finite and positive");
+    if (n > LP_RAYS_MAX_PATHS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n must not exceed 2^38");
+    const bool on_device = (gd.flags & LUPIN_PROBE_GRID_DEVICE_POINTERS) != 0;
+    if (on_device && ((((uintptr_t)sh | (uintptr_t)records | (uintptr_t)out) & 15u) || ((uintptr_t)depth & 7u)))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device coefficients, records and results must be 16-byte aligned, device maps 8-byte aligned");
+    if (n == 0) return LUPIN_OK;
+    // the scene is not read: no hierarchy is asked for and nothing is planned
+    if (int rc = query_flush(ctx)) return rc;
+    if (!on_device)
+        if (int rc = refuse_bad_host_records<ProbeGridRecordRule>(n, records)) return rc;
+    if (int rc = join_primary(ctx)) return rc;
+    if (on_device)
+        if (int rc = refuse_bad_device_records<ProbeGridRecordRule>(ctx, n, records)) return rc;
+    hipStream_t st = ctx->stream;
+
+    const uint64_t probes = slice * gd.dims[2];
+    ProbeGridDev g;
+    g.ox = gd.origin[0]; g.oy = gd.origin[1]; g.oz = gd.origin[2];
+    g.sx = gd.spacing[0]; g.sy = gd.spacing[1]; g.sz = gd.spacing[2];
+    g.nx = gd.dims[0]; g.ny = gd.dims[1]; g.nz = gd.dims[2];
+    g.flags = gd.flags;
+    g.eps = gd.ray_epsilon; g.bias = gd.normal_bias;
+    const uint32_t R = desc->resolution;
+
+    uint64_t chunk = std::min(n, LP_PROBE_GRID_MAX_LAUNCH);
+    const float4 *d_sh = reinterpret_cast<const float4 *>(sh);
+    const float2 *d_depth = reinterpret_cast<const float2 *>(depth);
+    const uint8_t *d_valid = valid;
+    DeviceBuffer b_sh, b_depth, b_valid, b_rec, b_res;   // host arrays: the grid whole, one chunk's records and results; they live for the call
+    if (!on_device)
+    {
+        chunk = std::min(chunk, LP_PROBE_GRID_MAX_STAGED_RECORDS);
+        const size_t sh_bytes = (size_t)probes * LUPIN_PROBE_RESULT_FLOATS * 4, depth_bytes = (size_t)probes * (R + 2u) * (R + 2u) * 8u;
+        HIP_TRY(DeviceBuffer::make(sh_bytes, &b_sh));
+        HIP_TRY(DeviceBuffer::make(depth_bytes, &b_depth));
+        HIP_TRY(DeviceBuffer::make((size_t)chunk * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, &b_rec));
+        HIP_TRY(DeviceBuffer::make((size_t)chunk * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, &b_res));
+        HIP_TRY(hipMemcpyAsync(b_sh.get(), sh, sh_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b_depth.get(), depth, depth_bytes, hipMemcpyHostToDevice, st));
+        d_sh = b_sh.as<float4>();
+        d_depth = b_depth.as<float2>();
+        if (valid)
+        {
+            HIP_TRY(DeviceBuffer::make((size_t)probes, &b_valid));
+            HIP_TRY(hipMemcpyAsync(b_valid.get(), valid, (size_t)probes, hipMemcpyHostToDevice, st));
+            d_valid = b_valid.as<uint8_t>();
+        }
+    }
+    for (uint64_t first = 0; first < n; first += chunk)
+    {
+        const uint32_t recs = (uint32_t)std::min(chunk, n - first);
+        const float *src = records + first * LUPIN_PROBE_GRID_RECORD_FLOATS;
+        float *dst = out + first * LUPIN_PROBE_GRID_RESULT_FLOATS;
+        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
+        float4 *d_res = reinterpret_cast<float4 *>(dst);
+        if (!on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(b_rec.get(), src, (size_t)recs * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
+            d_rec = b_rec.as<float4>();
+            d_res = b_res.as<float4>();
+        }
+        hipLaunchKernelGGL(k_probe_grid_depth, dim3((recs + LP_PROBE_GRID_RECORDS_PER_BLOCK - 1) / LP_PROBE_GRID_RECORDS_PER_BLOCK), dim3(LP_BLOCK), 0, st, recs,
+                           g, R, desc->max_distance, d_sh, d_depth, d_valid, d_rec, d_res);
+        HIP_TRY(hipGetLastError());
+        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_res, (size_t)recs * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    }
+    return query_end(ctx, "lupin_hip_sample_probe_grid_depth");
 }
 
 // ---- lightmap baking (no reference counterpart; kernels: lupin_lightmap.hpp) ----
