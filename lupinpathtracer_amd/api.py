@@ -1921,6 +1921,71 @@ def probe_grid_records(points, normals):
     return rec
 
 
+def _probe_grid_lookup(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, depth, points_or_records, normals, valid, call):
+    """What sample_probe_grid and sample_probe_grid_depth (the one with `depth`) do alike, which is all but the entry point:
+    the grid's descriptor, the gate for torch tensors or the conversion of arrays, and the output.
+    call(grid, R, sh, depth, valid, n, records, out) gets the descriptor and what the entry point takes for the arrays,
+    and returns its code."""
+    if normal_bias is None:
+        normal_bias = LIGHTMAP_OFFSET_FRACTION * scene_world_extent(scene)
+    nx, ny, nz = (int(d) for d in dims)
+    P = nx * ny * nz
+    R = None
+    if depth is not None:
+        if len(depth.shape) != 4 or depth.shape[1] != depth.shape[2] or depth.shape[1] < 3:
+            raise ValueError("depth must be (P, R + 2, R + 2, 2)")
+        R = int(depth.shape[1]) - 2
+    grid = _abi.ProbeGridDescC((C.c_float * 3)(*[float(x) for x in np.asarray(origin, np.float32).reshape(3)]),
+                               (C.c_float * 3)(*[float(x) for x in np.asarray(spacing, np.float32).reshape(3)]),
+                               (C.c_uint32 * 3)(nx, ny, nz), flags, float(ray_epsilon), float(np.float32(normal_bias)))
+    t = points_or_records
+    arrays = (t, sh) if depth is None else (t, sh, depth)
+    if any(hasattr(x, "data_ptr") for x in arrays):   # torch tensors
+        import torch
+        if not all(hasattr(x, "data_ptr") for x in arrays):
+            raise ValueError("sh and records must both be torch tensors, or neither" if depth is None else
+                             "sh, depth and records must all be torch tensors, or none of them")
+        if normals is not None:
+            raise ValueError("tensor records carry their normals: (n, 8)")
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == PROBE_GRID_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+        if not (sh.is_cuda and sh.dtype == torch.float32 and sh.is_contiguous() and tuple(sh.shape) == (P, PROBE_SH_COEFFS, 4)):
+            raise ValueError("sh must be a contiguous (P, 9, 4) float32 tensor on the context's device")
+        if depth is not None and not (depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous() and
+                                      tuple(depth.shape) == (P, R + 2, R + 2, 2)):
+            raise ValueError("depth must be a contiguous (P, R + 2, R + 2, 2) float32 tensor on the context's device")
+        if valid is not None and not (hasattr(valid, "data_ptr") and valid.is_cuda and valid.dtype in (torch.uint8, torch.bool) and
+                                      valid.is_contiguous() and valid.numel() == P):
+            raise ValueError("valid must be a contiguous uint8 or bool tensor of P elements on the context's device")
+        if any(x.device.index != ctx.device_ordinal for x in arrays + (() if valid is None else (valid,))):
+            raise ValueError("a tensor is on another device than the context")
+        out = torch.zeros((int(t.shape[0]), PROBE_GRID_RESULT_FLOATS), dtype=torch.float32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()   # the inputs (and the zero fill) are written
+        grid.flags |= PROBE_GRID_DEVICE_POINTERS
+        dev = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        check(call(grid, R, dev(sh), dev(depth), dev(valid), int(t.shape[0]), dev(t), dev(out)))
+        return out
+    if normals is not None:
+        rec = probe_grid_records(points_or_records, normals)
+    else:
+        rec = np.ascontiguousarray(points_or_records, np.float32).reshape(-1, PROBE_GRID_RECORD_FLOATS)
+    sh = np.ascontiguousarray(sh, np.float32)
+    if sh.shape != (P, PROBE_SH_COEFFS, 4):
+        raise ValueError(f"sh must be ({P}, 9, 4) for dims {(nx, ny, nz)}")
+    if depth is not None:
+        depth = np.ascontiguousarray(depth, np.float32)
+        if depth.shape != (P, R + 2, R + 2, 2):
+            raise ValueError(f"depth must be ({P}, R + 2, R + 2, 2) for dims {(nx, ny, nz)}")
+    v = None
+    if valid is not None:
+        v = np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, np.uint8)
+        if v.shape != (P,):
+            raise ValueError(f"valid must have {P} elements for dims {(nx, ny, nz)}")
+    out = np.zeros((len(rec), PROBE_GRID_RESULT_FLOATS), np.float32)
+    check(call(grid, R, ptr(sh), ptr(depth), ptr(v), len(rec), ptr(rec), ptr(out)))
+    return out
+
+
 def sample_probe_grid(ctx, scene, origin, spacing, dims, sh, points_or_records, normals=None, valid=None, visibility=True, backface=True,
                       ray_epsilon=0.001, normal_bias=None):
     """Irradiance from a grid of baked probes: (n, 4) float32, (r, g, b, w) per shading point -- the trilinear blend of the
@@ -1935,52 +2000,10 @@ def sample_probe_grid(ctx, scene, origin, spacing, dims, sh, points_or_records, 
     tensor there) and a tensor is returned.  Blocks until complete."""
     if ctx is None or scene.handle is None:
         raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "sample_probe_grid needs a GPU context and an uploaded scene; there is no CPU fallback")
-    if normal_bias is None:
-        normal_bias = LIGHTMAP_OFFSET_FRACTION * scene_world_extent(scene)
-    nx, ny, nz = (int(d) for d in dims)
-    P = nx * ny * nz
     flags = (PROBE_GRID_VISIBILITY if visibility else 0) | (PROBE_GRID_BACKFACE if backface else 0)
-    c = _abi.ProbeGridDescC((C.c_float * 3)(*[float(x) for x in np.asarray(origin, np.float32).reshape(3)]),
-                            (C.c_float * 3)(*[float(x) for x in np.asarray(spacing, np.float32).reshape(3)]),
-                            (C.c_uint32 * 3)(nx, ny, nz), flags, float(ray_epsilon), float(np.float32(normal_bias)))
     fn = lib().lupin_hip_sample_probe_grid
-    if hasattr(points_or_records, "data_ptr") or hasattr(sh, "data_ptr"):   # torch tensors
-        import torch
-        t = points_or_records
-        if not (hasattr(t, "data_ptr") and hasattr(sh, "data_ptr")):
-            raise ValueError("sh and records must both be torch tensors, or neither")
-        if normals is not None:
-            raise ValueError("tensor records carry their normals: (n, 8)")
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == PROBE_GRID_RECORD_FLOATS):
-            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
-        if not (sh.is_cuda and sh.dtype == torch.float32 and sh.is_contiguous() and tuple(sh.shape) == (P, PROBE_SH_COEFFS, 4)):
-            raise ValueError("sh must be a contiguous (P, 9, 4) float32 tensor on the context's device")
-        if valid is not None and not (hasattr(valid, "data_ptr") and valid.is_cuda and valid.dtype in (torch.uint8, torch.bool) and
-                                      valid.is_contiguous() and valid.numel() == P):
-            raise ValueError("valid must be a contiguous uint8 or bool tensor of P elements on the context's device")
-        if any(x.device.index != ctx.device_ordinal for x in (t, sh) + (() if valid is None else (valid,))):
-            raise ValueError("a tensor is on another device than the context")
-        out = torch.zeros((int(t.shape[0]), PROBE_GRID_RESULT_FLOATS), dtype=torch.float32, device=t.device)
-        torch.cuda.current_stream(t.device).synchronize()   # the inputs (and the zero fill) are written
-        c.flags |= PROBE_GRID_DEVICE_POINTERS
-        check(fn(ctx.handle, scene.handle, C.byref(c), C.c_void_p(sh.data_ptr()), None if valid is None else C.c_void_p(valid.data_ptr()),
-                 int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
-        return out
-    if normals is not None:
-        rec = probe_grid_records(points_or_records, normals)
-    else:
-        rec = np.ascontiguousarray(points_or_records, np.float32).reshape(-1, PROBE_GRID_RECORD_FLOATS)
-    sh = np.ascontiguousarray(sh, np.float32)
-    if sh.shape != (P, PROBE_SH_COEFFS, 4):
-        raise ValueError(f"sh must be ({P}, 9, 4) for dims {(nx, ny, nz)}")
-    v = None
-    if valid is not None:
-        v = np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, np.uint8)
-        if v.shape != (P,):
-            raise ValueError(f"valid must have {P} elements for dims {(nx, ny, nz)}")
-    out = np.zeros((len(rec), PROBE_GRID_RESULT_FLOATS), np.float32)
-    check(fn(ctx.handle, scene.handle, C.byref(c), ptr(sh), ptr(v), len(rec), ptr(rec), ptr(out)))
-    return out
+    return _probe_grid_lookup(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, None, points_or_records, normals, valid,
+                              lambda grid, R, sh, depth, valid, n, rec, out: fn(ctx.handle, scene.handle, C.byref(grid), sh, valid, n, rec, out))
 
 
 # ---- probe depth maps: lupin_hip_bake_probe_depth, lupin_hip_sample_probe_grid_depth (include/lupin_hip.h, DESIGN.md 25) ----
@@ -2080,57 +2103,8 @@ def sample_probe_grid_depth(ctx, scene, origin, spacing, dims, sh, depth, points
     tensor form included (then `depth` is a tensor as well)."""
     if ctx is None or scene.handle is None:
         raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "sample_probe_grid_depth needs a GPU context and an uploaded scene; there is no CPU fallback")
-    if normal_bias is None:
-        normal_bias = LIGHTMAP_OFFSET_FRACTION * scene_world_extent(scene)
-    nx, ny, nz = (int(d) for d in dims)
-    P = nx * ny * nz
-    if len(depth.shape) != 4 or depth.shape[1] != depth.shape[2] or depth.shape[1] < 3:
-        raise ValueError("depth must be (P, R + 2, R + 2, 2)")
-    R = int(depth.shape[1]) - 2
-    grid = _abi.ProbeGridDescC((C.c_float * 3)(*[float(x) for x in np.asarray(origin, np.float32).reshape(3)]),
-                               (C.c_float * 3)(*[float(x) for x in np.asarray(spacing, np.float32).reshape(3)]),
-                               (C.c_uint32 * 3)(nx, ny, nz), PROBE_GRID_BACKFACE if backface else 0, 0.0, float(np.float32(normal_bias)))
-    c = _abi.ProbeGridDepthDescC(grid, R, float(np.float32(max_distance)))
     fn = lib().lupin_hip_sample_probe_grid_depth
-    if any(hasattr(x, "data_ptr") for x in (points_or_records, sh, depth)):   # torch tensors
-        import torch
-        t = points_or_records
-        if not all(hasattr(x, "data_ptr") for x in (t, sh, depth)):
-            raise ValueError("sh, depth and records must all be torch tensors, or none of them")
-        if normals is not None:
-            raise ValueError("tensor records carry their normals: (n, 8)")
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == PROBE_GRID_RECORD_FLOATS):
-            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
-        if not (sh.is_cuda and sh.dtype == torch.float32 and sh.is_contiguous() and tuple(sh.shape) == (P, PROBE_SH_COEFFS, 4)):
-            raise ValueError("sh must be a contiguous (P, 9, 4) float32 tensor on the context's device")
-        if not (depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous() and tuple(depth.shape) == (P, R + 2, R + 2, 2)):
-            raise ValueError("depth must be a contiguous (P, R + 2, R + 2, 2) float32 tensor on the context's device")
-        if valid is not None and not (hasattr(valid, "data_ptr") and valid.is_cuda and valid.dtype in (torch.uint8, torch.bool) and
-                                      valid.is_contiguous() and valid.numel() == P):
-            raise ValueError("valid must be a contiguous uint8 or bool tensor of P elements on the context's device")
-        if any(x.device.index != ctx.device_ordinal for x in (t, sh, depth) + (() if valid is None else (valid,))):
-            raise ValueError("a tensor is on another device than the context")
-        out = torch.zeros((int(t.shape[0]), PROBE_GRID_RESULT_FLOATS), dtype=torch.float32, device=t.device)
-        torch.cuda.current_stream(t.device).synchronize()   # the inputs (and the zero fill) are written
-        c.grid.flags |= PROBE_GRID_DEVICE_POINTERS
-        check(fn(ctx.handle, scene.handle, C.byref(c), C.c_void_p(sh.data_ptr()), C.c_void_p(depth.data_ptr()),
-                 None if valid is None else C.c_void_p(valid.data_ptr()), int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
-        return out
-    if normals is not None:
-        rec = probe_grid_records(points_or_records, normals)
-    else:
-        rec = np.ascontiguousarray(points_or_records, np.float32).reshape(-1, PROBE_GRID_RECORD_FLOATS)
-    sh = np.ascontiguousarray(sh, np.float32)
-    if sh.shape != (P, PROBE_SH_COEFFS, 4):
-        raise ValueError(f"sh must be ({P}, 9, 4) for dims {(nx, ny, nz)}")
-    depth = np.ascontiguousarray(depth, np.float32)
-    if depth.shape != (P, R + 2, R + 2, 2):
-        raise ValueError(f"depth must be ({P}, R + 2, R + 2, 2) for dims {(nx, ny, nz)}")
-    v = None
-    if valid is not None:
-        v = np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, np.uint8)
-        if v.shape != (P,):
-            raise ValueError(f"valid must have {P} elements for dims {(nx, ny, nz)}")
-    out = np.zeros((len(rec), PROBE_GRID_RESULT_FLOATS), np.float32)
-    check(fn(ctx.handle, scene.handle, C.byref(c), ptr(sh), ptr(depth), ptr(v), len(rec), ptr(rec), ptr(out)))
-    return out
+    md = float(np.float32(max_distance))
+    return _probe_grid_lookup(ctx, scene, origin, spacing, dims, PROBE_GRID_BACKFACE if backface else 0, 0.0, normal_bias, sh, depth, points_or_records,
+                              normals, valid, lambda grid, R, sh, depth, valid, n, rec, out: fn(
+                                  ctx.handle, scene.handle, C.byref(_abi.ProbeGridDepthDescC(grid, R, md)), sh, depth, valid, n, rec, out))

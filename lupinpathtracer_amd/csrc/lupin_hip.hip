@@ -2645,17 +2645,27 @@ static int refuse_bad_device_records(LupinContext *ctx, uint64_t n, const float 
     return LUPIN_OK;
 }
 
-// The start of a query over `n` records of format Rule and a stack of the scene's depth, once the entry point's own
-// arguments are accepted: host records are looked at after the recorded calls have run and before anything is planned,
-// device records once the stream is the query's.  (The distance queries put the same pieces in their own order.)
+// The start of a query over `n` records of format Rule, once the entry point's own arguments are accepted: host records
+// are looked at after the recorded calls have run and before anything is planned, device records once the stream is the
+// query's.  The plan is for a stack of `stack_entries` (`stage`: traversal_lds'); t == nullptr: a query that does not read
+// the scene plans nothing.  (The distance queries put the same pieces in their own order.)
 template <typename Rule>
-static int query_start(LupinContext *ctx, const LupinScene *scene, bool on_device, uint64_t n, const float *records, TraversalLds *t)
+static int query_start(LupinContext *ctx, const LupinScene *scene, bool on_device, uint64_t n, const float *records, uint32_t stack_entries, bool stage,
+                       TraversalLds *t)
 {
     if (int rc = query_flush(ctx)) return rc;
     if (!on_device)
         if (int rc = refuse_bad_host_records<Rule>(n, records)) return rc;
-    if (int rc = query_plan(ctx, scene, scene->stack_entries, t)) return rc;
+    if (t)
+        if (int rc = traversal_lds(ctx, scene, stack_entries, stage, t)) return rc;
+    if (int rc = join_primary(ctx)) return rc;
     return on_device ? refuse_bad_device_records<Rule>(ctx, n, records) : LUPIN_OK;
+}
+// ... with a stack of the scene's depth: every query but the irradiance volume's two
+template <typename Rule>
+static int query_start(LupinContext *ctx, const LupinScene *scene, bool on_device, uint64_t n, const float *records, TraversalLds *t)
+{
+    return query_start<Rule>(ctx, scene, on_device, n, records, scene->stack_entries, true, t);
 }
 
 // The path queries (radiance queries, probe bakes: DESIGN.md 13, 15).
@@ -2816,6 +2826,62 @@ static int segment_chunk_records(LupinContext *ctx, bool on_device, uint64_t n, 
     HIP_TRY(grow_buffer(&ctx->occ_records, &ctx->occ_records_bytes, (size_t)*chunk_records * LUPIN_OCCLUSION_RECORD_FLOATS * 4));
     HIP_TRY(grow_buffer(&ctx->occ_counts, &ctx->occ_counts_bytes, (size_t)*chunk_records * 4));
     return LUPIN_OK;
+}
+
+// The irradiance volume's two lookups (by segments, by depth maps: DESIGN.md 23, 25).
+static constexpr uint64_t LP_PROBE_GRID_MAX_LAUNCH = 1ull << 27;          // records of one launch: eight lanes each, and the lane index fits 32 bits
+static constexpr uint64_t LP_PROBE_GRID_MAX_STAGED_RECORDS = 1ull << 20;  // host arrays: records of one launch (32 + 16 MB of staging)
+static constexpr uint64_t LP_PROBE_GRID_MAX_PROBES = 1ull << 31;
+
+// What both refuse in a grid, in this order (both look at ray_epsilon, whether they trace or not); *probes: the grid's.
+static int probe_grid_refuse(const LupinProbeGridDesc &d, uint32_t known_flags, const char *unknown_flag_msg, uint64_t *probes)
+{
+    if (d.flags & ~known_flags) return fail(LUPIN_ERR_INVALID_ARGUMENT, unknown_flag_msg);
+    for (int k = 0; k < 3; k++)
+    {
+        if (!std::isfinite(d.origin[k])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "origin must be finite");
+        if (!(std::isfinite(d.spacing[k]) && d.spacing[k] > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "spacing must be finite and positive");
+        if (d.dims[k] == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "a dimension is zero");
+    }
+    const uint64_t slice = (uint64_t)d.dims[0] * d.dims[1];   // below 2^64: both factors are below 2^32
+    if (slice > LP_PROBE_GRID_MAX_PROBES || d.dims[2] > LP_PROBE_GRID_MAX_PROBES / slice)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid must not exceed 2^31 probes");
+    for (int k = 0; k < 3; k++)   // the last probe, by the kernel's own expression: every probe of the axis lies between the first and this one
+        if (!std::isfinite(d.origin[k] + (float)(d.dims[k] - 1u) * d.spacing[k]))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid's last probe position is not finite");
+    if (!(std::isfinite(d.ray_epsilon) && d.ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
+    if (!(std::isfinite(d.normal_bias) && d.normal_bias >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "normal_bias must be finite and not negative");
+    *probes = slice * d.dims[2];
+    return LUPIN_OK;
+}
+static ProbeGridDev probe_grid_dev(const LupinProbeGridDesc &d)
+{
+    return ProbeGridDev{d.origin[0], d.origin[1], d.origin[2], d.spacing[0], d.spacing[1], d.spacing[2],
+                        d.dims[0],   d.dims[1],   d.dims[2],   d.flags,      d.ray_epsilon, d.normal_bias};
+}
+// records of one launch (host arrays: of one staging), and the launch's blocks
+static uint64_t probe_grid_chunk_records(bool on_device, uint64_t n) { return std::min(n, on_device ? LP_PROBE_GRID_MAX_LAUNCH : LP_PROBE_GRID_MAX_STAGED_RECORDS); }
+static dim3 probe_grid_blocks(uint32_t records) { return dim3((records + LP_PROBE_GRID_RECORDS_PER_BLOCK - 1) / LP_PROBE_GRID_RECORDS_PER_BLOCK); }
+// The chunk loop of the two: at most `chunk` records per launch, host arrays through `stage_records` / `stage_results`
+// (the entry point's, for `chunk` records: nothing is allocated here).  launch(records, d_records, d_results) enqueues one
+// chunk's kernel on the primary stream; its launch error is looked at here.
+template <typename Launch>
+static int probe_grid_chunks(LupinContext *ctx, const char *who, bool on_device, uint64_t n, uint64_t chunk, const float *records, float *out,
+                             void *stage_records, void *stage_results, Launch launch)
+{
+    hipStream_t st = ctx->stream;
+    for (uint64_t first = 0; first < n; first += chunk)
+    {
+        const uint32_t recs = (uint32_t)std::min(chunk, n - first);
+        const float *src = records + first * LUPIN_PROBE_GRID_RECORD_FLOATS;
+        float *dst = out + first * LUPIN_PROBE_GRID_RESULT_FLOATS;
+        if (!on_device) HIP_TRY(hipMemcpyAsync(stage_records, src, (size_t)recs * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
+        float4 *d_res = static_cast<float4 *>(on_device ? (void *)dst : stage_results);
+        launch(recs, static_cast<const float4 *>(on_device ? (const void *)src : stage_records), d_res);
+        HIP_TRY(hipGetLastError());
+        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_res, (size_t)recs * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    }
+    return query_end(ctx, who);
 }
 
 }   // extern "C++"
@@ -3100,30 +3166,13 @@ int lupin_hip_bake_distance_grid(LupinContext *ctx, const LupinScene *scene, uin
 
 // ---- irradiance volume lookup (no reference counterpart; kernel: lupin_probe_grid.hpp) ----
 
-static constexpr uint64_t LP_PROBE_GRID_MAX_LAUNCH = 1ull << 27;          // records of one launch: eight lanes each, and the lane index fits 32 bits
-static constexpr uint64_t LP_PROBE_GRID_MAX_STAGED_RECORDS = 1ull << 20;  // host arrays: records of one launch (32 + 16 MB of staging)
-static constexpr uint64_t LP_PROBE_GRID_MAX_PROBES = 1ull << 31;
-
 int lupin_hip_sample_probe_grid(LupinContext *ctx, const LupinScene *scene, const LupinProbeGridDesc *desc, const float *sh, const uint8_t *valid,
                                 uint64_t n, const float *records, float *out)
 {
     if (int rc = query_refuse(ctx, scene, desc && sh && records && out)) return rc;
-    constexpr uint32_t known = LUPIN_PROBE_GRID_DEVICE_POINTERS | LUPIN_PROBE_GRID_VISIBILITY | LUPIN_PROBE_GRID_BACKFACE;
-    if (desc->flags & ~known) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
-    for (int k = 0; k < 3; k++)
-    {
-        if (!std::isfinite(desc->origin[k])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "origin must be finite");
-        if (!(std::isfinite(desc->spacing[k]) && desc->spacing[k] > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "spacing must be finite and positive");
-        if (desc->dims[k] == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "a dimension is zero");
-    }
-    const uint64_t slice = (uint64_t)desc->dims[0] * desc->dims[1];   // below 2^64: both factors are below 2^32
-    if (slice > LP_PROBE_GRID_MAX_PROBES || desc->dims[2] > LP_PROBE_GRID_MAX_PROBES / slice)
-        return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid must not exceed 2^31 probes");
-    for (int k = 0; k < 3; k++)   // the last probe, by the kernel's own expression: every probe of the axis lies between the first and this one
-        if (!std::isfinite(desc->origin[k] + (float)(desc->dims[k] - 1u) * desc->spacing[k]))
-            return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid's last probe position is not finite");
-    if (!(std::isfinite(desc->ray_epsilon) && desc->ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
-    if (!(std::isfinite(desc->normal_bias) && desc->normal_bias >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "normal_bias must be finite and not negative");
+    uint64_t probes;
+    if (int rc = probe_grid_refuse(*desc, LUPIN_PROBE_GRID_DEVICE_POINTERS | LUPIN_PROBE_GRID_VISIBILITY | LUPIN_PROBE_GRID_BACKFACE, "unknown flag", &probes))
+        return rc;
     if (n > LP_RAYS_MAX_PATHS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n must not exceed 2^38");
     const bool vis = (desc->flags & LUPIN_PROBE_GRID_VISIBILITY) != 0;
     if (vis)
@@ -3132,31 +3181,16 @@ int lupin_hip_sample_probe_grid(LupinContext *ctx, const LupinScene *scene, cons
     if (on_device && (((uintptr_t)sh | (uintptr_t)records | (uintptr_t)out) & 15u))
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "device coefficients, records and results must be 16-byte aligned");
     if (n == 0) return LUPIN_OK;
-    // query_start's pieces with this query's own stack: none at all without visibility, where the scene is not read
-    if (int rc = query_flush(ctx)) return rc;
-    if (!on_device)
-        if (int rc = refuse_bad_host_records<ProbeGridRecordRule>(n, records)) return rc;
-    TraversalLds t;
-    if (int rc = traversal_lds(ctx, scene, vis ? scene->stack_entries : 0u, vis, &t)) return rc;
-    if (int rc = join_primary(ctx)) return rc;
-    if (on_device)
-        if (int rc = refuse_bad_device_records<ProbeGridRecordRule>(ctx, n, records)) return rc;
+    TraversalLds t;   // this query's own stack: none at all without visibility, where the scene is not read
+    if (int rc = query_start<ProbeGridRecordRule>(ctx, scene, on_device, n, records, vis ? scene->stack_entries : 0u, vis, &t)) return rc;
     hipStream_t st = ctx->stream;
 
-    const uint64_t probes = slice * desc->dims[2];
-    ProbeGridDev g;
-    g.ox = desc->origin[0]; g.oy = desc->origin[1]; g.oz = desc->origin[2];
-    g.sx = desc->spacing[0]; g.sy = desc->spacing[1]; g.sz = desc->spacing[2];
-    g.nx = desc->dims[0]; g.ny = desc->dims[1]; g.nz = desc->dims[2];
-    g.flags = desc->flags;
-    g.eps = desc->ray_epsilon; g.bias = desc->normal_bias;
-
-    uint64_t chunk = std::min(n, LP_PROBE_GRID_MAX_LAUNCH);
+    const ProbeGridDev g = probe_grid_dev(*desc);
+    const uint64_t chunk = probe_grid_chunk_records(on_device, n);
     const float4 *d_sh = reinterpret_cast<const float4 *>(sh);
     const uint8_t *d_valid = valid;
-    if (!on_device)
+    if (!on_device)   // host arrays: the grid whole, one chunk's records and results, in the context's staging
     {
-        chunk = std::min(chunk, LP_PROBE_GRID_MAX_STAGED_RECORDS);
         const size_t sh_bytes = (size_t)probes * LUPIN_PROBE_RESULT_FLOATS * 4;
         HIP_TRY(grow_buffer(&ctx->grid_sh, &ctx->grid_sh_bytes, sh_bytes));
         HIP_TRY(grow_buffer(&ctx->grid_records, &ctx->grid_records_bytes, (size_t)chunk * LUPIN_PROBE_GRID_RECORD_FLOATS * 4));
@@ -3170,30 +3204,15 @@ int lupin_hip_sample_probe_grid(LupinContext *ctx, const LupinScene *scene, cons
             d_valid = ctx->grid_valid.as<uint8_t>();
         }
     }
-    for (uint64_t first = 0; first < n; first += chunk)
-    {
-        const uint32_t recs = (uint32_t)std::min(chunk, n - first);
-        const float *src = records + first * LUPIN_PROBE_GRID_RECORD_FLOATS;
-        float *dst = out + first * LUPIN_PROBE_GRID_RESULT_FLOATS;
-        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
-        float4 *d_res = reinterpret_cast<float4 *>(dst);
-        if (!on_device)
-        {
-            HIP_TRY(hipMemcpyAsync(ctx->grid_records.get(), src, (size_t)recs * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
-            d_rec = ctx->grid_records.as<float4>();
-            d_res = ctx->grid_results.as<float4>();
-        }
-        const dim3 grid((recs + LP_PROBE_GRID_RECORDS_PER_BLOCK - 1) / LP_PROBE_GRID_RECORDS_PER_BLOCK);
+    auto launch = [&](uint32_t recs, const float4 *d_rec, float4 *d_res) {
         with_bool(t.geo, [&](auto G) {
             with_bool(vis, [&](auto V) {
-                hipLaunchKernelGGL((k_probe_grid<decltype(G)::value, decltype(V)::value>), grid, dim3(LP_BLOCK), t.lds, st, scene->dev, recs, g, d_sh,
-                                   d_valid, d_rec, d_res, t.stack_words);
+                hipLaunchKernelGGL((k_probe_grid<decltype(G)::value, decltype(V)::value>), probe_grid_blocks(recs), dim3(LP_BLOCK), t.lds, st, scene->dev,
+                                   recs, g, d_sh, d_valid, d_rec, d_res, t.stack_words);
             });
         });
-        HIP_TRY(hipGetLastError());
-        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_res, (size_t)recs * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
-    }
-    return query_end(ctx, "lupin_hip_sample_probe_grid");
+    };
+    return probe_grid_chunks(ctx, "lupin_hip_sample_probe_grid", on_device, n, chunk, records, out, ctx->grid_records.get(), ctx->grid_results.get(), launch);
 }
 
 // ---- probe depth maps (no reference counterpart; kernels: lupin_probe_depth.hpp) ----
@@ -3284,22 +3303,10 @@ int lupin_hip_sample_probe_grid_depth(LupinContext *ctx, const LupinScene *scene
 {
     if (int rc = query_refuse(ctx, scene, desc && sh && depth && records && out)) return rc;
     const LupinProbeGridDesc &gd = desc->grid;
-    constexpr uint32_t known = LUPIN_PROBE_GRID_DEVICE_POINTERS | LUPIN_PROBE_GRID_BACKFACE;   // the visibility is the maps': VISIBILITY is the other entry point's
-    if (gd.flags & ~known) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag (LUPIN_PROBE_GRID_VISIBILITY belongs to lupin_hip_sample_probe_grid)");
-    for (int k = 0; k < 3; k++)
-    {
-        if (!std::isfinite(gd.origin[k])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "origin must be finite");
-        if (!(std::isfinite(gd.spacing[k]) && gd.spacing[k] > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "spacing must be finite and positive");
-        if (gd.dims[k] == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "a dimension is zero");
-    }
-    const uint64_t slice = (uint64_t)gd.dims[0] * gd.dims[1];   // below 2^64: both factors are below 2^32
-    if (slice > LP_PROBE_GRID_MAX_PROBES || gd.dims[2] > LP_PROBE_GRID_MAX_PROBES / slice)
-        return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid must not exceed 2^31 probes");
-    for (int k = 0; k < 3; k++)
-        if (!std::isfinite(gd.origin[k] + (float)(gd.dims[k] - 1u) * gd.spacing[k]))
-            return fail(LUPIN_ERR_INVALID_ARGUMENT, "the grid's last probe position is not finite");
-    if (!(std::isfinite(gd.ray_epsilon) && gd.ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
-    if (!(std::isfinite(gd.normal_bias) && gd.normal_bias >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "normal_bias must be finite and not negative");
+    uint64_t probes;   // (the visibility is the maps': VISIBILITY is the other entry point's)
+    if (int rc = probe_grid_refuse(gd, LUPIN_PROBE_GRID_DEVICE_POINTERS | LUPIN_PROBE_GRID_BACKFACE,
+                                   "unknown flag (LUPIN_PROBE_GRID_VISIBILITY belongs to lupin_hip_sample_probe_grid)", &probes))
+        return rc;
     if (!probe_depth_resolution_ok(desc->resolution)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "resolution must be in [2, 64]");
     if (!(std::isfinite(desc->max_distance) && desc->max_distance > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_distance must be finite and positive");
     if (n > LP_RAYS_MAX_PATHS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n must not exceed 2^38");
@@ -3308,31 +3315,18 @@ int lupin_hip_sample_probe_grid_depth(LupinContext *ctx, const LupinScene *scene
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "device coefficients, records and results must be 16-byte aligned, device maps 8-byte aligned");
     if (n == 0) return LUPIN_OK;
     // the scene is not read: no hierarchy is asked for and nothing is planned
-    if (int rc = query_flush(ctx)) return rc;
-    if (!on_device)
-        if (int rc = refuse_bad_host_records<ProbeGridRecordRule>(n, records)) return rc;
-    if (int rc = join_primary(ctx)) return rc;
-    if (on_device)
-        if (int rc = refuse_bad_device_records<ProbeGridRecordRule>(ctx, n, records)) return rc;
+    if (int rc = query_start<ProbeGridRecordRule>(ctx, scene, on_device, n, records, 0u, false, nullptr)) return rc;
     hipStream_t st = ctx->stream;
 
-    const uint64_t probes = slice * gd.dims[2];
-    ProbeGridDev g;
-    g.ox = gd.origin[0]; g.oy = gd.origin[1]; g.oz = gd.origin[2];
-    g.sx = gd.spacing[0]; g.sy = gd.spacing[1]; g.sz = gd.spacing[2];
-    g.nx = gd.dims[0]; g.ny = gd.dims[1]; g.nz = gd.dims[2];
-    g.flags = gd.flags;
-    g.eps = gd.ray_epsilon; g.bias = gd.normal_bias;
+    const ProbeGridDev g = probe_grid_dev(gd);
     const uint32_t R = desc->resolution;
-
-    uint64_t chunk = std::min(n, LP_PROBE_GRID_MAX_LAUNCH);
+    const uint64_t chunk = probe_grid_chunk_records(on_device, n);
     const float4 *d_sh = reinterpret_cast<const float4 *>(sh);
     const float2 *d_depth = reinterpret_cast<const float2 *>(depth);
     const uint8_t *d_valid = valid;
     DeviceBuffer b_sh, b_depth, b_valid, b_rec, b_res;   // host arrays: the grid whole, one chunk's records and results; they live for the call
     if (!on_device)
     {
-        chunk = std::min(chunk, LP_PROBE_GRID_MAX_STAGED_RECORDS);
         const size_t sh_bytes = (size_t)probes * LUPIN_PROBE_RESULT_FLOATS * 4, depth_bytes = (size_t)probes * (R + 2u) * (R + 2u) * 8u;
         HIP_TRY(DeviceBuffer::make(sh_bytes, &b_sh));
         HIP_TRY(DeviceBuffer::make(depth_bytes, &b_depth));
@@ -3349,25 +3343,11 @@ int lupin_hip_sample_probe_grid_depth(LupinContext *ctx, const LupinScene *scene
             d_valid = b_valid.as<uint8_t>();
         }
     }
-    for (uint64_t first = 0; first < n; first += chunk)
-    {
-        const uint32_t recs = (uint32_t)std::min(chunk, n - first);
-        const float *src = records + first * LUPIN_PROBE_GRID_RECORD_FLOATS;
-        float *dst = out + first * LUPIN_PROBE_GRID_RESULT_FLOATS;
-        const float4 *d_rec = reinterpret_cast<const float4 *>(src);
-        float4 *d_res = reinterpret_cast<float4 *>(dst);
-        if (!on_device)
-        {
-            HIP_TRY(hipMemcpyAsync(b_rec.get(), src, (size_t)recs * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, hipMemcpyHostToDevice, st));
-            d_rec = b_rec.as<float4>();
-            d_res = b_res.as<float4>();
-        }
-        hipLaunchKernelGGL(k_probe_grid_depth, dim3((recs + LP_PROBE_GRID_RECORDS_PER_BLOCK - 1) / LP_PROBE_GRID_RECORDS_PER_BLOCK), dim3(LP_BLOCK), 0, st, recs,
-                           g, R, desc->max_distance, d_sh, d_depth, d_valid, d_rec, d_res);
-        HIP_TRY(hipGetLastError());
-        if (!on_device) HIP_TRY(hipMemcpyAsync(dst, d_res, (size_t)recs * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
-    }
-    return query_end(ctx, "lupin_hip_sample_probe_grid_depth");
+    auto launch = [&](uint32_t recs, const float4 *d_rec, float4 *d_res) {
+        hipLaunchKernelGGL(k_probe_grid_depth, probe_grid_blocks(recs), dim3(LP_BLOCK), 0, st, recs, g, R, desc->max_distance, d_sh, d_depth, d_valid, d_rec,
+                           d_res);
+    };
+    return probe_grid_chunks(ctx, "lupin_hip_sample_probe_grid_depth", on_device, n, chunk, records, out, b_rec.get(), b_res.get(), launch);
 }
 
 // ---- lightmap baking (no reference counterpart; kernels: lupin_lightmap.hpp) ----

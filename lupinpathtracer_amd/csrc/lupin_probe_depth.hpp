@@ -13,9 +13,9 @@
 //                          lanes of the texel add (d, d * d) by xor-shuffles, offset K * K / 2 .. 1, every lane ending with
 //                          the same sum; the texel's first lane divides and stores the texel and, where the texel lies on
 //                          the map's edge, the border texels it is the source of.
-//   k_probe_grid_depth     k_probe_grid's shape (eight adjacent lanes per record, one per corner; ballot of the corners in
-//                          use; the ascending sum by every lane) with the depth test in the segment's place.  No SceneDev,
-//                          no LDS.
+//   k_probe_grid_depth     k_probe_grid's shape (eight adjacent lanes per record, one per corner) with the depth test in the
+//                          segment's place, and k_probe_grid's own probe_grid_irradiance and probe_grid_fold_store (the
+//                          ballot of the corners in use; the ascending sum by every lane).  No SceneDev, no LDS.
 //
 // The order of every operation is the contract (include/lupin_hip.h) and restated in tests/probe_depth_ref.py.  The sum of
 // a texel is a butterfly: lane l adds lane l ^ offset, so every lane computes the same tree whatever K; the restatement
@@ -155,12 +155,14 @@ LP_DEV void probe_depth_axis(float px, uint32_t R, uint32_t &i, float &f)
 }
 
 // `records` and `out` point at the chunk's first record; n = the chunk's records, at most 2^27 (n * 8 lanes fit 32 bits).
-// Whole blocks run: the ballot and the shuffles see 64 lanes.  k_probe_grid's steps 1 to 5, its VIS block replaced.
+// Whole blocks run: the ballot and the shuffles see 64 lanes.  Steps 1 to 4 restate k_probe_grid's, line for line, with the
+// depth test in its VIS block's place; then its irradiance and its fold (lupin_probe_grid.hpp, which also says why a skipped
+// corner is not added and why the fold stands outside every branch).
 __global__ void __launch_bounds__(LP_BLOCK) k_probe_grid_depth(uint32_t n, ProbeGridDev g, uint32_t R, float maxd, const float4 *__restrict__ sh,
                                                                const float2 *__restrict__ depth, const uint8_t *__restrict__ valid,
                                                                const float4 *__restrict__ records, float4 *__restrict__ out)
 {
-    const uint32_t slot = blockIdx.x * LP_BLOCK + threadIdx.x, lane = threadIdx.x & 63u;
+    const uint32_t slot = blockIdx.x * LP_BLOCK + threadIdx.x;
     const uint32_t rec = slot / LP_PROBE_GRID_LANES, c = slot % LP_PROBE_GRID_LANES;
     const bool live = rec < n;
     bool use = false;
@@ -231,37 +233,6 @@ __global__ void __launch_bounds__(LP_BLOCK) k_probe_grid_depth(uint32_t n, Probe
             }
         }
     }
-    if (use)
-    {
-        float Y[LP_PROBE_SH];
-        probe_sh_basis(nrm, Y);
-        const float4 *__restrict__ s = sh + (size_t)index * LP_PROBE_SH;
-#pragma unroll
-        for (uint32_t j = 0; j < LP_PROBE_SH; j++)
-        {
-            const float B = (j == 0 ? LP_SH_A0 : j < 4 ? LP_SH_A1 : LP_SH_A2) * Y[j];
-            const float4 v = s[j];
-            er = er + B * v.x;
-            eg = eg + B * v.y;
-            eb = eb + B * v.z;
-        }
-    }
-    // every lane of the wave is here; the group's corners in ascending order
-    const uint32_t used = (uint32_t)(__ballot(use) >> (lane & ~(LP_PROBE_GRID_LANES - 1u))) & 0xFFu;
-    float ar = 0.0f, ag = 0.0f, ab = 0.0f, aw = 0.0f;
-#pragma unroll
-    for (uint32_t k = 0; k < LP_PROBE_GRID_LANES; k++)
-    {
-        const float tk = __shfl(t, (int)k, (int)LP_PROBE_GRID_LANES), rk = __shfl(er, (int)k, (int)LP_PROBE_GRID_LANES),
-                    gk = __shfl(eg, (int)k, (int)LP_PROBE_GRID_LANES), bk = __shfl(eb, (int)k, (int)LP_PROBE_GRID_LANES);
-        if (used & (1u << k))
-        {
-            ar = ar + tk * rk;
-            ag = ag + tk * gk;
-            ab = ab + tk * bk;
-            aw = aw + tk;
-        }
-    }
-    if (live && c == 0u)
-        out[rec] = aw > 0.0f ? make_float4(ar / aw, ag / aw, ab / aw, aw) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (use) probe_grid_irradiance(sh, index, nrm, er, eg, eb);
+    probe_grid_fold_store(use, t, er, eg, eb, live && c == 0u, out, rec);   // (every lane of the wave is here)
 }

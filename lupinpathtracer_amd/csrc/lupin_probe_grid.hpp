@@ -12,12 +12,10 @@
 //                          adds the ones in use in ascending c from +0; the group's first lane stores.
 //
 // The order of every operation is the contract (include/lupin_hip.h) and restated in tests/probe_grid_ref.py: the result
-// does not depend on the eight-lane shape.  A corner that is skipped (zero trilinear weight, invalid, blocked) is NOT
-// added: adding 0 * E would turn a NaN coefficient of a skipped probe into the result.  Which corners are in use travels as
-// a ballot, not as t == 0: a weight that underflows to 0 after the backface factor is still added.
-//
-// Every lane of a wave reaches the ballot and every shuffle: lanes of records past n, lanes whose corner was skipped and
-// lanes whose traversal ended early leave only the traversal, never the kernel.
+// does not depend on the eight-lane shape.  What follows a corner's visibility is written once, for this kernel and for
+// k_probe_grid_depth (lupin_probe_depth.hpp): probe_grid_irradiance and probe_grid_fold_store, below.  The corner itself
+// (steps 1 to 4) and, here, the irradiance stay in the kernels: as force-inlined functions they changed the kernels'
+// registers (DESIGN.md 23 "One fold, two corners").
 // VIS = false reserves no traversal stack and stages no geometry: the launch has no dynamic LDS.
 // Every float operation is f32 without contraction (-ffp-contract=off), division and square root correctly rounded.
 #pragma once
@@ -60,6 +58,52 @@ LP_DEV void probe_grid_axis(float o, float origin, float spacing, uint32_t dim, 
     f = g - (float)i;
 }
 
+// ---- what k_probe_grid and k_probe_grid_depth share once a corner's visibility is known ----
+// A corner that is skipped (zero trilinear weight, invalid, not visible) is NOT added: adding 0 * E would turn a NaN
+// coefficient of a skipped probe into the result.  Which corners are in use travels as a ballot, not as t == 0: a weight
+// that underflows to 0 after the backface factor is still added.
+// Every lane of a wave reaches the ballot and every shuffle, so probe_grid_fold_store stands outside every branch: lanes of
+// records past n, of skipped corners and of traversals that ended early leave only the traversal, never the kernel.
+
+// the clamped cosine's irradiance of probe `index` at nrm, added to (er, eg, eb) term by term from band 0
+LP_DEV void probe_grid_irradiance(const float4 *__restrict__ sh, uint32_t index, f3 nrm, float &er, float &eg, float &eb)
+{
+    float Y[LP_PROBE_SH];
+    probe_sh_basis(nrm, Y);
+    const float4 *__restrict__ s = sh + (size_t)index * LP_PROBE_SH;
+#pragma unroll
+    for (uint32_t j = 0; j < LP_PROBE_SH; j++)
+    {
+        const float B = (j == 0 ? LP_SH_A0 : j < 4 ? LP_SH_A1 : LP_SH_A2) * Y[j];
+        const float4 v = s[j];
+        er = er + B * v.x;
+        eg = eg + B * v.y;
+        eb = eb + B * v.z;
+    }
+}
+
+// EVERY LANE OF THE WAVE CALLS THIS: the group's (t, E) in use added in ascending c from +0, stored normalised where `store`
+LP_DEV void probe_grid_fold_store(bool use, float t, float er, float eg, float eb, bool store, float4 *__restrict__ out, uint32_t rec)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t used = (uint32_t)(__ballot(use) >> (lane & ~(LP_PROBE_GRID_LANES - 1u))) & 0xFFu;
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f, aw = 0.0f;
+#pragma unroll
+    for (uint32_t k = 0; k < LP_PROBE_GRID_LANES; k++)
+    {
+        const float tk = __shfl(t, (int)k, (int)LP_PROBE_GRID_LANES), rk = __shfl(er, (int)k, (int)LP_PROBE_GRID_LANES),
+                    gk = __shfl(eg, (int)k, (int)LP_PROBE_GRID_LANES), bk = __shfl(eb, (int)k, (int)LP_PROBE_GRID_LANES);
+        if (used & (1u << k))
+        {
+            ar = ar + tk * rk;
+            ag = ag + tk * gk;
+            ab = ab + tk * bk;
+            aw = aw + tk;
+        }
+    }
+    if (store) out[rec] = aw > 0.0f ? make_float4(ar / aw, ag / aw, ab / aw, aw) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
 // `records` and `out` point at the chunk's first record; n = the chunk's records, at most 2^27 (n * 8 lanes fit 32 bits).
 // Whole blocks run (make_geo<true> has a barrier; the ballot and the shuffles see 64 lanes).
 template <bool LDSGEO, bool VIS>
@@ -68,7 +112,7 @@ __global__ void __launch_bounds__(LP_BLOCK) k_probe_grid(SceneDev sc, uint32_t n
                                                          float4 *__restrict__ out, uint32_t stack_words)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
-    const uint32_t slot = blockIdx.x * LP_BLOCK + threadIdx.x, lane = threadIdx.x & 63u;
+    const uint32_t slot = blockIdx.x * LP_BLOCK + threadIdx.x;
     const uint32_t rec = slot / LP_PROBE_GRID_LANES, c = slot % LP_PROBE_GRID_LANES;
     const bool live = rec < n;
     bool use = false;
@@ -115,7 +159,7 @@ __global__ void __launch_bounds__(LP_BLOCK) k_probe_grid(SceneDev sc, uint32_t n
         if (use && len > 2.0f * g.eps)
             if (scene_any_hit(geo, sc, lds_stack, o, dir, g.eps, len - g.eps)) use = false;
     }
-    if (use)
+    if (use)   // probe_grid_irradiance, restated: the call costs this kernel three SGPRs and moves its VGPRs
     {
         float Y[LP_PROBE_SH];
         probe_sh_basis(nrm, Y);
@@ -130,22 +174,5 @@ __global__ void __launch_bounds__(LP_BLOCK) k_probe_grid(SceneDev sc, uint32_t n
             eb = eb + B * v.z;
         }
     }
-    // every lane of the wave is here; the group's corners in ascending order
-    const uint32_t used = (uint32_t)(__ballot(use) >> (lane & ~(LP_PROBE_GRID_LANES - 1u))) & 0xFFu;
-    float ar = 0.0f, ag = 0.0f, ab = 0.0f, aw = 0.0f;
-#pragma unroll
-    for (uint32_t k = 0; k < LP_PROBE_GRID_LANES; k++)
-    {
-        const float tk = __shfl(t, (int)k, (int)LP_PROBE_GRID_LANES), rk = __shfl(er, (int)k, (int)LP_PROBE_GRID_LANES),
-                    gk = __shfl(eg, (int)k, (int)LP_PROBE_GRID_LANES), bk = __shfl(eb, (int)k, (int)LP_PROBE_GRID_LANES);
-        if (used & (1u << k))
-        {
-            ar = ar + tk * rk;
-            ag = ag + tk * gk;
-            ab = ab + tk * bk;
-            aw = aw + tk;
-        }
-    }
-    if (live && c == 0u)
-        out[rec] = aw > 0.0f ? make_float4(ar / aw, ag / aw, ab / aw, aw) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    probe_grid_fold_store(use, t, er, eg, eb, live && c == 0u, out, rec);
 }

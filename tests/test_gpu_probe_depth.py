@@ -213,6 +213,43 @@ def test_lookup_word_for_word_against_the_restatement(gpu_ctx, kind, dims):
         assert name == "baked" or shut > 100, (name, shut)                       # ... and corners were shut by vis == 0
 
 
+@pytest.mark.parametrize("dims", [(1, 1, 1), (2, 1, 1), (3, 2, 2)])
+def test_maps_that_say_nothing_give_the_untraced_lookups_words(gpu_ctx, dims):
+    """Every texel (max_distance, max_distance^2): the bilinear mean is max_distance exactly (m + g * (m - m)), r =
+    min(len, max_distance) > m1 never holds and no corner is weighed -- what is left is what the two lookups share, so
+    sample_probe_grid_depth equals sample_probe_grid(visibility=False) in every word.  (1, 1, 1): all fractions 0, seven
+    corners skipped; (2, 1, 1): two degenerate axes; (3, 2, 2): a cell index that is not 0."""
+    c = X.case("small")
+    scene = device_scene(gpu_ctx, "small")
+    lo, hi = scene_box(c)
+    grid = grid_over(lo + F(0.3) * (hi - lo), hi - F(0.3) * (hi - lo), dims)
+    P, R = int(np.prod(dims)), 2
+    pos = api.probe_grid_positions(*grid)
+    rec = batch("small", grid)[:65].copy()          # surface points inside and outside the grid, and
+    rec[1, :3], rec[5, :3], rec[64, :3] = pos[0], pos[-1], pos[P // 2]          # ... points on probes (len == 0 with no bias),
+    rec[2, :3], rec[7, :3] = lo - F(1.0), hi + F(2.5)                           # ... and outside the scene's box
+    maxd = api.probe_grid_depth_max_distance(grid[1])
+    maps = np.empty((P, R + 2, R + 2, 2), F)
+    maps[..., 0], maps[..., 1] = maxd, maxd * maxd
+    rng = np.random.default_rng(3000 + P)
+    sh = rng.normal(size=(P, 9, 4)).astype(F)
+    some_valid = np.ones(P, np.uint8)
+    some_valid[::2] = 0
+    for valid in (None, some_valid):
+        for back in (False, True):
+            cn = G.corners(*grid, rec, 0.0, valid, back)
+            vis, was = D.visibility(cn, maps, R, maxd)
+            assert not was.any() and np.all(vis == 1)
+            want = G.sample(*grid, sh, rec, valid=valid, backface=back, blocked=None)
+            from_maps = D.sample(*grid, sh, maps, rec, maxd, valid=valid, backface=back)
+            assert np.array_equal(words(from_maps), words(want)), (dims, valid is not None, back)          # the restatements agree
+            for n in (1, 9, 65):
+                by_maps = lookup(gpu_ctx, scene, grid, sh, maps, rec[:n], maxd, valid, back, 0.0)
+                untraced = api.sample_probe_grid(gpu_ctx, scene, *grid, sh, rec[:n], valid=valid, visibility=False, backface=back, normal_bias=0.0)
+                for got, name in ((untraced, "sample_probe_grid"), (by_maps, "sample_probe_grid_depth")):
+                    assert got.shape == (n, 4) and np.array_equal(words(got), words(want[:n])), (name, dims, valid is not None, back, n)
+
+
 # ---- 4. properties --------------------------------------------------------------------------------------------------
 
 def test_no_light_through_a_wall_on_the_device(gpu_ctx):
@@ -471,6 +508,49 @@ def test_every_refusal_leaves_sentinels_in_all_outputs(gpu_ctx):
     # what follows is unharmed
     assert look(g, s, True, sh, maps, rec, out) == 0
     assert np.array_equal(words(out), words(D.sample(*grid, sh, maps, rec, 2.0, backface=True)))
+
+
+UNKNOWN_FLAG = ("unknown flag", "unknown flag (LUPIN_PROBE_GRID_VISIBILITY belongs to lupin_hip_sample_probe_grid)")
+BAD_GRIDS = {          # what both lookups refuse in a grid descriptor: the fields that differ from a good one, and the message
+    "unknown flag bit": (dict(flags=8), UNKNOWN_FLAG),
+    "NaN origin": (dict(origin=(0.0, np.nan, 0.0)), "origin must be finite"),
+    "infinite origin": (dict(origin=(0.0, 0.0, -np.inf)), "origin must be finite"),
+    "zero spacing": (dict(spacing=(1.0, 0.0, 1.0)), "spacing must be finite and positive"),
+    "negative spacing": (dict(spacing=(-1.0, 1.0, 1.0)), "spacing must be finite and positive"),
+    "NaN spacing": (dict(spacing=(1.0, 1.0, np.nan)), "spacing must be finite and positive"),
+    "zero dim": (dict(dims=(2, 0, 2)), "a dimension is zero"),
+    "more than 2^31 probes": (dict(dims=(1 << 16, 1 << 15, 2)), "the grid must not exceed 2^31 probes"),
+    "non-finite last probe": (dict(spacing=(3e38, 1.0, 1.0), dims=(3, 1, 1)), "the grid's last probe position is not finite"),
+    "NaN ray_epsilon": (dict(eps=np.nan), "ray_epsilon must be finite and not negative"),
+    "negative normal_bias": (dict(bias=-1.0), "normal_bias must be finite and not negative"),
+}
+
+
+@pytest.mark.parametrize("label", BAD_GRIDS)
+def test_one_bad_grid_descriptor_one_answer_from_both_lookups(gpu_ctx, label):
+    over, message = BAD_GRIDS[label]
+    scene = device_scene(gpu_ctx, "small")
+    lib = _abi.lib()
+    f = dict(origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0), dims=(2, 2, 2), flags=api.PROBE_GRID_BACKFACE, eps=0.0, bias=0.0)
+    rec = api.probe_grid_records([[0.5, 0.5, 0.5]], [[0.0, 0.0, 1.0]])
+    sh, maps = np.ones((8, 9, 4), F), np.ones((8, 4, 4, 2), F)
+
+    def both(**f):
+        gd = _abi.ProbeGridDescC((C.c_float * 3)(*f["origin"]), (C.c_float * 3)(*f["spacing"]), (C.c_uint32 * 3)(*f["dims"]), f["flags"], f["eps"], f["bias"])
+        outs = np.full((2, 1, 4), SENTINEL, F)
+        rc = [lib.lupin_hip_sample_probe_grid(gpu_ctx.handle, scene.handle, C.byref(gd), _abi.ptr(sh), None, 1, _abi.ptr(rec), _abi.ptr(outs[0]))]
+        said = [lib.lupin_hip_last_error().decode()]
+        rc.append(lib.lupin_hip_sample_probe_grid_depth(gpu_ctx.handle, scene.handle, C.byref(_abi.ProbeGridDepthDescC(gd, 2, 2.0)), _abi.ptr(sh),
+                                                        _abi.ptr(maps), None, 1, _abi.ptr(rec), _abi.ptr(outs[1])))
+        said.append(lib.lupin_hip_last_error().decode())
+        return rc, said, outs
+
+    rc, said, outs = both(**f)
+    assert rc == [0, 0] and not np.any(outs == SENTINEL)          # the good descriptor is accepted by both
+    rc, said, outs = both(**dict(f, **over))
+    assert rc == [-1, -1], (label, rc)
+    assert tuple(said) == (message if isinstance(message, tuple) else (message, message)), (label, said)
+    assert np.all(outs == SENTINEL), label
 
 
 # ---- 7. frames around the calls -------------------------------------------------------------------------------------
