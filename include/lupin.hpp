@@ -868,6 +868,40 @@ inline void sample_probe_grid_depth(const Device &d, const Scene &scene, const P
     check(lupin_hip_sample_probe_grid_depth(d.raw(), scene.raw(), &c, sh, depth, valid, n, records, out));
 }
 
+// baked-lighting view (no reference counterpart): a camera view of a baked irradiance volume -- one primary hit
+// per pixel, then emission + color / pi * E(p, n) with E from sample_probe_grid's lookup (depth == nullptr) or from
+// sample_probe_grid_depth's; every material is drawn as a matte surface of its color; lupin_hip.h states the arithmetic.
+struct BakedViewDesc
+{
+    LupinCameraParams camera_params{0u, 0.050f, 0.036f, 1.5f, 10000.0f, 0.0f};
+    LupinMat3x4 camera_transform{{{1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}, {0.0f, 0.0f, 0.0f}}};
+    ProbeGridDesc grid;             // flags: LUPIN_PROBE_GRID_BACKFACE, and without maps LUPIN_PROBE_GRID_VISIBILITY (clear it with maps)
+    uint32_t resolution = 16;       // of the maps; with depth only
+    float max_distance = 1.0f;      // the maps' bake's; with depth only
+    float ray_epsilon = 0.001f;     // the primary ray's
+    std::array<float, 3> ambient{{0.0f, 0.0f, 0.0f}};   // E where no probe answers
+    uint32_t flags = 0;             // LUPIN_BAKED_VIEW_DEVICE_POINTERS: sh, depth, valid and out_gbuffer are device memory
+    uint32_t max_slots = 0;         // pixels per launch; 0 = the library's default
+};
+// sh: P x 9 x 4; depth: nullptr or P x (R + 2) x (R + 2) x 2; valid: nullptr or P; out_gbuffer: nullptr or W x H x 16 floats
+inline void render_baked(const Device &d, const Scene &scene, TextureRef render_target, const BakedViewDesc &desc, const float *sh,
+                         const float *depth = nullptr, const uint8_t *valid = nullptr, float *out_gbuffer = nullptr)
+{
+    LupinBakedViewDesc c;
+    c.camera_params = desc.camera_params;
+    c.camera_transform = desc.camera_transform;
+    for (int k = 0; k < 3; k++) { c.grid.origin[k] = desc.grid.origin[k]; c.grid.spacing[k] = desc.grid.spacing[k]; c.grid.dims[k] = desc.grid.dims[k]; c.ambient[k] = desc.ambient[k]; }
+    c.grid.flags = desc.grid.flags;
+    c.grid.ray_epsilon = desc.grid.ray_epsilon;
+    c.grid.normal_bias = desc.grid.normal_bias;
+    c.resolution = desc.resolution;
+    c.max_distance = desc.max_distance;
+    c.ray_epsilon = desc.ray_epsilon;
+    c.flags = desc.flags;
+    c.max_slots = desc.max_slots;
+    check(lupin_hip_render_baked(d.raw(), scene.raw(), render_target.raw(), &c, sh, depth, valid, out_gbuffer));
+}
+
 }  // namespace lp
 
 namespace lpl {

@@ -1376,6 +1376,81 @@ int lupin_hip_sample_probe_grid_depth(LupinContext *ctx, const LupinScene *scene
                                       const uint8_t *valid /* NULL or P */, uint64_t n, const float *records /* n x 8 */,
                                       float *out /* n x 4 */);
 
+/* ---- baked-lighting view (no reference counterpart) ----
+ * "What does this baked volume look like from here?"  One primary hit per pixel, then emission + albedo / pi * E(p, n) with
+ * the irradiance E taken from an irradiance volume by one of the two lookups above: a camera view of a baked volume without
+ * a path traced, and the cheap frame to show while the path tracer converges.  The call is a composition of contracts
+ * stated elsewhere in this header and is held to them bit for bit.  Every float operation below is one rounded f32
+ * operation (no contraction), in the order written.
+ *
+ * render_target gives the image: W x H texels.  depth == NULL selects lupin_hip_sample_probe_grid's lookup (grid.flags may
+ * hold LUPIN_PROBE_GRID_VISIBILITY and LUPIN_PROBE_GRID_BACKFACE); depth != NULL selects lupin_hip_sample_probe_grid_depth's
+ * with desc.resolution and desc.max_distance (LUPIN_PROBE_GRID_BACKFACE only: VISIBILITY is refused, as that call refuses
+ * it).  Where sh, depth, valid and out_gbuffer live is said by desc.flags, not by grid.flags: LUPIN_PROBE_GRID_DEVICE_POINTERS
+ * in grid.flags is refused as an unknown flag.  For pixel (x, y), row 0 at the top:
+ *
+ * 1. (o, d) is lupin_hip_camera_probe's LUPIN_CAMERA_RAY_CENTRE ray for that pixel of a W x H image, bit for bit.  No RNG
+ *    number is drawn; the aperture is ignored.
+ * 2. (hit, dst, u, v, instance, tri) is lupin_hip_trace_rays' answer for (o, d, ray_epsilon), bit for bit: the binary
+ *    hierarchy; material opacity is not consulted, so cut-outs are opaque in this view.
+ * 3. On a miss:  rgb = lupin_hip_surface_probe's LUPIN_SURFACE_ENVIRONMENT [0..2] for d;  w = 0.
+ * 4. On a hit:   p = o + d * dst per axis (the product first);
+ *    ns = lupin_hip_surface_probe's LUPIN_SURFACE_NORMAL [0..2] (the shading normal) for (instance, tri, u, v);
+ *    c = (d.x * ns.x + d.y * ns.y) + d.z * ns.z;   n = c > 0 ? -ns : ns   (the surface is lit from the viewer's side);
+ *    color = LUPIN_SURFACE_MATERIAL [4..6], emission = LUPIN_SURFACE_MATERIAL [1..3] of the same record.
+ *    EVERY MATERIAL TYPE IS DRAWN AS A MATTE SURFACE OF ITS color: glossy, reflective, transparent, refractive and volumetric
+ *    materials get no highlights, reflections or transmission here.
+ * 5. (E.r, E.g, E.b, w) is the chosen lookup's result for the record (p | -, n | -), word for word (its steps 1 to 5).
+ *    The lookup is not asked, and (E, w) = (ambient, 0), where a coordinate of p or n is not finite or |n|^2 = (n.x * n.x +
+ *    n.y * n.y) + n.z * n.z is further than 1e-4 from 1: the lookups' own refusals, here per pixel and not per call.
+ *    Where the lookup answers w == 0 (no probe of the cell may be used), E = ambient.
+ * 6. rgb = emission + (color * E) * 0.31830988f, per channel.
+ * 7. The texel is rgb rounded to f16 by the context's store rounding (lupin_hip_set_f16_store_rounding: toward zero unless
+ *    nearest-even was selected), alpha 1.0.  Nothing is accumulated, there is no prev_frame, and rgb is not clamped.
+ *
+ * out_gbuffer is NULL or W x H x LUPIN_BAKED_VIEW_GBUFFER_FLOATS floats, row-major with row 0 at the top ("bits": the u32's
+ * bits in the float's place):
+ *   [0..2] p    [3] instance bits, or LUPIN_BAKED_VIEW_MISS    [4..6] n    [7] tri bits (within the instance's mesh)
+ *   [8..10] color    [11] w    [12..14] emission; on a miss the environment radiance    [15] dst
+ * What a miss does not define is 0.  The first eight words of a hit pixel are a LUPIN_PROBE_GRID_RECORD: handed to the
+ * chosen lookup they reproduce E and [11] (where step 5 asked the lookup).
+ *
+ * The image is cut into launches of max_slots pixels (0: LUPIN_BAKED_VIEW_DEFAULT_MAX_SLOTS; rounded down to a multiple of
+ * 64, at least 64): per launch a primary-hit kernel writes records into scratch memory of that size, the lookup's own kernel
+ * runs over them, and a third kernel composes and stores.  The picture does not depend on max_slots.
+ *
+ * The call behaves as the other scene queries do: the calls recorded on the context run first (and their error, if any, is
+ * returned), the work runs on the primary stream, host arrays (sh, depth, valid, out_gbuffer) go through device buffers
+ * that live for the call, and the call returns when the target and out_gbuffer are complete; frames rendered before and
+ * after are what they would be without the call.  With LUPIN_BAKED_VIEW_DEVICE_POINTERS sh and out_gbuffer are device memory
+ * of the context's device, 16-byte aligned, depth 8-byte aligned, valid of any alignment, and nothing is copied.  It works
+ * on a scene whose four-wide hierarchy is stale after lupin_hip_scene_update_instances.
+ *
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing traced, the target and out_gbuffer untouched, for: a NULL ctx, scene, render_target,
+ * desc or sh; a scene or a target of another or of a destroyed context; an unknown flag; a non-finite ambient; a
+ * ray_epsilon that is not finite or is negative; what the chosen lookup refuses in its grid (with depth: also a resolution
+ * outside 2 .. 64 and a max_distance that is not finite or not positive); misaligned device pointers; a hierarchy too deep
+ * for the traversal stack.  (Every LupinTexture is Rgba16Float: there is no other target to refuse.)  LUPIN_ERR_NO_SW_BVH
+ * for a scene without a software BVH.  Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_BAKED_VIEW_GBUFFER_FLOATS 16
+#define LUPIN_BAKED_VIEW_MISS 0xFFFFFFFFu
+#define LUPIN_BAKED_VIEW_DEFAULT_MAX_SLOTS (1u << 20)
+enum { LUPIN_BAKED_VIEW_DEVICE_POINTERS = 1u };   /* LupinBakedViewDesc.flags */
+typedef struct LupinBakedViewDesc {
+    LupinCameraParams camera_params;   /* as LupinPathtraceDesc carries them */
+    LupinMat3x4 camera_transform;
+    LupinProbeGridDesc grid;           /* flags: VISIBILITY (depth == NULL only), BACKFACE */
+    uint32_t resolution;               /* R of the maps; depth != NULL only */
+    float    max_distance;             /* the maps' bake's; depth != NULL only */
+    float    ray_epsilon;              /* of the primary ray: finite, >= 0 */
+    float    ambient[3];               /* E where no probe answers; finite */
+    uint32_t flags;                    /* LUPIN_BAKED_VIEW_DEVICE_POINTERS */
+    uint32_t max_slots;                /* 0 = library default; pixels per launch, rounded down to a multiple of 64, at least 64 */
+} LupinBakedViewDesc;
+int lupin_hip_render_baked(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target, const LupinBakedViewDesc *desc,
+                           const float *sh /* P x 9 x 4 */, const float *depth /* NULL or P x (R+2) x (R+2) x 2 */,
+                           const uint8_t *valid /* NULL or P */, float *out_gbuffer /* NULL or W x H x 16 */);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

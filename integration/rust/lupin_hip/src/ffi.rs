@@ -144,6 +144,14 @@ pub const LUPIN_PROBE_DEPTH_DEVICE_POINTERS: u32 = 1;
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinProbeGridDepthDesc {
     pub grid: LupinProbeGridDesc, pub resolution: u32, pub max_distance: f32,
 }
+// baked-lighting view (no reference counterpart)
+pub const LUPIN_BAKED_VIEW_GBUFFER_FLOATS: usize = 16;
+pub const LUPIN_BAKED_VIEW_MISS: u32 = 0xFFFF_FFFF;
+pub const LUPIN_BAKED_VIEW_DEVICE_POINTERS: u32 = 1;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinBakedViewDesc {
+    pub camera_params: LupinCameraParams, pub camera_transform: LupinMat3x4, pub grid: LupinProbeGridDesc, pub resolution: u32, pub max_distance: f32,
+    pub ray_epsilon: f32, pub ambient: [f32; 3], pub flags: u32, pub max_slots: u32,
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -256,6 +264,9 @@ extern "C" {
     // ... and the lookup that reads them: depth P x (R + 2) x (R + 2) x 2 f32; the rest as lupin_hip_sample_probe_grid
     pub fn lupin_hip_sample_probe_grid_depth(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinProbeGridDepthDesc, sh: *const f32,
                                              depth: *const f32, valid: *const u8, n: u64, records: *const f32, out: *mut f32) -> c_int;
+    // baked-lighting view: sh P x 9 x 4 f32, depth null or P x (R + 2) x (R + 2) x 2 f32, valid null or P bytes, out_gbuffer null or W x H x 16 f32
+    pub fn lupin_hip_render_baked(ctx: *mut LupinContext, scene: *const LupinScene, render_target: *mut LupinTexture, desc: *const LupinBakedViewDesc,
+                                  sh: *const f32, depth: *const f32, valid: *const u8, out_gbuffer: *mut f32) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

@@ -377,3 +377,29 @@ pub fn sample_probe_grid_depth(device: &Device, scene: &Scene, origin: [f32; 3],
                                                      n as u64, records.as_ptr(), out.as_mut_ptr()) });
     out
 }
+
+// ---- baked-lighting view (no reference counterpart) ----
+/// A camera view of a baked irradiance volume into `target`: per pixel the primary hit through the pixel's centre, then
+/// `emission + color / pi * E(p, n)` with `E` from `sample_probe_grid`'s lookup (`depth` = `None`; `visibility` traces the corners'
+/// segments) or from `sample_probe_grid_depth`'s (`depth` = the maps, their resolution and their bake's `max_distance`); a miss
+/// shows the environment, and where no probe answers `E` is `ambient`.  Every material is drawn as a matte surface of its colour.
+/// Returns the G-buffer, width x height x 16 floats (p | instance bits, n | triangle bits, color | w, emission | dst).
+#[allow(clippy::too_many_arguments)]
+pub fn render_baked(device: &Device, scene: &Scene, target: &Texture, camera_params: LupinCameraParams, camera_transform: LupinMat3x4, origin: [f32; 3],
+                    spacing: [f32; 3], dims: [u32; 3], sh: &[f32], depth: Option<(&[f32], u32, f32)>, valid: Option<&[u8]>, ambient: [f32; 3],
+                    visibility: bool, backface: bool, ray_epsilon: f32, normal_bias: f32) -> Vec<f32> {
+    let probes = dims[0] as usize * dims[1] as usize * dims[2] as usize;
+    assert!(sh.len() == probes * 36 && valid.map_or(true, |v| v.len() == probes));
+    let (maps, resolution, max_distance) = depth.map_or((std::ptr::null(), 0, 0.0), |(m, r, d)| {
+        assert!(m.len() == probes * (r as usize + 2) * (r as usize + 2) * 2);
+        (m.as_ptr(), r, d)
+    });
+    let (width, height) = unsafe { (lupin_hip_texture_width(target.raw) as usize, lupin_hip_texture_height(target.raw) as usize) };
+    let mut gbuffer = vec![0f32; width * height * LUPIN_BAKED_VIEW_GBUFFER_FLOATS];
+    let flags = (if visibility { LUPIN_PROBE_GRID_VISIBILITY } else { 0 }) | (if backface { LUPIN_PROBE_GRID_BACKFACE } else { 0 });
+    let grid = LupinProbeGridDesc { origin, spacing, dims, flags, ray_epsilon, normal_bias };
+    let c = LupinBakedViewDesc { camera_params, camera_transform, grid, resolution, max_distance, ray_epsilon, ambient, flags: 0, max_slots: 0 };
+    check(unsafe { lupin_hip_render_baked(device.raw, scene.raw, target.raw, &c, sh.as_ptr(), maps, valid.map_or(std::ptr::null(), |v| v.as_ptr()),
+                                          gbuffer.as_mut_ptr()) });
+    gbuffer
+}

@@ -202,6 +202,11 @@ class ProbeGridDepthDescC(C.Structure):   # LupinProbeGridDepthDesc
     _fields_ = [("grid", ProbeGridDescC), ("resolution", C.c_uint32), ("max_distance", C.c_float)]
 
 
+class BakedViewDescC(C.Structure):   # LupinBakedViewDesc
+    _fields_ = [("camera_params", CameraParamsC), ("camera_transform", Mat3x4), ("grid", ProbeGridDescC), ("resolution", C.c_uint32),
+                ("max_distance", C.c_float), ("ray_epsilon", C.c_float), ("ambient", C.c_float * 3), ("flags", C.c_uint32), ("max_slots", C.c_uint32)]
+
+
 class TlasBuildStatsC(C.Structure):   # LupinTlasBuildStats
     _fields_ = [("num_instances", C.c_uint32), ("state_in_lds", C.c_uint32), ("scans", C.c_uint64), ("kernel_ms", C.c_float)]
 
@@ -285,6 +290,7 @@ SYMBOLS = [
     ("lupin_hip_sample_probe_grid", C.c_int, [_P, _P, C.POINTER(ProbeGridDescC), _P, _P, C.c_uint64, _P, _P]),
     ("lupin_hip_bake_probe_depth", C.c_int, [_P, _P, C.POINTER(ProbeDepthDescC), C.c_uint64, _P, _P, _P]),
     ("lupin_hip_sample_probe_grid_depth", C.c_int, [_P, _P, C.POINTER(ProbeGridDepthDescC), _P, _P, _P, C.c_uint64, _P, _P]),
+    ("lupin_hip_render_baked", C.c_int, [_P, _P, _P, C.POINTER(BakedViewDescC), _P, _P, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),

@@ -1921,11 +1921,13 @@ def probe_grid_records(points, normals):
     return rec
 
 
-def _probe_grid_lookup(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, depth, points_or_records, normals, valid, call):
-    """What sample_probe_grid and sample_probe_grid_depth (the one with `depth`) do alike, which is all but the entry point:
-    the grid's descriptor, the gate for torch tensors or the conversion of arrays, and the output.
-    call(grid, R, sh, depth, valid, n, records, out) gets the descriptor and what the entry point takes for the arrays,
-    and returns its code."""
+def _probe_grid_arrays(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, depth, valid, records=None):
+    """What every consumer of a probe grid does alike with the grid itself (the two lookups through _probe_grid_lookup, and
+    render_baked): the grid's descriptor, and `sh`, `depth`, `valid` as the entry point takes them -- torch tensors through
+    the gate and in place, arrays converted.  `records`: the lookups' batch, which must be a tensor exactly when `sh` is.
+    Returns (grid, R, tensors, sh, depth, valid): tensors says that the arguments are device pointers (the caller sets its
+    entry point's DEVICE_POINTERS flag, and synchronises torch's current stream once its outputs are allocated).  The
+    pointers of converted arrays keep those arrays alive (ndarray.ctypes.data_as does)."""
     if normal_bias is None:
         normal_bias = LIGHTMAP_OFFSET_FRACTION * scene_world_extent(scene)
     nx, ny, nz = (int(d) for d in dims)
@@ -1938,17 +1940,12 @@ def _probe_grid_lookup(ctx, scene, origin, spacing, dims, flags, ray_epsilon, no
     grid = _abi.ProbeGridDescC((C.c_float * 3)(*[float(x) for x in np.asarray(origin, np.float32).reshape(3)]),
                                (C.c_float * 3)(*[float(x) for x in np.asarray(spacing, np.float32).reshape(3)]),
                                (C.c_uint32 * 3)(nx, ny, nz), flags, float(ray_epsilon), float(np.float32(normal_bias)))
-    t = points_or_records
-    arrays = (t, sh) if depth is None else (t, sh, depth)
+    arrays = tuple(x for x in (records, sh, depth) if x is not None)
     if any(hasattr(x, "data_ptr") for x in arrays):   # torch tensors
         import torch
         if not all(hasattr(x, "data_ptr") for x in arrays):
-            raise ValueError("sh and records must both be torch tensors, or neither" if depth is None else
-                             "sh, depth and records must all be torch tensors, or none of them")
-        if normals is not None:
-            raise ValueError("tensor records carry their normals: (n, 8)")
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == PROBE_GRID_RECORD_FLOATS):
-            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+            names = ["sh"] + (["depth"] if depth is not None else []) + (["records"] if records is not None else [])
+            raise ValueError(" and ".join(names) + " must all be torch tensors, or none of them")
         if not (sh.is_cuda and sh.dtype == torch.float32 and sh.is_contiguous() and tuple(sh.shape) == (P, PROBE_SH_COEFFS, 4)):
             raise ValueError("sh must be a contiguous (P, 9, 4) float32 tensor on the context's device")
         if depth is not None and not (depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous() and
@@ -1959,16 +1956,8 @@ def _probe_grid_lookup(ctx, scene, origin, spacing, dims, flags, ray_epsilon, no
             raise ValueError("valid must be a contiguous uint8 or bool tensor of P elements on the context's device")
         if any(x.device.index != ctx.device_ordinal for x in arrays + (() if valid is None else (valid,))):
             raise ValueError("a tensor is on another device than the context")
-        out = torch.zeros((int(t.shape[0]), PROBE_GRID_RESULT_FLOATS), dtype=torch.float32, device=t.device)
-        torch.cuda.current_stream(t.device).synchronize()   # the inputs (and the zero fill) are written
-        grid.flags |= PROBE_GRID_DEVICE_POINTERS
         dev = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        check(call(grid, R, dev(sh), dev(depth), dev(valid), int(t.shape[0]), dev(t), dev(out)))
-        return out
-    if normals is not None:
-        rec = probe_grid_records(points_or_records, normals)
-    else:
-        rec = np.ascontiguousarray(points_or_records, np.float32).reshape(-1, PROBE_GRID_RECORD_FLOATS)
+        return grid, R, True, dev(sh), dev(depth), dev(valid)
     sh = np.ascontiguousarray(sh, np.float32)
     if sh.shape != (P, PROBE_SH_COEFFS, 4):
         raise ValueError(f"sh must be ({P}, 9, 4) for dims {(nx, ny, nz)}")
@@ -1981,8 +1970,33 @@ def _probe_grid_lookup(ctx, scene, origin, spacing, dims, flags, ray_epsilon, no
         v = np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, np.uint8)
         if v.shape != (P,):
             raise ValueError(f"valid must have {P} elements for dims {(nx, ny, nz)}")
+    return grid, R, False, ptr(sh), ptr(depth), ptr(v)
+
+
+def _probe_grid_lookup(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, depth, points_or_records, normals, valid, call):
+    """What sample_probe_grid and sample_probe_grid_depth (the one with `depth`) do alike, which is all but the entry point:
+    _probe_grid_arrays, the records and the output.  call(grid, R, sh, depth, valid, n, records, out) gets the descriptor
+    and what the entry point takes for the arrays, and returns its code."""
+    t = points_or_records
+    if hasattr(t, "data_ptr"):   # torch tensors
+        import torch
+        if normals is not None:
+            raise ValueError("tensor records carry their normals: (n, 8)")
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == PROBE_GRID_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+        grid, R, _, d_sh, d_depth, d_valid = _probe_grid_arrays(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, depth, valid, t)
+        out = torch.zeros((int(t.shape[0]), PROBE_GRID_RESULT_FLOATS), dtype=torch.float32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()   # the inputs (and the zero fill) are written
+        grid.flags |= PROBE_GRID_DEVICE_POINTERS
+        check(call(grid, R, d_sh, d_depth, d_valid, int(t.shape[0]), C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+    if normals is not None:
+        rec = probe_grid_records(points_or_records, normals)
+    else:
+        rec = np.ascontiguousarray(points_or_records, np.float32).reshape(-1, PROBE_GRID_RECORD_FLOATS)
+    grid, R, tensors, p_sh, p_depth, p_valid = _probe_grid_arrays(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, depth, valid, rec)
     out = np.zeros((len(rec), PROBE_GRID_RESULT_FLOATS), np.float32)
-    check(call(grid, R, ptr(sh), ptr(depth), ptr(v), len(rec), ptr(rec), ptr(out)))
+    check(call(grid, R, p_sh, p_depth, p_valid, len(rec), ptr(rec), ptr(out)))
     return out
 
 
@@ -2108,3 +2122,54 @@ def sample_probe_grid_depth(ctx, scene, origin, spacing, dims, sh, depth, points
     return _probe_grid_lookup(ctx, scene, origin, spacing, dims, PROBE_GRID_BACKFACE if backface else 0, 0.0, normal_bias, sh, depth, points_or_records,
                               normals, valid, lambda grid, R, sh, depth, valid, n, rec, out: fn(
                                   ctx.handle, scene.handle, C.byref(_abi.ProbeGridDepthDescC(grid, R, md)), sh, depth, valid, n, rec, out))
+
+
+# ---- baked-lighting view: lupin_hip_render_baked (include/lupin_hip.h) ----
+BAKED_VIEW_GBUFFER_FLOATS = 16
+BAKED_VIEW_MISS = 0xFFFFFFFF
+BAKED_VIEW_DEVICE_POINTERS = 1
+BAKED_VIEW_DEFAULT_MAX_SLOTS = 1 << 20
+
+
+def render_baked(ctx, scene, render_target, camera_params, camera_transform, origin, spacing, dims, sh, depth=None, max_distance=None, valid=None,
+                 ambient=(0.0, 0.0, 0.0), visibility=False, backface=True, ray_epsilon=0.001, normal_bias=None, want_gbuffer=False, max_slots=0):
+    """A camera view of a baked irradiance volume into `render_target`: per pixel the primary hit through the pixel's centre,
+    then emission + color / pi * E(p, n), with E from sample_probe_grid's lookup (depth None; `visibility` traces the corners'
+    segments) or from sample_probe_grid_depth's (`depth` and `max_distance` as bake_probe_grid_depth returns them); a miss
+    shows the environment, and where no probe answers E is `ambient`.  Every material is drawn as a matte surface of its
+    colour; the normal is turned to the viewer's side.  `camera_transform` is a (4, 3) LupinMat3x4 as PathtraceDesc carries
+    it; grid, `sh`, `valid`, `backface` and `normal_bias` are sample_probe_grid's, the torch tensor form included (then
+    `depth` is a tensor as well).  `ray_epsilon` is the primary ray's and the segments'.  With want_gbuffer the (H, W, 16)
+    float32 G-buffer is returned (p | instance bits, n | triangle bits, color | w, emission | dst; a tensor where `sh` is
+    one); otherwise None.  The picture does not depend on `max_slots` (pixels per launch).  Blocks until complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "render_baked needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if render_target.format() != "Rgba16Float":
+        raise LupinError(-1, "render_baked: the render target must be Rgba16Float")
+    if depth is not None and max_distance is None:
+        raise ValueError("depth maps come with the max_distance of their bake")
+    cp = camera_params
+    cam = _abi.CameraParamsC(1 if cp.is_orthographic else 0, cp.lens, cp.film, cp.aspect, cp.focus, cp.aperture)
+    mat = _abi.Mat3x4()
+    m = np.asarray(camera_transform, np.float32).reshape(4, 3)
+    for col in range(4):
+        for row in range(3):
+            mat.m[col][row] = float(m[col][row])
+    amb = (C.c_float * 3)(*[float(x) for x in np.asarray(ambient, np.float32).reshape(3)])
+    md = 0.0 if max_distance is None else float(np.float32(max_distance))
+    H, W = render_target.height, render_target.width
+    flags = (PROBE_GRID_VISIBILITY if visibility else 0) | (PROBE_GRID_BACKFACE if backface else 0)
+    grid, R, tensors, p_sh, p_depth, p_valid = _probe_grid_arrays(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, depth, valid)
+    gbuffer, gb = None, None
+    if tensors:
+        import torch
+        if want_gbuffer:
+            gbuffer = torch.zeros((H, W, BAKED_VIEW_GBUFFER_FLOATS), dtype=torch.float32, device=sh.device)
+            gb = C.c_void_p(gbuffer.data_ptr())
+        torch.cuda.current_stream(sh.device).synchronize()   # the inputs (and the zero fill) are written
+    elif want_gbuffer:
+        gbuffer = np.zeros((H, W, BAKED_VIEW_GBUFFER_FLOATS), np.float32)
+        gb = ptr(gbuffer)
+    c = _abi.BakedViewDescC(cam, mat, grid, R or 0, md, float(ray_epsilon), amb, BAKED_VIEW_DEVICE_POINTERS if tensors else 0, int(max_slots))
+    check(lib().lupin_hip_render_baked(ctx.handle, scene.handle, render_target.handle, C.byref(c), p_sh, p_depth, p_valid, gb))
+    return gbuffer

@@ -37,6 +37,7 @@
 #include "lupin_distance.hpp"
 #include "lupin_probe_grid.hpp"
 #include "lupin_probe_depth.hpp"
+#include "lupin_baked_view.hpp"
 #include "lupin_internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -3348,6 +3349,120 @@ int lupin_hip_sample_probe_grid_depth(LupinContext *ctx, const LupinScene *scene
                            d_res);
     };
     return probe_grid_chunks(ctx, "lupin_hip_sample_probe_grid_depth", on_device, n, chunk, records, out, b_rec.get(), b_res.get(), launch);
+}
+
+// ---- baked-lighting view (no reference counterpart; kernels: lupin_baked_view.hpp) ----
+
+static constexpr uint64_t LP_BAKED_VIEW_DEFAULT_SLOTS = LUPIN_BAKED_VIEW_DEFAULT_MAX_SLOTS;
+static constexpr uint64_t LP_BAKED_VIEW_MAX_LAUNCH_SLOTS = LP_PROBE_GRID_MAX_LAUNCH;   // the lookup's kernel runs over a launch's slots
+
+int lupin_hip_render_baked(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target, const LupinBakedViewDesc *desc, const float *sh,
+                           const float *depth, const uint8_t *valid, float *out_gbuffer)
+{
+    if (int rc = query_refuse(ctx, scene, render_target && desc && sh)) return rc;
+    if (render_target->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the render target belongs to another context, or to one that has been destroyed");
+    if (desc->flags & ~(uint32_t)LUPIN_BAKED_VIEW_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(desc->ambient[k])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ambient must be finite");
+    if (!(std::isfinite(desc->ray_epsilon) && desc->ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
+    // the chosen lookup's refusals, by its own function and with its own message; where the arrays live is this descriptor's to say
+    const LupinProbeGridDesc &gd = desc->grid;
+    uint64_t probes;
+    if (int rc = depth ? probe_grid_refuse(gd, LUPIN_PROBE_GRID_BACKFACE, "unknown flag (LUPIN_PROBE_GRID_VISIBILITY belongs to lupin_hip_sample_probe_grid)", &probes)
+                       : probe_grid_refuse(gd, LUPIN_PROBE_GRID_VISIBILITY | LUPIN_PROBE_GRID_BACKFACE, "unknown flag", &probes))
+        return rc;
+    const uint32_t R = desc->resolution;
+    if (depth)
+    {
+        if (!probe_depth_resolution_ok(R)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "resolution must be in [2, 64]");
+        if (!(std::isfinite(desc->max_distance) && desc->max_distance > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_distance must be finite and positive");
+    }
+    if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
+    const bool on_device = (desc->flags & LUPIN_BAKED_VIEW_DEVICE_POINTERS) != 0;
+    if (on_device && ((((uintptr_t)sh | (uintptr_t)out_gbuffer) & 15u) || ((uintptr_t)depth & 7u)))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device coefficients and G-buffer must be 16-byte aligned, device maps 8-byte aligned");
+    const uint32_t W = render_target->width, H = render_target->height;
+    const uint64_t pixels = (uint64_t)W * H;   // (not 0: lupin_hip_texture_create makes no empty texture)
+    if (int rc = query_flush(ctx)) return rc;
+    // two plans: the primary hit's (a stack of the scene's depth, staged geometry) and the lookup's own (lupin_hip_sample_probe_grid's)
+    const bool vis = !depth && (gd.flags & LUPIN_PROBE_GRID_VISIBILITY) != 0;
+    TraversalLds t, tl;
+    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
+    if (int rc = traversal_lds(ctx, scene, vis ? scene->stack_entries : 0u, vis, &tl)) return rc;
+    if (int rc = join_primary(ctx)) return rc;
+    hipStream_t st = ctx->stream;
+
+    FrameParams fp;
+    memset(&fp, 0, sizeof(fp));
+    set_camera_constants(fp.pc, desc->camera_params, desc->camera_transform);
+    fp.width = W; fp.height = H; fp.reg_w = W; fp.reg_h = H;
+    const ProbeGridDev g = probe_grid_dev(gd);
+    const BakedViewDev v{desc->ambient[0], desc->ambient[1], desc->ambient[2], (ctx->store_rounding == 1) ? 1u : 0u};
+
+    const uint64_t asked = desc->max_slots ? (uint64_t)desc->max_slots : LP_BAKED_VIEW_DEFAULT_SLOTS;
+    const uint64_t max_slots = std::min(std::min(std::max<uint64_t>(asked / 64u * 64u, 64u), LP_BAKED_VIEW_MAX_LAUNCH_SLOTS), (pixels + 63u) / 64u * 64u);
+    // scratch for one launch; host arrays: the grid whole and one launch's G-buffer.  All of it lives for the call.
+    DeviceBuffer b_rec, b_aux, b_res, b_sh, b_depth, b_valid, b_gbuf;
+    HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, &b_rec));
+    HIP_TRY(DeviceBuffer::make((size_t)max_slots * 32, &b_aux));
+    HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, &b_res));
+    const float4 *d_sh = reinterpret_cast<const float4 *>(sh);
+    const float2 *d_depth = reinterpret_cast<const float2 *>(depth);
+    const uint8_t *d_valid = valid;
+    if (!on_device)
+    {
+        const size_t sh_bytes = (size_t)probes * LUPIN_PROBE_RESULT_FLOATS * 4;
+        HIP_TRY(DeviceBuffer::make(sh_bytes, &b_sh));
+        HIP_TRY(hipMemcpyAsync(b_sh.get(), sh, sh_bytes, hipMemcpyHostToDevice, st));
+        d_sh = b_sh.as<float4>();
+        if (depth)
+        {
+            const size_t depth_bytes = (size_t)probes * (R + 2u) * (R + 2u) * 8u;
+            HIP_TRY(DeviceBuffer::make(depth_bytes, &b_depth));
+            HIP_TRY(hipMemcpyAsync(b_depth.get(), depth, depth_bytes, hipMemcpyHostToDevice, st));
+            d_depth = b_depth.as<float2>();
+        }
+        if (valid)
+        {
+            HIP_TRY(DeviceBuffer::make((size_t)probes, &b_valid));
+            HIP_TRY(hipMemcpyAsync(b_valid.get(), valid, (size_t)probes, hipMemcpyHostToDevice, st));
+            d_valid = b_valid.as<uint8_t>();
+        }
+        if (out_gbuffer) HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_BAKED_VIEW_GBUFFER_FLOATS * 4, &b_gbuf));
+    }
+    render_target->accum32_valid = false;   // the f16 texels are the only truth of this picture
+    for (uint64_t first = 0; first < pixels; first += max_slots)
+    {
+        const uint32_t slots = (uint32_t)std::min(max_slots, pixels - first);
+        float *dst = out_gbuffer ? out_gbuffer + first * LUPIN_BAKED_VIEW_GBUFFER_FLOATS : nullptr;
+        float4 *d_gbuf = reinterpret_cast<float4 *>(out_gbuffer && !on_device ? b_gbuf.as<float>() : dst);
+        const dim3 blocks((slots + LP_BLOCK - 1) / LP_BLOCK);
+        with_bool(t.geo, [&](auto G) {
+            hipLaunchKernelGGL(k_baked_gbuffer<decltype(G)::value>, blocks, dim3(LP_BLOCK), t.lds, st, scene->dev, fp, (unsigned long long)first, slots,
+                               desc->ray_epsilon, b_rec.as<float4>(), b_aux.as<float4>(), d_gbuf, t.stack_words);
+        });
+        HIP_TRY(hipGetLastError());
+        if (depth)
+            hipLaunchKernelGGL(k_probe_grid_depth, probe_grid_blocks(slots), dim3(LP_BLOCK), 0, st, slots, g, R, desc->max_distance, d_sh, d_depth, d_valid,
+                               b_rec.as<float4>(), b_res.as<float4>());
+        else
+            with_bool(tl.geo, [&](auto G) {
+                with_bool(vis, [&](auto V) {
+                    hipLaunchKernelGGL((k_probe_grid<decltype(G)::value, decltype(V)::value>), probe_grid_blocks(slots), dim3(LP_BLOCK), tl.lds, st, scene->dev,
+                                       slots, g, d_sh, d_valid, b_rec.as<float4>(), b_res.as<float4>(), tl.stack_words);
+                });
+            });
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_baked_compose, blocks, dim3(LP_BLOCK), 0, st, v, (unsigned long long)first, slots, b_aux.as<float4>(), b_res.as<float4>(),
+                           render_target->data, d_gbuf);
+        HIP_TRY(hipGetLastError());
+        if (out_gbuffer && !on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(dst, d_gbuf, (size_t)slots * LUPIN_BAKED_VIEW_GBUFFER_FLOATS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));   // (the next launch writes the same buffer; the copy is to pageable memory)
+        }
+    }
+    return query_end(ctx, "lupin_hip_render_baked");
 }
 
 // ---- lightmap baking (no reference counterpart; kernels: lupin_lightmap.hpp) ----
