@@ -883,9 +883,7 @@ struct BakedViewDesc
     uint32_t flags = 0;             // LUPIN_BAKED_VIEW_DEVICE_POINTERS: sh, depth, valid and out_gbuffer are device memory
     uint32_t max_slots = 0;         // pixels per launch; 0 = the library's default
 };
-// sh: P x 9 x 4; depth: nullptr or P x (R + 2) x (R + 2) x 2; valid: nullptr or P; out_gbuffer: nullptr or W x H x 16 floats
-inline void render_baked(const Device &d, const Scene &scene, TextureRef render_target, const BakedViewDesc &desc, const float *sh,
-                         const float *depth = nullptr, const uint8_t *valid = nullptr, float *out_gbuffer = nullptr)
+inline LupinBakedViewDesc baked_view_desc_c(const BakedViewDesc &desc)
 {
     LupinBakedViewDesc c;
     c.camera_params = desc.camera_params;
@@ -899,7 +897,28 @@ inline void render_baked(const Device &d, const Scene &scene, TextureRef render_
     c.ray_epsilon = desc.ray_epsilon;
     c.flags = desc.flags;
     c.max_slots = desc.max_slots;
+    return c;
+}
+// sh: P x 9 x 4; depth: nullptr or P x (R + 2) x (R + 2) x 2; valid: nullptr or P; out_gbuffer: nullptr or W x H x 16 floats
+inline void render_baked(const Device &d, const Scene &scene, TextureRef render_target, const BakedViewDesc &desc, const float *sh,
+                         const float *depth = nullptr, const uint8_t *valid = nullptr, float *out_gbuffer = nullptr)
+{
+    const LupinBakedViewDesc c = baked_view_desc_c(desc);
     check(lupin_hip_render_baked(d.raw(), scene.raw(), render_target.raw(), &c, sh, depth, valid, out_gbuffer));
+}
+
+// lightmapped view (no reference counterpart): render_baked with a lightmap atlas as the irradiance source on
+// every instance that has a chart -- an ownership-aware bilinear fetch at the hit's texcoords -- and the volume (sh != nullptr)
+// or `view.ambient` on the rest; lupin_hip.h states the arithmetic.  `charts` are the bake's, `lightmap` is
+// lightmap_height x lightmap_width x 4 floats (bake_lightmap's or denoise_lightmap's atlas); view.grid, resolution and
+// max_distance are read only with sh; out_gbuffer: nullptr or W x H x 20 floats.
+inline void render_lightmapped(const Device &d, const Scene &scene, TextureRef render_target, const BakedViewDesc &view,
+                               const std::vector<LupinLightmapChart> &charts, const float *lightmap, uint32_t lightmap_width, uint32_t lightmap_height,
+                               const float *sh = nullptr, const float *depth = nullptr, const uint8_t *valid = nullptr, float *out_gbuffer = nullptr)
+{
+    const LupinLightmappedViewDesc c{baked_view_desc_c(view), lightmap_width, lightmap_height, (uint32_t)charts.size(), 0u};
+    check(lupin_hip_render_lightmapped(d.raw(), scene.raw(), render_target.raw(), &c, charts.empty() ? nullptr : charts.data(), lightmap, sh, depth, valid,
+                                       out_gbuffer));
 }
 
 }  // namespace lp

@@ -1451,6 +1451,73 @@ int lupin_hip_render_baked(LupinContext *ctx, const LupinScene *scene, LupinText
                            const float *sh /* P x 9 x 4 */, const float *depth /* NULL or P x (R+2) x (R+2) x 2 */,
                            const uint8_t *valid /* NULL or P */, float *out_gbuffer /* NULL or W x H x 16 */);
 
+/* ---- lightmapped view (no reference counterpart) ----
+ * "What does this baked lightmap look like from here?"  The baked-lighting view above with a lightmap atlas as the
+ * irradiance source on every surface that has a chart, and the irradiance volume (or `ambient`) on whatever has none:
+ * lightmaps on the static surfaces, probes as the fallback.  `lightmap` is lupin_hip_bake_lightmap's or
+ * lupin_hip_denoise_lightmap's out_rgba (H x W x 4 floats, row 0 first; alpha != 0 marks a texel a chart owns), and `charts`
+ * is the array the bake was given, unchanged.  desc.view carries the camera, ray_epsilon, ambient, flags and max_slots; its
+ * grid, resolution and max_distance are read only when sh != NULL, and then sh, depth and valid select and feed the lookup
+ * exactly as in lupin_hip_render_baked.  Every float operation below is one rounded f32 operation (no contraction), in the
+ * order written.  For pixel (x, y) of the target, row 0 at the top:
+ *
+ * 1.-4. lupin_hip_render_baked's steps 1 to 4, bit for bit: the centre ray (o, d), the binary hierarchy's hit
+ *    (dst, u, v, instance, tri), on a miss the environment radiance, on a hit p, the turned shading normal n, color, emission.
+ * 5. The chart of a hit instance is the chart of LOWEST index whose instance_idx names it; an instance no chart names is
+ *    uncharted.
+ * 6. For a charted hit, with (a, b, c) the texcoords of the triangle's three vertices:
+ *    w = 1 - u - v;   tu = a.x * w + b.x * u + c.x * v;   tv = a.y * w + b.y * u + c.y * v   (summed left to right: what the
+ *    material textures are sampled at);   au = tu * scale_u + offset_u;   av = tv * scale_v + offset_v;
+ *    X = au * W - 0.5f;   Y = av * H - 0.5f   (W, H the atlas size as floats; texel centres are at +0.5 and row 0 is v in
+ *    [0, 1 / H), as the bake rasterises).  If X or Y is not finite the pixel is UNCHARTED from here on, in every respect.
+ * 7. The fetch.  xf = min(max(X, 0), W - 1), clamped in float before any conversion to integer;  x0 = floor(xf);
+ *    x1 = min(x0 + 1, W - 1);  fx = xf - floor(xf);  y0, y1, fy likewise from Y and H.  The taps, in TAP ORDER, are the texels
+ *    (x0, y0), (x1, y0), (x0, y1), (x1, y1) with weights (1 - fx) * (1 - fy), fx * (1 - fy), (1 - fx) * fy, fx * fy.  A tap
+ *    is OWNED when its alpha != 0.  Every sum starts at 0.0f and adds in tap order.  cov = the sum of the weights of the
+ *    owned taps.  If cov > 0:  E = (the sum over the owned taps of weight * rgb) / cov per channel; a tap that is not owned
+ *    enters neither sum.  Otherwise E = the sum over all four taps of weight * rgb: what the bake's gutter passes are for.
+ *    Lightmap texels are not sanitised.  The pixel's source is LUPIN_LIGHTMAPPED_SOURCE_LIGHTMAP and its G-buffer word [11]
+ *    is cov.
+ * 8. For an uncharted hit:  with sh != NULL, lupin_hip_render_baked's step 5 with the chosen lookup, its per-pixel refusal
+ *    and `ambient` where w == 0 included; the source is LUPIN_LIGHTMAPPED_SOURCE_PROBES, or
+ *    LUPIN_LIGHTMAPPED_SOURCE_AMBIENT where ambient was used, and word [11] is the lookup's w (0 where it was not asked).
+ *    With sh == NULL:  E = ambient, the source is AMBIENT, word [11] is 0, and no lookup kernel is launched.
+ * 9. rgb = emission + (color * E) * 0.31830988f per channel, and the store: lupin_hip_render_baked's steps 6 and 7.
+ *
+ * out_gbuffer is NULL or W x H x LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS floats: [0..15] are lupin_hip_render_baked's, with
+ * [11] as said in steps 7 and 8;  [16] X  [17] Y of step 6, or 0 when uncharted;  [18] the chart index bits, or
+ * LUPIN_BAKED_VIEW_MISS when uncharted;  [19] the source bits (LUPIN_LIGHTMAPPED_SOURCE_MISS on a miss, where [16..18] are
+ * 0, 0 and LUPIN_BAKED_VIEW_MISS).
+ *
+ * Launches, ordering and host arrays are lupin_hip_render_baked's: launches of max_slots pixels, recorded calls first (their
+ * error is returned), the primary stream, host arrays (lightmap among them) through device buffers that live for the call;
+ * it works on a scene moved by lupin_hip_scene_update_instances.  `charts` is always a host array.  With
+ * LUPIN_BAKED_VIEW_DEVICE_POINTERS in view.flags lightmap, sh, depth, valid and out_gbuffer are device memory of the context's
+ * device: lightmap 16-byte aligned, the others as lupin_hip_render_baked asks.
+ *
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing launched, the target and out_gbuffer untouched, for: everything lupin_hip_render_baked
+ * refuses (a NULL sh is not refused; what it refuses in the grid, resolution and max_distance only when sh != NULL); depth
+ * or valid without sh; a NULL lightmap; charts == NULL with num_charts > 0; an atlas width or height of 0 or above
+ * LUPIN_LIGHTMAP_MAX_SIZE; reserved != 0; a chart whose instance is out of range, whose mesh has no texcoords, or whose
+ * scale or offset is not finite; a misaligned device lightmap.  LUPIN_ERR_NO_SW_BVH and LUPIN_ERR_NO_DEVICE as
+ * lupin_hip_render_baked. */
+#define LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS 20
+enum { LUPIN_LIGHTMAPPED_SOURCE_MISS = 0u, LUPIN_LIGHTMAPPED_SOURCE_LIGHTMAP = 1u,
+       LUPIN_LIGHTMAPPED_SOURCE_PROBES = 2u, LUPIN_LIGHTMAPPED_SOURCE_AMBIENT = 3u };
+typedef struct LupinLightmappedViewDesc {
+    LupinBakedViewDesc view;      /* camera, ray_epsilon, ambient, flags, max_slots; grid/resolution/max_distance read only when sh != NULL */
+    uint32_t lightmap_width;      /* atlas texels, 1 .. LUPIN_LIGHTMAP_MAX_SIZE */
+    uint32_t lightmap_height;
+    uint32_t num_charts;          /* may be 0 */
+    uint32_t reserved;            /* must be 0 */
+} LupinLightmappedViewDesc;
+int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target,
+                                 const LupinLightmappedViewDesc *desc,
+                                 const LupinLightmapChart *charts /* num_charts, host */,
+                                 const float *lightmap /* H x W x 4: bake_lightmap's or denoise_lightmap's out_rgba */,
+                                 const float *sh /* NULL: no volume */, const float *depth, const uint8_t *valid,
+                                 float *out_gbuffer /* NULL or Wimg x Himg x 20 */);
+
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc
 {

@@ -152,6 +152,14 @@ pub const LUPIN_BAKED_VIEW_DEVICE_POINTERS: u32 = 1;
     pub camera_params: LupinCameraParams, pub camera_transform: LupinMat3x4, pub grid: LupinProbeGridDesc, pub resolution: u32, pub max_distance: f32,
     pub ray_epsilon: f32, pub ambient: [f32; 3], pub flags: u32, pub max_slots: u32,
 }
+pub const LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS: usize = 20;
+pub const LUPIN_LIGHTMAPPED_SOURCE_MISS: u32 = 0;
+pub const LUPIN_LIGHTMAPPED_SOURCE_LIGHTMAP: u32 = 1;
+pub const LUPIN_LIGHTMAPPED_SOURCE_PROBES: u32 = 2;
+pub const LUPIN_LIGHTMAPPED_SOURCE_AMBIENT: u32 = 3;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmappedViewDesc {
+    pub view: LupinBakedViewDesc, pub lightmap_width: u32, pub lightmap_height: u32, pub num_charts: u32, pub reserved: u32,
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -267,6 +275,10 @@ extern "C" {
     // baked-lighting view: sh P x 9 x 4 f32, depth null or P x (R + 2) x (R + 2) x 2 f32, valid null or P bytes, out_gbuffer null or W x H x 16 f32
     pub fn lupin_hip_render_baked(ctx: *mut LupinContext, scene: *const LupinScene, render_target: *mut LupinTexture, desc: *const LupinBakedViewDesc,
                                   sh: *const f32, depth: *const f32, valid: *const u8, out_gbuffer: *mut f32) -> c_int;
+    // lightmapped view: charts num_charts (host), lightmap height x width x 4 f32, sh null for no volume, out_gbuffer null or W x H x 20
+    pub fn lupin_hip_render_lightmapped(ctx: *mut LupinContext, scene: *const LupinScene, render_target: *mut LupinTexture,
+                                        desc: *const LupinLightmappedViewDesc, charts: *const LupinLightmapChart, lightmap: *const f32, sh: *const f32,
+                                        depth: *const f32, valid: *const u8, out_gbuffer: *mut f32) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

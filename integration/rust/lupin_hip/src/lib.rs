@@ -403,3 +403,23 @@ pub fn render_baked(device: &Device, scene: &Scene, target: &Texture, camera_par
                                           gbuffer.as_mut_ptr()) });
     gbuffer
 }
+
+// ---- lightmapped view (no reference counterpart) ----
+/// `render_baked` with a lightmap as the irradiance source on every instance that has a chart: `charts` are the bake's, `lightmap`
+/// is the `lightmap_height` x `lightmap_width` x 4 atlas `bake_lightmap` or `denoise_lightmap` returned.  A hit without a chart takes
+/// `ambient`; this thin wrapper passes no volume (call `lupin_hip_render_lightmapped` with `sh` for probes as the fallback).
+/// Returns the G-buffer, width x height x 20 floats (`render_baked`'s 16, then atlas x, y, chart bits, source bits).
+#[allow(clippy::too_many_arguments)]
+pub fn render_lightmapped(device: &Device, scene: &Scene, target: &Texture, camera_params: LupinCameraParams, camera_transform: LupinMat3x4,
+                          charts: &[LupinLightmapChart], lightmap: &[f32], lightmap_width: u32, lightmap_height: u32, ambient: [f32; 3],
+                          ray_epsilon: f32) -> Vec<f32> {
+    assert!(lightmap.len() == lightmap_width as usize * lightmap_height as usize * 4);
+    let (width, height) = unsafe { (lupin_hip_texture_width(target.raw) as usize, lupin_hip_texture_height(target.raw) as usize) };
+    let mut gbuffer = vec![0f32; width * height * LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS];
+    let grid = LupinProbeGridDesc { origin: [0.0; 3], spacing: [0.0; 3], dims: [0; 3], flags: 0, ray_epsilon: 0.0, normal_bias: 0.0 };
+    let view = LupinBakedViewDesc { camera_params, camera_transform, grid, resolution: 0, max_distance: 0.0, ray_epsilon, ambient, flags: 0, max_slots: 0 };
+    let c = LupinLightmappedViewDesc { view, lightmap_width, lightmap_height, num_charts: charts.len() as u32, reserved: 0 };
+    check(unsafe { lupin_hip_render_lightmapped(device.raw, scene.raw, target.raw, &c, if charts.is_empty() { std::ptr::null() } else { charts.as_ptr() },
+                                                lightmap.as_ptr(), std::ptr::null(), std::ptr::null(), std::ptr::null(), gbuffer.as_mut_ptr()) });
+    gbuffer
+}

@@ -207,6 +207,11 @@ class BakedViewDescC(C.Structure):   # LupinBakedViewDesc
                 ("max_distance", C.c_float), ("ray_epsilon", C.c_float), ("ambient", C.c_float * 3), ("flags", C.c_uint32), ("max_slots", C.c_uint32)]
 
 
+class LightmappedViewDescC(C.Structure):   # LupinLightmappedViewDesc
+    _fields_ = [("view", BakedViewDescC), ("lightmap_width", C.c_uint32), ("lightmap_height", C.c_uint32), ("num_charts", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class TlasBuildStatsC(C.Structure):   # LupinTlasBuildStats
     _fields_ = [("num_instances", C.c_uint32), ("state_in_lds", C.c_uint32), ("scans", C.c_uint64), ("kernel_ms", C.c_float)]
 
@@ -291,6 +296,7 @@ SYMBOLS = [
     ("lupin_hip_bake_probe_depth", C.c_int, [_P, _P, C.POINTER(ProbeDepthDescC), C.c_uint64, _P, _P, _P]),
     ("lupin_hip_sample_probe_grid_depth", C.c_int, [_P, _P, C.POINTER(ProbeGridDepthDescC), _P, _P, _P, C.c_uint64, _P, _P]),
     ("lupin_hip_render_baked", C.c_int, [_P, _P, _P, C.POINTER(BakedViewDescC), _P, _P, _P, _P]),
+    ("lupin_hip_render_lightmapped", C.c_int, [_P, _P, _P, C.POINTER(LightmappedViewDescC), C.POINTER(LightmapChartC), _P, _P, _P, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),

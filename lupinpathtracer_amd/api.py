@@ -2142,10 +2142,23 @@ def render_baked(ctx, scene, render_target, camera_params, camera_transform, ori
     `depth` is a tensor as well).  `ray_epsilon` is the primary ray's and the segments'.  With want_gbuffer the (H, W, 16)
     float32 G-buffer is returned (p | instance bits, n | triangle bits, color | w, emission | dst; a tensor where `sh` is
     one); otherwise None.  The picture does not depend on `max_slots` (pixels per launch).  Blocks until complete."""
+    c, tensors, p_sh, p_depth, p_valid = _baked_view_desc("render_baked", ctx, scene, render_target, camera_params, camera_transform, origin, spacing, dims,
+                                                          sh, depth, max_distance, valid, ambient, visibility, backface, ray_epsilon, normal_bias, max_slots)
+    gbuffer, gb = _baked_view_gbuffer(render_target, BAKED_VIEW_GBUFFER_FLOATS, want_gbuffer, sh if tensors else None)
+    check(lib().lupin_hip_render_baked(ctx.handle, scene.handle, render_target.handle, C.byref(c), p_sh, p_depth, p_valid, gb))
+    return gbuffer
+
+
+def _baked_view_desc(who, ctx, scene, render_target, camera_params, camera_transform, origin, spacing, dims, sh, depth, max_distance, valid, ambient,
+                     visibility, backface, ray_epsilon, normal_bias, max_slots):
+    """What render_baked and render_lightmapped do alike before their entry points: the no-device and target checks, and the
+    LupinBakedViewDesc with the volume's arrays through _probe_grid_arrays.  `sh` None (render_lightmapped only): no volume,
+    a zero grid.  Returns (desc, tensors, sh, depth, valid) as _probe_grid_arrays returns them; desc.flags says DEVICE_POINTERS
+    where tensors."""
     if ctx is None or scene.handle is None:
-        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "render_baked needs a GPU context and an uploaded scene; there is no CPU fallback")
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), f"{who} needs a GPU context and an uploaded scene; there is no CPU fallback")
     if render_target.format() != "Rgba16Float":
-        raise LupinError(-1, "render_baked: the render target must be Rgba16Float")
+        raise LupinError(-1, f"{who}: the render target must be Rgba16Float")
     if depth is not None and max_distance is None:
         raise ValueError("depth maps come with the max_distance of their bake")
     cp = camera_params
@@ -2157,19 +2170,79 @@ def render_baked(ctx, scene, render_target, camera_params, camera_transform, ori
             mat.m[col][row] = float(m[col][row])
     amb = (C.c_float * 3)(*[float(x) for x in np.asarray(ambient, np.float32).reshape(3)])
     md = 0.0 if max_distance is None else float(np.float32(max_distance))
+    if sh is None:
+        if depth is not None or valid is not None:
+            raise ValueError("depth and valid belong to a volume: give sh")
+        grid, R, tensors, p_sh, p_depth, p_valid = _abi.ProbeGridDescC(), None, False, None, None, None
+    else:
+        flags = (PROBE_GRID_VISIBILITY if visibility else 0) | (PROBE_GRID_BACKFACE if backface else 0)
+        grid, R, tensors, p_sh, p_depth, p_valid = _probe_grid_arrays(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, depth, valid)
+    c = _abi.BakedViewDescC(cam, mat, grid, R or 0, md, float(ray_epsilon), amb, BAKED_VIEW_DEVICE_POINTERS if tensors else 0, int(max_slots))
+    return c, tensors, p_sh, p_depth, p_valid
+
+
+def _baked_view_gbuffer(render_target, floats, want_gbuffer, tensor):
+    """(gbuffer or None, its pointer or None) for a view: zeros of (H, W, floats), a torch tensor beside `tensor` where that
+    is one (then torch's current stream is synchronised: the inputs and the zero fill are written), a numpy array otherwise."""
     H, W = render_target.height, render_target.width
-    flags = (PROBE_GRID_VISIBILITY if visibility else 0) | (PROBE_GRID_BACKFACE if backface else 0)
-    grid, R, tensors, p_sh, p_depth, p_valid = _probe_grid_arrays(ctx, scene, origin, spacing, dims, flags, ray_epsilon, normal_bias, sh, depth, valid)
     gbuffer, gb = None, None
-    if tensors:
+    if tensor is not None:
         import torch
         if want_gbuffer:
-            gbuffer = torch.zeros((H, W, BAKED_VIEW_GBUFFER_FLOATS), dtype=torch.float32, device=sh.device)
+            gbuffer = torch.zeros((H, W, floats), dtype=torch.float32, device=tensor.device)
             gb = C.c_void_p(gbuffer.data_ptr())
-        torch.cuda.current_stream(sh.device).synchronize()   # the inputs (and the zero fill) are written
+        torch.cuda.current_stream(tensor.device).synchronize()
     elif want_gbuffer:
-        gbuffer = np.zeros((H, W, BAKED_VIEW_GBUFFER_FLOATS), np.float32)
+        gbuffer = np.zeros((H, W, floats), np.float32)
         gb = ptr(gbuffer)
-    c = _abi.BakedViewDescC(cam, mat, grid, R or 0, md, float(ray_epsilon), amb, BAKED_VIEW_DEVICE_POINTERS if tensors else 0, int(max_slots))
-    check(lib().lupin_hip_render_baked(ctx.handle, scene.handle, render_target.handle, C.byref(c), p_sh, p_depth, p_valid, gb))
+    return gbuffer, gb
+
+
+# ---- lightmapped view: lupin_hip_render_lightmapped (include/lupin_hip.h, DESIGN.md 27) ----
+LIGHTMAPPED_VIEW_GBUFFER_FLOATS = 20
+LIGHTMAPPED_SOURCE_MISS, LIGHTMAPPED_SOURCE_LIGHTMAP, LIGHTMAPPED_SOURCE_PROBES, LIGHTMAPPED_SOURCE_AMBIENT = 0, 1, 2, 3
+
+
+def render_lightmapped(ctx, scene, render_target, camera_params, camera_transform, charts, lightmap, *, origin=None, spacing=None, dims=None, sh=None,
+                       depth=None, max_distance=None, valid=None, ambient=(0.0, 0.0, 0.0), visibility=False, backface=True, ray_epsilon=0.001,
+                       normal_bias=None, want_gbuffer=False, max_slots=0):
+    """A camera view of baked lighting into `render_target`: render_baked with a lightmap as the irradiance source wherever
+    the hit instance has a chart, and the irradiance volume (or `ambient`) as the fallback.  `charts` are the LightmapChart
+    items the atlas was baked with and `lightmap` is the (height, width, 4) float32 atlas bake_lightmap or denoise_lightmap
+    returned: E is its bilinear fetch at the hit's texcoords over the texels a chart owns (alpha != 0), renormalised by
+    their coverage, or the plain bilinear fetch where none of the four is owned (the gutter).  A hit without a chart takes
+    E from the volume exactly as render_baked does when `sh` is given (with `origin`, `spacing`, `dims`, and `depth`,
+    `max_distance`, `valid`, `visibility`, `backface`, `normal_bias` as there), and `ambient` otherwise.  With torch tensors
+    `lightmap` is a contiguous float32 tensor on the context's device, and so is `sh` if given.  With want_gbuffer the
+    (H, W, 20) float32 G-buffer is returned: render_baked's 16 words ([11]: the owned coverage on a lightmapped pixel, the
+    lookup's w on a probe pixel), then the atlas coordinate x, y in texels, the chart index bits (BAKED_VIEW_MISS: none) and
+    the LIGHTMAPPED_SOURCE_* bits.  The picture does not depend on `max_slots`.  Blocks until complete."""
+    if sh is not None and (origin is None or spacing is None or dims is None):
+        raise ValueError("a volume comes with its origin, spacing and dims")
+    c, tensors, p_sh, p_depth, p_valid = _baked_view_desc("render_lightmapped", ctx, scene, render_target, camera_params, camera_transform, origin, spacing,
+                                                          dims, sh, depth, max_distance, valid, ambient, visibility, backface, ray_epsilon, normal_bias,
+                                                          max_slots)
+    items = [k if isinstance(k, LightmapChart) else LightmapChart(*k) for k in charts]
+    c_charts = (_abi.LightmapChartC * max(1, len(items)))(*[_abi.LightmapChartC(int(k.instance_idx), k.scale_u, k.scale_v, k.offset_u, k.offset_v)
+                                                           for k in items])
+    if hasattr(lightmap, "data_ptr"):   # a torch tensor
+        import torch
+        if sh is not None and not tensors:
+            raise ValueError("lightmap and sh must both be torch tensors, or neither")
+        if not (lightmap.is_cuda and lightmap.dtype == torch.float32 and lightmap.is_contiguous() and lightmap.dim() == 3 and lightmap.shape[2] == 4):
+            raise ValueError("lightmap must be a contiguous (height, width, 4) float32 tensor on the context's device")
+        if lightmap.device.index != ctx.device_ordinal:
+            raise ValueError("lightmap is on another device than the context")
+        c.flags = BAKED_VIEW_DEVICE_POINTERS
+        p_lm = C.c_void_p(lightmap.data_ptr())
+    else:
+        if tensors:
+            raise ValueError("lightmap and sh must both be torch tensors, or neither")
+        lightmap = np.ascontiguousarray(lightmap, np.float32)
+        if lightmap.ndim != 3 or lightmap.shape[2] != 4:
+            raise ValueError("lightmap must be (height, width, 4)")
+        p_lm = ptr(lightmap)
+    gbuffer, gb = _baked_view_gbuffer(render_target, LIGHTMAPPED_VIEW_GBUFFER_FLOATS, want_gbuffer, lightmap if hasattr(lightmap, "data_ptr") else None)
+    d = _abi.LightmappedViewDescC(c, int(lightmap.shape[1]), int(lightmap.shape[0]), len(items), 0)
+    check(lib().lupin_hip_render_lightmapped(ctx.handle, scene.handle, render_target.handle, C.byref(d), c_charts, p_lm, p_sh, p_depth, p_valid, gb))
     return gbuffer

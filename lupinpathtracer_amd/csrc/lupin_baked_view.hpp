@@ -31,6 +31,64 @@ struct BakedViewDev   // what of LupinBakedViewDesc and the context the compose 
     uint32_t store_rne;   // FrameParams::store_rne
 };
 
+// A pixel's primary hit, resolved once: what k_baked_gbuffer writes, and what the lightmapped view (lupin_lightmapped_view.hpp)
+// goes on from.  `s` is the hit's surface where hit, and not set otherwise.
+struct BakedPrimary
+{
+    Surface s;
+    f3 p, nrm, color, glow;
+    uint32_t inst, tri, state;
+    float dst;
+    bool hit;
+};
+
+// Steps 1 to 4 of the contract for pixel first + slot; the lane has passed make_geo's barrier.
+template <typename Geo>
+LP_DEV BakedPrimary baked_primary(const Geo &geo, const SceneDev &sc, const FrameParams &fp, uint32_t *lds_stack, unsigned long long pixel, float eps)
+{
+    const uint32_t gy = (uint32_t)(pixel / fp.width), gx = (uint32_t)(pixel - (unsigned long long)gy * fp.width);
+    f3 o, d;
+    camera_ray_centre(fp, gx, gy, o, d);
+    const Closest c = scene_closest(geo, sc, lds_stack, o, d, eps);
+    BakedPrimary r;
+    r.hit = c.t != LP_F32_MAX;
+    r.p = splat(0.0f); r.nrm = splat(0.0f); r.color = splat(0.0f);
+    r.inst = HIT_MISS; r.tri = 0u; r.state = LP_BAKED_MISS;
+    r.dst = 0.0f;
+    if (r.hit)
+    {
+        r.inst = c.inst;
+        r.dst = c.t;
+        r.s = resolve_surface(sc, c.inst, c.tri, c.u, c.v);
+        r.tri = c.tri - r.s.mesh.tri_offset;
+        r.p = mk3(o.x + d.x * r.dst, o.y + d.y * r.dst, o.z + d.z * r.dst);
+        const f3 ns = shading_normal(geo, sc, r.s);
+        const float cs = (d.x * ns.x + d.y * ns.y) + d.z * ns.z;
+        r.nrm = cs > 0.0f ? mk3(-ns.x, -ns.y, -ns.z) : ns;
+        const MatPoint m = material_point<false>(sc, r.s);
+        r.color = m.color;
+        r.glow = m.emission;
+        r.state = ray_record_ok(r.p.x, r.p.y, r.p.z, r.nrm.x, r.nrm.y, r.nrm.z, LP_RAY_DIRECTION) ? LP_BAKED_LOOKUP : LP_BAKED_NO_LOOKUP;
+    }
+    else r.glow = environment_radiance(sc, d);
+    return r;
+}
+
+// The lookup's record of a pixel (see the head of this file), and the G-buffer's 16 words.
+LP_DEV void baked_store_record(const BakedPrimary &r, bool ask, float4 *__restrict__ records, size_t slot)
+{
+    records[2 * slot] = ask ? make_float4(r.p.x, r.p.y, r.p.z, __uint_as_float(r.inst)) : make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(r.inst));
+    records[2 * slot + 1] = ask ? make_float4(r.nrm.x, r.nrm.y, r.nrm.z, __uint_as_float(r.tri)) : make_float4(0.0f, 0.0f, 1.0f, __uint_as_float(r.tri));
+}
+
+LP_DEV void baked_store_gbuffer(const BakedPrimary &r, float4 *__restrict__ g)
+{
+    g[0] = make_float4(r.p.x, r.p.y, r.p.z, __uint_as_float(r.inst));
+    g[1] = make_float4(r.nrm.x, r.nrm.y, r.nrm.z, __uint_as_float(r.tri));
+    g[2] = make_float4(r.color.x, r.color.y, r.color.z, 0.0f);   // [11] is the compose kernel's
+    g[3] = make_float4(r.glow.x, r.glow.y, r.glow.z, r.dst);
+}
+
 // `records` (2 float4 a slot), `aux` (2 float4 a slot) and `gbuffer` (nullptr, or 4 float4 a slot) point at the launch's first
 // slot; first = the launch's first pixel (y * W + x), n = the launch's slots.
 template <bool LDSGEO>
@@ -43,44 +101,11 @@ __global__ void __launch_bounds__(LP_BLOCK) k_baked_gbuffer(SceneDev sc, FramePa
     const uint32_t slot = blockIdx.x * LP_BLOCK + threadIdx.x;
     if (slot < n)   // (every lane of the block has passed the barrier)
     {
-        const unsigned long long pixel = first + slot;
-        const uint32_t gy = (uint32_t)(pixel / fp.width), gx = (uint32_t)(pixel - (unsigned long long)gy * fp.width);
-        f3 o, d;
-        camera_ray_centre(fp, gx, gy, o, d);
-        const Closest c = scene_closest(geo, sc, lds_stack, o, d, eps);
-        const bool hit = c.t != LP_F32_MAX;
-        f3 p = splat(0.0f), nrm = splat(0.0f), color = splat(0.0f), glow;
-        uint32_t inst = HIT_MISS, tri = 0u, state = LP_BAKED_MISS;
-        float dst = 0.0f;
-        if (hit)
-        {
-            inst = c.inst;
-            dst = c.t;
-            const Surface s = resolve_surface(sc, c.inst, c.tri, c.u, c.v);
-            tri = c.tri - s.mesh.tri_offset;
-            p = mk3(o.x + d.x * dst, o.y + d.y * dst, o.z + d.z * dst);
-            const f3 ns = shading_normal(geo, sc, s);
-            const float cs = (d.x * ns.x + d.y * ns.y) + d.z * ns.z;
-            nrm = cs > 0.0f ? mk3(-ns.x, -ns.y, -ns.z) : ns;
-            const MatPoint m = material_point<false>(sc, s);
-            color = m.color;
-            glow = m.emission;
-            state = ray_record_ok(p.x, p.y, p.z, nrm.x, nrm.y, nrm.z, LP_RAY_DIRECTION) ? LP_BAKED_LOOKUP : LP_BAKED_NO_LOOKUP;
-        }
-        else glow = environment_radiance(sc, d);
-        const bool ask = state == LP_BAKED_LOOKUP;
-        records[2 * (size_t)slot] = ask ? make_float4(p.x, p.y, p.z, __uint_as_float(inst)) : make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(inst));
-        records[2 * (size_t)slot + 1] = ask ? make_float4(nrm.x, nrm.y, nrm.z, __uint_as_float(tri)) : make_float4(0.0f, 0.0f, 1.0f, __uint_as_float(tri));
-        aux[2 * (size_t)slot] = make_float4(color.x, color.y, color.z, __uint_as_float(state));
-        aux[2 * (size_t)slot + 1] = make_float4(glow.x, glow.y, glow.z, dst);
-        if (gbuffer)
-        {
-            float4 *__restrict__ g = gbuffer + 4 * (size_t)slot;
-            g[0] = make_float4(p.x, p.y, p.z, __uint_as_float(inst));
-            g[1] = make_float4(nrm.x, nrm.y, nrm.z, __uint_as_float(tri));
-            g[2] = make_float4(color.x, color.y, color.z, 0.0f);   // [11] is k_baked_compose's
-            g[3] = make_float4(glow.x, glow.y, glow.z, dst);
-        }
+        const BakedPrimary r = baked_primary(geo, sc, fp, lds_stack, first + slot, eps);
+        baked_store_record(r, r.state == LP_BAKED_LOOKUP, records, slot);
+        aux[2 * (size_t)slot] = make_float4(r.color.x, r.color.y, r.color.z, __uint_as_float(r.state));
+        aux[2 * (size_t)slot + 1] = make_float4(r.glow.x, r.glow.y, r.glow.z, r.dst);
+        if (gbuffer) baked_store_gbuffer(r, gbuffer + 4 * (size_t)slot);
     }
 }
 

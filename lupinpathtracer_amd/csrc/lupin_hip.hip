@@ -38,6 +38,7 @@
 #include "lupin_probe_grid.hpp"
 #include "lupin_probe_depth.hpp"
 #include "lupin_baked_view.hpp"
+#include "lupin_lightmapped_view.hpp"
 #include "lupin_internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -3356,27 +3357,110 @@ int lupin_hip_sample_probe_grid_depth(LupinContext *ctx, const LupinScene *scene
 static constexpr uint64_t LP_BAKED_VIEW_DEFAULT_SLOTS = LUPIN_BAKED_VIEW_DEFAULT_MAX_SLOTS;
 static constexpr uint64_t LP_BAKED_VIEW_MAX_LAUNCH_SLOTS = LP_PROBE_GRID_MAX_LAUNCH;   // the lookup's kernel runs over a launch's slots
 
-int lupin_hip_render_baked(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target, const LupinBakedViewDesc *desc, const float *sh,
-                           const float *depth, const uint8_t *valid, float *out_gbuffer)
+// What the two views (this one and the lightmapped view) refuse alike in a target and a view descriptor, neither of them NULL.
+// `volume`: an irradiance volume was given (sh != NULL); the grid, and with depth maps their resolution and max_distance,
+// are looked at only then, and *probes is the grid's probe count (0 without a volume).
+static int baked_view_refuse(const LupinContext *ctx, const LupinTexture *render_target, const LupinBakedViewDesc *desc, bool volume, const float *depth,
+                             uint64_t *probes)
 {
-    if (int rc = query_refuse(ctx, scene, render_target && desc && sh)) return rc;
+    *probes = 0;
     if (render_target->ctx != ctx) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the render target belongs to another context, or to one that has been destroyed");
     if (desc->flags & ~(uint32_t)LUPIN_BAKED_VIEW_DEVICE_POINTERS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
     for (int k = 0; k < 3; k++)
         if (!std::isfinite(desc->ambient[k])) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ambient must be finite");
     if (!(std::isfinite(desc->ray_epsilon) && desc->ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
+    if (!volume) return LUPIN_OK;
     // the chosen lookup's refusals, by its own function and with its own message; where the arrays live is this descriptor's to say
-    const LupinProbeGridDesc &gd = desc->grid;
-    uint64_t probes;
-    if (int rc = depth ? probe_grid_refuse(gd, LUPIN_PROBE_GRID_BACKFACE, "unknown flag (LUPIN_PROBE_GRID_VISIBILITY belongs to lupin_hip_sample_probe_grid)", &probes)
-                       : probe_grid_refuse(gd, LUPIN_PROBE_GRID_VISIBILITY | LUPIN_PROBE_GRID_BACKFACE, "unknown flag", &probes))
+    if (int rc = depth ? probe_grid_refuse(desc->grid, LUPIN_PROBE_GRID_BACKFACE,
+                                           "unknown flag (LUPIN_PROBE_GRID_VISIBILITY belongs to lupin_hip_sample_probe_grid)", probes)
+                       : probe_grid_refuse(desc->grid, LUPIN_PROBE_GRID_VISIBILITY | LUPIN_PROBE_GRID_BACKFACE, "unknown flag", probes))
         return rc;
-    const uint32_t R = desc->resolution;
     if (depth)
     {
-        if (!probe_depth_resolution_ok(R)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "resolution must be in [2, 64]");
+        if (!probe_depth_resolution_ok(desc->resolution)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "resolution must be in [2, 64]");
         if (!(std::isfinite(desc->max_distance) && desc->max_distance > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_distance must be finite and positive");
     }
+    return LUPIN_OK;
+}
+
+// An irradiance volume as the lookup kernels take it.  Host arrays go whole into buffers that live as long as this does.
+struct BakedVolume
+{
+    DeviceBuffer b_sh, b_depth, b_valid;
+    const float4 *sh = nullptr;
+    const float2 *depth = nullptr;
+    const uint8_t *valid = nullptr;
+};
+
+static int baked_volume_stage(hipStream_t st, bool on_device, uint64_t probes, uint32_t R, const float *sh, const float *depth, const uint8_t *valid,
+                              BakedVolume *v)
+{
+    v->sh = reinterpret_cast<const float4 *>(sh);
+    v->depth = reinterpret_cast<const float2 *>(depth);
+    v->valid = valid;
+    if (on_device) return LUPIN_OK;
+    const size_t sh_bytes = (size_t)probes * LUPIN_PROBE_RESULT_FLOATS * 4;
+    HIP_TRY(DeviceBuffer::make(sh_bytes, &v->b_sh));
+    HIP_TRY(hipMemcpyAsync(v->b_sh.get(), sh, sh_bytes, hipMemcpyHostToDevice, st));
+    v->sh = v->b_sh.as<float4>();
+    if (depth)
+    {
+        const size_t depth_bytes = (size_t)probes * (R + 2u) * (R + 2u) * 8u;
+        HIP_TRY(DeviceBuffer::make(depth_bytes, &v->b_depth));
+        HIP_TRY(hipMemcpyAsync(v->b_depth.get(), depth, depth_bytes, hipMemcpyHostToDevice, st));
+        v->depth = v->b_depth.as<float2>();
+    }
+    if (valid)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)probes, &v->b_valid));
+        HIP_TRY(hipMemcpyAsync(v->b_valid.get(), valid, (size_t)probes, hipMemcpyHostToDevice, st));
+        v->valid = v->b_valid.as<uint8_t>();
+    }
+    return LUPIN_OK;
+}
+
+// The chosen lookup's own kernel over a launch's records: with depth maps k_probe_grid_depth, otherwise k_probe_grid by the
+// lookup's plan `tl`.
+static void baked_view_lookup(const LupinScene *scene, hipStream_t st, const LupinBakedViewDesc *desc, const BakedVolume &vol, bool vis, const TraversalLds &tl,
+                              uint32_t slots, const float4 *rec, float4 *res)
+{
+    const ProbeGridDev g = probe_grid_dev(desc->grid);
+    if (vol.depth)
+        hipLaunchKernelGGL(k_probe_grid_depth, probe_grid_blocks(slots), dim3(LP_BLOCK), 0, st, slots, g, desc->resolution, desc->max_distance, vol.sh, vol.depth,
+                           vol.valid, rec, res);
+    else
+        with_bool(tl.geo, [&](auto G) {
+            with_bool(vis, [&](auto V) {
+                hipLaunchKernelGGL((k_probe_grid<decltype(G)::value, decltype(V)::value>), probe_grid_blocks(slots), dim3(LP_BLOCK), tl.lds, st, scene->dev, slots,
+                                   g, vol.sh, vol.valid, rec, res, tl.stack_words);
+            });
+        });
+}
+
+// The pixels of one launch: max_slots as asked (0: the default), a multiple of 64, at least 64, no more than the image needs.
+static uint64_t baked_view_launch_slots(uint32_t asked_slots, uint64_t pixels)
+{
+    const uint64_t asked = asked_slots ? (uint64_t)asked_slots : LP_BAKED_VIEW_DEFAULT_SLOTS;
+    return std::min(std::min(std::max<uint64_t>(asked / 64u * 64u, 64u), LP_BAKED_VIEW_MAX_LAUNCH_SLOTS), (pixels + 63u) / 64u * 64u);
+}
+
+static FrameParams baked_view_frame(const LupinBakedViewDesc *desc, uint32_t W, uint32_t H)
+{
+    FrameParams fp;
+    memset(&fp, 0, sizeof(fp));
+    set_camera_constants(fp.pc, desc->camera_params, desc->camera_transform);
+    fp.width = W; fp.height = H; fp.reg_w = W; fp.reg_h = H;
+    return fp;
+}
+
+int lupin_hip_render_baked(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target, const LupinBakedViewDesc *desc, const float *sh,
+                           const float *depth, const uint8_t *valid, float *out_gbuffer)
+{
+    if (int rc = query_refuse(ctx, scene, render_target && desc && sh)) return rc;
+    uint64_t probes;
+    if (int rc = baked_view_refuse(ctx, render_target, desc, true, depth, &probes)) return rc;
+    const LupinProbeGridDesc &gd = desc->grid;
+    const uint32_t R = desc->resolution;
     if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
     const bool on_device = (desc->flags & LUPIN_BAKED_VIEW_DEVICE_POINTERS) != 0;
     if (on_device && ((((uintptr_t)sh | (uintptr_t)out_gbuffer) & 15u) || ((uintptr_t)depth & 7u)))
@@ -3392,44 +3476,18 @@ int lupin_hip_render_baked(LupinContext *ctx, const LupinScene *scene, LupinText
     if (int rc = join_primary(ctx)) return rc;
     hipStream_t st = ctx->stream;
 
-    FrameParams fp;
-    memset(&fp, 0, sizeof(fp));
-    set_camera_constants(fp.pc, desc->camera_params, desc->camera_transform);
-    fp.width = W; fp.height = H; fp.reg_w = W; fp.reg_h = H;
-    const ProbeGridDev g = probe_grid_dev(gd);
+    const FrameParams fp = baked_view_frame(desc, W, H);
     const BakedViewDev v{desc->ambient[0], desc->ambient[1], desc->ambient[2], (ctx->store_rounding == 1) ? 1u : 0u};
 
-    const uint64_t asked = desc->max_slots ? (uint64_t)desc->max_slots : LP_BAKED_VIEW_DEFAULT_SLOTS;
-    const uint64_t max_slots = std::min(std::min(std::max<uint64_t>(asked / 64u * 64u, 64u), LP_BAKED_VIEW_MAX_LAUNCH_SLOTS), (pixels + 63u) / 64u * 64u);
+    const uint64_t max_slots = baked_view_launch_slots(desc->max_slots, pixels);
     // scratch for one launch; host arrays: the grid whole and one launch's G-buffer.  All of it lives for the call.
-    DeviceBuffer b_rec, b_aux, b_res, b_sh, b_depth, b_valid, b_gbuf;
+    DeviceBuffer b_rec, b_aux, b_res, b_gbuf;
+    BakedVolume vol;
     HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, &b_rec));
     HIP_TRY(DeviceBuffer::make((size_t)max_slots * 32, &b_aux));
     HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, &b_res));
-    const float4 *d_sh = reinterpret_cast<const float4 *>(sh);
-    const float2 *d_depth = reinterpret_cast<const float2 *>(depth);
-    const uint8_t *d_valid = valid;
-    if (!on_device)
-    {
-        const size_t sh_bytes = (size_t)probes * LUPIN_PROBE_RESULT_FLOATS * 4;
-        HIP_TRY(DeviceBuffer::make(sh_bytes, &b_sh));
-        HIP_TRY(hipMemcpyAsync(b_sh.get(), sh, sh_bytes, hipMemcpyHostToDevice, st));
-        d_sh = b_sh.as<float4>();
-        if (depth)
-        {
-            const size_t depth_bytes = (size_t)probes * (R + 2u) * (R + 2u) * 8u;
-            HIP_TRY(DeviceBuffer::make(depth_bytes, &b_depth));
-            HIP_TRY(hipMemcpyAsync(b_depth.get(), depth, depth_bytes, hipMemcpyHostToDevice, st));
-            d_depth = b_depth.as<float2>();
-        }
-        if (valid)
-        {
-            HIP_TRY(DeviceBuffer::make((size_t)probes, &b_valid));
-            HIP_TRY(hipMemcpyAsync(b_valid.get(), valid, (size_t)probes, hipMemcpyHostToDevice, st));
-            d_valid = b_valid.as<uint8_t>();
-        }
-        if (out_gbuffer) HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_BAKED_VIEW_GBUFFER_FLOATS * 4, &b_gbuf));
-    }
+    if (int rc = baked_volume_stage(st, on_device, probes, R, sh, depth, valid, &vol)) return rc;
+    if (!on_device && out_gbuffer) HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_BAKED_VIEW_GBUFFER_FLOATS * 4, &b_gbuf));
     render_target->accum32_valid = false;   // the f16 texels are the only truth of this picture
     for (uint64_t first = 0; first < pixels; first += max_slots)
     {
@@ -3442,16 +3500,7 @@ int lupin_hip_render_baked(LupinContext *ctx, const LupinScene *scene, LupinText
                                desc->ray_epsilon, b_rec.as<float4>(), b_aux.as<float4>(), d_gbuf, t.stack_words);
         });
         HIP_TRY(hipGetLastError());
-        if (depth)
-            hipLaunchKernelGGL(k_probe_grid_depth, probe_grid_blocks(slots), dim3(LP_BLOCK), 0, st, slots, g, R, desc->max_distance, d_sh, d_depth, d_valid,
-                               b_rec.as<float4>(), b_res.as<float4>());
-        else
-            with_bool(tl.geo, [&](auto G) {
-                with_bool(vis, [&](auto V) {
-                    hipLaunchKernelGGL((k_probe_grid<decltype(G)::value, decltype(V)::value>), probe_grid_blocks(slots), dim3(LP_BLOCK), tl.lds, st, scene->dev,
-                                       slots, g, d_sh, d_valid, b_rec.as<float4>(), b_res.as<float4>(), tl.stack_words);
-                });
-            });
+        baked_view_lookup(scene, st, desc, vol, vis, tl, slots, b_rec.as<float4>(), b_res.as<float4>());
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_baked_compose, blocks, dim3(LP_BLOCK), 0, st, v, (unsigned long long)first, slots, b_aux.as<float4>(), b_res.as<float4>(),
                            render_target->data, d_gbuf);
@@ -3463,6 +3512,109 @@ int lupin_hip_render_baked(LupinContext *ctx, const LupinScene *scene, LupinText
         }
     }
     return query_end(ctx, "lupin_hip_render_baked");
+}
+
+// ---- lightmapped view (no reference counterpart; kernels: lupin_lightmapped_view.hpp) ----
+
+int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target, const LupinLightmappedViewDesc *desc,
+                                 const LupinLightmapChart *charts, const float *lightmap, const float *sh, const float *depth, const uint8_t *valid,
+                                 float *out_gbuffer)
+{
+    if (int rc = query_refuse(ctx, scene, render_target && desc && lightmap)) return rc;
+    const LupinBakedViewDesc *view = &desc->view;
+    uint64_t probes;
+    if (int rc = baked_view_refuse(ctx, render_target, view, sh != nullptr, depth, &probes)) return rc;
+    if (!sh && (depth || valid)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "depth and valid belong to a volume: sh is NULL");
+    const uint32_t AW = desc->lightmap_width, AH = desc->lightmap_height, num_charts = desc->num_charts;
+    if (AW == 0 || AH == 0 || AW > LUPIN_LIGHTMAP_MAX_SIZE || AH > LUPIN_LIGHTMAP_MAX_SIZE)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "lightmap_width and lightmap_height must be in [1, 16384]");
+    if (desc->reserved != 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "reserved must be 0");
+    if (num_charts > 0 && !charts) return fail(LUPIN_ERR_INVALID_ARGUMENT, "charts is NULL with num_charts > 0");
+    // the chart of an instance is the first that names it; a chart is refused as lupin_hip_bake_lightmap refuses it
+    const uint32_t num_instances = (uint32_t)scene->host_instances.size();
+    std::vector<uint32_t> h_chart_of(std::max<uint32_t>(num_instances, 1u), LP_LMV_NO_CHART);
+    std::vector<float4> h_charts(std::max<uint32_t>(num_charts, 1u), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (uint32_t c = 0; c < num_charts; c++)
+    {
+        const LupinLightmapChart &ch = charts[c];
+        if (ch.instance_idx >= num_instances) return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": instance index out of range");
+        if (!scene->mesh_has_texcoords[scene->host_instances[ch.instance_idx].mesh_idx])
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": the instance's mesh has no texcoords");
+        if (!(std::isfinite(ch.scale_u) && std::isfinite(ch.scale_v) && std::isfinite(ch.offset_u) && std::isfinite(ch.offset_v)))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": non-finite scale or offset");
+        h_charts[c] = make_float4(ch.scale_u, ch.scale_v, ch.offset_u, ch.offset_v);
+        if (h_chart_of[ch.instance_idx] == LP_LMV_NO_CHART) h_chart_of[ch.instance_idx] = c;
+    }
+    if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
+    const bool on_device = (view->flags & LUPIN_BAKED_VIEW_DEVICE_POINTERS) != 0;
+    if (on_device && ((((uintptr_t)lightmap | (uintptr_t)sh | (uintptr_t)out_gbuffer) & 15u) || ((uintptr_t)depth & 7u)))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device lightmap, coefficients and G-buffer must be 16-byte aligned, device maps 8-byte aligned");
+    const uint32_t W = render_target->width, H = render_target->height;
+    const uint64_t pixels = (uint64_t)W * H;
+    if (int rc = query_flush(ctx)) return rc;
+    // two plans, as lupin_hip_render_baked: the primary hit's and, with a volume, the lookup's own
+    const bool vis = sh && !depth && (view->grid.flags & LUPIN_PROBE_GRID_VISIBILITY) != 0;
+    TraversalLds t, tl;
+    if (int rc = traversal_lds(ctx, scene, scene->stack_entries, true, &t)) return rc;
+    if (int rc = traversal_lds(ctx, scene, vis ? scene->stack_entries : 0u, vis, &tl)) return rc;
+    if (int rc = join_primary(ctx)) return rc;
+    hipStream_t st = ctx->stream;
+
+    const FrameParams fp = baked_view_frame(view, W, H);
+    const LightmappedViewDev v{{view->ambient[0], view->ambient[1], view->ambient[2], (ctx->store_rounding == 1) ? 1u : 0u}, AW, AH, sh ? 1u : 0u};
+
+    const uint64_t max_slots = baked_view_launch_slots(view->max_slots, pixels);
+    // scratch for one launch (the lookup's results only with a volume); the chart tables; host arrays: the atlas and the grid
+    // whole, one launch's G-buffer.  All of it lives for the call.
+    DeviceBuffer b_rec, b_aux, b_lm, b_res, b_chart_of, b_charts, b_atlas, b_gbuf;
+    BakedVolume vol;
+    HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, &b_rec));
+    HIP_TRY(DeviceBuffer::make((size_t)max_slots * 32, &b_aux));
+    HIP_TRY(DeviceBuffer::make((size_t)max_slots * 16, &b_lm));
+    if (sh) HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, &b_res));
+    HIP_TRY(DeviceBuffer::make(h_chart_of.size() * 4, &b_chart_of));
+    HIP_TRY(DeviceBuffer::make(h_charts.size() * 16, &b_charts));
+    HIP_TRY(hipMemcpyAsync(b_chart_of.get(), h_chart_of.data(), h_chart_of.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b_charts.get(), h_charts.data(), h_charts.size() * 16, hipMemcpyHostToDevice, st));
+    const float4 *d_atlas = reinterpret_cast<const float4 *>(lightmap);
+    if (!on_device)
+    {
+        const size_t atlas_bytes = (size_t)AW * AH * 16;
+        HIP_TRY(DeviceBuffer::make(atlas_bytes, &b_atlas));
+        HIP_TRY(hipMemcpyAsync(b_atlas.get(), lightmap, atlas_bytes, hipMemcpyHostToDevice, st));
+        d_atlas = b_atlas.as<float4>();
+        if (out_gbuffer) HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS * 4, &b_gbuf));
+    }
+    if (sh)
+        if (int rc = baked_volume_stage(st, on_device, probes, view->resolution, sh, depth, valid, &vol)) return rc;
+    render_target->accum32_valid = false;   // the f16 texels are the only truth of this picture
+    for (uint64_t first = 0; first < pixels; first += max_slots)
+    {
+        const uint32_t slots = (uint32_t)std::min(max_slots, pixels - first);
+        float *dst = out_gbuffer ? out_gbuffer + first * LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS : nullptr;
+        float4 *d_gbuf = reinterpret_cast<float4 *>(out_gbuffer && !on_device ? b_gbuf.as<float>() : dst);
+        const dim3 blocks((slots + LP_BLOCK - 1) / LP_BLOCK);
+        with_bool(t.geo, [&](auto G) {
+            hipLaunchKernelGGL(k_lightmapped_gbuffer<decltype(G)::value>, blocks, dim3(LP_BLOCK), t.lds, st, scene->dev, fp, v, (unsigned long long)first, slots,
+                               view->ray_epsilon, b_chart_of.as<uint32_t>(), b_charts.as<float4>(), b_rec.as<float4>(), b_aux.as<float4>(), b_lm.as<float4>(),
+                               d_gbuf, t.stack_words);
+        });
+        HIP_TRY(hipGetLastError());
+        if (sh)
+        {
+            baked_view_lookup(scene, st, view, vol, vis, tl, slots, b_rec.as<float4>(), b_res.as<float4>());
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_lightmapped_compose, blocks, dim3(LP_BLOCK), 0, st, v, (unsigned long long)first, slots, b_aux.as<float4>(), b_lm.as<float4>(),
+                           b_res.as<float4>(), d_atlas, render_target->data, d_gbuf);
+        HIP_TRY(hipGetLastError());
+        if (out_gbuffer && !on_device)
+        {
+            HIP_TRY(hipMemcpyAsync(dst, d_gbuf, (size_t)slots * LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));   // (the next launch writes the same buffer; the copy is to pageable memory)
+        }
+    }
+    return query_end(ctx, "lupin_hip_render_lightmapped");
 }
 
 // ---- lightmap baking (no reference counterpart; kernels: lupin_lightmap.hpp) ----
