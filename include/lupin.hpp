@@ -624,6 +624,35 @@ inline uint64_t bake_lightmap(const Device &d, const Scene &scene, const Lightma
     return covered;
 }
 
+// ambient-occlusion and bent-normal atlases (no reference counterpart): bake_lightmap's texels and records,
+// every owned texel queried by the bent-normal kernel up to max_distance
+struct LightmapAoDesc
+{
+    uint32_t width = 0, height = 0;
+    uint32_t samples = 64;
+    uint32_t max_slots = 0;
+    uint32_t flags = 0;            // LUPIN_LIGHTMAP_SMOOTH_NORMALS | LUPIN_LIGHTMAP_AO_OPACITY
+    uint32_t dilate = 0;           // gutter passes
+    uint32_t counter = 0;
+    float surface_offset = 0.0f;   // world units along the geometric normal; the caller chooses (> 0)
+    float max_distance = std::numeric_limits<float>::infinity();
+    float ray_epsilon = 0.001f;
+};
+// out_ao: height x width x 4 floats (visibility, alpha = ownership); out_bent: nullptr or height x width x 4 (unit bent
+// normal); out_records: nullptr or height x width x 8; returns the number of owned texels
+inline uint64_t bake_lightmap_ao(const Device &d, const Scene &scene, const LightmapAoDesc &desc, const LightmapChart *charts, uint32_t num_charts,
+                                 float *out_ao, float *out_bent = nullptr, float *out_records = nullptr)
+{
+    const LupinLightmapAoDesc c{desc.width, desc.height, desc.samples, desc.max_slots, desc.flags, desc.dilate, desc.counter, desc.surface_offset,
+                                desc.max_distance, desc.ray_epsilon};
+    std::vector<LupinLightmapChart> cc(num_charts);
+    for (uint32_t k = 0; k < num_charts; k++)
+        cc[k] = LupinLightmapChart{charts[k].instance_idx, charts[k].scale_u, charts[k].scale_v, charts[k].offset_u, charts[k].offset_v};
+    uint64_t covered = 0;
+    check(lupin_hip_bake_lightmap_ao(d.raw(), scene.raw(), &c, cc.data(), num_charts, out_ao, out_bent, out_records, &covered));
+    return covered;
+}
+
 // lightmap denoising (no reference counterpart): an edge-avoiding a-trous filter in atlas space, guided by the
 // records of the bake; `out_rgba` may be `rgba`
 struct LightmapDenoiseDesc
@@ -740,6 +769,21 @@ inline void transmittance_rays(const Device &d, const Scene &scene, const Occlus
 {
     const LupinOcclusionDesc c{(uint32_t)desc.mode, desc.samples, desc.flags, desc.ray_epsilon};
     check(lupin_hip_transmittance_rays(d.raw(), scene.raw(), &c, n, records, out_sum));
+}
+// bent-normal queries (no reference counterpart): hemisphere-mode occlusion records; out: n x 4 floats, per
+// record (sum T d.x, sum T d.y, sum T d.z, sum T) over its cosine-weighted slots, T = 1 / 0 (open / blocked) or, with
+// LUPIN_BENT_NORMAL_OPACITY, the slot's transmittance.  The caller divides .w by samples and normalises .xyz.
+struct BentNormalDesc
+{
+    uint32_t samples = 64;
+    uint32_t flags = 0;        // LUPIN_BENT_NORMAL_DEVICE_POINTERS | LUPIN_BENT_NORMAL_OPACITY
+    uint32_t max_slots = 0;    // 0: the library's default
+    float ray_epsilon = 0.001f;
+};
+inline void bent_normal_rays(const Device &d, const Scene &scene, const BentNormalDesc &desc, uint64_t n, const float *records, float *out)
+{
+    const LupinBentNormalDesc c{desc.samples, desc.flags, desc.max_slots, desc.ray_epsilon};
+    check(lupin_hip_bent_normal_rays(d.raw(), scene.raw(), &c, n, records, out));
 }
 // The transmittance between p[i] and q[i] (n x 3 floats each); the segments are lp::visible's.
 inline std::vector<float> transmittance(const Device &d, const Scene &scene, uint64_t n, const float *p, const float *q, float ray_epsilon = 0.001f)

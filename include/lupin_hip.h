@@ -951,6 +951,45 @@ typedef struct LupinLightmapStats {
 } LupinLightmapStats;
 void lupin_hip_lightmap_stats(LupinLightmapStats *out);
 
+/* ---- ambient-occlusion and bent-normal atlases (no reference counterpart) ----
+ * Two more channels in the lightmap's atlas.  Rasterisation, ownership, record emission and out_records are
+ * lupin_hip_bake_lightmap's, word for word, for the same charts, flags (LUPIN_LIGHTMAP_SMOOTH_NORMALS), counter and
+ * surface_offset: the same kernels run.  Every owned texel's record is then queried by lupin_hip_bent_normal_rays' kernel
+ * (below) with `samples` slots, ray_epsilon, LUPIN_LIGHTMAP_AO_OPACITY as its OPACITY flag, and max_distance as the tmax of
+ * every slot (the record's word [7] stays the radiance query's mode).  With a = the query's four floats for the texel, each
+ * operation one rounded f32 operation:
+ *   v = a.w / (float)samples                       out_ao texel   = (v, v, v, 1.0f)
+ *   len = sqrtf((a.x*a.x + a.y*a.y) + a.z*a.z)     out_bent texel = (a.x / len, a.y / len, a.z / len, 1.0f),
+ *                                                  or (n.x, n.y, n.z, 1.0f) with n the record's bake normal where len == 0
+ * Texels that are not owned hold zeros in both planes.  Then both planes get `dilate` gutter passes exactly as
+ * lupin_hip_bake_lightmap's (the same kernel; gutter alpha stays 0; dilated bent normals are not renormalised).
+ * Intermediates stay on the device; only the outputs cross the bus.
+ *
+ * out_ao (with out_records) is a valid input to lupin_hip_denoise_lightmap, and a valid `lightmap` for
+ * lupin_hip_render_lightmapped: both take any H x W x 4 plane with alpha as ownership.
+ *
+ * Ordering as lupin_hip_bake_lightmap.  LUPIN_ERR_INVALID_ARGUMENT with the outputs untouched for what
+ * lupin_hip_bake_lightmap refuses in the atlas, the charts and the records (out_bent, out_records and out_num_covered may be
+ * NULL), an unknown flag, samples == 0 or above 2^20, a ray_epsilon that is not finite or is negative, and a max_distance
+ * that is NaN or <= 0.  An atlas without an owned texel: LUPIN_OK, all zeros.  Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+enum { LUPIN_LIGHTMAP_AO_OPACITY = 2u };                                /* desc.flags, with LUPIN_LIGHTMAP_SMOOTH_NORMALS */
+typedef struct LupinLightmapAoDesc {
+    uint32_t width;                 /* atlas texels, 1 .. LUPIN_LIGHTMAP_MAX_SIZE */
+    uint32_t height;
+    uint32_t samples;               /* 1 .. 2^20 slots per texel */
+    uint32_t max_slots;             /* as LupinBentNormalDesc */
+    uint32_t flags;
+    uint32_t dilate;                /* gutter passes, 0 .. LUPIN_LIGHTMAP_MAX_DILATE */
+    uint32_t counter;               /* seeds: rng_seed_for(texel linear index, counter) */
+    float surface_offset;           /* as LupinLightmapDesc */
+    float max_distance;             /* tmax of every slot: > 0; +inf = unbounded; NaN or <= 0 refused */
+    float ray_epsilon;              /* finite, >= 0 */
+} LupinLightmapAoDesc;
+int lupin_hip_bake_lightmap_ao(LupinContext *ctx, const LupinScene *scene, const LupinLightmapAoDesc *desc,
+                               const LupinLightmapChart *charts, uint32_t num_charts, float *out_ao /* H*W*4 */,
+                               float *out_bent /* NULL, or H*W*4 */, float *out_records /* NULL, or H*W*8 */,
+                               uint64_t *out_num_covered /* NULL ok */);
+
 /* ---- lightmap denoising (no reference counterpart) ----
  * An edge-avoiding a-trous filter in atlas space for what lupin_hip_bake_lightmap writes: `rgba` is its out_rgba (or several
  * bakes with different `counter`, averaged by the caller), `records` its out_records.  No scene is needed.  Texel p is
@@ -1151,6 +1190,56 @@ int lupin_hip_occlusion_rays(LupinContext *ctx, const LupinScene *scene, const L
  * n == 0: LUPIN_OK, nothing touched.  Without a HIP device: LUPIN_ERR_NO_DEVICE. */
 int lupin_hip_transmittance_rays(LupinContext *ctx, const LupinScene *scene, const LupinOcclusionDesc *desc,
                                  uint64_t n, const float *records /* n x 8 */, float *out_sum /* n */);
+
+/* ---- bent-normal queries (no reference counterpart) ----
+ * "How much of the hemisphere is open, and which way does the open part point?": ambient occlusion and the cosine-weighted
+ * bent normal of surface points, in one launch per batch.
+ *
+ * Records are lupin_hip_occlusion_rays' records read in LUPIN_OCCLUSION_COSINE_HEMISPHERE mode: [0..2] origin, [3] RNG word
+ * (bits), [4..6] unit surface normal, [7] tmax.  Slot s of record i (s < samples) has the RNG state and direction d_s of
+ * that mode, bit for bit -- the out_rays of lupin_hip_pathtrace_rays on the same record.
+ *
+ * Weight per slot, for the segment (o, d_s, ray_epsilon, tmax):
+ *   without LUPIN_BENT_NORMAL_OPACITY   T_s = 1.0f if the segment is not BLOCKED in lupin_hip_occlusion_rays' sense, else 0.0f
+ *   with LUPIN_BENT_NORMAL_OPACITY      T_s = lupin_hip_transmittance_rays' T for that segment, word for word
+ *
+ * out[i], LUPIN_BENT_NORMAL_RESULT_FLOATS floats, is summed as one wave of 64 lanes; every float operation is one rounded
+ * f32 operation, no contraction:
+ *   1. lane l takes slots s = l, l + 64, ... in ascending order;
+ *   2. it adds them to acc = (+0, +0, +0, +0):  acc.x = acc.x + T_s * d_s.x,  acc.y = acc.y + T_s * d_s.y,
+ *      acc.z = acc.z + T_s * d_s.z,  acc.w = acc.w + T_s;
+ *   3. for off = 32, 16, 8, 4, 2, 1:  acc = acc + acc of lane (l xor off), component by component;
+ *   4. out[i] = acc of lane 0.
+ * Lanes without a slot (samples < 64) hold +0 and take part in step 3.  No float atomics, no per-slot plane in memory, no
+ * second kernel; the same records give the same words, whatever max_slots is and however the batch is cut into launches.
+ * out[i].w / samples is the ambient-occlusion visibility; out[i].xyz, normalised, is the cosine-weighted bent normal (its
+ * expectation per slot is E[T d]: (0, 0, 2/3) about a normal +z under an open sky).  The caller divides and normalises.
+ *   - With LUPIN_BENT_NORMAL_OPACITY, out[i].w is lupin_hip_transmittance_rays' out_sum for the same records, bit for bit.
+ *   - Without it, out[i].w is exactly (float)(samples - blocked) of lupin_hip_occlusion_rays: every partial sum is an integer
+ *     of at most 2^20, which f32 holds exactly.
+ *
+ * The call behaves as lupin_hip_transmittance_rays does: recorded calls run first (their error is returned), the work runs
+ * on the primary stream, host arrays go through staging buffers the context keeps, and LUPIN_BENT_NORMAL_DEVICE_POINTERS
+ * takes device memory of the context's device in place (records and out 16-byte aligned).  A launch holds whole records:
+ * max_slots / samples of them, at least one, and never more than 2^25.  Only the binary hierarchy is read: it works after
+ * lupin_hip_scene_update_instances.
+ *
+ * LUPIN_ERR_INVALID_ARGUMENT, nothing traced and `out` untouched, for everything lupin_hip_transmittance_rays refuses in
+ * hemisphere mode (a NULL argument; n * samples above 2^38; a scene of another or of a destroyed context; a record with a
+ * non-finite origin or normal, a normal whose squared length is further than 1e-4 from 1, a tmax that is NaN or <= 0; a
+ * ray_epsilon that is not finite or is negative; a hierarchy too deep for the traversal stack), an unknown flag, samples
+ * == 0 or above 2^20, and misaligned device pointers.  n == 0: LUPIN_OK, nothing touched.
+ * Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_BENT_NORMAL_RESULT_FLOATS 4
+enum { LUPIN_BENT_NORMAL_DEVICE_POINTERS = 1u, LUPIN_BENT_NORMAL_OPACITY = 2u };   /* desc.flags */
+typedef struct LupinBentNormalDesc {
+    uint32_t samples;               /* S: 1 .. 2^20 slots per record */
+    uint32_t flags;
+    uint32_t max_slots;             /* 0 = library default (2^30); slots per launch; a launch holds whole records, at least one */
+    float ray_epsilon;              /* finite, >= 0 */
+} LupinBentNormalDesc;
+int lupin_hip_bent_normal_rays(LupinContext *ctx, const LupinScene *scene, const LupinBentNormalDesc *desc,
+                               uint64_t n, const float *records /* n x 8 */, float *out /* n x 4 */);
 
 /* ---- distance queries (no reference counterpart) ----
  * "How far is the nearest surface, where is it, and which side of it am I on?" for POINTS: clearances for bake offsets, probe

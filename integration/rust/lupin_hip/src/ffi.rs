@@ -121,6 +121,18 @@ pub const LUPIN_OCCLUSION_DEVICE_POINTERS: u32 = 1;
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinOcclusionDesc {
     pub mode: u32, pub samples: u32, pub flags: u32, pub ray_epsilon: f32,
 }
+// bent-normal queries and the ambient-occlusion atlas (no reference counterpart)
+pub const LUPIN_BENT_NORMAL_RESULT_FLOATS: usize = 4;
+pub const LUPIN_BENT_NORMAL_DEVICE_POINTERS: u32 = 1;
+pub const LUPIN_BENT_NORMAL_OPACITY: u32 = 2;
+pub const LUPIN_LIGHTMAP_AO_OPACITY: u32 = 2;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinBentNormalDesc {
+    pub samples: u32, pub flags: u32, pub max_slots: u32, pub ray_epsilon: f32,
+}
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmapAoDesc {
+    pub width: u32, pub height: u32, pub samples: u32, pub max_slots: u32, pub flags: u32, pub dilate: u32, pub counter: u32,
+    pub surface_offset: f32, pub max_distance: f32, pub ray_epsilon: f32,
+}
 // distance queries (no reference counterpart)
 pub const LUPIN_DISTANCE_RECORD_FLOATS: usize = 4;
 pub const LUPIN_DISTANCE_RESULT_FLOATS: usize = 12;
@@ -259,6 +271,12 @@ extern "C" {
     pub fn lupin_hip_occlusion_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinOcclusionDesc, n: u64,
                                     records: *const f32, out_blocked: *mut u32) -> c_int;
     pub fn lupin_hip_transmittance_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinOcclusionDesc, n: u64, records: *const f32, out_sum: *mut f32) -> c_int;
+    // bent-normal queries: hemisphere-mode occlusion records, out n x 4 f32 (sum T d.xyz | sum T)
+    pub fn lupin_hip_bent_normal_rays(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinBentNormalDesc, n: u64, records: *const f32, out: *mut f32) -> c_int;
+    // ambient-occlusion atlas: out_ao height x width x 4 f32, out_bent null or the same, out_records null or height x width x 8, out_num_covered null ok
+    pub fn lupin_hip_bake_lightmap_ao(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinLightmapAoDesc,
+                                      charts: *const LupinLightmapChart, num_charts: u32, out_ao: *mut f32, out_bent: *mut f32,
+                                      out_records: *mut f32, out_num_covered: *mut u64) -> c_int;
     // distance queries: records n x 4 f32 (point | rmax), out_results n x 12 f32 words; the grid: x fastest, one f32 per voxel
     pub fn lupin_hip_distance_points(ctx: *mut LupinContext, scene: *const LupinScene, flags: u32, n: u64, records: *const f32, out_results: *mut f32) -> c_int;
     pub fn lupin_hip_bake_distance_grid(ctx: *mut LupinContext, scene: *const LupinScene, flags: u32, origin: *const f32, spacing: *const f32,

@@ -302,6 +302,29 @@ pub fn transmittance_rays(device: &Device, scene: &Scene, records: &[f32], mode:
     out
 }
 
+// ---- bent-normal queries and the ambient-occlusion atlas (no reference counterpart) ----
+/// Per hemisphere-mode record of `occlusion_rays`' layout, four sums over its `samples` cosine-weighted slots:
+/// `(sum T d.x, sum T d.y, sum T d.z, sum T)`, `T` = 1 / 0 (open / blocked) or with `opacity` the slot's transmittance.
+/// `[3] / samples` is the ambient-occlusion visibility, `[0..3]` normalised the bent normal.
+pub fn bent_normal_rays(device: &Device, scene: &Scene, records: &[f32], samples: u32, ray_epsilon: f32, opacity: bool) -> Vec<f32> {
+    assert!(records.len() % LUPIN_OCCLUSION_RECORD_FLOATS == 0);
+    let n = records.len() / LUPIN_OCCLUSION_RECORD_FLOATS;
+    let mut out = vec![0f32; n * LUPIN_BENT_NORMAL_RESULT_FLOATS];
+    let c = LupinBentNormalDesc { samples, flags: if opacity { LUPIN_BENT_NORMAL_OPACITY } else { 0 }, max_slots: 0, ray_epsilon };
+    check(unsafe { lupin_hip_bent_normal_rays(device.raw, scene.raw, &c, n as u64, records.as_ptr(), out.as_mut_ptr()) });
+    out
+}
+
+/// The ambient-occlusion map and the bent-normal map of `charts` in a `desc.height` x `desc.width` atlas (x 4 floats each,
+/// alpha = ownership), laid out as `lupin_hip_bake_lightmap` lays out its lightmap.
+pub fn bake_lightmap_ao(device: &Device, scene: &Scene, desc: &LupinLightmapAoDesc, charts: &[LupinLightmapChart]) -> (Vec<f32>, Vec<f32>) {
+    let texels = desc.width as usize * desc.height as usize;
+    let (mut ao, mut bent) = (vec![0f32; texels * 4], vec![0f32; texels * 4]);
+    check(unsafe { lupin_hip_bake_lightmap_ao(device.raw, scene.raw, desc, charts.as_ptr(), charts.len() as u32, ao.as_mut_ptr(), bent.as_mut_ptr(),
+                                              std::ptr::null_mut(), std::ptr::null_mut()) });
+    (ao, bent)
+}
+
 // ---- distance queries (no reference counterpart) ----
 /// The twelve words of a result.  `side` is the side of the reported triangle, not an inside / outside classification.
 #[repr(C)] #[derive(Copy, Clone, Debug, Default)] pub struct DistanceResult {

@@ -188,6 +188,16 @@ class OcclusionDescC(C.Structure):   # LupinOcclusionDesc
     _fields_ = [("mode", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32), ("ray_epsilon", C.c_float)]
 
 
+class BentNormalDescC(C.Structure):   # LupinBentNormalDesc
+    _fields_ = [("samples", C.c_uint32), ("flags", C.c_uint32), ("max_slots", C.c_uint32), ("ray_epsilon", C.c_float)]
+
+
+class LightmapAoDescC(C.Structure):   # LupinLightmapAoDesc
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("samples", C.c_uint32), ("max_slots", C.c_uint32), ("flags", C.c_uint32),
+                ("dilate", C.c_uint32), ("counter", C.c_uint32), ("surface_offset", C.c_float), ("max_distance", C.c_float),
+                ("ray_epsilon", C.c_float)]
+
+
 class ProbeGridDescC(C.Structure):   # LupinProbeGridDesc
     _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_uint32 * 3), ("flags", C.c_uint32),
                 ("ray_epsilon", C.c_float), ("normal_bias", C.c_float)]
@@ -290,6 +300,8 @@ SYMBOLS = [
     ("lupin_hip_bake_probes", C.c_int, [_P, _P, C.POINTER(ProbeDescC), C.c_uint64, _P, _P, _P]),
     ("lupin_hip_occlusion_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),
     ("lupin_hip_transmittance_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),
+    ("lupin_hip_bent_normal_rays", C.c_int, [_P, _P, C.POINTER(BentNormalDescC), C.c_uint64, _P, _P]),
+    ("lupin_hip_bake_lightmap_ao", C.c_int, [_P, _P, C.POINTER(LightmapAoDescC), C.POINTER(LightmapChartC), _U32, _P, _P, _P, C.POINTER(C.c_uint64)]),
     ("lupin_hip_distance_points", C.c_int, [_P, _P, _U32, C.c_uint64, _P, _P]),
     ("lupin_hip_bake_distance_grid", C.c_int, [_P, _P, _U32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_float, _P]),
     ("lupin_hip_sample_probe_grid", C.c_int, [_P, _P, C.POINTER(ProbeGridDescC), _P, _P, C.c_uint64, _P, _P]),

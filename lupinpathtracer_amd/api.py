@@ -1790,6 +1790,105 @@ def ambient_occlusion(ctx, scene, points, normals, radius, samples=64, ray_epsil
     return np.float32(1.0) - blocked.astype(np.float32) / np.float32(samples)
 
 
+# ---- bent-normal queries: lupin_hip_bent_normal_rays, lupin_hip_bake_lightmap_ao (include/lupin_hip.h) ----
+BENT_NORMAL_RESULT_FLOATS = 4
+BENT_NORMAL_DEVICE_POINTERS = 1
+BENT_NORMAL_OPACITY = 2
+BENT_NORMAL_MAX_SAMPLES = 1 << 20
+LIGHTMAP_AO_OPACITY = 2
+
+
+def bent_normal_rays(ctx, scene, records, samples, ray_epsilon=0.001, opacity=False, max_slots=0):
+    """Per record, the four sums over its `samples` cosine-weighted slots (sum T d.x, sum T d.y, sum T d.z, sum T):
+    (n, 4) float32.  T is 1 or 0 (the slot's segment is not / is blocked, as occlusion_rays decides), or with opacity=True
+    the slot's transmittance (transmittance_rays' T).  [:, 3] / samples is the ambient-occlusion visibility, [:, :3]
+    normalised the cosine-weighted bent normal; bent_normal_resolve does both.  `records` are occlusion_records read in
+    OcclusionMode.COSINE_HEMISPHERE: an (n, OCCLUSION_RECORD_FLOATS) float32 numpy array, or a contiguous float32 torch
+    tensor on the context's device: then torch's current stream is synchronised, the device memory is used in place and
+    a float32 tensor is returned.  max_slots: slots per launch (0: the library's default); the words do not depend on it.
+    Blocks until complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bent_normal_rays needs a GPU context and an uploaded scene; there is no CPU fallback")
+    c = _abi.BentNormalDescC(int(samples), BENT_NORMAL_OPACITY if opacity else 0, int(max_slots), float(ray_epsilon))
+    if hasattr(records, "data_ptr"):   # a torch tensor
+        import torch
+        t = records
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == OCCLUSION_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+        if t.device.index != ctx.device_ordinal:
+            raise ValueError("records are on another device than the context")
+        out = torch.zeros((int(t.shape[0]), BENT_NORMAL_RESULT_FLOATS), dtype=torch.float32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()   # the records (and the zero fill) are written
+        c.flags |= BENT_NORMAL_DEVICE_POINTERS
+        check(lib().lupin_hip_bent_normal_rays(ctx.handle, scene.handle, C.byref(c), int(t.shape[0]), C.c_void_p(t.data_ptr()),
+                                               C.c_void_p(out.data_ptr())))
+        return out
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, OCCLUSION_RECORD_FLOATS)
+    out = np.zeros((len(rec), BENT_NORMAL_RESULT_FLOATS), np.float32)
+    check(lib().lupin_hip_bent_normal_rays(ctx.handle, scene.handle, C.byref(c), len(rec), ptr(rec), ptr(out)))
+    return out
+
+
+def bent_normal_resolve(sums, samples, normals):
+    """(ao (n,), bent (n, 3)) float32 from bent_normal_rays' sums, by the atlas bake's formulas in float32:
+    ao = sums.w / samples;  len = sqrt((x*x + y*y) + z*z);  bent = sums.xyz / len, or the row of `normals` where len == 0."""
+    a = np.asarray(sums, np.float32).reshape(-1, BENT_NORMAL_RESULT_FLOATS)
+    normals = np.asarray(normals, np.float32).reshape(-1, 3)
+    ao = a[:, 3] / np.float32(samples)
+    length = np.sqrt((a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2], dtype=np.float32)
+    zero = length == np.float32(0.0)
+    bent = a[:, :3] / np.where(zero, np.float32(1.0), length)[:, None]
+    bent[zero] = normals[zero]
+    return ao, bent
+
+
+def bent_normals(ctx, scene, points, normals, radius, samples=64, ray_epsilon=0.001, counter=0, surface_offset=None, opacity=False):
+    """(ao (n,), bent (n, 3)) float32 at `points` (n, 3) with unit `normals` (n, 3): the ambient-occlusion visibility
+    ambient_occlusion returns, and the cosine-weighted mean unoccluded direction, unit length -- or the point's normal where
+    nothing is open.  Seeds, offset default, `radius` and `opacity` are ambient_occlusion's: the two see the same slots."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bent_normals needs a GPU context and an uploaded scene; there is no CPU fallback")
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    normals = np.asarray(normals, np.float32).reshape(-1, 3)
+    if surface_offset is None:
+        surface_offset = LIGHTMAP_OFFSET_FRACTION * scene_world_extent(scene)
+    rec = occlusion_records(points + normals * np.float32(surface_offset), normals, radius, rng_seed_for(np.arange(len(points), dtype=np.uint32), counter))
+    return bent_normal_resolve(bent_normal_rays(ctx, scene, rec, samples, ray_epsilon, opacity), samples, normals)
+
+
+def bake_lightmap_ao(ctx, scene, charts, width, height, samples=64, max_distance=np.inf, ray_epsilon=0.001, counter=0, max_slots=0,
+                     smooth_normals=False, opacity=False, dilate=0, surface_offset=None, want_bent=False, want_records=False, denoise=False):
+    """An ambient-occlusion map in bake_lightmap's atlas: (height, width, 4) float32, rgb = the visibility (the share of
+    `samples` cosine-weighted directions that are open up to `max_distance`; with opacity=True their mean transmittance),
+    alpha 1 on rasterised texels and 0 elsewhere (gutter texels filled by `dilate` passes keep alpha 0).  charts,
+    smooth_normals, counter, surface_offset and the records are bake_lightmap's: the same texels, the same records.
+    want_bent: also the bent-normal map (height, width, 4): xyz = the cosine-weighted mean open direction, unit length on
+    owned texels (the bake normal where nothing is open), not renormalised in the gutters.  want_records: also the
+    (height, width, 8) records.  denoise: the visibility's owned texels are filtered by denoise_lightmap with its defaults,
+    and its gutters are refilled from the filtered texels by `dilate` passes; the bent normals are not filtered.
+    Returns ao, or (ao[, bent][, records]) in that order.  Blocks until the result is complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_lightmap_ao needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if surface_offset is None:
+        surface_offset = LIGHTMAP_OFFSET_FRACTION * (scene_world_extent(scene) or 1.0)
+    items = [c if isinstance(c, LightmapChart) else LightmapChart(*c) for c in charts]
+    c_charts = (_abi.LightmapChartC * max(1, len(items)))(*[_abi.LightmapChartC(int(c.instance_idx), c.scale_u, c.scale_v, c.offset_u, c.offset_v)
+                                                           for c in items])
+    flags = (LIGHTMAP_SMOOTH_NORMALS if smooth_normals else 0) | (LIGHTMAP_AO_OPACITY if opacity else 0)
+    d = _abi.LightmapAoDescC(int(width), int(height), int(samples), int(max_slots), flags, int(dilate), int(counter), float(surface_offset),
+                             float(max_distance), float(ray_epsilon))
+    shape_ok = 0 < int(width) <= LIGHTMAP_MAX_SIZE and 0 < int(height) <= LIGHTMAP_MAX_SIZE
+    hw = (int(height), int(width)) if shape_ok else (1, 1)      # a refused size: the library says so
+    ao = np.zeros(hw + (4,), np.float32)
+    bent = np.zeros(hw + (4,), np.float32) if want_bent else None
+    rec = np.zeros(hw + (RAY_RECORD_FLOATS,), np.float32) if (want_records or denoise) else None
+    check(lib().lupin_hip_bake_lightmap_ao(ctx.handle, scene.handle, C.byref(d), c_charts, len(items), ptr(ao), ptr(bent), ptr(rec), None))
+    if denoise:   # (the filter reads owned texels only and refills the gutters itself)
+        ao = denoise_lightmap(ctx, ao, rec, dilate=dilate)
+    out = (ao,) + ((bent,) if want_bent else ()) + ((rec,) if want_records else ())
+    return out if len(out) > 1 else ao
+
+
 # ---- distance queries: lupin_hip_distance_points, lupin_hip_bake_distance_grid (include/lupin_hip.h, DESIGN.md 20) ----
 DISTANCE_RECORD_FLOATS = 4
 DISTANCE_RESULT_FLOATS = 12

@@ -34,6 +34,7 @@
 #include "lupin_lightmap_denoise.hpp"
 #include "lupin_occlusion.hpp"
 #include "lupin_transmittance.hpp"
+#include "lupin_bent_normal.hpp"
 #include "lupin_distance.hpp"
 #include "lupin_probe_grid.hpp"
 #include "lupin_probe_depth.hpp"
@@ -143,6 +144,9 @@ struct LupinContext
     // per-slot plane of hemisphere mode (one float per slot of a chunk), kept and grown the same way
     DeviceBuffer trans_plane;
     size_t trans_plane_bytes = 0;
+    // lupin_hip_bent_normal_rays: it shares occ_records and adds the staging of one chunk's results (four floats per record)
+    DeviceBuffer bent_results;
+    size_t bent_results_bytes = 0;
     // lupin_hip_distance_points / lupin_hip_bake_distance_grid: the same for the distance queries, and the per-instance
     // auxiliary array (local -> world rows and c_i) that every call rebuilds from the scene's current rows
     DeviceBuffer dist_records, dist_results, dist_aux;
@@ -2830,6 +2834,64 @@ static int segment_chunk_records(LupinContext *ctx, bool on_device, uint64_t n, 
     return LUPIN_OK;
 }
 
+// The bent-normal query: lupin_hip_bent_normal_rays and the query inside lupin_hip_bake_lightmap_ao.
+static constexpr uint32_t LP_BENT_NORMAL_MAX_SAMPLES = 1u << 20;
+static constexpr uint64_t LP_BENT_NORMAL_DEFAULT_SLOTS = 1ull << 30;
+static constexpr uint64_t LP_BENT_NORMAL_MAX_LAUNCH_RECORDS = 1ull << 25;   // one wave per record: the grid's threads fit 32 bits
+static constexpr uint64_t LP_BENT_NORMAL_MAX_STAGED_RECORDS = 1ull << 22;   // host arrays: records of one launch (128 + 64 MB of staging)
+struct BentNormalQuery
+{
+    const char *who;
+    uint32_t samples, max_slots;
+    bool opacity, on_device;
+    float ray_epsilon;
+    bool fixed_tmax;    // every slot's tmax is `tmax`; the records' word [7] is the Rule's
+    float tmax;
+};
+// what both entry points refuse in these fields
+static int bent_normal_refuse(uint32_t samples, float ray_epsilon)
+{
+    if (samples == 0 || samples > LP_BENT_NORMAL_MAX_SAMPLES) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^20]");
+    if (!(std::isfinite(ray_epsilon) && ray_epsilon >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "ray_epsilon must be finite and not negative");
+    return LUPIN_OK;
+}
+// From query_start to query_end, once the arguments are accepted and n != 0: whole records per launch, at most
+// max_slots / samples of them (at least one), host arrays through the context's staging, four floats of result per record.
+template <typename Rule>
+static int bent_normal_query(LupinContext *ctx, const LupinScene *scene, const BentNormalQuery &q, uint64_t n, const float *records, float *out)
+{
+    TraversalLds t;
+    if (int rc = query_start<Rule>(ctx, scene, q.on_device, n, records, &t)) return rc;
+    const uint64_t S = q.samples, max_slots = q.max_slots ? q.max_slots : LP_BENT_NORMAL_DEFAULT_SLOTS;
+    uint64_t chunk = std::min({n, std::max<uint64_t>(1, max_slots / S), LP_BENT_NORMAL_MAX_LAUNCH_RECORDS});
+    if (!q.on_device)
+    {
+        chunk = std::min(chunk, LP_BENT_NORMAL_MAX_STAGED_RECORDS);
+        HIP_TRY(grow_buffer(&ctx->occ_records, &ctx->occ_records_bytes, (size_t)chunk * Rule::FLOATS * 4));
+        HIP_TRY(grow_buffer(&ctx->bent_results, &ctx->bent_results_bytes, (size_t)chunk * LUPIN_BENT_NORMAL_RESULT_FLOATS * 4));
+    }
+    hipStream_t st = ctx->stream;
+    for (uint64_t first = 0; first < n; first += chunk)
+    {
+        const uint32_t recs = (uint32_t)std::min(chunk, n - first);
+        const float *src = records + first * Rule::FLOATS;
+        float *dst = out + first * LUPIN_BENT_NORMAL_RESULT_FLOATS;
+        if (!q.on_device) HIP_TRY(hipMemcpyAsync(ctx->occ_records.get(), src, (size_t)recs * Rule::FLOATS * 4, hipMemcpyHostToDevice, st));
+        const float4 *d_rec = q.on_device ? reinterpret_cast<const float4 *>(src) : ctx->occ_records.as<float4>();
+        float4 *d_out = q.on_device ? reinterpret_cast<float4 *>(dst) : ctx->bent_results.as<float4>();
+        const dim3 blocks((recs + LP_BENT_NORMAL_RECORDS_PER_BLOCK - 1) / LP_BENT_NORMAL_RECORDS_PER_BLOCK);
+        with_bool(t.geo, [&](auto G) {
+            with_bool(q.opacity, [&](auto O) {
+                hipLaunchKernelGGL((k_bent_normal<decltype(G)::value, decltype(O)::value>), blocks, dim3(LP_BLOCK), t.lds, st, scene->dev, recs, d_rec,
+                                   q.samples, q.ray_epsilon, q.fixed_tmax ? 1u : 0u, q.tmax, d_out, t.stack_words);
+            });
+        });
+        HIP_TRY(hipGetLastError());
+        if (!q.on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, (size_t)recs * LUPIN_BENT_NORMAL_RESULT_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    }
+    return query_end(ctx, q.who);
+}
+
 // The irradiance volume's two lookups (by segments, by depth maps: DESIGN.md 23, 25).
 static constexpr uint64_t LP_PROBE_GRID_MAX_LAUNCH = 1ull << 27;          // records of one launch: eight lanes each, and the lane index fits 32 bits
 static constexpr uint64_t LP_PROBE_GRID_MAX_STAGED_RECORDS = 1ull << 20;  // host arrays: records of one launch (32 + 16 MB of staging)
@@ -2996,6 +3058,24 @@ int lupin_hip_transmittance_rays(LupinContext *ctx, const LupinScene *scene, con
         }
         return LUPIN_OK;
     });
+}
+
+// ---- bent-normal queries (no reference counterpart; kernels: lupin_bent_normal.hpp) ----
+
+int lupin_hip_bent_normal_rays(LupinContext *ctx, const LupinScene *scene, const LupinBentNormalDesc *desc, uint64_t n, const float *records, float *out)
+{
+    if (int rc = query_refuse(ctx, scene, desc && records && out)) return rc;
+    if (desc->flags & ~(uint32_t)(LUPIN_BENT_NORMAL_DEVICE_POINTERS | LUPIN_BENT_NORMAL_OPACITY)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (int rc = bent_normal_refuse(desc->samples, desc->ray_epsilon)) return rc;
+    if (n > LP_RAYS_MAX_PATHS / desc->samples) return fail(LUPIN_ERR_INVALID_ARGUMENT, "n * samples must not exceed 2^38");
+    if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
+    const bool on_device = (desc->flags & LUPIN_BENT_NORMAL_DEVICE_POINTERS) != 0;
+    if (on_device && (((uintptr_t)records & 15u) || ((uintptr_t)out & 15u)))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "device records and device results must be 16-byte aligned");
+    if (n == 0) return LUPIN_OK;
+    const BentNormalQuery q = {"lupin_hip_bent_normal_rays", desc->samples, desc->max_slots, (desc->flags & LUPIN_BENT_NORMAL_OPACITY) != 0, on_device,
+                               desc->ray_epsilon, false, 0.0f};
+    return bent_normal_query<OcclusionRecordRule>(ctx, scene, q, n, records, out);
 }
 
 // ---- distance queries (no reference counterpart; kernels: lupin_distance.hpp) ----
@@ -3622,25 +3702,22 @@ int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, Lup
 static thread_local LupinLightmapStats g_lightmap_stats = {0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 void lupin_hip_lightmap_stats(LupinLightmapStats *out) { if (out) *out = g_lightmap_stats; }
 
-int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc, const LupinLightmapChart *charts,
-                            uint32_t num_charts, float *out_rgba, float *out_records, uint64_t *out_num_covered)
+// What the two atlas bakes (lupin_hip_bake_lightmap, lupin_hip_bake_lightmap_ao) share: the refusals about the atlas ...
+static int lightmap_refuse_atlas(uint32_t W, uint32_t H, uint32_t num_charts, uint32_t unknown_flags, uint32_t dilate, float surface_offset)
 {
-    const char *who = "lupin_hip_bake_lightmap";
-    if (int rc = query_refuse(ctx, scene, desc && charts && out_rgba)) return rc;
-    const uint32_t W = desc->width, H = desc->height;
     if (W == 0 || H == 0 || W > LUPIN_LIGHTMAP_MAX_SIZE || H > LUPIN_LIGHTMAP_MAX_SIZE)
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "width and height must be in [1, 16384]");
     if (num_charts == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "no charts");
-    if (desc->flags & ~(uint32_t)LUPIN_LIGHTMAP_SMOOTH_NORMALS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
-    if (desc->dilate > LUPIN_LIGHTMAP_MAX_DILATE) return fail(LUPIN_ERR_INVALID_ARGUMENT, "dilate must be <= 64");
-    if (!(std::isfinite(desc->surface_offset) && desc->surface_offset > 0.0f))
-        return fail(LUPIN_ERR_INVALID_ARGUMENT, "surface_offset must be finite and positive");
-    // what the query refuses in a descriptor, here as well: an atlas without an owned texel never reaches the query
-    if (desc->pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
-    if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
-    if (desc->max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
-    if (int rc = query_refuse_hierarchy(ctx, scene, true)) return rc;
-    std::vector<LmChartDev> h_charts(num_charts);
+    if (unknown_flags) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown flag");
+    if (dilate > LUPIN_LIGHTMAP_MAX_DILATE) return fail(LUPIN_ERR_INVALID_ARGUMENT, "dilate must be <= 64");
+    if (!(std::isfinite(surface_offset) && surface_offset > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "surface_offset must be finite and positive");
+    return LUPIN_OK;
+}
+// ... the refusals about the charts, and the charts as the kernels read them
+static int lightmap_host_charts(const LupinScene *scene, const LupinLightmapChart *charts, uint32_t num_charts, std::vector<LmChartDev> *h_charts,
+                                uint64_t *keys)
+{
+    h_charts->resize(num_charts);
     uint64_t total_keys = 0;
     for (uint32_t c = 0; c < num_charts; c++)
     {
@@ -3650,24 +3727,29 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
         if (!scene->mesh_has_texcoords[mesh]) return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": the instance's mesh has no texcoords");
         if (!(std::isfinite(ch.scale_u) && std::isfinite(ch.scale_v) && std::isfinite(ch.offset_u) && std::isfinite(ch.offset_v)))
             return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": non-finite scale or offset");
-        h_charts[c] = LmChartDev{ch.instance_idx, (uint32_t)total_keys, scene->mesh_tri_count[mesh], 0u, ch.scale_u, ch.scale_v, ch.offset_u, ch.offset_v};
+        (*h_charts)[c] = LmChartDev{ch.instance_idx, (uint32_t)total_keys, scene->mesh_tri_count[mesh], 0u, ch.scale_u, ch.scale_v, ch.offset_u, ch.offset_v};
         total_keys += scene->mesh_tri_count[mesh];
         if (total_keys >= 0xFFFFFFFFull) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the charts hold 2^32 - 1 or more triangles");
     }
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
-    hipStream_t st = ctx->lanes[0].stream;   // the primary stream, the query's own
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<float, std::milli>(clk::now() - t0).count(); };
-    LupinLightmapStats stats = {0, (uint32_t)total_keys, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-
+    *keys = total_keys;
+    return LUPIN_OK;
+}
+using LmClock = std::chrono::steady_clock;
+static float lm_ms_since(LmClock::time_point t0) { return std::chrono::duration<float, std::milli>(LmClock::now() - t0).count(); }
+// ... and the records: raster, count, scan, emit on the primary stream `st`, each phase ending synchronised.  *n: the owned
+// texels; with *n != 0, d_rec holds their records in ascending texel order and d_texel their texel indices.
+static int lightmap_emit_records(const LupinScene *scene, hipStream_t st, const char *who, uint32_t W, uint32_t H, const std::vector<LmChartDev> &h_charts,
+                                 uint64_t total_keys, uint32_t flags, uint32_t counter, float surface_offset, uint32_t *n_out, DeviceBuffer *d_rec,
+                                 DeviceBuffer *d_texel, float *raster_ms, float *compact_ms)
+{
+    const uint32_t num_charts = (uint32_t)h_charts.size();
     const uint32_t texels = W * H;
     const uint32_t texel_blocks = (texels + LP_BLOCK - 1) / LP_BLOCK;
     DeviceBuffer d_charts, d_owner, d_totals;
     HIP_TRY(DeviceBuffer::make(h_charts.size() * sizeof(LmChartDev), &d_charts));
     HIP_TRY(DeviceBuffer::make((size_t)texels * 4, &d_owner));
     HIP_TRY(DeviceBuffer::make(((size_t)texel_blocks + 1) * 4, &d_totals));
-    auto t0 = clk::now();
+    auto t0 = LmClock::now();
     HIP_TRY(hipMemcpyAsync(d_charts.get(), h_charts.data(), h_charts.size() * sizeof(LmChartDev), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_owner.get(), 0xFF, (size_t)texels * 4, st));
     if (total_keys)
@@ -3675,9 +3757,9 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
                            d_charts.as<LmChartDev>(), num_charts, (uint32_t)total_keys, W, H, d_owner.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    stats.raster_ms = ms_since(t0);
+    *raster_ms = lm_ms_since(t0);
 
-    t0 = clk::now();
+    t0 = LmClock::now();
     hipLaunchKernelGGL(k_lm_count, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, d_owner.as<uint32_t>(), texels, d_totals.as<uint32_t>());
     hipLaunchKernelGGL(k_lm_scan, dim3(1), dim3(LP_LM_SCAN_THREADS), 0, st, d_totals.as<uint32_t>(), texel_blocks);
     HIP_TRY(hipGetLastError());
@@ -3685,29 +3767,62 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
     HIP_TRY(hipMemcpyAsync(&n, d_totals.as<uint32_t>() + texel_blocks, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (n > texels) return fail(LUPIN_ERR_HIP, std::string(who) + ": the compaction counted more texels than the atlas has");
+    *n_out = n;
+    if (n != 0)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)n * LUPIN_RAY_RECORD_FLOATS * 4, d_rec));
+        HIP_TRY(DeviceBuffer::make((size_t)n * 4, d_texel));
+        hipLaunchKernelGGL(k_lm_emit, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, scene->dev, d_charts.as<LmChartDev>(), num_charts, W, H,
+                           d_owner.as<uint32_t>(), d_totals.as<uint32_t>(), flags, counter, surface_offset, d_rec->as<float4>(), d_texel->as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    *compact_ms = lm_ms_since(t0);
+    return LUPIN_OK;
+}
+
+int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc, const LupinLightmapChart *charts,
+                            uint32_t num_charts, float *out_rgba, float *out_records, uint64_t *out_num_covered)
+{
+    const char *who = "lupin_hip_bake_lightmap";
+    if (int rc = query_refuse(ctx, scene, desc && charts && out_rgba)) return rc;
+    const uint32_t W = desc->width, H = desc->height;
+    if (int rc = lightmap_refuse_atlas(W, H, num_charts, desc->flags & ~(uint32_t)LUPIN_LIGHTMAP_SMOOTH_NORMALS, desc->dilate, desc->surface_offset)) return rc;
+    // what the query refuses in a descriptor, here as well: an atlas without an owned texel never reaches the query
+    if (desc->pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
+    if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
+    if (desc->max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
+    if (int rc = query_refuse_hierarchy(ctx, scene, true)) return rc;
+    std::vector<LmChartDev> h_charts;
+    uint64_t total_keys = 0;
+    if (int rc = lightmap_host_charts(scene, charts, num_charts, &h_charts, &total_keys)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
+    hipStream_t st = ctx->lanes[0].stream;   // the primary stream, the query's own
+    using clk = LmClock;
+    auto ms_since = lm_ms_since;
+    LupinLightmapStats stats = {0, (uint32_t)total_keys, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+
+    const uint32_t texels = W * H;
+    const uint32_t texel_blocks = (texels + LP_BLOCK - 1) / LP_BLOCK;
+    uint32_t n = 0;
+    DeviceBuffer d_rec, d_texel, d_mean;
+    if (int rc = lightmap_emit_records(scene, st, who, W, H, h_charts, total_keys, desc->flags, desc->counter, desc->surface_offset, &n, &d_rec, &d_texel,
+                                       &stats.raster_ms, &stats.compact_ms))
+        return rc;
     stats.covered_texels = n;
     if (n == 0)
     {
         memset(out_rgba, 0, (size_t)texels * 16);
         if (out_records) memset(out_records, 0, (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4);
         if (out_num_covered) *out_num_covered = 0;
-        stats.compact_ms = ms_since(t0);
         g_lightmap_stats = stats;
         return LUPIN_OK;
     }
-    DeviceBuffer d_rec, d_texel, d_mean;
-    HIP_TRY(DeviceBuffer::make((size_t)n * LUPIN_RAY_RECORD_FLOATS * 4, &d_rec));
-    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &d_texel));
     HIP_TRY(DeviceBuffer::make((size_t)n * LUPIN_RAY_RESULT_FLOATS * 4, &d_mean));
-    hipLaunchKernelGGL(k_lm_emit, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, scene->dev, d_charts.as<LmChartDev>(), num_charts, W, H,
-                       d_owner.as<uint32_t>(), d_totals.as<uint32_t>(), desc->flags, desc->counter, desc->surface_offset, d_rec.as<float4>(),
-                       d_texel.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    stats.compact_ms = ms_since(t0);
 
     // one query on the device records: its validation, its chunks
-    t0 = clk::now();
+    auto t0 = clk::now();
     const LupinRayQueryDesc q{desc->pathtrace_type, desc->max_bounces, desc->samples, LUPIN_RAYS_DEVICE_POINTERS, desc->max_slots, desc->advanced};
     if (int rc = lupin_hip_pathtrace_rays(ctx, scene, &q, n, d_rec.as<float>(), d_mean.as<float>(), nullptr)) return rc;
     stats.trace_ms = ms_since(t0);
@@ -3745,6 +3860,88 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
     stats.download_ms = ms_since(t0);
     if (out_num_covered) *out_num_covered = n;
     g_lightmap_stats = stats;
+    return LUPIN_OK;
+}
+
+// ---- ambient-occlusion and bent-normal atlases (kernels: lupin_lightmap.hpp, lupin_bent_normal.hpp) ----
+
+int lupin_hip_bake_lightmap_ao(LupinContext *ctx, const LupinScene *scene, const LupinLightmapAoDesc *desc, const LupinLightmapChart *charts,
+                               uint32_t num_charts, float *out_ao, float *out_bent, float *out_records, uint64_t *out_num_covered)
+{
+    const char *who = "lupin_hip_bake_lightmap_ao";
+    if (int rc = query_refuse(ctx, scene, desc && charts && out_ao)) return rc;
+    const uint32_t W = desc->width, H = desc->height;
+    if (int rc = lightmap_refuse_atlas(W, H, num_charts, desc->flags & ~(uint32_t)(LUPIN_LIGHTMAP_SMOOTH_NORMALS | LUPIN_LIGHTMAP_AO_OPACITY), desc->dilate,
+                                       desc->surface_offset))
+        return rc;
+    // what the query refuses in a descriptor, here as well: an atlas without an owned texel never reaches the query
+    if (int rc = bent_normal_refuse(desc->samples, desc->ray_epsilon)) return rc;
+    if (!(desc->max_distance > 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_distance must be positive (+inf: unbounded)");   // (NaN > 0 is false)
+    if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
+    std::vector<LmChartDev> h_charts;
+    uint64_t total_keys = 0;
+    if (int rc = lightmap_host_charts(scene, charts, num_charts, &h_charts, &total_keys)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
+    hipStream_t st = ctx->lanes[0].stream;   // the primary stream, the query's own
+
+    const uint32_t texels = W * H;
+    const uint32_t texel_blocks = (texels + LP_BLOCK - 1) / LP_BLOCK;
+    uint32_t n = 0;
+    DeviceBuffer d_rec, d_texel, d_sums;
+    float raster_ms, compact_ms;
+    if (int rc = lightmap_emit_records(scene, st, who, W, H, h_charts, total_keys, desc->flags & LUPIN_LIGHTMAP_SMOOTH_NORMALS, desc->counter,
+                                       desc->surface_offset, &n, &d_rec, &d_texel, &raster_ms, &compact_ms))
+        return rc;
+    if (n == 0)
+    {
+        memset(out_ao, 0, (size_t)texels * 16);
+        if (out_bent) memset(out_bent, 0, (size_t)texels * 16);
+        if (out_records) memset(out_records, 0, (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4);
+        if (out_num_covered) *out_num_covered = 0;
+        return LUPIN_OK;
+    }
+    // one query on the device records (the radiance query's: word [7] is its mode, the slots' tmax is max_distance)
+    HIP_TRY(DeviceBuffer::make((size_t)n * LUPIN_BENT_NORMAL_RESULT_FLOATS * 4, &d_sums));
+    const BentNormalQuery q = {who, desc->samples, desc->max_slots, (desc->flags & LUPIN_LIGHTMAP_AO_OPACITY) != 0, true, desc->ray_epsilon, true,
+                               desc->max_distance};
+    if (int rc = bent_normal_query<RayRecordRule>(ctx, scene, q, n, d_rec.as<float>(), d_sums.as<float>())) return rc;
+
+    // both planes: the per-texel formulas, then the gutter passes of lupin_hip_bake_lightmap (the filled bytes are the same for both)
+    DeviceBuffer d_ao[2], d_bent[2], d_filled[2], d_plane;
+    const int planes = desc->dilate ? 2 : 1;
+    for (int k = 0; k < planes; k++)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)texels * 16, &d_ao[k]));
+        if (out_bent) HIP_TRY(DeviceBuffer::make((size_t)texels * 16, &d_bent[k]));
+        HIP_TRY(DeviceBuffer::make((size_t)texels, &d_filled[k]));
+    }
+    HIP_TRY(hipMemsetAsync(d_ao[0].get(), 0, (size_t)texels * 16, st));
+    if (out_bent) HIP_TRY(hipMemsetAsync(d_bent[0].get(), 0, (size_t)texels * 16, st));
+    HIP_TRY(hipMemsetAsync(d_filled[0].get(), 0, (size_t)texels, st));
+    if (out_records)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, &d_plane));
+        HIP_TRY(hipMemsetAsync(d_plane.get(), 0, (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, st));
+    }
+    hipLaunchKernelGGL(k_lm_ao_scatter, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, st, n, d_texel.as<uint32_t>(), d_sums.as<float4>(),
+                       d_rec.as<float4>(), (float)desc->samples, d_ao[0].as<float4>(), d_bent[0].as<float4>(), d_filled[0].as<uint8_t>(),
+                       d_plane.as<float4>());
+    int cur = 0;
+    for (uint32_t pass = 0; pass < desc->dilate; pass++, cur ^= 1)
+    {
+        if (out_bent)
+            hipLaunchKernelGGL(k_lm_dilate, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, W, H, d_bent[cur].as<float4>(), d_filled[cur].as<uint8_t>(),
+                               d_bent[cur ^ 1].as<float4>(), d_filled[cur ^ 1].as<uint8_t>());
+        hipLaunchKernelGGL(k_lm_dilate, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, W, H, d_ao[cur].as<float4>(), d_filled[cur].as<uint8_t>(),
+                           d_ao[cur ^ 1].as<float4>(), d_filled[cur ^ 1].as<uint8_t>());
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_ao, d_ao[cur].get(), (size_t)texels * 16, hipMemcpyDeviceToHost, st));
+    if (out_bent) HIP_TRY(hipMemcpyAsync(out_bent, d_bent[cur].get(), (size_t)texels * 16, hipMemcpyDeviceToHost, st));
+    if (out_records) HIP_TRY(hipMemcpyAsync(out_records, d_plane.get(), (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    if (int rc = query_end(ctx, who)) return rc;
+    if (out_num_covered) *out_num_covered = n;
     return LUPIN_OK;
 }
 

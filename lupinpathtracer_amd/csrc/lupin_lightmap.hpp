@@ -12,6 +12,7 @@
 //   (lupin_hip_pathtrace_rays on the compacted device records)
 //   k_lm_scatter   pi * mean radiance and alpha 1 to the texel, the record to its place in the record plane if asked
 //   k_lm_dilate    one gutter pass, ping-pong
+//   k_lm_ao_scatter  lupin_hip_bake_lightmap_ao's k_lm_scatter: visibility and bent normal from the bent-normal query's sums
 //
 // Geometry is read from plain global memory (GeoGlobal): every triangle is fetched once per wave in the raster and once per
 // owned texel in the emit, neighbouring texels share it through the cache, and nothing here iterates over a hierarchy --
@@ -291,4 +292,32 @@ __global__ void __launch_bounds__(LP_BLOCK) k_lm_dilate(uint32_t W, uint32_t H, 
     }
     dst[i] = c;
     dst_filled[i] = f;
+}
+
+// lupin_hip_bake_lightmap_ao, one thread per covered texel (planes cleared before), from the sums of
+// k_bent_normal (lupin_bent_normal.hpp).  With a = sums[j]: v = a.w / samples_f; ao texel = (v, v, v, 1);
+// len = sqrtf((a.x*a.x + a.y*a.y) + a.z*a.z);  bent texel = (a.x / len, a.y / len, a.z / len, 1), or the record's bake
+// normal where len == 0;  `filled` 1;  the record plane its record.  bent and record_plane may be null.
+__global__ void __launch_bounds__(LP_BLOCK) k_lm_ao_scatter(uint32_t n, const uint32_t *__restrict__ texel_of, const float4 *__restrict__ sums,
+                                                            const float4 *__restrict__ records, float samples_f, float4 *__restrict__ ao,
+                                                            float4 *__restrict__ bent, uint8_t *__restrict__ filled, float4 *__restrict__ record_plane)
+{
+    const uint32_t j = blockIdx.x * LP_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t texel = texel_of[j];
+    const float4 a = sums[j];
+    const float4 r0 = records[2 * (size_t)j], r1 = records[2 * (size_t)j + 1];
+    const float v = a.w / samples_f;
+    ao[texel] = make_float4(v, v, v, 1.0f);
+    if (bent)
+    {
+        const float len = sqrtf((a.x * a.x + a.y * a.y) + a.z * a.z);
+        bent[texel] = len == 0.0f ? make_float4(r1.x, r1.y, r1.z, 1.0f) : make_float4(a.x / len, a.y / len, a.z / len, 1.0f);
+    }
+    filled[texel] = 1u;
+    if (record_plane)
+    {
+        record_plane[2 * (size_t)texel] = r0;
+        record_plane[2 * (size_t)texel + 1] = r1;
+    }
 }
