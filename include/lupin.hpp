@@ -624,6 +624,24 @@ inline uint64_t bake_lightmap(const Device &d, const Scene &scene, const Lightma
     return covered;
 }
 
+// directional lightmaps (no reference counterpart): bake_lightmap's texels, records and paths, resolved into the
+// four L0 / L1 coefficient planes of the cosine-weighted incident radiance that render_lightmapped_directional shades normal
+// maps from.  out_sh: 4 x height x width x 4 floats, plane j first; out_records: nullptr or height x width x 8; returns the
+// number of owned texels.
+inline uint64_t bake_lightmap_directional(const Device &d, const Scene &scene, const LightmapDesc &desc, const LightmapChart *charts,
+                                          uint32_t num_charts, float *out_sh, float *out_records = nullptr)
+{
+    const LupinLightmapDesc c{desc.width, desc.height, (uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.max_slots, desc.flags,
+                              desc.dilate, desc.counter, desc.surface_offset,
+                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
+    std::vector<LupinLightmapChart> cc(num_charts);
+    for (uint32_t k = 0; k < num_charts; k++)
+        cc[k] = LupinLightmapChart{charts[k].instance_idx, charts[k].scale_u, charts[k].scale_v, charts[k].offset_u, charts[k].offset_v};
+    uint64_t covered = 0;
+    check(lupin_hip_bake_lightmap_directional(d.raw(), scene.raw(), &c, cc.data(), num_charts, out_sh, out_records, &covered));
+    return covered;
+}
+
 // ambient-occlusion and bent-normal atlases (no reference counterpart): bake_lightmap's texels and records,
 // every owned texel queried by the bent-normal kernel up to max_distance
 struct LightmapAoDesc
@@ -963,6 +981,19 @@ inline void render_lightmapped(const Device &d, const Scene &scene, TextureRef r
     const LupinLightmappedViewDesc c{baked_view_desc_c(view), lightmap_width, lightmap_height, (uint32_t)charts.size(), 0u};
     check(lupin_hip_render_lightmapped(d.raw(), scene.raw(), render_target.raw(), &c, charts.empty() ? nullptr : charts.data(), lightmap, sh, depth, valid,
                                        out_gbuffer));
+}
+
+// ... with a directional lightmap: `directional` is bake_lightmap_directional's 4 x lightmap_height x
+// lightmap_width x 4 floats for the same atlas and charts, bake_flags that bake's flags; a lightmapped pixel's irradiance is
+// scaled by what its shading normal receives against what the bake normal did.  out_gbuffer: nullptr or W x H x 24 floats.
+inline void render_lightmapped_directional(const Device &d, const Scene &scene, TextureRef render_target, const BakedViewDesc &view,
+                                           const std::vector<LupinLightmapChart> &charts, const float *lightmap, const float *directional,
+                                           uint32_t lightmap_width, uint32_t lightmap_height, uint32_t bake_flags = 0, const float *sh = nullptr,
+                                           const float *depth = nullptr, const uint8_t *valid = nullptr, float *out_gbuffer = nullptr)
+{
+    const LupinLightmappedDirectionalDesc c{{baked_view_desc_c(view), lightmap_width, lightmap_height, (uint32_t)charts.size(), 0u}, bake_flags, {0u, 0u, 0u}};
+    check(lupin_hip_render_lightmapped_directional(d.raw(), scene.raw(), render_target.raw(), &c, charts.empty() ? nullptr : charts.data(), lightmap,
+                                                   directional, sh, depth, valid, out_gbuffer));
 }
 
 }  // namespace lp

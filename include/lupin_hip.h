@@ -990,6 +990,41 @@ int lupin_hip_bake_lightmap_ao(LupinContext *ctx, const LupinScene *scene, const
                                float *out_bent /* NULL, or H*W*4 */, float *out_records /* NULL, or H*W*8 */,
                                uint64_t *out_num_covered /* NULL ok */);
 
+/* ---- directional lightmaps (no reference counterpart) ----
+ * lupin_hip_bake_lightmap with four coefficient planes in place of one irradiance plane, so that the lightmapped view can
+ * shade a normal map (lupin_hip_render_lightmapped_directional).  Rasterisation, ownership, record emission, out_records and
+ * out_num_covered are lupin_hip_bake_lightmap's, word for word, for the same charts, flags (LUPIN_LIGHTMAP_SMOOTH_NORMALS),
+ * counter and surface_offset: the same kernels run.  The owned texels' records run through the radiance query's wavefront
+ * with `samples` paths each, exactly as lupin_hip_pathtrace_rays runs mode-1 records (pathtrace_type, max_bounces, max_slots
+ * and advanced are the query's).  The resolve is this one, per record, with d_s the FIRST direction of slot s (what the
+ * query reports in out_rays) and L_s the slot's clamped path radiance (what the query with samples == 1 would return for it):
+ *
+ *   Y0 = 0.28209479f;  Y1 = 0.48860251f * d.y;  Y2 = 0.48860251f * d.z;  Y3 = 0.48860251f * d.x   (the first four values of
+ *   lupin_hip_bake_probes' basis, its literals).  Lane l = 0..63 takes slots s = l, l + 64, ... in ascending order and adds,
+ *   from +0.0f, acc[j][c] += L_s[c] * Yj(d_s) for j = 0..3 and c in r, g, b (the product rounded, then the sum).  The 64 lanes'
+ *   accumulators are added by an xor butterfly over lane offsets 32, 16, 8, 4, 2, 1: at each offset every lane's value becomes
+ *   its own plus that of lane ^ offset.  Coefficient j, channel c = (acc[j][c] * 3.14159265f) / (float)samples, with w = 1.0f.
+ *   Every operation is one rounded f32 operation without contraction.  A record is never split between waves or launches:
+ *   the words do not depend on max_slots.
+ *
+ * Coefficient j estimates the integral of L(w) (w . n)+ Yj(w) over the sphere, the L1 projection of the cosine-weighted
+ * incident radiance: coefficient 0 / 0.28209479 is lupin_hip_bake_lightmap's irradiance (the same terms, summed in another
+ * order), coefficients 1..3 / 0.48860251 are that irradiance times its mean direction's y, z, x.
+ *
+ * out_sh (LUPIN_LIGHTMAP_DIRECTIONAL_PLANES x H x W x 4, host; plane j first): on owned texels coefficient j's rgb and alpha
+ * 1.0f, zeros elsewhere; then `dilate` gutter passes of lupin_hip_bake_lightmap's on each plane (gutter alpha stays 0).
+ * Alpha is ownership in every plane, so each is a valid input to lupin_hip_denoise_lightmap.  Intermediates stay on the
+ * device.
+ *
+ * Ordering, refusals (LUPIN_ERR_INVALID_ARGUMENT with the outputs untouched; out_records and out_num_covered may be NULL),
+ * the atlas without an owned texel (LUPIN_OK, all zeros) and LUPIN_ERR_NO_DEVICE are lupin_hip_bake_lightmap's.
+ * LUPIN_ERR_OUT_OF_MEMORY, outputs untouched, when the planes (64 bytes per texel, twice that with gutter passes) cannot be
+ * allocated. */
+#define LUPIN_LIGHTMAP_DIRECTIONAL_PLANES 4
+int lupin_hip_bake_lightmap_directional(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc,
+                                        const LupinLightmapChart *charts, uint32_t num_charts, float *out_sh /* 4*H*W*4 */,
+                                        float *out_records /* NULL, or H*W*8 */, uint64_t *out_num_covered /* NULL ok */);
+
 /* ---- lightmap denoising (no reference counterpart) ----
  * An edge-avoiding a-trous filter in atlas space for what lupin_hip_bake_lightmap writes: `rgba` is its out_rgba (or several
  * bakes with different `counter`, averaged by the caller), `records` its out_records.  No scene is needed.  Texel p is
@@ -1606,6 +1641,59 @@ int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, Lup
                                  const float *lightmap /* H x W x 4: bake_lightmap's or denoise_lightmap's out_rgba */,
                                  const float *sh /* NULL: no volume */, const float *depth, const uint8_t *valid,
                                  float *out_gbuffer /* NULL or Wimg x Himg x 20 */);
+
+/* ---- lightmapped view with a directional lightmap (no reference counterpart) ----
+ * lupin_hip_render_lightmapped with one more input: `directional`, the four coefficient planes of
+ * lupin_hip_bake_lightmap_directional (LUPIN_LIGHTMAP_DIRECTIONAL_PLANES x H x W x 4 floats, plane j first, for the same atlas
+ * and charts as `lightmap`), and desc.bake_flags, the flags that bake was given (0 or LUPIN_LIGHTMAP_SMOOTH_NORMALS).  On a
+ * charted surface the scalar lightmap's E is scaled by how much more or less light the pixel's shading normal (a normal map, a
+ * smooth-shaded mesh) receives than the bake normal did, so the atlas responds to normal detail.  desc.base is
+ * lupin_hip_render_lightmapped's descriptor and steps 1 to 9 are that function's, bit for bit.  Between steps 7 and 9, for a
+ * pixel whose source is LUPIN_LIGHTMAPPED_SOURCE_LIGHTMAP, every operation one rounded f32 operation in the order written:
+ *
+ * 7a. C0..C3 (rgb each) are step 7's fetch from the four planes: the same four taps in tap order, the same weights, the same
+ *     cov, and OWNED still means that the tap's alpha in `lightmap` (not in the plane) != 0.  If cov > 0, Cj = (the sum over
+ *     the owned taps of weight * plane j's rgb) / cov, otherwise the sum over all four taps.
+ * 7b. n' = step 4's turned shading normal n.  n_b = the bake normal at the hit: what lupin_hip_bake_lightmap writes into the
+ *     record of a texel whose centre maps to (instance, tri, u, v) under bake_flags (the geometric normal g; with
+ *     SMOOTH_NORMALS on a mesh with normals the interpolated vertex normal in world space, negated if it points away from g).
+ *     With k0 = 0.28209479f, k1 = 0.48860251f, per channel:
+ *       num = ((C0 * k0 + C1 * (k1 * n'.y)) + C2 * (k1 * n'.z)) + C3 * (k1 * n'.x)
+ *       den = ((C0 * k0 + C1 * (k1 * n_b.y)) + C2 * (k1 * n_b.z)) + C3 * (k1 * n_b.x)
+ * 7c. r = 1.0f when the ray meets the triangle's back face, (d.x * g.x + d.y * g.y) + d.z * g.z > 0 with g as
+ *     lupin_hip_surface_probe's LUPIN_SURFACE_NORMAL reports it at [3..5] (the bake lit the other side); or when den <= 0; or
+ *     when num or den is not finite.  Otherwise r = max(num, 0) / den, the maximum being (num > 0 ? num : +0.0f).
+ *     E = E * r per channel, and step 9 follows.
+ *
+ * With n' == n_b num and den are the same operations on the same numbers, so r == 1.0f and the picture is
+ * lupin_hip_render_lightmapped's.  For planes baked from non-negative radiance 0 <= r <= 4 up to rounding and Monte Carlo
+ * noise of the fetch: num and den are the radiance integrated against (1 + 3 w . n') / (4 pi) and (1 + 3 w . n_b) / (4 pi)
+ * times (w . n_b)+, and on the hemisphere about n_b the first weight lies in [-2, 4] / (4 pi), the second in [1, 4] / (4 pi).
+ *
+ * out_gbuffer is NULL or W x H x LUPIN_LIGHTMAPPED_DIRECTIONAL_GBUFFER_FLOATS floats: [0..19] are
+ * lupin_hip_render_lightmapped's;  [20..22] r per channel, 1.0f wherever no ratio was applied (every pixel that is not
+ * LIGHTMAP among them);  [23] bits: LUPIN_LIGHTMAPPED_DIRECTIONAL_APPLIED (r = max(num, 0) / den was taken in at least one
+ * channel), _BACK_FACE, _DEN_NOT_POSITIVE (den <= 0 in at least one channel of a front-face pixel), _NOT_FINITE (num or den
+ * not finite in at least one channel of a front-face pixel); 0 where the source is not LIGHTMAP.
+ *
+ * Launches, ordering, host arrays and LUPIN_BAKED_VIEW_DEVICE_POINTERS (in desc.base.view.flags; `directional` is then device
+ * memory, 16-byte aligned) are lupin_hip_render_lightmapped's.  LUPIN_ERR_INVALID_ARGUMENT, nothing launched, the target and
+ * out_gbuffer untouched, for everything lupin_hip_render_lightmapped refuses and: a NULL directional; a bake_flags bit other
+ * than LUPIN_LIGHTMAP_SMOOTH_NORMALS; a misaligned device directional; a non-zero reserved word. */
+#define LUPIN_LIGHTMAPPED_DIRECTIONAL_GBUFFER_FLOATS 24
+enum { LUPIN_LIGHTMAPPED_DIRECTIONAL_APPLIED = 1u, LUPIN_LIGHTMAPPED_DIRECTIONAL_BACK_FACE = 2u,
+       LUPIN_LIGHTMAPPED_DIRECTIONAL_DEN_NOT_POSITIVE = 4u, LUPIN_LIGHTMAPPED_DIRECTIONAL_NOT_FINITE = 8u };
+typedef struct LupinLightmappedDirectionalDesc {
+    LupinLightmappedViewDesc base;
+    uint32_t bake_flags;          /* the directional bake's desc.flags: 0 or LUPIN_LIGHTMAP_SMOOTH_NORMALS */
+    uint32_t reserved[3];         /* must be 0 */
+} LupinLightmappedDirectionalDesc;
+int lupin_hip_render_lightmapped_directional(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target,
+                                             const LupinLightmappedDirectionalDesc *desc,
+                                             const LupinLightmapChart *charts /* num_charts, host */,
+                                             const float *lightmap /* H x W x 4 */, const float *directional /* 4 x H x W x 4 */,
+                                             const float *sh /* NULL: no volume */, const float *depth, const uint8_t *valid,
+                                             float *out_gbuffer /* NULL or Wimg x Himg x 24 */);
 
 /* tonemapping.rs:106-132  TonemapDesc (+ Viewport :144-151) */
 typedef struct LupinTonemapDesc

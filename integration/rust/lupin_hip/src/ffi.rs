@@ -172,6 +172,16 @@ pub const LUPIN_LIGHTMAPPED_SOURCE_AMBIENT: u32 = 3;
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmappedViewDesc {
     pub view: LupinBakedViewDesc, pub lightmap_width: u32, pub lightmap_height: u32, pub num_charts: u32, pub reserved: u32,
 }
+// directional lightmaps and their view (no reference counterpart)
+pub const LUPIN_LIGHTMAP_DIRECTIONAL_PLANES: usize = 4;
+pub const LUPIN_LIGHTMAPPED_DIRECTIONAL_GBUFFER_FLOATS: usize = 24;
+pub const LUPIN_LIGHTMAPPED_DIRECTIONAL_APPLIED: u32 = 1;
+pub const LUPIN_LIGHTMAPPED_DIRECTIONAL_BACK_FACE: u32 = 2;
+pub const LUPIN_LIGHTMAPPED_DIRECTIONAL_DEN_NOT_POSITIVE: u32 = 4;
+pub const LUPIN_LIGHTMAPPED_DIRECTIONAL_NOT_FINITE: u32 = 8;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmappedDirectionalDesc {
+    pub base: LupinLightmappedViewDesc, pub bake_flags: u32, pub reserved: [u32; 3],
+}
 
 extern "C" {
     pub fn lupin_hip_last_error() -> *const c_char;
@@ -297,6 +307,15 @@ extern "C" {
     pub fn lupin_hip_render_lightmapped(ctx: *mut LupinContext, scene: *const LupinScene, render_target: *mut LupinTexture,
                                         desc: *const LupinLightmappedViewDesc, charts: *const LupinLightmapChart, lightmap: *const f32, sh: *const f32,
                                         depth: *const f32, valid: *const u8, out_gbuffer: *mut f32) -> c_int;
+    // directional lightmap: out_sh 4 x height x width x 4 f32 (plane j first), out_records null or height x width x 8, out_num_covered null ok
+    pub fn lupin_hip_bake_lightmap_directional(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinLightmapDesc,
+                                               charts: *const LupinLightmapChart, num_charts: u32, out_sh: *mut f32, out_records: *mut f32,
+                                               out_num_covered: *mut u64) -> c_int;
+    // ... and the lightmapped view that shades from it: directional 4 x height x width x 4 f32, out_gbuffer null or W x H x 24
+    pub fn lupin_hip_render_lightmapped_directional(ctx: *mut LupinContext, scene: *const LupinScene, render_target: *mut LupinTexture,
+                                                    desc: *const LupinLightmappedDirectionalDesc, charts: *const LupinLightmapChart,
+                                                    lightmap: *const f32, directional: *const f32, sh: *const f32, depth: *const f32,
+                                                    valid: *const u8, out_gbuffer: *mut f32) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

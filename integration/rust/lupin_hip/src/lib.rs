@@ -446,3 +446,37 @@ pub fn render_lightmapped(device: &Device, scene: &Scene, target: &Texture, came
                                                 lightmap.as_ptr(), std::ptr::null(), std::ptr::null(), std::ptr::null(), gbuffer.as_mut_ptr()) });
     gbuffer
 }
+
+// ---- directional lightmaps (no reference counterpart) ----
+/// `lupin_hip_bake_lightmap`'s texels, records and paths, resolved into four L0 / L1 coefficient planes of the cosine-weighted
+/// incident radiance: 4 x `desc.height` x `desc.width` x 4 floats, plane j first, alpha = ownership in every plane.
+pub fn bake_lightmap_directional(device: &Device, scene: &Scene, desc: &LupinLightmapDesc, charts: &[LupinLightmapChart]) -> Vec<f32> {
+    let texels = desc.width as usize * desc.height as usize;
+    let mut planes = vec![0f32; LUPIN_LIGHTMAP_DIRECTIONAL_PLANES * texels * 4];
+    check(unsafe { lupin_hip_bake_lightmap_directional(device.raw, scene.raw, desc, charts.as_ptr(), charts.len() as u32, planes.as_mut_ptr(),
+                                                       std::ptr::null_mut(), std::ptr::null_mut()) });
+    planes
+}
+
+/// `render_lightmapped` with `directional`, the planes `bake_lightmap_directional` returned for the same atlas and charts, and
+/// `bake_flags`, that bake's flags: a lightmapped pixel's irradiance is scaled by what its shading normal receives against what
+/// the bake normal did, so normal maps show.  Returns the G-buffer, width x height x 24 floats (`render_lightmapped`'s 20,
+/// then the ratio per channel and the `LUPIN_LIGHTMAPPED_DIRECTIONAL_*` bits).
+#[allow(clippy::too_many_arguments)]
+pub fn render_lightmapped_directional(device: &Device, scene: &Scene, target: &Texture, camera_params: LupinCameraParams,
+                                      camera_transform: LupinMat3x4, charts: &[LupinLightmapChart], lightmap: &[f32], directional: &[f32],
+                                      lightmap_width: u32, lightmap_height: u32, bake_flags: u32, ambient: [f32; 3], ray_epsilon: f32) -> Vec<f32> {
+    let texels = lightmap_width as usize * lightmap_height as usize;
+    assert!(lightmap.len() == texels * 4 && directional.len() == LUPIN_LIGHTMAP_DIRECTIONAL_PLANES * texels * 4);
+    let (width, height) = unsafe { (lupin_hip_texture_width(target.raw) as usize, lupin_hip_texture_height(target.raw) as usize) };
+    let mut gbuffer = vec![0f32; width * height * LUPIN_LIGHTMAPPED_DIRECTIONAL_GBUFFER_FLOATS];
+    let grid = LupinProbeGridDesc { origin: [0.0; 3], spacing: [0.0; 3], dims: [0; 3], flags: 0, ray_epsilon: 0.0, normal_bias: 0.0 };
+    let view = LupinBakedViewDesc { camera_params, camera_transform, grid, resolution: 0, max_distance: 0.0, ray_epsilon, ambient, flags: 0, max_slots: 0 };
+    let base = LupinLightmappedViewDesc { view, lightmap_width, lightmap_height, num_charts: charts.len() as u32, reserved: 0 };
+    let c = LupinLightmappedDirectionalDesc { base, bake_flags, reserved: [0; 3] };
+    check(unsafe { lupin_hip_render_lightmapped_directional(device.raw, scene.raw, target.raw, &c,
+                                                            if charts.is_empty() { std::ptr::null() } else { charts.as_ptr() }, lightmap.as_ptr(),
+                                                            directional.as_ptr(), std::ptr::null(), std::ptr::null(), std::ptr::null(),
+                                                            gbuffer.as_mut_ptr()) });
+    gbuffer
+}

@@ -222,6 +222,10 @@ class LightmappedViewDescC(C.Structure):   # LupinLightmappedViewDesc
                 ("reserved", C.c_uint32)]
 
 
+class LightmappedDirectionalDescC(C.Structure):   # LupinLightmappedDirectionalDesc
+    _fields_ = [("base", LightmappedViewDescC), ("bake_flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class TlasBuildStatsC(C.Structure):   # LupinTlasBuildStats
     _fields_ = [("num_instances", C.c_uint32), ("state_in_lds", C.c_uint32), ("scans", C.c_uint64), ("kernel_ms", C.c_float)]
 
@@ -302,6 +306,7 @@ SYMBOLS = [
     ("lupin_hip_transmittance_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),
     ("lupin_hip_bent_normal_rays", C.c_int, [_P, _P, C.POINTER(BentNormalDescC), C.c_uint64, _P, _P]),
     ("lupin_hip_bake_lightmap_ao", C.c_int, [_P, _P, C.POINTER(LightmapAoDescC), C.POINTER(LightmapChartC), _U32, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    ("lupin_hip_bake_lightmap_directional", C.c_int, [_P, _P, C.POINTER(LightmapDescC), C.POINTER(LightmapChartC), _U32, _P, _P, C.POINTER(C.c_uint64)]),
     ("lupin_hip_distance_points", C.c_int, [_P, _P, _U32, C.c_uint64, _P, _P]),
     ("lupin_hip_bake_distance_grid", C.c_int, [_P, _P, _U32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_float, _P]),
     ("lupin_hip_sample_probe_grid", C.c_int, [_P, _P, C.POINTER(ProbeGridDescC), _P, _P, C.c_uint64, _P, _P]),
@@ -309,6 +314,8 @@ SYMBOLS = [
     ("lupin_hip_sample_probe_grid_depth", C.c_int, [_P, _P, C.POINTER(ProbeGridDepthDescC), _P, _P, _P, C.c_uint64, _P, _P]),
     ("lupin_hip_render_baked", C.c_int, [_P, _P, _P, C.POINTER(BakedViewDescC), _P, _P, _P, _P]),
     ("lupin_hip_render_lightmapped", C.c_int, [_P, _P, _P, C.POINTER(LightmappedViewDescC), C.POINTER(LightmapChartC), _P, _P, _P, _P, _P]),
+    ("lupin_hip_render_lightmapped_directional", C.c_int,
+     [_P, _P, _P, C.POINTER(LightmappedDirectionalDescC), C.POINTER(LightmapChartC), _P, _P, _P, _P, _P, _P]),
     ("lupin_hip_tonemap_and_fit_aspect", C.c_int, [_P, _P, _P, _U32, _U32, C.POINTER(TonemapDescC)]),
     ("lupin_hip_build_denoise_resources", C.c_int, [_P, _U32, _U32, _PP]),
     ("lupin_hip_destroy_denoise_resources", None, [_P]),

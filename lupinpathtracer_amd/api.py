@@ -1889,6 +1889,60 @@ def bake_lightmap_ao(ctx, scene, charts, width, height, samples=64, max_distance
     return out if len(out) > 1 else ao
 
 
+# ---- directional lightmaps: lupin_hip_bake_lightmap_directional (include/lupin_hip.h) ----
+LIGHTMAP_DIRECTIONAL_PLANES = 4
+SH_K0, SH_K1 = np.float32(0.28209479), np.float32(0.48860251)   # the header's literals for Y0 and Y1..Y3
+
+
+def bake_lightmap_directional(ctx, scene, charts, width, height, samples=64, pathtrace_type=PathtraceType.Standard, max_bounces=8, advanced=None,
+                              counter=0, max_slots=0, smooth_normals=False, dilate=0, surface_offset=None, want_records=False):
+    """A directional lightmap in bake_lightmap's atlas: (4, height, width, 4) float32, plane j the L0 / L1 coefficient j
+    (basis 1, y, z, x with sh_basis' normalisation) of the cosine-weighted incident radiance under each texel centre, rgb,
+    with alpha 1 on rasterised texels and 0 elsewhere (gutter texels filled by `dilate` passes keep alpha 0).  Plane 0 / SH_K0
+    is bake_lightmap's irradiance (the same paths, summed in another order); planes 1..3 / SH_K1 are that irradiance times
+    the y, z, x of its mean direction.  Every argument is bake_lightmap's: the same texels, the same records, the same paths.
+    render_lightmapped(..., directional=planes, bake_flags=...) shades normal maps from it.  With want_records also the
+    (height, width, 8) records.  Blocks until the result is complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_lightmap_directional needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if surface_offset is None:
+        surface_offset = LIGHTMAP_OFFSET_FRACTION * (scene_world_extent(scene) or 1.0)
+    adv = advanced or AdvancedParams()
+    items = [c if isinstance(c, LightmapChart) else LightmapChart(*c) for c in charts]
+    c_charts = (_abi.LightmapChartC * max(1, len(items)))(*[_abi.LightmapChartC(int(c.instance_idx), c.scale_u, c.scale_v, c.offset_u, c.offset_v)
+                                                           for c in items])
+    d = _abi.LightmapDescC(int(width), int(height), int(pathtrace_type), int(max_bounces), int(samples), int(max_slots),
+                           LIGHTMAP_SMOOTH_NORMALS if smooth_normals else 0, int(dilate), int(counter), float(surface_offset),
+                           _abi.AdvancedParamsC(adv.max_radiance, adv.rng_seed, adv.ray_epsilon))
+    shape_ok = 0 < int(width) <= LIGHTMAP_MAX_SIZE and 0 < int(height) <= LIGHTMAP_MAX_SIZE
+    hw = (int(height), int(width)) if shape_ok else (1, 1)      # a refused size: the library says so
+    out = np.zeros((LIGHTMAP_DIRECTIONAL_PLANES,) + hw + (4,), np.float32)
+    rec = np.zeros(hw + (RAY_RECORD_FLOATS,), np.float32) if want_records else None
+    check(lib().lupin_hip_bake_lightmap_directional(ctx.handle, scene.handle, C.byref(d), c_charts, len(items), ptr(out), ptr(rec), None))
+    return (out, rec) if want_records else out
+
+
+def lightmap_directional_ratio(coeffs, n_shade, n_bake):
+    """The factor render_lightmapped(..., directional=...) scales a lightmapped pixel's irradiance by, in numpy float32 and in
+    the header's order of operations: `coeffs` (..., 4, 3 or 4) the fetched coefficients C0..C3 (only r, g, b are read),
+    `n_shade` (..., 3) the pixel's shading normal n', `n_bake` (..., 3) the bake normal n_b.  Per channel
+    num = ((C0 k0 + C1 (k1 n'.y)) + C2 (k1 n'.z)) + C3 (k1 n'.x), den the same with n_b; the ratio is max(num, 0) / den, and
+    1 where den <= 0 or either is not finite.  (..., 3) float32; 0 <= ratio <= 4 for coefficients of non-negative radiance,
+    and exactly 1 where n_shade == n_bake.  (The view also returns 1 on a back face, which only it can see.)"""
+    c = np.asarray(coeffs, np.float32)[..., :3]
+    one = np.float32(1.0)
+
+    def project(n):
+        n = np.asarray(n, np.float32)
+        y1, y2, y3 = (SH_K1 * n[..., 1])[..., None], (SH_K1 * n[..., 2])[..., None], (SH_K1 * n[..., 0])[..., None]
+        return ((c[..., 0, :] * SH_K0 + c[..., 1, :] * y1) + c[..., 2, :] * y2) + c[..., 3, :] * y3
+
+    with np.errstate(all="ignore"):
+        num, den = project(n_shade), project(n_bake)
+        ok = np.isfinite(num) & np.isfinite(den) & ~(den <= 0)
+        return np.where(ok, np.where(num > 0, num, np.float32(0.0)) / np.where(ok, den, one), one).astype(np.float32)
+
+
 # ---- distance queries: lupin_hip_distance_points, lupin_hip_bake_distance_grid (include/lupin_hip.h, DESIGN.md 20) ----
 DISTANCE_RECORD_FLOATS = 4
 DISTANCE_RESULT_FLOATS = 12
@@ -2300,11 +2354,14 @@ def _baked_view_gbuffer(render_target, floats, want_gbuffer, tensor):
 # ---- lightmapped view: lupin_hip_render_lightmapped (include/lupin_hip.h) ----
 LIGHTMAPPED_VIEW_GBUFFER_FLOATS = 20
 LIGHTMAPPED_SOURCE_MISS, LIGHTMAPPED_SOURCE_LIGHTMAP, LIGHTMAPPED_SOURCE_PROBES, LIGHTMAPPED_SOURCE_AMBIENT = 0, 1, 2, 3
+LIGHTMAPPED_DIRECTIONAL_GBUFFER_FLOATS = 24   # lupin_hip_render_lightmapped_directional
+LIGHTMAPPED_DIRECTIONAL_APPLIED, LIGHTMAPPED_DIRECTIONAL_BACK_FACE = 1, 2
+LIGHTMAPPED_DIRECTIONAL_DEN_NOT_POSITIVE, LIGHTMAPPED_DIRECTIONAL_NOT_FINITE = 4, 8
 
 
 def render_lightmapped(ctx, scene, render_target, camera_params, camera_transform, charts, lightmap, *, origin=None, spacing=None, dims=None, sh=None,
                        depth=None, max_distance=None, valid=None, ambient=(0.0, 0.0, 0.0), visibility=False, backface=True, ray_epsilon=0.001,
-                       normal_bias=None, want_gbuffer=False, max_slots=0):
+                       normal_bias=None, want_gbuffer=False, max_slots=0, directional=None, bake_flags=0):
     """A camera view of baked lighting into `render_target`: render_baked with a lightmap as the irradiance source wherever
     the hit instance has a chart, and the irradiance volume (or `ambient`) as the fallback.  `charts` are the LightmapChart
     items the atlas was baked with and `lightmap` is the (height, width, 4) float32 atlas bake_lightmap or denoise_lightmap
@@ -2315,7 +2372,13 @@ def render_lightmapped(ctx, scene, render_target, camera_params, camera_transfor
     `lightmap` is a contiguous float32 tensor on the context's device, and so is `sh` if given.  With want_gbuffer the
     (H, W, 20) float32 G-buffer is returned: render_baked's 16 words ([11]: the owned coverage on a lightmapped pixel, the
     lookup's w on a probe pixel), then the atlas coordinate x, y in texels, the chart index bits (BAKED_VIEW_MISS: none) and
-    the LIGHTMAPPED_SOURCE_* bits.  The picture does not depend on `max_slots`.  Blocks until complete."""
+    the LIGHTMAPPED_SOURCE_* bits.  The picture does not depend on `max_slots`.  Blocks until complete.
+    With `directional`, the (4, height, width, 4) planes bake_lightmap_directional returned for the same atlas and charts (a
+    tensor where `lightmap` is one), and `bake_flags`, that bake's flags (0, or LIGHTMAP_SMOOTH_NORMALS for smooth_normals=True),
+    a lightmapped pixel's E is scaled per channel by lightmap_directional_ratio(fetched coefficients, the pixel's shading
+    normal, the bake normal at the hit), so normal maps and smooth-shaded meshes show in the baked view; a pixel seen from
+    its back face is not scaled.  The G-buffer then has 24 words: [20..22] the ratio (1 where none was applied) and [23] the
+    LIGHTMAPPED_DIRECTIONAL_* bits.  Without `directional` the call and its picture are what they were."""
     if sh is not None and (origin is None or spacing is None or dims is None):
         raise ValueError("a volume comes with its origin, spacing and dims")
     c, tensors, p_sh, p_depth, p_valid = _baked_view_desc("render_lightmapped", ctx, scene, render_target, camera_params, camera_transform, origin, spacing,
@@ -2341,7 +2404,28 @@ def render_lightmapped(ctx, scene, render_target, camera_params, camera_transfor
         if lightmap.ndim != 3 or lightmap.shape[2] != 4:
             raise ValueError("lightmap must be (height, width, 4)")
         p_lm = ptr(lightmap)
-    gbuffer, gb = _baked_view_gbuffer(render_target, LIGHTMAPPED_VIEW_GBUFFER_FLOATS, want_gbuffer, lightmap if hasattr(lightmap, "data_ptr") else None)
     d = _abi.LightmappedViewDescC(c, int(lightmap.shape[1]), int(lightmap.shape[0]), len(items), 0)
-    check(lib().lupin_hip_render_lightmapped(ctx.handle, scene.handle, render_target.handle, C.byref(d), c_charts, p_lm, p_sh, p_depth, p_valid, gb))
+    if directional is None:
+        gbuffer, gb = _baked_view_gbuffer(render_target, LIGHTMAPPED_VIEW_GBUFFER_FLOATS, want_gbuffer, lightmap if hasattr(lightmap, "data_ptr") else None)
+        check(lib().lupin_hip_render_lightmapped(ctx.handle, scene.handle, render_target.handle, C.byref(d), c_charts, p_lm, p_sh, p_depth, p_valid, gb))
+        return gbuffer
+    planes = (LIGHTMAP_DIRECTIONAL_PLANES,) + tuple(int(k) for k in lightmap.shape)
+    if hasattr(lightmap, "data_ptr"):
+        import torch
+        if not (hasattr(directional, "data_ptr") and directional.is_cuda and directional.dtype == torch.float32 and directional.is_contiguous()
+                and tuple(directional.shape) == planes and directional.device == lightmap.device):
+            raise ValueError("directional must be a contiguous (4, height, width, 4) float32 tensor beside lightmap")
+        p_dir = C.c_void_p(directional.data_ptr())
+    else:
+        if hasattr(directional, "data_ptr"):
+            raise ValueError("lightmap and directional must both be torch tensors, or neither")
+        directional = np.ascontiguousarray(directional, np.float32)
+        if directional.shape != planes:
+            raise ValueError("directional must be (4, height, width, 4), the lightmap's atlas four times")
+        p_dir = ptr(directional)
+    gbuffer, gb = _baked_view_gbuffer(render_target, LIGHTMAPPED_DIRECTIONAL_GBUFFER_FLOATS, want_gbuffer,
+                                      lightmap if hasattr(lightmap, "data_ptr") else None)
+    dd = _abi.LightmappedDirectionalDescC(d, int(bake_flags), (C.c_uint32 * 3)(0, 0, 0))
+    check(lib().lupin_hip_render_lightmapped_directional(ctx.handle, scene.handle, render_target.handle, C.byref(dd), c_charts, p_lm, p_dir, p_sh, p_depth,
+                                                         p_valid, gb))
     return gbuffer

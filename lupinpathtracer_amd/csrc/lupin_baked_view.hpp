@@ -42,13 +42,20 @@ struct BakedPrimary
     bool hit;
 };
 
+// Step 1 of the contract: the centre ray of pixel `pixel` (y * W + x).  baked_primary traces it; the directional lightmapped
+// view asks for it again where it needs the direction.
+LP_DEV void baked_primary_ray(const FrameParams &fp, unsigned long long pixel, f3 &o, f3 &d)
+{
+    const uint32_t gy = (uint32_t)(pixel / fp.width), gx = (uint32_t)(pixel - (unsigned long long)gy * fp.width);
+    camera_ray_centre(fp, gx, gy, o, d);
+}
+
 // Steps 1 to 4 of the contract for pixel first + slot; the lane has passed make_geo's barrier.
 template <typename Geo>
 LP_DEV BakedPrimary baked_primary(const Geo &geo, const SceneDev &sc, const FrameParams &fp, uint32_t *lds_stack, unsigned long long pixel, float eps)
 {
-    const uint32_t gy = (uint32_t)(pixel / fp.width), gx = (uint32_t)(pixel - (unsigned long long)gy * fp.width);
     f3 o, d;
-    camera_ray_centre(fp, gx, gy, o, d);
+    baked_primary_ray(fp, pixel, o, d);
     const Closest c = scene_closest(geo, sc, lds_stack, o, d, eps);
     BakedPrimary r;
     r.hit = c.t != LP_F32_MAX;

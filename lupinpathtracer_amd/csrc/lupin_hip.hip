@@ -31,6 +31,7 @@
 #include "lupin_rays.hpp"
 #include "lupin_probes.hpp"
 #include "lupin_lightmap.hpp"
+#include "lupin_lightmap_directional.hpp"
 #include "lupin_lightmap_denoise.hpp"
 #include "lupin_occlusion.hpp"
 #include "lupin_transmittance.hpp"
@@ -3596,12 +3597,15 @@ int lupin_hip_render_baked(LupinContext *ctx, const LupinScene *scene, LupinText
 
 // ---- lightmapped view (no reference counterpart; kernels: lupin_lightmapped_view.hpp) ----
 
-int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target, const LupinLightmappedViewDesc *desc,
-                                 const LupinLightmapChart *charts, const float *lightmap, const float *sh, const float *depth, const uint8_t *valid,
-                                 float *out_gbuffer)
+// Both entry points of the view.  dd == NULL: lupin_hip_render_lightmapped (`directional` is not looked at); otherwise the
+// directional variant, whose desc (dd->base) `desc` is.
+static int render_lightmapped(const char *who, LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target, const LupinLightmappedViewDesc *desc,
+                              const LupinLightmappedDirectionalDesc *dd, const LupinLightmapChart *charts, const float *lightmap, const float *directional,
+                              const float *sh, const float *depth, const uint8_t *valid, float *out_gbuffer)
 {
-    if (int rc = query_refuse(ctx, scene, render_target && desc && lightmap)) return rc;
+    if (int rc = query_refuse(ctx, scene, render_target && desc && lightmap && (!dd || directional))) return rc;
     const LupinBakedViewDesc *view = &desc->view;
+    const uint32_t gbuffer_floats = dd ? LUPIN_LIGHTMAPPED_DIRECTIONAL_GBUFFER_FLOATS : LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS;
     uint64_t probes;
     if (int rc = baked_view_refuse(ctx, render_target, view, sh != nullptr, depth, &probes)) return rc;
     if (!sh && (depth || valid)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "depth and valid belong to a volume: sh is NULL");
@@ -3609,6 +3613,11 @@ int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, Lup
     if (AW == 0 || AH == 0 || AW > LUPIN_LIGHTMAP_MAX_SIZE || AH > LUPIN_LIGHTMAP_MAX_SIZE)
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "lightmap_width and lightmap_height must be in [1, 16384]");
     if (desc->reserved != 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "reserved must be 0");
+    if (dd)
+    {
+        if (dd->bake_flags & ~(uint32_t)LUPIN_LIGHTMAP_SMOOTH_NORMALS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown bake_flags bit");
+        if (dd->reserved[0] | dd->reserved[1] | dd->reserved[2]) return fail(LUPIN_ERR_INVALID_ARGUMENT, "reserved must be 0");
+    }
     if (num_charts > 0 && !charts) return fail(LUPIN_ERR_INVALID_ARGUMENT, "charts is NULL with num_charts > 0");
     // the chart of an instance is the first that names it; a chart is refused as lupin_hip_bake_lightmap refuses it
     const uint32_t num_instances = (uint32_t)scene->host_instances.size();
@@ -3627,7 +3636,7 @@ int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, Lup
     }
     if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
     const bool on_device = (view->flags & LUPIN_BAKED_VIEW_DEVICE_POINTERS) != 0;
-    if (on_device && ((((uintptr_t)lightmap | (uintptr_t)sh | (uintptr_t)out_gbuffer) & 15u) || ((uintptr_t)depth & 7u)))
+    if (on_device && ((((uintptr_t)lightmap | (uintptr_t)sh | (uintptr_t)out_gbuffer | (dd ? (uintptr_t)directional : 0u)) & 15u) || ((uintptr_t)depth & 7u)))
         return fail(LUPIN_ERR_INVALID_ARGUMENT, "device lightmap, coefficients and G-buffer must be 16-byte aligned, device maps 8-byte aligned");
     const uint32_t W = render_target->width, H = render_target->height;
     const uint64_t pixels = (uint64_t)W * H;
@@ -3646,24 +3655,31 @@ int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, Lup
     const uint64_t max_slots = baked_view_launch_slots(view->max_slots, pixels);
     // scratch for one launch (the lookup's results only with a volume); the chart tables; host arrays: the atlas and the grid
     // whole, one launch's G-buffer.  All of it lives for the call.
-    DeviceBuffer b_rec, b_aux, b_lm, b_res, b_chart_of, b_charts, b_atlas, b_gbuf;
+    DeviceBuffer b_rec, b_aux, b_lm, b_res, b_chart_of, b_charts, b_atlas, b_gbuf, b_dir, b_planes;
     BakedVolume vol;
     HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, &b_rec));
     HIP_TRY(DeviceBuffer::make((size_t)max_slots * 32, &b_aux));
     HIP_TRY(DeviceBuffer::make((size_t)max_slots * 16, &b_lm));
+    if (dd) HIP_TRY(DeviceBuffer::make((size_t)max_slots * 32, &b_dir));
     if (sh) HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_PROBE_GRID_RESULT_FLOATS * 4, &b_res));
     HIP_TRY(DeviceBuffer::make(h_chart_of.size() * 4, &b_chart_of));
     HIP_TRY(DeviceBuffer::make(h_charts.size() * 16, &b_charts));
     HIP_TRY(hipMemcpyAsync(b_chart_of.get(), h_chart_of.data(), h_chart_of.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b_charts.get(), h_charts.data(), h_charts.size() * 16, hipMemcpyHostToDevice, st));
-    const float4 *d_atlas = reinterpret_cast<const float4 *>(lightmap);
+    const float4 *d_atlas = reinterpret_cast<const float4 *>(lightmap), *d_planes = reinterpret_cast<const float4 *>(directional);
     if (!on_device)
     {
         const size_t atlas_bytes = (size_t)AW * AH * 16;
         HIP_TRY(DeviceBuffer::make(atlas_bytes, &b_atlas));
         HIP_TRY(hipMemcpyAsync(b_atlas.get(), lightmap, atlas_bytes, hipMemcpyHostToDevice, st));
         d_atlas = b_atlas.as<float4>();
-        if (out_gbuffer) HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS * 4, &b_gbuf));
+        if (dd)
+        {
+            HIP_TRY(DeviceBuffer::make(atlas_bytes * LUPIN_LIGHTMAP_DIRECTIONAL_PLANES, &b_planes));
+            HIP_TRY(hipMemcpyAsync(b_planes.get(), directional, atlas_bytes * LUPIN_LIGHTMAP_DIRECTIONAL_PLANES, hipMemcpyHostToDevice, st));
+            d_planes = b_planes.as<float4>();
+        }
+        if (out_gbuffer) HIP_TRY(DeviceBuffer::make((size_t)max_slots * gbuffer_floats * 4, &b_gbuf));
     }
     if (sh)
         if (int rc = baked_volume_stage(st, on_device, probes, view->resolution, sh, depth, valid, &vol)) return rc;
@@ -3671,13 +3687,18 @@ int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, Lup
     for (uint64_t first = 0; first < pixels; first += max_slots)
     {
         const uint32_t slots = (uint32_t)std::min(max_slots, pixels - first);
-        float *dst = out_gbuffer ? out_gbuffer + first * LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS : nullptr;
+        float *dst = out_gbuffer ? out_gbuffer + first * gbuffer_floats : nullptr;
         float4 *d_gbuf = reinterpret_cast<float4 *>(out_gbuffer && !on_device ? b_gbuf.as<float>() : dst);
         const dim3 blocks((slots + LP_BLOCK - 1) / LP_BLOCK);
         with_bool(t.geo, [&](auto G) {
-            hipLaunchKernelGGL(k_lightmapped_gbuffer<decltype(G)::value>, blocks, dim3(LP_BLOCK), t.lds, st, scene->dev, fp, v, (unsigned long long)first, slots,
-                               view->ray_epsilon, b_chart_of.as<uint32_t>(), b_charts.as<float4>(), b_rec.as<float4>(), b_aux.as<float4>(), b_lm.as<float4>(),
-                               d_gbuf, t.stack_words);
+            if (dd)
+                hipLaunchKernelGGL(k_lightmapped_gbuffer_directional<decltype(G)::value>, blocks, dim3(LP_BLOCK), t.lds, st, scene->dev, fp, v,
+                                   (unsigned long long)first, slots, view->ray_epsilon, b_chart_of.as<uint32_t>(), b_charts.as<float4>(), b_rec.as<float4>(),
+                                   b_aux.as<float4>(), b_lm.as<float4>(), d_gbuf, t.stack_words, dd->bake_flags, b_dir.as<float4>());
+            else
+                hipLaunchKernelGGL(k_lightmapped_gbuffer<decltype(G)::value>, blocks, dim3(LP_BLOCK), t.lds, st, scene->dev, fp, v, (unsigned long long)first,
+                                   slots, view->ray_epsilon, b_chart_of.as<uint32_t>(), b_charts.as<float4>(), b_rec.as<float4>(), b_aux.as<float4>(),
+                                   b_lm.as<float4>(), d_gbuf, t.stack_words);
         });
         HIP_TRY(hipGetLastError());
         if (sh)
@@ -3685,16 +3706,37 @@ int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, Lup
             baked_view_lookup(scene, st, view, vol, vis, tl, slots, b_rec.as<float4>(), b_res.as<float4>());
             HIP_TRY(hipGetLastError());
         }
-        hipLaunchKernelGGL(k_lightmapped_compose, blocks, dim3(LP_BLOCK), 0, st, v, (unsigned long long)first, slots, b_aux.as<float4>(), b_lm.as<float4>(),
-                           b_res.as<float4>(), d_atlas, render_target->data, d_gbuf);
+        if (dd)
+            hipLaunchKernelGGL(k_lightmapped_compose_directional, blocks, dim3(LP_BLOCK), 0, st, v, (unsigned long long)first, slots, b_aux.as<float4>(),
+                               b_lm.as<float4>(), b_res.as<float4>(), d_atlas, render_target->data, d_gbuf, d_planes, b_dir.as<float4>());
+        else
+            hipLaunchKernelGGL(k_lightmapped_compose, blocks, dim3(LP_BLOCK), 0, st, v, (unsigned long long)first, slots, b_aux.as<float4>(),
+                               b_lm.as<float4>(), b_res.as<float4>(), d_atlas, render_target->data, d_gbuf);
         HIP_TRY(hipGetLastError());
         if (out_gbuffer && !on_device)
         {
-            HIP_TRY(hipMemcpyAsync(dst, d_gbuf, (size_t)slots * LUPIN_LIGHTMAPPED_VIEW_GBUFFER_FLOATS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(dst, d_gbuf, (size_t)slots * gbuffer_floats * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));   // (the next launch writes the same buffer; the copy is to pageable memory)
         }
     }
-    return query_end(ctx, "lupin_hip_render_lightmapped");
+    return query_end(ctx, who);
+}
+
+int lupin_hip_render_lightmapped(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target, const LupinLightmappedViewDesc *desc,
+                                 const LupinLightmapChart *charts, const float *lightmap, const float *sh, const float *depth, const uint8_t *valid,
+                                 float *out_gbuffer)
+{
+    return render_lightmapped("lupin_hip_render_lightmapped", ctx, scene, render_target, desc, nullptr, charts, lightmap, nullptr, sh, depth, valid,
+                              out_gbuffer);
+}
+
+// (kernels: the _directional variants of lupin_lightmapped_view.hpp)
+int lupin_hip_render_lightmapped_directional(LupinContext *ctx, const LupinScene *scene, LupinTexture *render_target,
+                                             const LupinLightmappedDirectionalDesc *desc, const LupinLightmapChart *charts, const float *lightmap,
+                                             const float *directional, const float *sh, const float *depth, const uint8_t *valid, float *out_gbuffer)
+{
+    return render_lightmapped("lupin_hip_render_lightmapped_directional", ctx, scene, render_target, desc ? &desc->base : nullptr, desc, charts, lightmap,
+                              directional, sh, depth, valid, out_gbuffer);
 }
 
 // ---- lightmap baking (no reference counterpart; kernels: lupin_lightmap.hpp) ----
@@ -3781,6 +3823,16 @@ static int lightmap_emit_records(const LupinScene *scene, hipStream_t st, const 
     return LUPIN_OK;
 }
 
+// What the radiance query refuses in a descriptor, refused by the two path-traced bakes as well: an atlas without an owned texel
+// never reaches the query.
+static int lightmap_refuse_query(const LupinLightmapDesc *desc)
+{
+    if (desc->pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
+    if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
+    if (desc->max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
+    return LUPIN_OK;
+}
+
 int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc, const LupinLightmapChart *charts,
                             uint32_t num_charts, float *out_rgba, float *out_records, uint64_t *out_num_covered)
 {
@@ -3788,10 +3840,7 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
     if (int rc = query_refuse(ctx, scene, desc && charts && out_rgba)) return rc;
     const uint32_t W = desc->width, H = desc->height;
     if (int rc = lightmap_refuse_atlas(W, H, num_charts, desc->flags & ~(uint32_t)LUPIN_LIGHTMAP_SMOOTH_NORMALS, desc->dilate, desc->surface_offset)) return rc;
-    // what the query refuses in a descriptor, here as well: an atlas without an owned texel never reaches the query
-    if (desc->pathtrace_type > LUPIN_PATHTRACE_DIRECT) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown pathtrace_type");
-    if (desc->samples == 0 || desc->samples > LP_RAYS_MAX_CHUNK_SLOTS) return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples must be in [1, 2^27]");
-    if (desc->max_bounces >= META_BOUNCE_MASK) return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_bounces must be < 4095");
+    if (int rc = lightmap_refuse_query(desc)) return rc;
     if (int rc = query_refuse_hierarchy(ctx, scene, true)) return rc;
     std::vector<LmChartDev> h_charts;
     uint64_t total_keys = 0;
@@ -3860,6 +3909,87 @@ int lupin_hip_bake_lightmap(LupinContext *ctx, const LupinScene *scene, const Lu
     stats.download_ms = ms_since(t0);
     if (out_num_covered) *out_num_covered = n;
     g_lightmap_stats = stats;
+    return LUPIN_OK;
+}
+
+// ---- directional lightmaps (kernels: lupin_lightmap_directional.hpp) ----
+
+int lupin_hip_bake_lightmap_directional(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc, const LupinLightmapChart *charts,
+                                        uint32_t num_charts, float *out_sh, float *out_records, uint64_t *out_num_covered)
+{
+    const char *who = "lupin_hip_bake_lightmap_directional";
+    if (int rc = query_refuse(ctx, scene, desc && charts && out_sh)) return rc;
+    const uint32_t W = desc->width, H = desc->height;
+    if (int rc = lightmap_refuse_atlas(W, H, num_charts, desc->flags & ~(uint32_t)LUPIN_LIGHTMAP_SMOOTH_NORMALS, desc->dilate, desc->surface_offset)) return rc;
+    if (int rc = lightmap_refuse_query(desc)) return rc;
+    if (int rc = query_refuse_hierarchy(ctx, scene, true)) return rc;
+    std::vector<LmChartDev> h_charts;
+    uint64_t total_keys = 0;
+    if (int rc = lightmap_host_charts(scene, charts, num_charts, &h_charts, &total_keys)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
+    hipStream_t st = ctx->lanes[0].stream;   // the primary stream, the query's own
+
+    const uint32_t texels = W * H;
+    const uint32_t texel_blocks = (texels + LP_BLOCK - 1) / LP_BLOCK;
+    const size_t plane_bytes = (size_t)texels * 16, planes_bytes = plane_bytes * LP_LM_SH;
+    // the planes before anything is launched: a refusal for want of memory leaves the outputs untouched and the device idle
+    DeviceBuffer d_planes[2], d_filled[2], d_plane;
+    const int sets = desc->dilate ? 2 : 1;
+    for (int k = 0; k < sets; k++)
+        if (DeviceBuffer::make(planes_bytes, &d_planes[k]) != hipSuccess || DeviceBuffer::make((size_t)texels, &d_filled[k]) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            return fail(LUPIN_ERR_OUT_OF_MEMORY, std::string(who) + ": no device memory for the coefficient planes");
+        }
+    uint32_t n = 0;
+    DeviceBuffer d_rec, d_texel, d_coef;
+    float raster_ms, compact_ms;
+    if (int rc = lightmap_emit_records(scene, st, who, W, H, h_charts, total_keys, desc->flags, desc->counter, desc->surface_offset, &n, &d_rec, &d_texel,
+                                       &raster_ms, &compact_ms))
+        return rc;
+    if (n == 0)
+    {
+        memset(out_sh, 0, planes_bytes);
+        if (out_records) memset(out_records, 0, (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4);
+        if (out_num_covered) *out_num_covered = 0;
+        return LUPIN_OK;
+    }
+    HIP_TRY(DeviceBuffer::make((size_t)n * LP_LM_SH * 16, &d_coef));
+
+    // one query on the device records: its validation, its chunks (whole records), its wavefront; the resolve is this bake's
+    const PathQuery q = {who, desc->pathtrace_type, LUPIN_RAYS_DEVICE_POINTERS, desc->samples, desc->max_bounces, desc->max_slots, &desc->advanced,
+                         LP_LM_SH * 4u};
+    if (int rc = path_query<RayRecordRule>(ctx, scene, q, n, d_rec.as<float>(), d_coef.as<float>(), nullptr, [ctx, scene](const PathChunk &c) -> int {
+            const RayBegin rb{c.d_records, c.samples, c.d_rays};
+            HIP_TRY(enqueue_wavefront(ctx, c.ln, scene, c.pathtrace_type, c.slots, c.sh, c.iterations, nullptr, &rb));
+            hipLaunchKernelGGL(k_resolve_lightmap_sh, dim3((c.records + LP_LM_SH_RECORDS_PER_BLOCK - 1) / LP_LM_SH_RECORDS_PER_BLOCK), dim3(LP_BLOCK), 0,
+                               c.ln->stream, c.ln->pb, c.records, c.d_records, c.samples, c.d_out);
+            HIP_TRY(hipGetLastError());
+            return LUPIN_OK;
+        }))
+        return rc;
+
+    HIP_TRY(hipMemsetAsync(d_planes[0].get(), 0, planes_bytes, st));
+    HIP_TRY(hipMemsetAsync(d_filled[0].get(), 0, (size_t)texels, st));
+    if (out_records)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, &d_plane));
+        HIP_TRY(hipMemsetAsync(d_plane.get(), 0, (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, st));
+    }
+    hipLaunchKernelGGL(k_lm_sh_scatter, dim3((n + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, st, n, d_texel.as<uint32_t>(), d_coef.as<float4>(),
+                       d_rec.as<float4>(), texels, d_planes[0].as<float4>(), d_filled[0].as<uint8_t>(), d_plane.as<float4>());
+    // the gutter passes of lupin_hip_bake_lightmap on each plane (the filled bytes are the same for all four)
+    int cur = 0;
+    for (uint32_t pass = 0; pass < desc->dilate; pass++, cur ^= 1)
+        for (uint32_t j = 0; j < LP_LM_SH; j++)
+            hipLaunchKernelGGL(k_lm_dilate, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, W, H, d_planes[cur].as<float4>() + (size_t)j * texels,
+                               d_filled[cur].as<uint8_t>(), d_planes[cur ^ 1].as<float4>() + (size_t)j * texels, d_filled[cur ^ 1].as<uint8_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_sh, d_planes[cur].get(), planes_bytes, hipMemcpyDeviceToHost, st));
+    if (out_records) HIP_TRY(hipMemcpyAsync(out_records, d_plane.get(), (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    if (int rc = query_end(ctx, who)) return rc;
+    if (out_num_covered) *out_num_covered = n;
     return LUPIN_OK;
 }
 

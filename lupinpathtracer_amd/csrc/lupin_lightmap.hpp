@@ -13,6 +13,7 @@
 //   k_lm_scatter   pi * mean radiance and alpha 1 to the texel, the record to its place in the record plane if asked
 //   k_lm_dilate    one gutter pass, ping-pong
 //   k_lm_ao_scatter  lupin_hip_bake_lightmap_ao's k_lm_scatter: visibility and bent normal from the bent-normal query's sums
+//   (lupin_hip_bake_lightmap_directional's resolve and scatter kernels are in lupin_lightmap_directional.hpp)
 //
 // Geometry is read from plain global memory (GeoGlobal): every triangle is fetched once per wave in the raster and once per
 // owned texel in the emit, neighbouring texels share it through the cache, and nothing here iterates over a hierarchy --
@@ -196,6 +197,28 @@ LP_DEV f3 lm_local_to_world(const InstanceDev &in, f3 lp)
     return add(add(add(scale(m0, lp.x), scale(m1, lp.y)), scale(m2, lp.z)), scale(m3, 1.0f));
 }
 
+// The bake normal at barycentrics (u, v) of global triangle gtri (vertex ids i0, i1, i2) of an instance: the geometric normal
+// `ng`, or with LP_LM_SMOOTH_NORMALS on a mesh that has normals the interpolated vertex normal in world space, turned to
+// ng's side.  k_lm_emit writes it into the record; the directional lightmapped view (lupin_lightmapped_view.hpp) computes it
+// again at a pixel's hit: both go through here.
+template <typename Geo>
+LP_DEV f3 lm_bake_normal(const Geo &geo, const SceneDev &sc, const InstanceDev &in, const MeshDev &mesh, uint32_t gtri, uint32_t i0, uint32_t i1,
+                         uint32_t i2, float u, float v, uint32_t flags, f3 &ng)
+{
+    ng = geometric_normal(geo, in, gtri);
+    f3 n = ng;
+    if ((flags & LP_LM_SMOOTH_NORMALS) && mesh.normals_base != LUPIN_SENTINEL_IDX)
+    {
+        const float w = 1.0f - u - v;
+        const f3 n0 = xyz(sc.normals[mesh.normals_base + i0]);
+        const f3 n1 = xyz(sc.normals[mesh.normals_base + i1]);
+        const f3 n2 = xyz(sc.normals[mesh.normals_base + i2]);
+        n = normal_to_world(in, normalize3(add(add(scale(n0, w), scale(n1, u)), scale(n2, v))));
+        if (dot3(n, ng) < 0.0f) n = neg(n);
+    }
+    return n;
+}
+
 __global__ void __launch_bounds__(LP_BLOCK) k_lm_emit(SceneDev sc, const LmChartDev *__restrict__ charts, uint32_t num_charts, uint32_t W, uint32_t H,
                                                       const uint32_t *__restrict__ owner, const uint32_t *__restrict__ block_offsets, uint32_t flags,
                                                       uint32_t counter, float surface_offset, float4 *__restrict__ records,
@@ -224,16 +247,8 @@ __global__ void __launch_bounds__(LP_BLOCK) k_lm_emit(SceneDev sc, const LmChart
     const TriVerts tv = geo.tri_fetch(t.gtri);
     const f3 lp = add(add(scale(xyz(tv.v0), w), scale(xyz(tv.v1), u)), scale(xyz(tv.v2), v));
     const f3 wp = lm_local_to_world(in, lp);
-    const f3 ng = geometric_normal(geo, in, t.gtri);
-    f3 n = ng;
-    if ((flags & LP_LM_SMOOTH_NORMALS) && t.mesh.normals_base != LUPIN_SENTINEL_IDX)
-    {
-        const f3 n0 = xyz(sc.normals[t.mesh.normals_base + t.i0]);
-        const f3 n1 = xyz(sc.normals[t.mesh.normals_base + t.i1]);
-        const f3 n2 = xyz(sc.normals[t.mesh.normals_base + t.i2]);
-        n = normal_to_world(in, normalize3(add(add(scale(n0, w), scale(n1, u)), scale(n2, v))));
-        if (dot3(n, ng) < 0.0f) n = neg(n);
-    }
+    f3 ng;
+    const f3 n = lm_bake_normal(geo, sc, in, t.mesh, t.gtri, t.i0, t.i1, t.i2, u, v, flags, ng);
     const f3 o = add(wp, scale(ng, surface_offset));
     records[2 * (size_t)slot] = make_float4(o.x, o.y, o.z, __uint_as_float(rng_seed_for(i, counter)));
     records[2 * (size_t)slot + 1] = make_float4(n.x, n.y, n.z, __uint_as_float(LP_RAY_COSINE_HEMISPHERE));

@@ -71,6 +71,23 @@ struct RayRecordRule
     }
 };
 
+// RNG state of path s of the record (a, b) (the query's rule) and the path's first direction: the record's own in mode 0; in
+// mode 1 two draws, then the matte BSDF's sampler (sample_cos_hemisphere) about the record's normal.  k_begin_rays hands the
+// direction out, k_resolve_lightmap_sh (lupin_lightmap_directional.hpp) computes it again from the same record: both go
+// through here.
+LP_DEV f3 ray_first_direction(float4 a, float4 b, uint32_t s, uint32_t &rng)
+{
+    rng = __float_as_uint(a.w);
+    if (s != 0u) rng = hash_u32(rng + s * LP_RAY_SAMPLE_STRIDE);
+    f3 d = mk3(b.x, b.y, b.z);
+    if (__float_as_uint(b.w) == LP_RAY_COSINE_HEMISPHERE)
+    {
+        const float r0 = rnd(rng), r1 = rnd(rng);
+        d = sample_cos_hemisphere(d, r0, r1);
+    }
+    return d;
+}
+
 // `records` and `out_rays` point at the chunk's first record / first slot; n = the chunk's slots (records * samples)
 __global__ void __launch_bounds__(LP_BLOCK) k_begin_rays(PathBuffers pb, uint32_t n, const float4 *__restrict__ records, uint32_t samples,
                                                          float4 *__restrict__ out_rays)
@@ -82,15 +99,8 @@ __global__ void __launch_bounds__(LP_BLOCK) k_begin_rays(PathBuffers pb, uint32_
     if (!live) return;
     const uint32_t rec = slot / samples, s = slot - rec * samples;
     const float4 a = records[2 * (size_t)rec], b = records[2 * (size_t)rec + 1];
-    uint32_t rng = __float_as_uint(a.w);
-    if (s != 0u) rng = hash_u32(rng + s * LP_RAY_SAMPLE_STRIDE);
-    f3 d = mk3(b.x, b.y, b.z);
-    if (__float_as_uint(b.w) == LP_RAY_COSINE_HEMISPHERE)
-    {
-        // the matte BSDF's sampler (sample_cos_hemisphere) about the record's normal, two draws
-        const float r0 = rnd(rng), r1 = rnd(rng);
-        d = sample_cos_hemisphere(d, r0, r1);
-    }
+    uint32_t rng;
+    const f3 d = ray_first_direction(a, b, s, rng);
     const float4 orr = make_float4(a.x, a.y, a.z, __uint_as_float(rng));
     pb.ori_rng[slot] = orr;
     pb.dir_meta[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(META_NEXT_EMISSION));
