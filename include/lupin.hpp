@@ -642,6 +642,46 @@ inline uint64_t bake_lightmap_directional(const Device &d, const Scene &scene, c
     return covered;
 }
 
+// adaptive lightmap baking (no reference counterpart).  pathtrace_rays_moments is pathtrace_rays with the moments
+// of every record's paths: out n x 8 floats (mean r, g, b, 1, the mean luminance, M2 about it, samples, 0).
+inline void pathtrace_rays_moments(const Device &d, const Scene &scene, const RayQueryDesc &desc, uint64_t n, const float *records, float *out)
+{
+    const LupinRayQueryDesc c{(uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.flags, desc.max_slots,
+                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
+    check(lupin_hip_pathtrace_rays_moments(d.raw(), scene.raw(), &c, n, records, out));
+}
+// bake_lightmap in rounds of desc.samples paths per texel: a texel stops once the relative standard error of its luminance is
+// below the threshold and no atlas neighbour wants samples.  out_rgba: height x width x 4 floats; out_stats: nullptr or the
+// same shape (paths taken, relative error, standard error of the irradiance's luminance, converged); out_records: nullptr or
+// height x width x 8; returns the number of owned texels.
+struct LightmapAdaptiveDesc
+{
+    float threshold = 0.05f;
+    uint32_t min_rounds = 2;
+    uint32_t max_rounds = 64;      // <= LUPIN_LIGHTMAP_ADAPTIVE_MAX_ROUNDS; samples * max_rounds <= 2^24
+};
+inline uint64_t bake_lightmap_adaptive(const Device &d, const Scene &scene, const LightmapDesc &desc, const LightmapAdaptiveDesc &adaptive,
+                                       const LightmapChart *charts, uint32_t num_charts, float *out_rgba, float *out_stats = nullptr,
+                                       float *out_records = nullptr)
+{
+    const LupinLightmapDesc c{desc.width, desc.height, (uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.max_slots, desc.flags,
+                              desc.dilate, desc.counter, desc.surface_offset,
+                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
+    const LupinLightmapAdaptiveDesc a{adaptive.threshold, adaptive.min_rounds, adaptive.max_rounds, 0u};
+    std::vector<LupinLightmapChart> cc(num_charts);
+    for (uint32_t k = 0; k < num_charts; k++)
+        cc[k] = LupinLightmapChart{charts[k].instance_idx, charts[k].scale_u, charts[k].scale_v, charts[k].offset_u, charts[k].offset_v};
+    uint64_t covered = 0;
+    check(lupin_hip_bake_lightmap_adaptive(d.raw(), scene.raw(), &c, &a, cc.data(), num_charts, out_rgba, out_stats, out_records, &covered));
+    return covered;
+}
+inline LupinLightmapAdaptiveStats lightmap_adaptive_stats()
+{
+    LupinLightmapAdaptiveStats s;
+    lupin_hip_lightmap_adaptive_stats(&s);
+    return s;
+}
+
 // ambient-occlusion and bent-normal atlases (no reference counterpart): bake_lightmap's texels and records,
 // every owned texel queried by the bent-normal kernel up to max_distance
 struct LightmapAoDesc

@@ -878,6 +878,27 @@ int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const L
                              uint64_t n, const float *records /* n x 8 */, float *out /* n x 4 */,
                              float *out_rays /* NULL, or n*S x 8 */);
 
+/* ---- moments of a record's paths (no reference counterpart) ----
+ * lupin_hip_pathtrace_rays with another resolve and without out_rays: the descriptor, the flags
+ * (LUPIN_RAYS_DEVICE_POINTERS), the records, their validation, the chunks of max_slots paths (whole records), the ordering and
+ * every refusal are that call's; the paths traced are the same paths.  Result, LUPIN_RAY_MOMENTS_FLOATS floats per record:
+ *   [0..2] mean r, g, b    [3] 1.0f    [4] ml, the mean luminance    [5] M2 = sum over the paths of (lum - ml)^2
+ *   [6] (float)samples     [7] 0.0f
+ * With c_s the clamped radiance of slot s (what the query with samples == 1 returns for the path), S = samples and
+ * lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b, every operation one rounded f32 operation without contraction,
+ * in this order:
+ *   Pass 1.  Lane l = 0..63 takes slots s = l, l + 64, ... in ascending order and adds c_s.r, c_s.g, c_s.b and lum(c_s) to
+ *   four partial sums that start from +0.0f.  Each of the four is then summed over the lanes by an xor butterfly over lane
+ *   offsets 32, 16, 8, 4, 2, 1: at each offset every lane's value becomes its own plus that of lane ^ offset.
+ *   mean_c = sum_c / (float)S,  ml = sum_lum / (float)S.
+ *   Pass 2.  The same slots in the same order: q += (lum(c_s) - ml) * (lum(c_s) - ml) from +0.0f, the same butterfly: M2.
+ * The mean is therefore lupin_hip_pathtrace_rays' mean summed in another order (the same words for S <= 2).  M2 is taken
+ * about the mean in a second pass, not as sum lum^2 - S * ml^2: that difference cancels in f32 exactly where the paths
+ * agree.  A record is never split between waves or launches: the words do not depend on max_slots. */
+#define LUPIN_RAY_MOMENTS_FLOATS 8
+int lupin_hip_pathtrace_rays_moments(LupinContext *ctx, const LupinScene *scene, const LupinRayQueryDesc *desc,
+                                     uint64_t n, const float *records /* n x 8 */, float *out /* n x 8 */);
+
 /* ---- lightmap baking (no reference counterpart) ----
  * Irradiance on the scene's surfaces, laid out by the meshes' texcoords: every chart places one instance's UVs in the atlas
  * (atlas uv = mesh uv * scale + offset), its triangles are rasterised to texels, and every owned texel is path-traced over
@@ -1024,6 +1045,76 @@ int lupin_hip_bake_lightmap_ao(LupinContext *ctx, const LupinScene *scene, const
 int lupin_hip_bake_lightmap_directional(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc,
                                         const LupinLightmapChart *charts, uint32_t num_charts, float *out_sh /* 4*H*W*4 */,
                                         float *out_records /* NULL, or H*W*8 */, uint64_t *out_num_covered /* NULL ok */);
+
+/* ---- adaptive lightmap baking (no reference counterpart) ----
+ * lupin_hip_bake_lightmap in rounds: desc->samples is S, the paths per texel PER ROUND; a texel stops taking rounds once the
+ * relative standard error of its luminance is below ad->threshold and no atlas neighbour wants samples either.
+ * Rasterisation, ownership, record emission, out_records, out_num_covered and the `dilate` gutter passes are
+ * lupin_hip_bake_lightmap's, word for word, for the same charts, flags, counter and surface_offset: the same kernels run.
+ * Record i below is the i-th owned texel in ascending texel order.
+ *
+ * State per record, zero at the start of the call: n_i (u32 paths), rounds_i (u32), mean_i (r, g, b), ml_i, M2_i.
+ * Round r = 0, 1, ... (every operation one rounded f32 operation without contraction):
+ *   1. The active records (round 0: all) are compacted in ascending i.  Active record i becomes record j of the round: its
+ *      own record with the RNG word replaced by word_r = word for r == 0, else hash_u32(word + r * 0x85EBCA6B) (r is the
+ *      round of the call, not rounds_i).  No active record: the loop ends.
+ *   2. lupin_hip_pathtrace_rays_moments' query on the round's records with S samples (pathtrace_type, max_bounces, max_slots
+ *      and advanced are the query's).  Every round pays that query's validation of its records and its synchronisation.
+ *   3. Merge, with (round_c, ml_round, M2_round) the query's result for j and i its record.  n_i == 0: the state becomes
+ *      the round's.  Otherwise  nA = (float)n_i;  nB = (float)S;  w = nB / (nA + nB);  delta = ml_round - ml_i;
+ *        mean_c = mean_c + (round_c - mean_c) * w  per channel;   ml = ml_i + delta * w;
+ *        M2 = (M2_i + M2_round) + ((delta * delta) * nA) * w.
+ *      Then n_i += S, rounds_i += 1,
+ *        e_i = +inf if n_i < 2 or ml_i or M2_i is not finite, else sqrtf(M2_i / (nf * (nf - 1.0f))) / (ml_i + 1e-3f), nf = (float)n_i
+ *      (lupin_hip_pathtrace_scene_adaptive's per-pixel error), and
+ *        want_i = rounds_i < max_rounds && (rounds_i < min_rounds || !(e_i < threshold)).
+ *   4. Mask: active_i = rounds_i < max_rounds && (want_i || want of any of the texel's eight atlas neighbours inside the
+ *      atlas).  Texels that are not owned never want; a neighbour at max_rounds has want == 0 and keeps nobody alive.  (A texel
+ *      whose first rounds all returned zero has M2 == 0 and would stop at min_rounds beside a neighbour still finding the light.)
+ * Every round adds one to rounds_i of the records it traces and none is active at max_rounds, so the loop ends; a texel that
+ * a neighbour woke late is behind the call's round r, so the call may run more than max_rounds rounds.
+ *
+ * out_rgba (H x W x 4, host): 3.14159265f * mean_c and alpha 1.0f on owned texels, zeros elsewhere, then the gutter passes.
+ * out_stats (NULL, or H x W x 4, host; not dilated, zeros where not owned):
+ *   [0] (float)n_i   [1] e_i   [2] 3.14159265f * sqrtf(M2_i / (nf * (nf - 1.0f))), the standard error of the irradiance's
+ *   luminance, 0.0f when n_i < 2   [3] 1.0f if rounds_i >= min_rounds && e_i < threshold, else 0.0f.
+ * With threshold == 0 and min_rounds == max_rounds == R every texel takes R * S paths.
+ *
+ * Ordering as lupin_hip_bake_lightmap.  LUPIN_ERR_INVALID_ARGUMENT with the outputs untouched for everything
+ * lupin_hip_bake_lightmap refuses (out_stats, out_records and out_num_covered may be NULL), a NULL ad, a threshold that is
+ * negative or not finite, min_rounds == 0, max_rounds below min_rounds or above LUPIN_LIGHTMAP_ADAPTIVE_MAX_ROUNDS,
+ * samples * max_rounds above 2^24 ((float)n_i must be exact), a non-zero ad->flags.  LUPIN_ERR_OUT_OF_MEMORY, outputs
+ * untouched and nothing launched, when the atlas planes cannot be allocated.  An atlas without an owned texel: LUPIN_OK, all
+ * zeros.  Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_LIGHTMAP_ADAPTIVE_MAX_ROUNDS 4096u
+#define LUPIN_LIGHTMAP_ADAPTIVE_STATS_FLOATS 4
+typedef struct LupinLightmapAdaptiveDesc {
+    float threshold;                /* finite, >= 0: a texel wants no more samples once its relative standard error is < threshold */
+    uint32_t min_rounds;            /* >= 1 */
+    uint32_t max_rounds;            /* >= min_rounds, <= LUPIN_LIGHTMAP_ADAPTIVE_MAX_ROUNDS; desc->samples * max_rounds <= 2^24 */
+    uint32_t flags;                 /* 0 */
+} LupinLightmapAdaptiveDesc;
+int lupin_hip_bake_lightmap_adaptive(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc,
+                                     const LupinLightmapAdaptiveDesc *ad, const LupinLightmapChart *charts, uint32_t num_charts,
+                                     float *out_rgba /* H*W*4 */, float *out_stats /* NULL, or H*W*4 */,
+                                     float *out_records /* NULL, or H*W*8 */, uint64_t *out_num_covered /* NULL ok */);
+/* The calling thread's latest successful adaptive bake; host-clock milliseconds, summed over the rounds (each phase ends
+ * synchronised). */
+typedef struct LupinLightmapAdaptiveStats {
+    uint64_t covered_texels;
+    uint64_t paths;                 /* paths traced: S * the sum of the rounds' active records */
+    uint64_t converged_texels;      /* out_stats [3] == 1 */
+    uint64_t capped_texels;         /* stopped by max_rounds without [3] == 1 */
+    uint32_t rounds;                /* rounds that traced */
+    uint32_t keys;                  /* (chart, triangle) pairs rasterised */
+    float raster_ms;
+    float compact_ms;               /* the records' count, scan, emit, and every round's */
+    float trace_ms;                 /* the rounds' queries */
+    float merge_mask_ms;
+    float scatter_dilate_ms;        /* with the statistics plane */
+    float download_ms;
+} LupinLightmapAdaptiveStats;
+void lupin_hip_lightmap_adaptive_stats(LupinLightmapAdaptiveStats *out);
 
 /* ---- lightmap denoising (no reference counterpart) ----
  * An edge-avoiding a-trous filter in atlas space for what lupin_hip_bake_lightmap writes: `rgba` is its out_rgba (or several

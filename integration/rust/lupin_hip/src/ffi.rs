@@ -95,6 +95,17 @@ pub const LUPIN_LIGHTMAP_SMOOTH_NORMALS: u32 = 1;
 #[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinLightmapStats {
     pub covered_texels: u64, pub keys: u32, pub raster_ms: f32, pub compact_ms: f32, pub trace_ms: f32, pub scatter_dilate_ms: f32, pub download_ms: f32,
 }
+// adaptive lightmap baking (no reference counterpart)
+pub const LUPIN_RAY_MOMENTS_FLOATS: usize = 8;
+pub const LUPIN_LIGHTMAP_ADAPTIVE_MAX_ROUNDS: u32 = 4096;
+pub const LUPIN_LIGHTMAP_ADAPTIVE_STATS_FLOATS: usize = 4;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmapAdaptiveDesc {
+    pub threshold: f32, pub min_rounds: u32, pub max_rounds: u32, pub flags: u32,
+}
+#[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinLightmapAdaptiveStats {
+    pub covered_texels: u64, pub paths: u64, pub converged_texels: u64, pub capped_texels: u64, pub rounds: u32, pub keys: u32,
+    pub raster_ms: f32, pub compact_ms: f32, pub trace_ms: f32, pub merge_mask_ms: f32, pub scatter_dilate_ms: f32, pub download_ms: f32,
+}
 // lightmap denoising (no reference counterpart)
 pub const LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS: u32 = 1;
 pub const LUPIN_LIGHTMAP_DENOISE_MAX_PASSES: u32 = 8;
@@ -316,6 +327,14 @@ extern "C" {
                                                     desc: *const LupinLightmappedDirectionalDesc, charts: *const LupinLightmapChart,
                                                     lightmap: *const f32, directional: *const f32, sh: *const f32, depth: *const f32,
                                                     valid: *const u8, out_gbuffer: *mut f32) -> c_int;
+    // moments of a record's paths: records n x 8 f32, out n x 8 f32 (mean rgb, 1, mean luminance, M2, samples, 0)
+    pub fn lupin_hip_pathtrace_rays_moments(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinRayQueryDesc, n: u64,
+                                            records: *const f32, out: *mut f32) -> c_int;
+    // adaptive lightmap: out_rgba height x width x 4 f32, out_stats null or the same shape, out_records null or height x width x 8
+    pub fn lupin_hip_bake_lightmap_adaptive(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinLightmapDesc,
+                                            ad: *const LupinLightmapAdaptiveDesc, charts: *const LupinLightmapChart, num_charts: u32,
+                                            out_rgba: *mut f32, out_stats: *mut f32, out_records: *mut f32, out_num_covered: *mut u64) -> c_int;
+    pub fn lupin_hip_lightmap_adaptive_stats(out: *mut LupinLightmapAdaptiveStats);
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

@@ -170,6 +170,16 @@ class LightmapStatsC(C.Structure):   # LupinLightmapStats
                 ("trace_ms", C.c_float), ("scatter_dilate_ms", C.c_float), ("download_ms", C.c_float)]
 
 
+class LightmapAdaptiveDescC(C.Structure):   # LupinLightmapAdaptiveDesc
+    _fields_ = [("threshold", C.c_float), ("min_rounds", C.c_uint32), ("max_rounds", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LightmapAdaptiveStatsC(C.Structure):   # LupinLightmapAdaptiveStats
+    _fields_ = [("covered_texels", C.c_uint64), ("paths", C.c_uint64), ("converged_texels", C.c_uint64), ("capped_texels", C.c_uint64),
+                ("rounds", C.c_uint32), ("keys", C.c_uint32), ("raster_ms", C.c_float), ("compact_ms", C.c_float), ("trace_ms", C.c_float),
+                ("merge_mask_ms", C.c_float), ("scatter_dilate_ms", C.c_float), ("download_ms", C.c_float)]
+
+
 class LightmapDenoiseDescC(C.Structure):   # LupinLightmapDenoiseDesc
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("passes", C.c_uint32), ("normal_squarings", C.c_uint32),
                 ("dilate", C.c_uint32), ("flags", C.c_uint32), ("max_stretch", C.c_float)]
@@ -307,6 +317,10 @@ SYMBOLS = [
     ("lupin_hip_bent_normal_rays", C.c_int, [_P, _P, C.POINTER(BentNormalDescC), C.c_uint64, _P, _P]),
     ("lupin_hip_bake_lightmap_ao", C.c_int, [_P, _P, C.POINTER(LightmapAoDescC), C.POINTER(LightmapChartC), _U32, _P, _P, _P, C.POINTER(C.c_uint64)]),
     ("lupin_hip_bake_lightmap_directional", C.c_int, [_P, _P, C.POINTER(LightmapDescC), C.POINTER(LightmapChartC), _U32, _P, _P, C.POINTER(C.c_uint64)]),
+    ("lupin_hip_pathtrace_rays_moments", C.c_int, [_P, _P, C.POINTER(RayQueryDescC), C.c_uint64, _P, _P]),
+    ("lupin_hip_bake_lightmap_adaptive", C.c_int,
+     [_P, _P, C.POINTER(LightmapDescC), C.POINTER(LightmapAdaptiveDescC), C.POINTER(LightmapChartC), _U32, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    ("lupin_hip_lightmap_adaptive_stats", None, [C.POINTER(LightmapAdaptiveStatsC)]),
     ("lupin_hip_distance_points", C.c_int, [_P, _P, _U32, C.c_uint64, _P, _P]),
     ("lupin_hip_bake_distance_grid", C.c_int, [_P, _P, _U32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_float, _P]),
     ("lupin_hip_sample_probe_grid", C.c_int, [_P, _P, C.POINTER(ProbeGridDescC), _P, _P, C.c_uint64, _P, _P]),

@@ -1943,6 +1943,96 @@ def lightmap_directional_ratio(coeffs, n_shade, n_bake):
         return np.where(ok, np.where(num > 0, num, np.float32(0.0)) / np.where(ok, den, one), one).astype(np.float32)
 
 
+# ---- adaptive lightmap baking: lupin_hip_pathtrace_rays_moments, lupin_hip_bake_lightmap_adaptive (include/lupin_hip.h) ----
+RAY_MOMENTS_FLOATS = 8
+LIGHTMAP_ADAPTIVE_MAX_ROUNDS = 4096
+LIGHTMAP_ADAPTIVE_STATS_FLOATS = 4
+LIGHTMAP_ADAPTIVE_ROUND_STRIDE = 0x85EBCA6B
+
+
+def lightmap_round_word(word, r):
+    """RNG word of a lightmap record in round `r` of bake_lightmap_adaptive: the record's own for r == 0,
+    hash_u32(word + r * 0x85EBCA6B) otherwise."""
+    word = np.asarray(word, np.uint32)
+    r = np.asarray(r, np.uint32)
+    with np.errstate(over="ignore"):
+        return np.where(r == 0, word, _hash_u32(word + r * np.uint32(LIGHTMAP_ADAPTIVE_ROUND_STRIDE))).astype(np.uint32)
+
+
+def pathtrace_rays_moments(ctx, scene, records, desc: Optional[RayQueryDesc] = None):
+    """pathtrace_rays with the moments of every record's desc.samples paths: (n, RAY_MOMENTS_FLOATS) float32 -- mean r, g, b,
+    1, the mean luminance ml, M2 = the sum of (luminance - ml)^2 over the paths, float(samples), 0.  The same records, the same
+    paths; the mean is summed in another order than pathtrace_rays' (include/lupin_hip.h).  `records` as pathtrace_rays
+    takes them: a numpy array, or a contiguous float32 torch tensor on the context's device (then a tensor comes back)."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "pathtrace_rays_moments needs a GPU context and an uploaded scene; there is no CPU fallback")
+    desc = desc or RayQueryDesc()
+    flags = int(desc.flags)
+    c = _abi.RayQueryDescC(int(desc.pathtrace_type), int(desc.max_bounces), int(desc.samples), flags, int(desc.max_slots),
+                           _abi.AdvancedParamsC(desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon))
+    if hasattr(records, "data_ptr"):   # a torch tensor
+        import torch
+        t = records
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == RAY_RECORD_FLOATS):
+            raise ValueError("records must be a contiguous (n, 8) float32 tensor on the context's device")
+        if t.device.index != ctx.device_ordinal:
+            raise ValueError("records are on another device than the context")
+        n = int(t.shape[0])
+        out = torch.zeros((n, RAY_MOMENTS_FLOATS), dtype=torch.float32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()   # the records (and the zero fill) are written
+        c.flags = flags | RAYS_DEVICE_POINTERS
+        check(lib().lupin_hip_pathtrace_rays_moments(ctx.handle, scene.handle, C.byref(c), n, C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, RAY_RECORD_FLOATS)
+    out = np.zeros((len(rec), RAY_MOMENTS_FLOATS), np.float32)
+    check(lib().lupin_hip_pathtrace_rays_moments(ctx.handle, scene.handle, C.byref(c), len(rec), ptr(rec), ptr(out)))
+    return out
+
+
+def lightmap_adaptive_stats():
+    """The calling thread's latest successful bake_lightmap_adaptive: covered texels, rounds that traced, paths traced, texels
+    that converged and texels the cap stopped, (chart, triangle) pairs, host-clock ms per phase summed over the rounds."""
+    s = _abi.LightmapAdaptiveStatsC()
+    lib().lupin_hip_lightmap_adaptive_stats(C.byref(s))
+    return {"covered_texels": int(s.covered_texels), "rounds": int(s.rounds), "paths": int(s.paths), "converged_texels": int(s.converged_texels),
+            "capped_texels": int(s.capped_texels), "keys": int(s.keys), "raster_ms": float(s.raster_ms), "compact_ms": float(s.compact_ms),
+            "trace_ms": float(s.trace_ms), "merge_mask_ms": float(s.merge_mask_ms), "scatter_dilate_ms": float(s.scatter_dilate_ms),
+            "download_ms": float(s.download_ms)}
+
+
+def bake_lightmap_adaptive(ctx, scene, charts, width, height, samples_per_round=16, threshold=0.05, min_rounds=2, max_rounds=64,
+                           pathtrace_type=PathtraceType.Standard, max_bounces=8, advanced=None, counter=0, max_slots=0, smooth_normals=False,
+                           dilate=0, surface_offset=None, want_stats=False, want_records=False):
+    """bake_lightmap in rounds of `samples_per_round` paths per texel: a texel takes at least min_rounds and at most max_rounds
+    rounds and stops in between once the relative standard error of its luminance is below `threshold` and none of its eight
+    atlas neighbours still wants samples.  (height, width, 4) float32 as bake_lightmap returns it; the other arguments are
+    bake_lightmap's.  With want_stats also (height, width, 4) per-texel statistics, zeros where not rasterised: [0] the paths
+    taken, [1] the relative standard error (+inf without an estimate), [2] the standard error of the irradiance's luminance,
+    [3] 1 where the texel converged and 0 where the cap stopped it.  With want_records also the records.  The result is
+    (rgba[, stats][, records]).  lightmap_adaptive_stats() has the call's totals.  Blocks until the result is complete."""
+    if ctx is None or scene.handle is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "bake_lightmap_adaptive needs a GPU context and an uploaded scene; there is no CPU fallback")
+    if surface_offset is None:
+        surface_offset = LIGHTMAP_OFFSET_FRACTION * (scene_world_extent(scene) or 1.0)
+    adv = advanced or AdvancedParams()
+    items = [c if isinstance(c, LightmapChart) else LightmapChart(*c) for c in charts]
+    c_charts = (_abi.LightmapChartC * max(1, len(items)))(*[_abi.LightmapChartC(int(c.instance_idx), c.scale_u, c.scale_v, c.offset_u, c.offset_v)
+                                                           for c in items])
+    d = _abi.LightmapDescC(int(width), int(height), int(pathtrace_type), int(max_bounces), int(samples_per_round), int(max_slots),
+                           LIGHTMAP_SMOOTH_NORMALS if smooth_normals else 0, int(dilate), int(counter), float(surface_offset),
+                           _abi.AdvancedParamsC(adv.max_radiance, adv.rng_seed, adv.ray_epsilon))
+    a = _abi.LightmapAdaptiveDescC(float(threshold), int(min_rounds), int(max_rounds), 0)
+    shape_ok = 0 < int(width) <= LIGHTMAP_MAX_SIZE and 0 < int(height) <= LIGHTMAP_MAX_SIZE
+    hw = (int(height), int(width)) if shape_ok else (1, 1)      # a refused size: the library says so
+    out = np.zeros(hw + (4,), np.float32)
+    stats = np.zeros(hw + (LIGHTMAP_ADAPTIVE_STATS_FLOATS,), np.float32) if want_stats else None
+    rec = np.zeros(hw + (RAY_RECORD_FLOATS,), np.float32) if want_records else None
+    check(lib().lupin_hip_bake_lightmap_adaptive(ctx.handle, scene.handle, C.byref(d), C.byref(a), c_charts, len(items), ptr(out), ptr(stats), ptr(rec),
+                                                 None))
+    result = (out,) + ((stats,) if want_stats else ()) + ((rec,) if want_records else ())
+    return result if len(result) > 1 else out
+
+
 # ---- distance queries: lupin_hip_distance_points, lupin_hip_bake_distance_grid (include/lupin_hip.h, DESIGN.md 20) ----
 DISTANCE_RECORD_FLOATS = 4
 DISTANCE_RESULT_FLOATS = 12

@@ -3,7 +3,7 @@
 // traversal / material / light device functions in lupin_device.hpp, the CPU builders in builders.cpp, the device BLAS
 // builder in lbvh.hip, the denoiser's kernels in lupin_denoise.hpp, adaptive sampling's in lupin_adaptive.hpp, its
 // reprojection's in lupin_reproject.hpp, the radiance queries' in lupin_rays.hpp, light-probe baking's in lupin_probes.hpp,
-// lightmap baking's in lupin_lightmap.hpp, the occlusion queries' in lupin_occlusion.hpp, the distance queries' in
+// lightmap baking's in lupin_lightmap.hpp and lupin_lightmap_adaptive.hpp, the occlusion queries' in lupin_occlusion.hpp, the distance queries' in
 // lupin_distance.hpp.
 //
 // THERE IS NO CPU FALLBACK: without a HIP device every entry point that needs one fails with LUPIN_ERR_NO_DEVICE.
@@ -32,6 +32,7 @@
 #include "lupin_probes.hpp"
 #include "lupin_lightmap.hpp"
 #include "lupin_lightmap_directional.hpp"
+#include "lupin_lightmap_adaptive.hpp"
 #include "lupin_lightmap_denoise.hpp"
 #include "lupin_occlusion.hpp"
 #include "lupin_transmittance.hpp"
@@ -2968,6 +2969,28 @@ int lupin_hip_pathtrace_rays(LupinContext *ctx, const LupinScene *scene, const L
     });
 }
 
+// lupin_hip_pathtrace_rays with k_resolve_moments (lupin_lightmap_adaptive.hpp) as its resolve: the launch of a
+// chunk, shared with the rounds of lupin_hip_bake_lightmap_adaptive
+static int launch_moments_chunk(LupinContext *ctx, const LupinScene *scene, const PathChunk &c)
+{
+    const RayBegin rb{c.d_records, c.samples, c.d_rays};
+    HIP_TRY(enqueue_wavefront(ctx, c.ln, scene, c.pathtrace_type, c.slots, c.sh, c.iterations, nullptr, &rb));
+    hipLaunchKernelGGL(k_resolve_moments, dim3((c.records + LP_LM_AD_RECORDS_PER_BLOCK - 1) / LP_LM_AD_RECORDS_PER_BLOCK), dim3(LP_BLOCK), 0, c.ln->stream,
+                       c.ln->pb, c.records, c.samples, c.d_out);
+    HIP_TRY(hipGetLastError());
+    return LUPIN_OK;
+}
+
+int lupin_hip_pathtrace_rays_moments(LupinContext *ctx, const LupinScene *scene, const LupinRayQueryDesc *desc, uint64_t n, const float *records,
+                                     float *out)
+{
+    if (int rc = query_refuse(ctx, scene, desc && records && out)) return rc;
+    const PathQuery q = {"lupin_hip_pathtrace_rays_moments", desc->pathtrace_type, desc->flags, desc->samples, desc->max_bounces, desc->max_slots,
+                         &desc->advanced, LUPIN_RAY_MOMENTS_FLOATS};
+    return path_query<RayRecordRule>(ctx, scene, q, n, records, out, nullptr,
+                                     [ctx, scene](const PathChunk &c) -> int { return launch_moments_chunk(ctx, scene, c); });
+}
+
 int lupin_hip_bake_probes(LupinContext *ctx, const LupinScene *scene, const LupinProbeDesc *desc, uint64_t n, const float *probes, float *out_sh,
                           float *out_rays)
 {
@@ -3990,6 +4013,169 @@ int lupin_hip_bake_lightmap_directional(LupinContext *ctx, const LupinScene *sce
     if (out_records) HIP_TRY(hipMemcpyAsync(out_records, d_plane.get(), (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
     if (int rc = query_end(ctx, who)) return rc;
     if (out_num_covered) *out_num_covered = n;
+    return LUPIN_OK;
+}
+
+// ---- adaptive lightmap baking (kernels: lupin_lightmap_adaptive.hpp) ----
+
+static thread_local LupinLightmapAdaptiveStats g_lightmap_adaptive_stats = {0, 0, 0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+void lupin_hip_lightmap_adaptive_stats(LupinLightmapAdaptiveStats *out) { if (out) *out = g_lightmap_adaptive_stats; }
+
+int lupin_hip_bake_lightmap_adaptive(LupinContext *ctx, const LupinScene *scene, const LupinLightmapDesc *desc, const LupinLightmapAdaptiveDesc *ad,
+                                     const LupinLightmapChart *charts, uint32_t num_charts, float *out_rgba, float *out_stats, float *out_records,
+                                     uint64_t *out_num_covered)
+{
+    const char *who = "lupin_hip_bake_lightmap_adaptive";
+    if (int rc = query_refuse(ctx, scene, desc && ad && charts && out_rgba)) return rc;
+    const uint32_t W = desc->width, H = desc->height;
+    if (int rc = lightmap_refuse_atlas(W, H, num_charts, desc->flags & ~(uint32_t)LUPIN_LIGHTMAP_SMOOTH_NORMALS, desc->dilate, desc->surface_offset)) return rc;
+    if (int rc = lightmap_refuse_query(desc)) return rc;
+    if (!(std::isfinite(ad->threshold) && ad->threshold >= 0.0f)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "threshold must be finite and not negative");
+    if (ad->min_rounds == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "min_rounds must be >= 1");
+    if (ad->max_rounds < ad->min_rounds || ad->max_rounds > LUPIN_LIGHTMAP_ADAPTIVE_MAX_ROUNDS)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "max_rounds must be in [min_rounds, 4096]");
+    if ((uint64_t)desc->samples * ad->max_rounds > (1ull << 24))   // (float)n_i is exact
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "samples * max_rounds must not exceed 2^24");
+    if (ad->flags) return fail(LUPIN_ERR_INVALID_ARGUMENT, "unknown adaptive flag");
+    if (int rc = query_refuse_hierarchy(ctx, scene, true)) return rc;
+    std::vector<LmChartDev> h_charts;
+    uint64_t total_keys = 0;
+    if (int rc = lightmap_host_charts(scene, charts, num_charts, &h_charts, &total_keys)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
+    hipStream_t st = ctx->lanes[0].stream;   // the primary stream, the query's own
+    LupinLightmapAdaptiveStats stats = {0, 0, 0, 0, 0, (uint32_t)total_keys, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+
+    const uint32_t texels = W * H;
+    const uint32_t texel_blocks = (texels + LP_BLOCK - 1) / LP_BLOCK;
+    const size_t plane_bytes = (size_t)texels * 16, record_plane_bytes = (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4;
+    // the planes before anything is launched: a refusal for want of memory leaves the outputs untouched and the device idle
+    DeviceBuffer d_rgba[2], d_filled[2], d_stats, d_plane, d_want, d_counts;
+    {
+        bool ok = true;
+        for (int k = 0; k < (desc->dilate ? 2 : 1); k++)
+            ok = ok && DeviceBuffer::make(plane_bytes, &d_rgba[k]) == hipSuccess && DeviceBuffer::make((size_t)texels, &d_filled[k]) == hipSuccess;
+        ok = ok && DeviceBuffer::make(plane_bytes, &d_stats) == hipSuccess && DeviceBuffer::make((size_t)texels, &d_want) == hipSuccess;
+        ok = ok && DeviceBuffer::make(2 * sizeof(unsigned long long), &d_counts) == hipSuccess;
+        if (out_records) ok = ok && DeviceBuffer::make(record_plane_bytes, &d_plane) == hipSuccess;
+        if (!ok)
+        {
+            (void)hipGetLastError();
+            return fail(LUPIN_ERR_OUT_OF_MEMORY, std::string(who) + ": no device memory for the atlas planes");
+        }
+    }
+    uint32_t n = 0;
+    DeviceBuffer d_rec, d_texel;
+    if (int rc = lightmap_emit_records(scene, st, who, W, H, h_charts, total_keys, desc->flags, desc->counter, desc->surface_offset, &n, &d_rec, &d_texel,
+                                       &stats.raster_ms, &stats.compact_ms))
+        return rc;
+    stats.covered_texels = n;
+    if (n == 0)
+    {
+        memset(out_rgba, 0, plane_bytes);
+        if (out_stats) memset(out_stats, 0, plane_bytes);
+        if (out_records) memset(out_records, 0, record_plane_bytes);
+        if (out_num_covered) *out_num_covered = 0;
+        g_lightmap_adaptive_stats = stats;
+        return LUPIN_OK;
+    }
+
+    // per record: the state, the active bytes; per round (sized for a round of all records): its records, their indices, their moments
+    const uint32_t S = desc->samples;
+    const uint32_t rec_blocks = (n + LP_BLOCK - 1) / LP_BLOCK;
+    DeviceBuffer d_samples, d_rounds, d_mean, d_m2, d_active, d_totals, d_round_rec, d_index, d_moments;
+    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &d_samples));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &d_rounds));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 16, &d_mean));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &d_m2));
+    HIP_TRY(DeviceBuffer::make((size_t)n, &d_active));
+    HIP_TRY(DeviceBuffer::make(((size_t)rec_blocks + 1) * 4, &d_totals));
+    HIP_TRY(DeviceBuffer::make((size_t)n * LUPIN_RAY_RECORD_FLOATS * 4, &d_round_rec));
+    HIP_TRY(DeviceBuffer::make((size_t)n * 4, &d_index));
+    HIP_TRY(DeviceBuffer::make((size_t)n * LUPIN_RAY_MOMENTS_FLOATS * 4, &d_moments));
+    const LmAdaptiveDev state{d_samples.as<uint32_t>(), d_rounds.as<uint32_t>(), d_mean.as<float4>(), d_m2.as<float>()};
+    HIP_TRY(hipMemsetAsync(d_samples.get(), 0, (size_t)n * 4, st));
+    HIP_TRY(hipMemsetAsync(d_rounds.get(), 0, (size_t)n * 4, st));
+    HIP_TRY(hipMemsetAsync(d_mean.get(), 0, (size_t)n * 16, st));
+    HIP_TRY(hipMemsetAsync(d_m2.get(), 0, (size_t)n * 4, st));
+    HIP_TRY(hipMemsetAsync(d_active.get(), 1, (size_t)n, st));   // round 0: every record
+    HIP_TRY(hipMemsetAsync(d_want.get(), 0, (size_t)texels, st));
+    HIP_TRY(hipMemsetAsync(d_counts.get(), 0, 2 * sizeof(unsigned long long), st));
+
+    // Every round pays the query's validation of its records and its synchronisation: the price of running the wavefront
+    // through path_query unchanged.  The loop ends when no record is active.  Every round that traces adds one to rounds_i of
+    // each of its records and no record is active at max_rounds, so it ends; a record that a neighbour woke late is behind the
+    // call's round count, so the call may run more than max_rounds rounds.
+    const PathQuery q = {who, desc->pathtrace_type, LUPIN_RAYS_DEVICE_POINTERS, S, desc->max_bounces, desc->max_slots, &desc->advanced, LUPIN_RAY_MOMENTS_FLOATS};
+    for (uint32_t round = 0;; round++)
+    {
+        auto t0 = LmClock::now();
+        hipLaunchKernelGGL(k_lm_ad_count, dim3(rec_blocks), dim3(LP_BLOCK), 0, st, d_active.as<uint8_t>(), n, d_totals.as<uint32_t>());
+        hipLaunchKernelGGL(k_lm_scan, dim3(1), dim3(LP_LM_SCAN_THREADS), 0, st, d_totals.as<uint32_t>(), rec_blocks);
+        HIP_TRY(hipGetLastError());
+        uint32_t n_active = 0;
+        HIP_TRY(hipMemcpyAsync(&n_active, d_totals.as<uint32_t>() + rec_blocks, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_active > n) return fail(LUPIN_ERR_HIP, std::string(who) + ": the compaction counted more records than the atlas owns");
+        if (n_active == 0)
+        {
+            stats.compact_ms += lm_ms_since(t0);
+            break;
+        }
+        hipLaunchKernelGGL(k_lm_ad_emit, dim3(rec_blocks), dim3(LP_BLOCK), 0, st, d_active.as<uint8_t>(), n, d_totals.as<uint32_t>(), d_rec.as<float4>(), round,
+                           d_round_rec.as<float4>(), d_index.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        stats.compact_ms += lm_ms_since(t0);
+
+        t0 = LmClock::now();
+        if (int rc = path_query<RayRecordRule>(ctx, scene, q, n_active, d_round_rec.as<float>(), d_moments.as<float>(), nullptr,
+                                               [ctx, scene](const PathChunk &c) -> int { return launch_moments_chunk(ctx, scene, c); }))
+            return rc;
+        stats.trace_ms += lm_ms_since(t0);
+        stats.rounds++;
+        stats.paths += (uint64_t)n_active * S;
+
+        t0 = LmClock::now();
+        hipLaunchKernelGGL(k_lm_ad_merge, dim3((n_active + LP_BLOCK - 1) / LP_BLOCK), dim3(LP_BLOCK), 0, st, n_active, d_index.as<uint32_t>(),
+                           d_moments.as<float4>(), S, state, d_texel.as<uint32_t>(), ad->threshold, ad->min_rounds, ad->max_rounds, d_want.as<uint8_t>());
+        hipLaunchKernelGGL(k_lm_ad_mask, dim3(rec_blocks), dim3(LP_BLOCK), 0, st, n, d_texel.as<uint32_t>(), W, H, d_want.as<uint8_t>(),
+                           d_rounds.as<uint32_t>(), ad->max_rounds, d_active.as<uint8_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        stats.merge_mask_ms += lm_ms_since(t0);
+    }
+
+    // the plain bake's scatter (it reads the means' r, g, b) and gutter passes; the statistics are not dilated
+    auto t0 = LmClock::now();
+    HIP_TRY(hipMemsetAsync(d_rgba[0].get(), 0, plane_bytes, st));
+    HIP_TRY(hipMemsetAsync(d_filled[0].get(), 0, (size_t)texels, st));
+    HIP_TRY(hipMemsetAsync(d_stats.get(), 0, plane_bytes, st));
+    if (out_records) HIP_TRY(hipMemsetAsync(d_plane.get(), 0, record_plane_bytes, st));
+    hipLaunchKernelGGL(k_lm_scatter, dim3(rec_blocks), dim3(LP_BLOCK), 0, st, n, d_texel.as<uint32_t>(), d_mean.as<float4>(), d_rec.as<float4>(),
+                       d_rgba[0].as<float4>(), d_filled[0].as<uint8_t>(), d_plane.as<float4>());
+    hipLaunchKernelGGL(k_lm_ad_stats, dim3(rec_blocks), dim3(LP_BLOCK), 0, st, n, d_texel.as<uint32_t>(), state, ad->threshold, ad->min_rounds, ad->max_rounds,
+                       d_stats.as<float4>(), d_counts.as<unsigned long long>());
+    int cur = 0;
+    for (uint32_t pass = 0; pass < desc->dilate; pass++, cur ^= 1)
+        hipLaunchKernelGGL(k_lm_dilate, dim3(texel_blocks), dim3(LP_BLOCK), 0, st, W, H, d_rgba[cur].as<float4>(), d_filled[cur].as<uint8_t>(),
+                           d_rgba[cur ^ 1].as<float4>(), d_filled[cur ^ 1].as<uint8_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    stats.scatter_dilate_ms = lm_ms_since(t0);
+
+    t0 = LmClock::now();
+    unsigned long long counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba[cur].get(), plane_bytes, hipMemcpyDeviceToHost, st));
+    if (out_stats) HIP_TRY(hipMemcpyAsync(out_stats, d_stats.get(), plane_bytes, hipMemcpyDeviceToHost, st));
+    if (out_records) HIP_TRY(hipMemcpyAsync(out_records, d_plane.get(), record_plane_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counts, d_counts.get(), sizeof(counts), hipMemcpyDeviceToHost, st));
+    if (int rc = query_end(ctx, who)) return rc;
+    stats.download_ms = lm_ms_since(t0);
+    stats.converged_texels = counts[0];
+    stats.capped_texels = counts[1];
+    if (out_num_covered) *out_num_covered = n;
+    g_lightmap_adaptive_stats = stats;
     return LUPIN_OK;
 }
 
