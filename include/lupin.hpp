@@ -15,6 +15,7 @@
 #pragma once
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -94,6 +95,8 @@ class Device   // the reference's (wgpu::Device, wgpu::Queue) pair
 {
   public:
     explicit Device(int ordinal = 0) { check(lupin_hip_create_context(ordinal, &ctx_)); }
+    // no context: what the host-side entry points and refusals need on a machine without a device; every device call fails
+    explicit Device(std::nullptr_t) {}
     ~Device() { lupin_hip_destroy_context(ctx_); }
     Device(const Device &) = delete;
     Device &operator=(const Device &) = delete;
@@ -116,7 +119,10 @@ class PathtraceResources
   public:
     PathtraceResources(const Device &d, const BakedPathtraceParams &p)
     {
-        LupinBakedPathtraceParams c{p.with_runtime_checks ? 1u : 0u, p.max_bounces, p.samples_per_pixel};
+        LupinBakedPathtraceParams c{};
+        c.with_runtime_checks = p.with_runtime_checks ? 1u : 0u;
+        c.max_bounces = p.max_bounces;
+        c.samples_per_pixel = p.samples_per_pixel;
         check(lupin_hip_build_pathtrace_resources(d.raw(), &c, &res_));
     }
     ~PathtraceResources() { lupin_hip_destroy_pathtrace_resources(res_); }
@@ -334,16 +340,30 @@ inline Scene build_accel_structures_and_upload(const Device &d, const SceneCPU &
     return out;
 }
 
+// The C descriptors are filled member by member, by name: their fields are mostly uint32_t, and a positional initialiser
+// that falls out of step with include/lupin_hip.h would still compile.
 namespace detail {
+inline LupinCameraParams camera_params_c(const CameraParams &p)
+{
+    LupinCameraParams c{};
+    c.is_orthographic = p.is_orthographic ? 1u : 0u;
+    c.lens = p.lens; c.film = p.film; c.aspect = p.aspect; c.focus = p.focus; c.aperture = p.aperture;
+    return c;
+}
+inline LupinAdvancedParams advanced_c(const AdvancedParams &a)
+{
+    LupinAdvancedParams c{};
+    c.max_radiance = a.max_radiance; c.rng_seed = a.rng_seed; c.ray_epsilon = a.ray_epsilon;
+    return c;
+}
 inline void fill_desc(const PathtraceDesc &desc, LupinAccumulationParams &ap, LupinTileParams &tp, LupinPathtraceDesc &c)
 {
     if (desc.accum_params) { ap.prev_frame = desc.accum_params->prev_frame.raw(); ap.accum_counter = desc.accum_params->accum_counter; c.accum_params = &ap; }
     if (desc.tile_params) { tp.tile_size = desc.tile_params->tile_size; tp.tile_idx = desc.tile_params->tile_idx; c.tile_params = &tp; }
-    c.camera_params = LupinCameraParams{desc.camera_params.is_orthographic ? 1u : 0u, desc.camera_params.lens, desc.camera_params.film,
-                                        desc.camera_params.aspect, desc.camera_params.focus, desc.camera_params.aperture};
+    c.camera_params = camera_params_c(desc.camera_params);
     c.camera_transform = desc.camera_transform;
     c.force_software_bvh = desc.force_software_bvh ? 1u : 0u;
-    c.advanced = LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon};
+    c.advanced = advanced_c(desc.advanced);
 }
 }  // namespace detail
 
@@ -432,7 +452,11 @@ inline void pathtrace_scene_debug(const Device &d, const PathtraceResources &res
     LupinTileParams tp{};
     LupinPathtraceDesc c{};
     detail::fill_desc(desc, ap, tp, c);
-    const LupinDebugVizDesc dd{(uint32_t)debug_desc.viz_type, debug_desc.heatmap_min, debug_desc.heatmap_max, debug_desc.first_hit_only ? 1u : 0u};
+    LupinDebugVizDesc dd{};
+    dd.viz_type = (uint32_t)debug_desc.viz_type;
+    dd.heatmap_min = debug_desc.heatmap_min;
+    dd.heatmap_max = debug_desc.heatmap_max;
+    dd.first_hit_only = debug_desc.first_hit_only ? 1u : 0u;
     check(lupin_hip_pathtrace_scene_debug(d.raw(), res.raw(), scene.raw(), render_target.raw(), &dd, &c));
 }
 
@@ -474,8 +498,12 @@ struct DenoiseDesc
 };
 inline void denoise(const Device &d, DenoiseResources &res, const DenoiseDesc &desc)
 {
-    const LupinDenoiseDesc c{desc.pathtrace_output.raw(), desc.albedo ? desc.albedo->raw() : nullptr, desc.normals ? desc.normals->raw() : nullptr,
-                             desc.denoise_output.raw(), (uint32_t)desc.quality};
+    LupinDenoiseDesc c{};
+    c.pathtrace_output = desc.pathtrace_output.raw();
+    c.albedo = desc.albedo ? desc.albedo->raw() : nullptr;
+    c.normals = desc.normals ? desc.normals->raw() : nullptr;
+    c.denoise_output = desc.denoise_output.raw();
+    c.quality = (uint32_t)desc.quality;
     check(lupin_hip_denoise(d.raw(), res.raw(), &c));
 }
 
@@ -515,7 +543,10 @@ inline void pathtrace_scene_adaptive(const Device &d, const PathtraceResources &
     LupinTileParams tp{};
     LupinPathtraceDesc c{};
     detail::fill_desc(desc, ap, tp, c);
-    const LupinAdaptiveParams p{params.threshold, params.min_frames, params.max_frames};
+    LupinAdaptiveParams p{};
+    p.threshold = params.threshold;
+    p.min_frames = params.min_frames;
+    p.max_frames = params.max_frames;
     check(lupin_hip_pathtrace_scene_adaptive(d.raw(), res.raw(), scene.raw(), render_target.raw(), (uint32_t)type, &c, ares.raw(), &p));
 }
 
@@ -557,8 +588,7 @@ inline void adaptive_reproject(const Device &d, AdaptiveResources &ares, Reproje
                                TextureRef history_in, TextureRef history_out)
 {
     LupinReprojectDesc c{};
-    c.camera_params = LupinCameraParams{desc.camera_params.is_orthographic ? 1u : 0u, desc.camera_params.lens, desc.camera_params.film,
-                                        desc.camera_params.aspect, desc.camera_params.focus, desc.camera_params.aperture};
+    c.camera_params = detail::camera_params_c(desc.camera_params);
     c.camera_transform = desc.camera_transform;
     c.ray_epsilon = desc.ray_epsilon;
     c.depth_tolerance = desc.depth_tolerance;
@@ -580,12 +610,24 @@ struct RayQueryDesc
     uint32_t max_slots = 0;        // paths per wavefront; 0 = the library's default
     AdvancedParams advanced;
 };
+namespace detail {
+inline LupinRayQueryDesc ray_query_desc_c(const RayQueryDesc &desc)
+{
+    LupinRayQueryDesc c{};
+    c.pathtrace_type = (uint32_t)desc.pathtrace_type;
+    c.max_bounces = desc.max_bounces;
+    c.samples = desc.samples;
+    c.flags = desc.flags;
+    c.max_slots = desc.max_slots;
+    c.advanced = advanced_c(desc.advanced);
+    return c;
+}
+}  // namespace detail
 // records: n x 8 floats (origin | RNG bits, direction or normal | mode bits); out: n x 4; out_rays: nullptr or n * samples x 8
 inline void pathtrace_rays(const Device &d, const Scene &scene, const RayQueryDesc &desc, uint64_t n, const float *records, float *out,
                            float *out_rays = nullptr)
 {
-    const LupinRayQueryDesc c{(uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.flags, desc.max_slots,
-                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
+    const LupinRayQueryDesc c = detail::ray_query_desc_c(desc);
     check(lupin_hip_pathtrace_rays(d.raw(), scene.raw(), &c, n, records, out, out_rays));
 }
 
@@ -609,16 +651,41 @@ struct LightmapDesc
     float surface_offset = 0.0f;   // world units along the geometric normal; the caller chooses (> 0)
     AdvancedParams advanced;
 };
+namespace detail {
+inline LupinLightmapDesc lightmap_desc_c(const LightmapDesc &desc)
+{
+    LupinLightmapDesc c{};
+    c.width = desc.width;
+    c.height = desc.height;
+    c.pathtrace_type = (uint32_t)desc.pathtrace_type;
+    c.max_bounces = desc.max_bounces;
+    c.samples = desc.samples;
+    c.max_slots = desc.max_slots;
+    c.flags = desc.flags;
+    c.dilate = desc.dilate;
+    c.counter = desc.counter;
+    c.surface_offset = desc.surface_offset;
+    c.advanced = advanced_c(desc.advanced);
+    return c;
+}
+inline std::vector<LupinLightmapChart> charts_c(const LightmapChart *charts, uint32_t num_charts)
+{
+    std::vector<LupinLightmapChart> cc(num_charts);
+    for (uint32_t k = 0; k < num_charts; k++)
+    {
+        cc[k].instance_idx = charts[k].instance_idx;
+        cc[k].scale_u = charts[k].scale_u; cc[k].scale_v = charts[k].scale_v;
+        cc[k].offset_u = charts[k].offset_u; cc[k].offset_v = charts[k].offset_v;
+    }
+    return cc;
+}
+}  // namespace detail
 // out_rgba: height x width x 4 floats; out_records: nullptr or height x width x 8; returns the number of owned texels
 inline uint64_t bake_lightmap(const Device &d, const Scene &scene, const LightmapDesc &desc, const LightmapChart *charts, uint32_t num_charts,
                               float *out_rgba, float *out_records = nullptr)
 {
-    const LupinLightmapDesc c{desc.width, desc.height, (uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.max_slots, desc.flags,
-                              desc.dilate, desc.counter, desc.surface_offset,
-                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
-    std::vector<LupinLightmapChart> cc(num_charts);
-    for (uint32_t k = 0; k < num_charts; k++)
-        cc[k] = LupinLightmapChart{charts[k].instance_idx, charts[k].scale_u, charts[k].scale_v, charts[k].offset_u, charts[k].offset_v};
+    const LupinLightmapDesc c = detail::lightmap_desc_c(desc);
+    const std::vector<LupinLightmapChart> cc = detail::charts_c(charts, num_charts);
     uint64_t covered = 0;
     check(lupin_hip_bake_lightmap(d.raw(), scene.raw(), &c, cc.data(), num_charts, out_rgba, out_records, &covered));
     return covered;
@@ -631,12 +698,8 @@ inline uint64_t bake_lightmap(const Device &d, const Scene &scene, const Lightma
 inline uint64_t bake_lightmap_directional(const Device &d, const Scene &scene, const LightmapDesc &desc, const LightmapChart *charts,
                                           uint32_t num_charts, float *out_sh, float *out_records = nullptr)
 {
-    const LupinLightmapDesc c{desc.width, desc.height, (uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.max_slots, desc.flags,
-                              desc.dilate, desc.counter, desc.surface_offset,
-                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
-    std::vector<LupinLightmapChart> cc(num_charts);
-    for (uint32_t k = 0; k < num_charts; k++)
-        cc[k] = LupinLightmapChart{charts[k].instance_idx, charts[k].scale_u, charts[k].scale_v, charts[k].offset_u, charts[k].offset_v};
+    const LupinLightmapDesc c = detail::lightmap_desc_c(desc);
+    const std::vector<LupinLightmapChart> cc = detail::charts_c(charts, num_charts);
     uint64_t covered = 0;
     check(lupin_hip_bake_lightmap_directional(d.raw(), scene.raw(), &c, cc.data(), num_charts, out_sh, out_records, &covered));
     return covered;
@@ -646,8 +709,7 @@ inline uint64_t bake_lightmap_directional(const Device &d, const Scene &scene, c
 // of every record's paths: out n x 8 floats (mean r, g, b, 1, the mean luminance, M2 about it, samples, 0).
 inline void pathtrace_rays_moments(const Device &d, const Scene &scene, const RayQueryDesc &desc, uint64_t n, const float *records, float *out)
 {
-    const LupinRayQueryDesc c{(uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.flags, desc.max_slots,
-                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
+    const LupinRayQueryDesc c = detail::ray_query_desc_c(desc);
     check(lupin_hip_pathtrace_rays_moments(d.raw(), scene.raw(), &c, n, records, out));
 }
 // bake_lightmap in rounds of desc.samples paths per texel: a texel stops once the relative standard error of its luminance is
@@ -664,13 +726,13 @@ inline uint64_t bake_lightmap_adaptive(const Device &d, const Scene &scene, cons
                                        const LightmapChart *charts, uint32_t num_charts, float *out_rgba, float *out_stats = nullptr,
                                        float *out_records = nullptr)
 {
-    const LupinLightmapDesc c{desc.width, desc.height, (uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.max_slots, desc.flags,
-                              desc.dilate, desc.counter, desc.surface_offset,
-                              LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
-    const LupinLightmapAdaptiveDesc a{adaptive.threshold, adaptive.min_rounds, adaptive.max_rounds, 0u};
-    std::vector<LupinLightmapChart> cc(num_charts);
-    for (uint32_t k = 0; k < num_charts; k++)
-        cc[k] = LupinLightmapChart{charts[k].instance_idx, charts[k].scale_u, charts[k].scale_v, charts[k].offset_u, charts[k].offset_v};
+    const LupinLightmapDesc c = detail::lightmap_desc_c(desc);
+    LupinLightmapAdaptiveDesc a{};
+    a.threshold = adaptive.threshold;
+    a.min_rounds = adaptive.min_rounds;
+    a.max_rounds = adaptive.max_rounds;
+    a.flags = 0u;
+    const std::vector<LupinLightmapChart> cc = detail::charts_c(charts, num_charts);
     uint64_t covered = 0;
     check(lupin_hip_bake_lightmap_adaptive(d.raw(), scene.raw(), &c, &a, cc.data(), num_charts, out_rgba, out_stats, out_records, &covered));
     return covered;
@@ -701,11 +763,18 @@ struct LightmapAoDesc
 inline uint64_t bake_lightmap_ao(const Device &d, const Scene &scene, const LightmapAoDesc &desc, const LightmapChart *charts, uint32_t num_charts,
                                  float *out_ao, float *out_bent = nullptr, float *out_records = nullptr)
 {
-    const LupinLightmapAoDesc c{desc.width, desc.height, desc.samples, desc.max_slots, desc.flags, desc.dilate, desc.counter, desc.surface_offset,
-                                desc.max_distance, desc.ray_epsilon};
-    std::vector<LupinLightmapChart> cc(num_charts);
-    for (uint32_t k = 0; k < num_charts; k++)
-        cc[k] = LupinLightmapChart{charts[k].instance_idx, charts[k].scale_u, charts[k].scale_v, charts[k].offset_u, charts[k].offset_v};
+    LupinLightmapAoDesc c{};
+    c.width = desc.width;
+    c.height = desc.height;
+    c.samples = desc.samples;
+    c.max_slots = desc.max_slots;
+    c.flags = desc.flags;
+    c.dilate = desc.dilate;
+    c.counter = desc.counter;
+    c.surface_offset = desc.surface_offset;
+    c.max_distance = desc.max_distance;
+    c.ray_epsilon = desc.ray_epsilon;
+    const std::vector<LupinLightmapChart> cc = detail::charts_c(charts, num_charts);
     uint64_t covered = 0;
     check(lupin_hip_bake_lightmap_ao(d.raw(), scene.raw(), &c, cc.data(), num_charts, out_ao, out_bent, out_records, &covered));
     return covered;
@@ -724,7 +793,14 @@ struct LightmapDenoiseDesc
 };
 inline void denoise_lightmap(const Device &d, const LightmapDenoiseDesc &desc, const float *rgba, const float *records, float *out_rgba)
 {
-    const LupinLightmapDenoiseDesc c{desc.width, desc.height, desc.passes, desc.normal_squarings, desc.dilate, desc.flags, desc.max_stretch};
+    LupinLightmapDenoiseDesc c{};
+    c.width = desc.width;
+    c.height = desc.height;
+    c.passes = desc.passes;
+    c.normal_squarings = desc.normal_squarings;
+    c.dilate = desc.dilate;
+    c.flags = desc.flags;
+    c.max_stretch = desc.max_stretch;
     check(lupin_hip_denoise_lightmap(d.raw(), &c, rgba, records, out_rgba));
 }
 
@@ -742,8 +818,13 @@ struct ProbeDesc
 inline void bake_probes(const Device &d, const Scene &scene, const ProbeDesc &desc, uint64_t n, const float *probes, float *out_sh,
                         float *out_rays = nullptr)
 {
-    const LupinProbeDesc c{(uint32_t)desc.pathtrace_type, desc.max_bounces, desc.samples, desc.flags, desc.max_slots,
-                           LupinAdvancedParams{desc.advanced.max_radiance, desc.advanced.rng_seed, desc.advanced.ray_epsilon}};
+    LupinProbeDesc c{};
+    c.pathtrace_type = (uint32_t)desc.pathtrace_type;
+    c.max_bounces = desc.max_bounces;
+    c.samples = desc.samples;
+    c.flags = desc.flags;
+    c.max_slots = desc.max_slots;
+    c.advanced = detail::advanced_c(desc.advanced);
     check(lupin_hip_bake_probes(d.raw(), scene.raw(), &c, n, probes, out_sh, out_rays));
 }
 // Irradiance (r, g, b) at a surface with unit normal n from one probe's 9 x 4 coefficients: Ramamoorthi-Hanrahan, the clamped
@@ -770,29 +851,50 @@ struct OcclusionDesc
     uint32_t flags = 0;            // LUPIN_OCCLUSION_DEVICE_POINTERS: records and out_blocked are device memory
     float ray_epsilon = 0.001f;
 };
+namespace detail {
+inline LupinOcclusionDesc occlusion_desc_c(const OcclusionDesc &desc)
+{
+    LupinOcclusionDesc c{};
+    c.mode = (uint32_t)desc.mode;
+    c.samples = desc.samples;
+    c.flags = desc.flags;
+    c.ray_epsilon = desc.ray_epsilon;
+    return c;
+}
+}  // namespace detail
 // records: n x 8 floats (origin | RNG bits, unit direction or normal | tmax); out_blocked: n counts of blocked slots
 inline void occlusion_rays(const Device &d, const Scene &scene, const OcclusionDesc &desc, uint64_t n, const float *records, uint32_t *out_blocked)
 {
-    const LupinOcclusionDesc c{(uint32_t)desc.mode, desc.samples, desc.flags, desc.ray_epsilon};
+    const LupinOcclusionDesc c = detail::occlusion_desc_c(desc);
     check(lupin_hip_occlusion_rays(d.raw(), scene.raw(), &c, n, records, out_blocked));
 }
-// Whether nothing lies between p[i] and q[i] (n x 3 floats each), in f32: dir = (q - p) / len, tmax = len - ray_epsilon.
-// A pair no further apart than 2 * ray_epsilon is refused (std::invalid_argument).
-inline std::vector<uint8_t> visible(const Device &d, const Scene &scene, uint64_t n, const float *p, const float *q, float ray_epsilon = 0.001f)
+// Direction-mode records of the segments p[i] -> q[i] (n x 3 floats each), in f32: d = q - p, len = sqrt((dx dx + dy dy) + dz dz),
+// dir = d / len, tmax = len - ray_epsilon (the far end point's own surface does not block).  A pair no further apart than
+// 2 * ray_epsilon is refused (std::invalid_argument, `who` names the caller) before anything touches the device.
+inline std::vector<float> segment_records(uint64_t n, const float *p, const float *q, float ray_epsilon, const char *who = "lp::segment_records")
 {
     std::vector<float> rec(n * LUPIN_OCCLUSION_RECORD_FLOATS, 0.0f);
     for (uint64_t i = 0; i < n; i++)
     {
         const float dx = q[3 * i] - p[3 * i], dy = q[3 * i + 1] - p[3 * i + 1], dz = q[3 * i + 2] - p[3 * i + 2];
         const float len = std::sqrt((dx * dx + dy * dy) + dz * dz);
-        if (!(len > 2.0f * ray_epsilon)) throw std::invalid_argument("lp::visible: a segment is not longer than 2 * ray_epsilon");
+        if (!(len > 2.0f * ray_epsilon)) throw std::invalid_argument(std::string(who) + ": a segment is not longer than 2 * ray_epsilon");
         float *r = &rec[i * LUPIN_OCCLUSION_RECORD_FLOATS];
         r[0] = p[3 * i]; r[1] = p[3 * i + 1]; r[2] = p[3 * i + 2];
         r[4] = dx / len; r[5] = dy / len; r[6] = dz / len;
         r[7] = len - ray_epsilon;
     }
+    return rec;
+}
+// Whether nothing lies between p[i] and q[i] (n x 3 floats each); the segments are segment_records'.
+inline std::vector<uint8_t> visible(const Device &d, const Scene &scene, uint64_t n, const float *p, const float *q, float ray_epsilon = 0.001f)
+{
+    const std::vector<float> rec = segment_records(n, p, q, ray_epsilon, "lp::visible");
     std::vector<uint32_t> blocked(n, 0u);
     OcclusionDesc desc;
+    desc.mode = OcclusionMode::Direction;
+    desc.samples = 1;
+    desc.flags = 0;
     desc.ray_epsilon = ray_epsilon;
     occlusion_rays(d, scene, desc, n, rec.data(), blocked.data());
     std::vector<uint8_t> out(n);
@@ -814,7 +916,12 @@ inline std::vector<float> ambient_occlusion(const Device &d, const Scene &scene,
         r[7] = radius;
     }
     std::vector<uint32_t> blocked(n, 0u);
-    occlusion_rays(d, scene, OcclusionDesc{OcclusionMode::CosineHemisphere, samples, 0u, ray_epsilon}, n, rec.data(), blocked.data());
+    OcclusionDesc desc;
+    desc.mode = OcclusionMode::CosineHemisphere;
+    desc.samples = samples;
+    desc.flags = 0;
+    desc.ray_epsilon = ray_epsilon;
+    occlusion_rays(d, scene, desc, n, rec.data(), blocked.data());
     std::vector<float> out(n);
     for (uint64_t i = 0; i < n; i++) out[i] = 1.0f - (float)blocked[i] / (float)samples;
     return out;
@@ -825,7 +932,7 @@ inline std::vector<float> ambient_occlusion(const Device &d, const Scene &scene,
 // met): the expected result of the integrators' stochastic alpha skip.  The caller divides by samples.
 inline void transmittance_rays(const Device &d, const Scene &scene, const OcclusionDesc &desc, uint64_t n, const float *records, float *out_sum)
 {
-    const LupinOcclusionDesc c{(uint32_t)desc.mode, desc.samples, desc.flags, desc.ray_epsilon};
+    const LupinOcclusionDesc c = detail::occlusion_desc_c(desc);
     check(lupin_hip_transmittance_rays(d.raw(), scene.raw(), &c, n, records, out_sum));
 }
 // bent-normal queries (no reference counterpart): hemisphere-mode occlusion records; out: n x 4 floats, per
@@ -840,25 +947,22 @@ struct BentNormalDesc
 };
 inline void bent_normal_rays(const Device &d, const Scene &scene, const BentNormalDesc &desc, uint64_t n, const float *records, float *out)
 {
-    const LupinBentNormalDesc c{desc.samples, desc.flags, desc.max_slots, desc.ray_epsilon};
+    LupinBentNormalDesc c{};
+    c.samples = desc.samples;
+    c.flags = desc.flags;
+    c.max_slots = desc.max_slots;
+    c.ray_epsilon = desc.ray_epsilon;
     check(lupin_hip_bent_normal_rays(d.raw(), scene.raw(), &c, n, records, out));
 }
-// The transmittance between p[i] and q[i] (n x 3 floats each); the segments are lp::visible's.
+// The transmittance between p[i] and q[i] (n x 3 floats each); the segments are segment_records'.
 inline std::vector<float> transmittance(const Device &d, const Scene &scene, uint64_t n, const float *p, const float *q, float ray_epsilon = 0.001f)
 {
-    std::vector<float> rec(n * LUPIN_OCCLUSION_RECORD_FLOATS, 0.0f);
-    for (uint64_t i = 0; i < n; i++)
-    {
-        const float dx = q[3 * i] - p[3 * i], dy = q[3 * i + 1] - p[3 * i + 1], dz = q[3 * i + 2] - p[3 * i + 2];
-        const float len = std::sqrt((dx * dx + dy * dy) + dz * dz);
-        if (!(len > 2.0f * ray_epsilon)) throw std::invalid_argument("lp::transmittance: a segment is not longer than 2 * ray_epsilon");
-        float *r = &rec[i * LUPIN_OCCLUSION_RECORD_FLOATS];
-        r[0] = p[3 * i]; r[1] = p[3 * i + 1]; r[2] = p[3 * i + 2];
-        r[4] = dx / len; r[5] = dy / len; r[6] = dz / len;
-        r[7] = len - ray_epsilon;
-    }
+    const std::vector<float> rec = segment_records(n, p, q, ray_epsilon, "lp::transmittance");
     std::vector<float> out(n, 0.0f);
     OcclusionDesc desc;
+    desc.mode = OcclusionMode::Direction;
+    desc.samples = 1;
+    desc.flags = 0;
     desc.ray_epsilon = ray_epsilon;
     transmittance_rays(d, scene, desc, n, rec.data(), out.data());
     return out;
@@ -887,7 +991,8 @@ inline std::vector<float> bake_distance_grid(const Device &d, const Scene &scene
                                              const std::array<uint32_t, 3> &dims, float rmax = std::numeric_limits<float>::infinity(), bool is_signed = false)
 {
     std::vector<float> out((size_t)dims[0] * dims[1] * dims[2]);
-    check(lupin_hip_bake_distance_grid(d.raw(), scene.raw(), is_signed ? LUPIN_DISTANCE_GRID_SIGNED : 0u, origin.data(), spacing.data(), dims.data(), rmax, out.data()));
+    const uint32_t flags = is_signed ? (uint32_t)LUPIN_DISTANCE_GRID_SIGNED : 0u;
+    check(lupin_hip_bake_distance_grid(d.raw(), scene.raw(), flags, origin.data(), spacing.data(), dims.data(), rmax, out.data()));
     return out;
 }
 
@@ -1018,7 +1123,12 @@ inline void render_lightmapped(const Device &d, const Scene &scene, TextureRef r
                                const std::vector<LupinLightmapChart> &charts, const float *lightmap, uint32_t lightmap_width, uint32_t lightmap_height,
                                const float *sh = nullptr, const float *depth = nullptr, const uint8_t *valid = nullptr, float *out_gbuffer = nullptr)
 {
-    const LupinLightmappedViewDesc c{baked_view_desc_c(view), lightmap_width, lightmap_height, (uint32_t)charts.size(), 0u};
+    LupinLightmappedViewDesc c{};
+    c.view = baked_view_desc_c(view);
+    c.lightmap_width = lightmap_width;
+    c.lightmap_height = lightmap_height;
+    c.num_charts = (uint32_t)charts.size();
+    c.reserved = 0u;
     check(lupin_hip_render_lightmapped(d.raw(), scene.raw(), render_target.raw(), &c, charts.empty() ? nullptr : charts.data(), lightmap, sh, depth, valid,
                                        out_gbuffer));
 }
@@ -1031,7 +1141,13 @@ inline void render_lightmapped_directional(const Device &d, const Scene &scene, 
                                            uint32_t lightmap_width, uint32_t lightmap_height, uint32_t bake_flags = 0, const float *sh = nullptr,
                                            const float *depth = nullptr, const uint8_t *valid = nullptr, float *out_gbuffer = nullptr)
 {
-    const LupinLightmappedDirectionalDesc c{{baked_view_desc_c(view), lightmap_width, lightmap_height, (uint32_t)charts.size(), 0u}, bake_flags, {0u, 0u, 0u}};
+    LupinLightmappedDirectionalDesc c{};
+    c.base.view = baked_view_desc_c(view);
+    c.base.lightmap_width = lightmap_width;
+    c.base.lightmap_height = lightmap_height;
+    c.base.num_charts = (uint32_t)charts.size();
+    c.base.reserved = 0u;
+    c.bake_flags = bake_flags;
     check(lupin_hip_render_lightmapped_directional(d.raw(), scene.raw(), render_target.raw(), &c, charts.empty() ? nullptr : charts.data(), lightmap,
                                                    directional, sh, depth, valid, out_gbuffer));
 }
