@@ -235,6 +235,9 @@ class Scene   // lp::Scene, software-BVH configuration (renderer.rs:17-60)
     {
         check(lupin_hip_scene_update_instances(scene_, transpose_inverse_transforms.data(), (uint32_t)transpose_inverse_transforms.size(), device_tlas ? 1 : 0));
     }
+    // Gives a mesh a lightmap UV set (lupin_hip_scene_set_lightmap_uvs): one (u, v) per triangle corner in the
+    // scene's own triangle order, 6 floats a triangle; nullptr removes it.  lp::unwrap_lightmap_uvs (lupin_unwrap.hpp) makes one.
+    void set_lightmap_uvs(uint32_t mesh_idx, const float *uvs, uint64_t num_corners) { check(lupin_hip_scene_set_lightmap_uvs(scene_, mesh_idx, uvs, num_corners)); }
     LupinScene *scene_ = nullptr;
 };
 

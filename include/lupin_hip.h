@@ -1116,6 +1116,85 @@ typedef struct LupinLightmapAdaptiveStats {
 } LupinLightmapAdaptiveStats;
 void lupin_hip_lightmap_adaptive_stats(LupinLightmapAdaptiveStats *out);
 
+/* ---- lightmap UV sets: a second UV set per mesh, and its generation (no reference counterpart) ----
+ * A mesh may carry a LIGHTMAP UV SET beside its material texcoords: one UV per triangle CORNER (3 * triangles float pairs, in
+ * the scene's own triangle order), per corner because a vertex on a chart seam needs two coordinates and vertices are not
+ * split.  Where the mesh of a chart's instance has a set, every lightmap consumer (lupin_hip_bake_lightmap and its _ao,
+ * _directional and _adaptive variants, lupin_hip_render_lightmapped and its _directional variant) takes corner k of
+ * triangle t from lm_uvs[3 * t + k] in place of texcoords[index_k]; nothing else about rasterisation, ownership, records, the
+ * view's fetch or a chart's scale and offset changes, and material evaluation (albedo, normal maps, opacity) keeps reading
+ * the material texcoords.  "A mesh without texcoords" is refused only for a mesh that has neither.
+ *
+ * lupin_hip_scene_set_lightmap_uvs copies num_corners float pairs to the device (uvs == NULL removes the mesh's set;
+ * num_corners is then not looked at).  Non-finite values are allowed: the rasteriser's rule skips such triangles.  Ordering as
+ * lupin_hip_scene_update_instances: recorded calls run first and see the previous set.  LUPIN_ERR_INVALID_ARGUMENT, the
+ * scene untouched, for a NULL scene, a mesh index out of range, a num_corners that is not three times the mesh's triangle
+ * count. */
+int lupin_hip_scene_set_lightmap_uvs(LupinScene *scene, uint32_t mesh_idx, const float *uvs /* num_corners x 2, or NULL */,
+                                     uint64_t num_corners);
+/* The triangle count of a mesh, as the scene holds it: what sizes a lightmap UV set and lupin_hip_unwrap_lightmap_uvs' outputs.
+ * LUPIN_ERR_INVALID_ARGUMENT for a NULL scene or a mesh index out of range.  Needs no device. */
+int64_t lupin_hip_scene_mesh_triangle_count(const LupinScene *scene, uint32_t mesh_idx);
+
+/* lupin_hip_unwrap_lightmap_uvs generates such a set on the device, from the mesh's local positions and indices where they
+ * already live in device memory, and writes host arrays; it does not attach the result.  The unit of the UVs is the texel of
+ * the mesh's own atlas of out_info->width x height texels, so a chart with scale = m / W and offset = X / W places the mesh
+ * at texel X of a W-wide atlas at m times the resolution.  Every float operation is one rounded f32 operation without
+ * contraction, IEEE division; tests/lightmap_unwrap_ref.py restates the rule.
+ *
+ * Classify.  With p0, p1, p2 the triangle's local positions, a = p1 - p0, b = p2 - p0,
+ *   n = (a.y*b.z - a.z*b.y,  a.z*b.x - a.x*b.z,  a.x*b.y - a.y*b.x).
+ * The bucket is the axis k of the largest |n_k|, a tie going to the lower axis (x before y before z), with sign + when
+ * n_k >= 0: six buckets.  A triangle whose n has a non-finite component or is all zero is DEGENERATE: its chart is
+ * LUPIN_UNWRAP_NO_CHART, its UVs are 0 (the rasteriser skips zero area), and it is counted in degenerate_tris.
+ *
+ * Charts.  Two triangles are linked when they are in the same bucket and share a vertex INDEX; a chart is a connected
+ * component.  Its label is the smallest triangle index in it, its dense number (out_chart_of_tri) the rank of its label.
+ * (Device: atomicMin of the triangle index on a (bucket, vertex) table of 6 * V words, then a lock-free union-find that
+ * always hooks the larger root under the smaller, then a flatten pass: the labels do not depend on scheduling.)
+ *
+ * Project.  For axis k the plane coordinates of a point p are (s, t) = (p[(k+1)%3] + 0.0f, p[(k+2)%3] + 0.0f), swapped for a
+ * negative bucket: every non-degenerate triangle has positive area in the plane, no chart is mirrored.  (+ 0.0f: -0 is +0.)
+ *
+ * Rectangles.  Per chart the exact min and max of s and of t over its corners; extent = ceilf((max - min) / texel_size), at
+ * least 1, per axis; the chart's rectangle is extent + 2 * padding on each side.
+ *
+ * Pack (host, integers; include/lupin_pack.hpp).  Charts sorted by rectangle height descending, then width descending, then
+ * label ascending.  Atlas width = max(widest rectangle, isqrt_ceil(sum of rectangle areas)); rectangles are placed left to
+ * right, a new shelf opens when the next rectangle would cross the width; the height is the bottom of the last shelf.
+ *
+ * UVs.  Corner uv = ((float)(rect.x + padding) + (s - min_s) / texel_size,  (float)(rect.y + padding) + (t - min_t) / texel_size).
+ *
+ * Known limits.  A chart is a height field over its plane only locally: a helicoid-like patch can overlap itself, and the
+ * rasteriser's smallest-key rule then decides who owns the texel.  A mesh with duplicated vertices per face falls into one
+ * chart per face.  Stretch reaches sqrt(3) in area at a (1,1,1) normal.  Non-uniform instance scale distorts density.
+ *
+ * Ordering as lupin_hip_pathtrace_rays: recorded calls run first, the call returns when the outputs are complete.
+ * LUPIN_ERR_INVALID_ARGUMENT with the outputs untouched for: a NULL argument (out_chart_of_tri may be NULL); a mesh index out
+ * of range; a texel_size that is not finite and positive; padding above LUPIN_UNWRAP_MAX_PADDING; a non-zero flags; an atlas
+ * wider or higher than LUPIN_LIGHTMAP_MAX_SIZE.  A mesh without a non-degenerate triangle: LUPIN_OK, 0 charts, 0 x 0.
+ * Without a HIP device: LUPIN_ERR_NO_DEVICE. */
+#define LUPIN_UNWRAP_MAX_PADDING 16u
+#define LUPIN_UNWRAP_NO_CHART 0xFFFFFFFFu
+typedef struct LupinUnwrapDesc {
+    float texel_size;               /* local units per texel; finite, > 0 */
+    uint32_t padding;               /* texels around every chart, 0 .. LUPIN_UNWRAP_MAX_PADDING */
+    uint32_t flags;                 /* 0 */
+} LupinUnwrapDesc;
+typedef struct LupinUnwrapInfo {
+    uint32_t num_charts;
+    uint32_t width;                 /* the mesh's own atlas, texels */
+    uint32_t height;
+    uint32_t degenerate_tris;
+    float charts_ms;                /* host-clock milliseconds (each phase ends synchronised): classify, union, flatten */
+    float rects_ms;                 /* count, scan, compact, and the charts' boxes to the host */
+    float pack_ms;                  /* the host's rectangles and shelf packer */
+    float uvs_ms;                   /* the origins to the device, the UVs, and the results to the host */
+} LupinUnwrapInfo;
+int lupin_hip_unwrap_lightmap_uvs(LupinContext *ctx, const LupinScene *scene, uint32_t mesh_idx, const LupinUnwrapDesc *desc,
+                                  float *out_uvs /* tris*3*2 */, uint32_t *out_chart_of_tri /* NULL, or tris */,
+                                  LupinUnwrapInfo *out_info);
+
 /* ---- lightmap denoising (no reference counterpart) ----
  * An edge-avoiding a-trous filter in atlas space for what lupin_hip_bake_lightmap writes: `rgba` is its out_rgba (or several
  * bakes with different `counter`, averaged by the caller), `records` its out_records.  No scene is needed.  Texel p is

@@ -106,6 +106,16 @@ pub const LUPIN_LIGHTMAP_ADAPTIVE_STATS_FLOATS: usize = 4;
     pub covered_texels: u64, pub paths: u64, pub converged_texels: u64, pub capped_texels: u64, pub rounds: u32, pub keys: u32,
     pub raster_ms: f32, pub compact_ms: f32, pub trace_ms: f32, pub merge_mask_ms: f32, pub scatter_dilate_ms: f32, pub download_ms: f32,
 }
+// lightmap UV sets and their generation (no reference counterpart)
+pub const LUPIN_UNWRAP_MAX_PADDING: u32 = 16;
+pub const LUPIN_UNWRAP_NO_CHART: u32 = 0xFFFF_FFFF;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinUnwrapDesc {
+    pub texel_size: f32, pub padding: u32, pub flags: u32,
+}
+#[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinUnwrapInfo {
+    pub num_charts: u32, pub width: u32, pub height: u32, pub degenerate_tris: u32,
+    pub charts_ms: f32, pub rects_ms: f32, pub pack_ms: f32, pub uvs_ms: f32,
+}
 // lightmap denoising (no reference counterpart)
 pub const LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS: u32 = 1;
 pub const LUPIN_LIGHTMAP_DENOISE_MAX_PASSES: u32 = 8;
@@ -335,6 +345,12 @@ extern "C" {
                                             ad: *const LupinLightmapAdaptiveDesc, charts: *const LupinLightmapChart, num_charts: u32,
                                             out_rgba: *mut f32, out_stats: *mut f32, out_records: *mut f32, out_num_covered: *mut u64) -> c_int;
     pub fn lupin_hip_lightmap_adaptive_stats(out: *mut LupinLightmapAdaptiveStats);
+    // lightmap UV sets: uvs num_corners x 2 f32 (one per triangle corner) or null to remove the set
+    pub fn lupin_hip_scene_set_lightmap_uvs(scene: *mut LupinScene, mesh_idx: u32, uvs: *const f32, num_corners: u64) -> c_int;
+    pub fn lupin_hip_scene_mesh_triangle_count(scene: *const LupinScene, mesh_idx: u32) -> i64;
+    // out_uvs triangles x 3 x 2 f32 in texels of the mesh's own atlas, out_chart_of_tri null or triangles u32
+    pub fn lupin_hip_unwrap_lightmap_uvs(ctx: *mut LupinContext, scene: *const LupinScene, mesh_idx: u32, desc: *const LupinUnwrapDesc,
+                                         out_uvs: *mut f32, out_chart_of_tri: *mut u32, out_info: *mut LupinUnwrapInfo) -> c_int;
     // host-side builders with the results of lupin/src/data_structures.rs
     pub fn lupin_build_bvh(verts_pos4: *const f32, num_verts: u32, indices: *mut u32, num_indices: u32, out_nodes: *mut LupinBvhNode, cap: u64) -> i64;
     // the same tree built on the GPU (csrc/sahbvh.hip); cap = 2 * triangles - 1 always suffices

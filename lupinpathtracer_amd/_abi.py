@@ -180,6 +180,15 @@ class LightmapAdaptiveStatsC(C.Structure):   # LupinLightmapAdaptiveStats
                 ("merge_mask_ms", C.c_float), ("scatter_dilate_ms", C.c_float), ("download_ms", C.c_float)]
 
 
+class UnwrapDescC(C.Structure):   # LupinUnwrapDesc
+    _fields_ = [("texel_size", C.c_float), ("padding", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class UnwrapInfoC(C.Structure):   # LupinUnwrapInfo
+    _fields_ = [("num_charts", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("degenerate_tris", C.c_uint32),
+                ("charts_ms", C.c_float), ("rects_ms", C.c_float), ("pack_ms", C.c_float), ("uvs_ms", C.c_float)]
+
+
 class LightmapDenoiseDescC(C.Structure):   # LupinLightmapDenoiseDesc
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("passes", C.c_uint32), ("normal_squarings", C.c_uint32),
                 ("dilate", C.c_uint32), ("flags", C.c_uint32), ("max_stretch", C.c_float)]
@@ -321,6 +330,9 @@ SYMBOLS = [
     ("lupin_hip_bake_lightmap_adaptive", C.c_int,
      [_P, _P, C.POINTER(LightmapDescC), C.POINTER(LightmapAdaptiveDescC), C.POINTER(LightmapChartC), _U32, _P, _P, _P, C.POINTER(C.c_uint64)]),
     ("lupin_hip_lightmap_adaptive_stats", None, [C.POINTER(LightmapAdaptiveStatsC)]),
+    ("lupin_hip_scene_set_lightmap_uvs", C.c_int, [_P, _U32, _P, C.c_uint64]),
+    ("lupin_hip_scene_mesh_triangle_count", C.c_int64, [_P, _U32]),
+    ("lupin_hip_unwrap_lightmap_uvs", C.c_int, [_P, _P, _U32, C.POINTER(UnwrapDescC), _P, _P, C.POINTER(UnwrapInfoC)]),
     ("lupin_hip_distance_points", C.c_int, [_P, _P, _U32, C.c_uint64, _P, _P]),
     ("lupin_hip_bake_distance_grid", C.c_int, [_P, _P, _U32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_float, _P]),
     ("lupin_hip_sample_probe_grid", C.c_int, [_P, _P, C.POINTER(ProbeGridDescC), _P, _P, C.c_uint64, _P, _P]),

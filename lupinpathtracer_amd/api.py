@@ -23,6 +23,7 @@ Where the reference panics (assert!/panic!), these raise (`LupinError` for ABI e
 `AssertionError`/`ValueError` for host-side validation).
 """
 import ctypes as C
+import math
 import os
 import enum
 from dataclasses import dataclass, field
@@ -626,6 +627,48 @@ class Scene:
         self.desc.instances = ptr(instances)
         self.desc.tlas_nodes = ptr(tlas) if len(tlas) else None
         self.desc.num_tlas_nodes = len(tlas)
+
+    def mesh_triangle_count(self, mesh_idx):
+        """Triangles of mesh `mesh_idx`, from the descriptor the scene was created with."""
+        if not 0 <= int(mesh_idx) < int(self.desc.num_meshes):
+            raise LupinError(_abi_code("LUPIN_ERR_INVALID_ARGUMENT"), "mesh index out of range")
+        return int(self.desc.meshes[int(mesh_idx)].num_indices) // 3
+
+    def set_lightmap_uvs(self, mesh_idx, uvs):
+        """Give mesh `mesh_idx` a lightmap UV set (lupin_hip_scene_set_lightmap_uvs): `uvs` holds one UV per
+        triangle corner, (3 * triangles, 2) or (triangles, 3, 2) float32, in the scene's own triangle order; None removes
+        the set.  Every lightmap bake and the lightmapped views then place the instances of this mesh by the set instead of
+        its material texcoords; materials keep reading the texcoords.  Calls recorded before run first.  On an error the
+        scene keeps the set it had."""
+        if self.handle is None:
+            raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "scene was built without a device context; there is no CPU fallback")
+        if uvs is None:
+            check(lib().lupin_hip_scene_set_lightmap_uvs(self.handle, int(mesh_idx), None, 0))
+            return
+        a = np.ascontiguousarray(uvs, np.float32)
+        if a.size % 2:
+            raise ValueError("uvs must hold float pairs")
+        check(lib().lupin_hip_scene_set_lightmap_uvs(self.handle, int(mesh_idx), ptr(a), a.size // 2))
+
+    def unwrap_lightmap_uvs(self, mesh_idx, texel_size, padding=2, attach=True, want_charts=False):
+        """Generate a lightmap UV set for mesh `mesh_idx` on the device (lupin_hip_unwrap_lightmap_uvs) and, with `attach`,
+        give it to the mesh (set_lightmap_uvs).  texel_size: local units per texel; padding: texels around every chart.
+        Returns (uvs, info) or (uvs, chart_of_tri, info): uvs (triangles, 3, 2) float32 in texels of the mesh's own atlas of
+        info["width"] x info["height"] texels; chart_of_tri uint32 (UNWRAP_NO_CHART for a degenerate triangle)."""
+        if self.handle is None or self.ctx is None:
+            raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "scene was built without a device context; there is no CPU fallback")
+        tris = int(lib().lupin_hip_scene_mesh_triangle_count(self.handle, int(mesh_idx)))      # the scene's own count sizes the outputs
+        if tris < 0:
+            check(tris)
+        uvs = np.zeros((tris, 3, 2), np.float32)
+        chart = np.zeros(tris, np.uint32)
+        d = _abi.UnwrapDescC(float(texel_size), int(padding), 0)
+        info = _abi.UnwrapInfoC()
+        check(lib().lupin_hip_unwrap_lightmap_uvs(self.ctx.handle, self.handle, int(mesh_idx), C.byref(d), ptr(uvs), ptr(chart), C.byref(info)))
+        if attach:
+            self.set_lightmap_uvs(mesh_idx, uvs)
+        out = {k: (float if k.endswith("_ms") else int)(getattr(info, k)) for k, _ in _abi.UnwrapInfoC._fields_}
+        return (uvs, chart, out) if want_charts else (uvs, out)
 
     def __del__(self):
         try:
@@ -1559,6 +1602,71 @@ def bake_lightmap(ctx, scene, charts, width, height, samples=64, pathtrace_type=
     rec = np.zeros((int(height), int(width), RAY_RECORD_FLOATS) if shape_ok else (1, 1, RAY_RECORD_FLOATS), np.float32) if want_records else None
     check(lib().lupin_hip_bake_lightmap(ctx.handle, scene.handle, C.byref(d), c_charts, len(items), ptr(out), ptr(rec), None))
     return (out, rec) if want_records else out
+
+
+# ---- lightmap UV sets: Scene.set_lightmap_uvs, Scene.unwrap_lightmap_uvs, the shelf packer (include/lupin_pack.hpp) ----
+UNWRAP_MAX_PADDING = 16
+UNWRAP_NO_CHART = 0xFFFFFFFF
+
+
+def isqrt_ceil(n):
+    """The smallest r with r * r >= n."""
+    r = math.isqrt(int(n))
+    return r if r * r == int(n) else r + 1
+
+
+def shelf_pack(sizes):
+    """include/lupin_pack.hpp's shelf packer, in integers.  sizes: (w, h) per rectangle; its index is its label.
+    Rectangles sorted by height descending, then width descending, then label ascending; the atlas is
+    max(widest, isqrt_ceil(sum of areas)) wide; placed left to right, a new shelf opens when the next rectangle would cross
+    the width; the height is the bottom of the last shelf.  Returns (width, height, [(x, y) per rectangle])."""
+    rects = [(int(w), int(h)) for w, h in sizes]
+    order = sorted(range(len(rects)), key=lambda i: (-rects[i][1], -rects[i][0], i))
+    width = max([w for w, _ in rects] + [isqrt_ceil(sum(w * h for w, h in rects))])
+    place = [None] * len(rects)
+    x = y = shelf = 0
+    for i in order:
+        w, h = rects[i]
+        if x + w > width:
+            y, x, shelf = y + shelf, 0, 0
+        place[i] = (x, y)
+        x += w
+        shelf = max(shelf, h)
+    return width, y + shelf, place
+
+
+def pack_lightmap_instances(sizes, multipliers, gutter=2):
+    """Place instances in one atlas, on the host: (width, height, [LightmapChart per entry]).  sizes: per entry the (width,
+    height) in texels of its mesh's own atlas (unwrap_lightmap_uvs' info); multipliers: per entry the resolution m relative
+    to that atlas; gutter: texels kept free around every entry.  Entry i gets the rectangle ceil(size * m) + 2 * gutter per
+    side (the product one f32 operation), the rectangles go through shelf_pack, and its chart is instance_idx = i,
+    scale = (m / W, m / H), offset = ((x + gutter) / W, (y + gutter) / H), each one f32 division: the unit of the mesh's
+    lightmap UVs is a texel of its own atlas.  ValueError for a multiplier that is not finite and positive, a size of 0, or
+    a rectangle or an atlas above LIGHTMAP_MAX_SIZE."""
+    f32 = np.float32
+    ms = [f32(m) for m in multipliers]
+    if len(ms) != len(sizes):
+        raise ValueError("one multiplier per size")
+    gutter = int(gutter)
+    if not 0 <= gutter <= LIGHTMAP_MAX_SIZE:
+        raise ValueError("gutter out of range")
+    rects = []
+    for (w, h), m in zip(sizes, ms):
+        side = []
+        for s in (int(w), int(h)):
+            if not (np.isfinite(m) and m > 0) or not 0 < s <= LIGHTMAP_MAX_SIZE:
+                raise ValueError("sizes must be in [1, LIGHTMAP_MAX_SIZE] and multipliers finite and positive")
+            c = np.ceil(f32(s) * m)
+            if not c <= LIGHTMAP_MAX_SIZE or max(int(c), 1) + 2 * gutter > LIGHTMAP_MAX_SIZE:
+                raise ValueError("a placed instance is larger than LIGHTMAP_MAX_SIZE")
+            side.append(max(int(c), 1) + 2 * gutter)
+        rects.append(tuple(side))
+    width, height, place = shelf_pack(rects)
+    if width > LIGHTMAP_MAX_SIZE or height > LIGHTMAP_MAX_SIZE:
+        raise ValueError("the atlas is larger than LIGHTMAP_MAX_SIZE")
+    charts = [LightmapChart(i, float(m / f32(width)), float(m / f32(height)), float(f32(x + gutter) / f32(width)), float(f32(y + gutter) / f32(height)))
+              for i, ((x, y), m) in enumerate(zip(place, ms))]
+    return width, height, charts
 
 
 # ---- lightmap denoising: lupin_hip_denoise_lightmap (include/lupin_hip.h, DESIGN.md 22) ----

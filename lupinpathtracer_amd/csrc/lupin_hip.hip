@@ -34,6 +34,7 @@
 #include "lupin_lightmap_directional.hpp"
 #include "lupin_lightmap_adaptive.hpp"
 #include "lupin_lightmap_denoise.hpp"
+#include "lupin_unwrap.hpp"
 #include "lupin_occlusion.hpp"
 #include "lupin_transmittance.hpp"
 #include "lupin_bent_normal.hpp"
@@ -43,6 +44,7 @@
 #include "lupin_baked_view.hpp"
 #include "lupin_lightmapped_view.hpp"
 #include "lupin_internal.hpp"
+#include "../../include/lupin_pack.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // Host side
@@ -211,7 +213,11 @@ struct LupinScene
     std::vector<InstanceDev> host_instances;        // as uploaded (mesh_idx, mat_idx, blas_root and flags never change)
     std::vector<uint32_t> light_instance;           // light -> instance
     std::vector<uint32_t> mesh_tri_count;           // per mesh; with num_textures what lupin_hip_surface_probe checks a record's indices against
-    std::vector<uint8_t> mesh_has_texcoords;        // per mesh; lupin_hip_bake_lightmap refuses a chart on a mesh without them
+    std::vector<uint8_t> mesh_has_texcoords;        // per mesh; lupin_hip_bake_lightmap refuses a chart on a mesh without them and without a lightmap set
+    std::vector<uint32_t> mesh_vert_count;          // per mesh; lupin_hip_unwrap_lightmap_uvs sizes its (bucket, vertex) table by it
+    std::vector<uint32_t> mesh_tri_offset;          // per mesh: MeshDev::tri_offset, its first global triangle
+    std::vector<DeviceBuffer> lightmap_uvs;         // per mesh: the lightmap UV set (one float2 per triangle corner), empty without one
+    const float2 *lightmap_set(uint32_t mesh) const { return lightmap_uvs[mesh].as<float2>(); }
     uint32_t num_textures = 0;
     std::vector<LupinTlasNode> tlas_nodes;          // the TLAS in lupin_build_tlas' format (lupin_hip_scene_get_tlas)
     uint32_t nblas = 0, ntlas = 0;                  // the one node array is [nblas BLAS nodes | ntlas TLAS nodes]
@@ -1446,6 +1452,9 @@ int lupin_hip_scene_create(LupinContext *ctx, const LupinSceneDesc *desc, LupinS
         uint32_t ntris = m.num_indices / 3;
         sc->mesh_tri_count.push_back(ntris);
         sc->mesh_has_texcoords.push_back(md.texcoords_base != LUPIN_SENTINEL_IDX);
+        sc->mesh_vert_count.push_back(m.num_verts);
+        sc->mesh_tri_offset.push_back(md.tri_offset);
+        sc->lightmap_uvs.emplace_back();
         for (uint32_t i = 0; i < ntris * 3; i++)
             if (m.indices[i] >= m.num_verts) { lupin_hip_scene_destroy(sc); return fail(LUPIN_ERR_INVALID_ARGUMENT, "vertex index out of range"); }
         for (uint32_t t = 0; t < ntris; t++)
@@ -3646,15 +3655,18 @@ static int render_lightmapped(const char *who, LupinContext *ctx, const LupinSce
     const uint32_t num_instances = (uint32_t)scene->host_instances.size();
     std::vector<uint32_t> h_chart_of(std::max<uint32_t>(num_instances, 1u), LP_LMV_NO_CHART);
     std::vector<float4> h_charts(std::max<uint32_t>(num_charts, 1u), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    std::vector<const float2 *> h_chart_uvs(std::max<uint32_t>(num_charts, 1u), nullptr);   // per chart: its mesh's lightmap UV set, or null (the texcoords)
     for (uint32_t c = 0; c < num_charts; c++)
     {
         const LupinLightmapChart &ch = charts[c];
         if (ch.instance_idx >= num_instances) return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": instance index out of range");
-        if (!scene->mesh_has_texcoords[scene->host_instances[ch.instance_idx].mesh_idx])
-            return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": the instance's mesh has no texcoords");
+        const uint32_t mesh = scene->host_instances[ch.instance_idx].mesh_idx;
+        if (!scene->mesh_has_texcoords[mesh] && !scene->lightmap_set(mesh))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": the instance's mesh has no texcoords and no lightmap UV set");
         if (!(std::isfinite(ch.scale_u) && std::isfinite(ch.scale_v) && std::isfinite(ch.offset_u) && std::isfinite(ch.offset_v)))
             return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": non-finite scale or offset");
         h_charts[c] = make_float4(ch.scale_u, ch.scale_v, ch.offset_u, ch.offset_v);
+        h_chart_uvs[c] = scene->lightmap_set(mesh);
         if (h_chart_of[ch.instance_idx] == LP_LMV_NO_CHART) h_chart_of[ch.instance_idx] = c;
     }
     if (int rc = query_refuse_hierarchy(ctx, scene, false)) return rc;
@@ -3678,7 +3690,7 @@ static int render_lightmapped(const char *who, LupinContext *ctx, const LupinSce
     const uint64_t max_slots = baked_view_launch_slots(view->max_slots, pixels);
     // scratch for one launch (the lookup's results only with a volume); the chart tables; host arrays: the atlas and the grid
     // whole, one launch's G-buffer.  All of it lives for the call.
-    DeviceBuffer b_rec, b_aux, b_lm, b_res, b_chart_of, b_charts, b_atlas, b_gbuf, b_dir, b_planes;
+    DeviceBuffer b_rec, b_aux, b_lm, b_res, b_chart_of, b_charts, b_chart_uvs, b_atlas, b_gbuf, b_dir, b_planes;
     BakedVolume vol;
     HIP_TRY(DeviceBuffer::make((size_t)max_slots * LUPIN_PROBE_GRID_RECORD_FLOATS * 4, &b_rec));
     HIP_TRY(DeviceBuffer::make((size_t)max_slots * 32, &b_aux));
@@ -3689,6 +3701,8 @@ static int render_lightmapped(const char *who, LupinContext *ctx, const LupinSce
     HIP_TRY(DeviceBuffer::make(h_charts.size() * 16, &b_charts));
     HIP_TRY(hipMemcpyAsync(b_chart_of.get(), h_chart_of.data(), h_chart_of.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b_charts.get(), h_charts.data(), h_charts.size() * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(DeviceBuffer::make(h_chart_uvs.size() * sizeof(const float2 *), &b_chart_uvs));
+    HIP_TRY(hipMemcpyAsync(b_chart_uvs.get(), h_chart_uvs.data(), h_chart_uvs.size() * sizeof(const float2 *), hipMemcpyHostToDevice, st));
     const float4 *d_atlas = reinterpret_cast<const float4 *>(lightmap), *d_planes = reinterpret_cast<const float4 *>(directional);
     if (!on_device)
     {
@@ -3717,11 +3731,12 @@ static int render_lightmapped(const char *who, LupinContext *ctx, const LupinSce
             if (dd)
                 hipLaunchKernelGGL(k_lightmapped_gbuffer_directional<decltype(G)::value>, blocks, dim3(LP_BLOCK), t.lds, st, scene->dev, fp, v,
                                    (unsigned long long)first, slots, view->ray_epsilon, b_chart_of.as<uint32_t>(), b_charts.as<float4>(), b_rec.as<float4>(),
-                                   b_aux.as<float4>(), b_lm.as<float4>(), d_gbuf, t.stack_words, dd->bake_flags, b_dir.as<float4>());
+                                   b_aux.as<float4>(), b_lm.as<float4>(), d_gbuf, t.stack_words, dd->bake_flags, b_dir.as<float4>(),
+                                   b_chart_uvs.as<const float2 *>());
             else
                 hipLaunchKernelGGL(k_lightmapped_gbuffer<decltype(G)::value>, blocks, dim3(LP_BLOCK), t.lds, st, scene->dev, fp, v, (unsigned long long)first,
                                    slots, view->ray_epsilon, b_chart_of.as<uint32_t>(), b_charts.as<float4>(), b_rec.as<float4>(), b_aux.as<float4>(),
-                                   b_lm.as<float4>(), d_gbuf, t.stack_words);
+                                   b_lm.as<float4>(), d_gbuf, t.stack_words, b_chart_uvs.as<const float2 *>());
         });
         HIP_TRY(hipGetLastError());
         if (sh)
@@ -3789,10 +3804,12 @@ static int lightmap_host_charts(const LupinScene *scene, const LupinLightmapChar
         const LupinLightmapChart &ch = charts[c];
         if (ch.instance_idx >= scene->host_instances.size()) return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": instance index out of range");
         const uint32_t mesh = scene->host_instances[ch.instance_idx].mesh_idx;
-        if (!scene->mesh_has_texcoords[mesh]) return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": the instance's mesh has no texcoords");
+        if (!scene->mesh_has_texcoords[mesh] && !scene->lightmap_set(mesh))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": the instance's mesh has no texcoords and no lightmap UV set");
         if (!(std::isfinite(ch.scale_u) && std::isfinite(ch.scale_v) && std::isfinite(ch.offset_u) && std::isfinite(ch.offset_v)))
             return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + ": non-finite scale or offset");
-        (*h_charts)[c] = LmChartDev{ch.instance_idx, (uint32_t)total_keys, scene->mesh_tri_count[mesh], 0u, ch.scale_u, ch.scale_v, ch.offset_u, ch.offset_v};
+        (*h_charts)[c] = LmChartDev{ch.instance_idx, (uint32_t)total_keys, scene->mesh_tri_count[mesh], 0u, ch.scale_u, ch.scale_v, ch.offset_u, ch.offset_v,
+                                    scene->lightmap_set(mesh)};
         total_keys += scene->mesh_tri_count[mesh];
         if (total_keys >= 0xFFFFFFFFull) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the charts hold 2^32 - 1 or more triangles");
     }
@@ -4258,6 +4275,155 @@ int lupin_hip_bake_lightmap_ao(LupinContext *ctx, const LupinScene *scene, const
     if (out_records) HIP_TRY(hipMemcpyAsync(out_records, d_plane.get(), (size_t)texels * LUPIN_RAY_RECORD_FLOATS * 4, hipMemcpyDeviceToHost, st));
     if (int rc = query_end(ctx, who)) return rc;
     if (out_num_covered) *out_num_covered = n;
+    return LUPIN_OK;
+}
+
+// ---- lightmap UV sets (no reference counterpart; kernels: lupin_unwrap.hpp, packer: include/lupin_pack.hpp) ----
+
+int lupin_hip_scene_set_lightmap_uvs(LupinScene *scene, uint32_t mesh_idx, const float *uvs, uint64_t num_corners)
+{
+    if (!scene) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    LupinContext *ctx = scene->ctx;
+    CTX_ALIVE_TRY(ctx);
+    if (mesh_idx >= scene->mesh_tri_count.size()) return fail(LUPIN_ERR_INVALID_ARGUMENT, "set_lightmap_uvs: mesh index out of range");
+    const uint64_t want = (uint64_t)scene->mesh_tri_count[mesh_idx] * 3;
+    if (uvs && num_corners != want)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "set_lightmap_uvs: " + std::to_string(num_corners) + " corners for a mesh of " + std::to_string(want));
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = flush_pending(ctx)) return rc;   // calls recorded so far see the previous set (no frame reads one: only the order is kept)
+    DeviceBuffer fresh;
+    if (uvs)
+    {
+        // (an empty mesh keeps a 16-byte set, so that "has a set" stays "has a buffer")
+        HIP_TRY(DeviceBuffer::make(std::max<size_t>((size_t)want * sizeof(float2), 16), &fresh));
+        if (want) HIP_TRY(hipMemcpyAsync(fresh.get(), uvs, (size_t)want * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+    }
+    // every consumer of a set ends synchronised on the primary stream; the copy has landed and the old set is free to go
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    scene->lightmap_uvs[mesh_idx].swap(fresh);
+    return LUPIN_OK;
+}
+
+int64_t lupin_hip_scene_mesh_triangle_count(const LupinScene *scene, uint32_t mesh_idx)
+{
+    if (!scene) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    if (mesh_idx >= scene->mesh_tri_count.size()) return fail(LUPIN_ERR_INVALID_ARGUMENT, "mesh index out of range");
+    return (int64_t)scene->mesh_tri_count[mesh_idx];
+}
+
+// include/lupin_pack.hpp knows no HIP header and restates the two limits: here, where both are seen, they are held together
+static_assert(lupin_pack::MAX_SIZE == LUPIN_LIGHTMAP_MAX_SIZE && lupin_pack::MAX_PADDING == LUPIN_UNWRAP_MAX_PADDING, "lupin_pack.hpp and lupin_hip.h disagree");
+static_assert(LUPIN_LIGHTMAP_MAX_SIZE == 16384u && LUPIN_UNWRAP_MAX_PADDING == 16u, "the refusals' messages name 16384 and 16");
+
+int lupin_hip_unwrap_lightmap_uvs(LupinContext *ctx, const LupinScene *scene, uint32_t mesh_idx, const LupinUnwrapDesc *desc, float *out_uvs,
+                                  uint32_t *out_chart_of_tri, LupinUnwrapInfo *out_info)
+{
+    const char *who = "lupin_hip_unwrap_lightmap_uvs";
+    if (int rc = query_refuse(ctx, scene, desc && out_uvs && out_info)) return rc;
+    if (mesh_idx >= scene->mesh_tri_count.size()) return fail(LUPIN_ERR_INVALID_ARGUMENT, "mesh index out of range");
+    if (const char *why = lupin_pack::unwrap_desc_refusal(desc->texel_size, desc->padding, desc->flags)) return fail(LUPIN_ERR_INVALID_ARGUMENT, why);
+    if (int rc = query_flush(ctx)) return rc;
+    if (int rc = join_primary(ctx)) return rc;
+    hipStream_t st = ctx->stream;
+    const uint32_t T = scene->mesh_tri_count[mesh_idx], V = scene->mesh_vert_count[mesh_idx], pad = desc->padding;
+    LupinUnwrapInfo info = {0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (T == 0) { *out_info = info; return LUPIN_OK; }
+    const uint32_t tri_offset = scene->mesh_tri_offset[mesh_idx];
+    const TriVerts *tris = scene->dev.tris + tri_offset;
+    const uint32_t *indices = scene->dev.tri_indices + (size_t)tri_offset * 3;
+    const uint32_t blocks = (T + LP_BLOCK - 1) / LP_BLOCK;
+    const size_t table_bytes = std::max<size_t>((size_t)6 * V * 4, 16);
+
+    DeviceBuffer d_bucket, d_parent, d_table, d_label, d_roots, d_min, d_max, d_totals, d_dense, d_chart_label, d_chart_box, d_origin, d_uvs, d_chart;
+    HIP_TRY(DeviceBuffer::make((size_t)T * 4, &d_bucket));
+    HIP_TRY(DeviceBuffer::make((size_t)T * 4, &d_parent));
+    HIP_TRY(DeviceBuffer::make(table_bytes, &d_table));
+    HIP_TRY(DeviceBuffer::make((size_t)T * 4, &d_label));
+    HIP_TRY(DeviceBuffer::make((size_t)T * 4, &d_roots));
+    HIP_TRY(DeviceBuffer::make((size_t)T * 8, &d_min));
+    HIP_TRY(DeviceBuffer::make((size_t)T * 8, &d_max));
+    HIP_TRY(DeviceBuffer::make(((size_t)blocks + 1) * 4, &d_totals));
+    HIP_TRY(DeviceBuffer::make((size_t)T * 4, &d_dense));
+    HIP_TRY(DeviceBuffer::make((size_t)T * 24, &d_uvs));
+    HIP_TRY(DeviceBuffer::make((size_t)T * 4, &d_chart));
+
+    // ---- charts: classify, union, flatten (with the charts' boxes) ----
+    auto t0 = LmClock::now();
+    HIP_TRY(hipMemsetAsync(d_table.get(), 0xFF, table_bytes, st));
+    HIP_TRY(hipMemsetAsync(d_min.get(), 0xFF, (size_t)T * 8, st));
+    HIP_TRY(hipMemsetAsync(d_max.get(), 0, (size_t)T * 8, st));
+    hipLaunchKernelGGL(k_uw_classify, dim3(blocks), dim3(LP_BLOCK), 0, st, tris, indices, T, V, d_bucket.as<uint32_t>(), d_parent.as<uint32_t>(),
+                       d_table.as<uint32_t>());
+    hipLaunchKernelGGL(k_uw_union, dim3(blocks), dim3(LP_BLOCK), 0, st, indices, T, V, d_bucket.as<uint32_t>(), d_table.as<uint32_t>(), d_parent.as<uint32_t>());
+    hipLaunchKernelGGL(k_uw_flatten, dim3(blocks), dim3(LP_BLOCK), 0, st, tris, T, d_bucket.as<uint32_t>(), d_parent.as<uint32_t>(), d_label.as<uint32_t>(),
+                       d_roots.as<uint32_t>(), d_min.as<uint32_t>(), d_max.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    info.charts_ms = lm_ms_since(t0);
+
+    // ---- the charts in ascending label, their boxes to the host ----
+    t0 = LmClock::now();
+    hipLaunchKernelGGL(k_lm_count, dim3(blocks), dim3(LP_BLOCK), 0, st, d_roots.as<uint32_t>(), T, d_totals.as<uint32_t>());
+    hipLaunchKernelGGL(k_lm_scan, dim3(1), dim3(LP_LM_SCAN_THREADS), 0, st, d_totals.as<uint32_t>(), blocks);
+    HIP_TRY(hipGetLastError());
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, d_totals.as<uint32_t>() + blocks, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n > T) return fail(LUPIN_ERR_HIP, std::string(who) + ": the compaction counted more charts than the mesh has triangles");
+    std::vector<uint32_t> h_label(n);
+    std::vector<float4> h_box(n);
+    if (n != 0)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)n * 4, &d_chart_label));
+        HIP_TRY(DeviceBuffer::make((size_t)n * 16, &d_chart_box));
+        HIP_TRY(DeviceBuffer::make((size_t)n * 8, &d_origin));
+        hipLaunchKernelGGL(k_uw_compact, dim3(blocks), dim3(LP_BLOCK), 0, st, T, d_roots.as<uint32_t>(), d_totals.as<uint32_t>(), d_min.as<uint32_t>(),
+                           d_max.as<uint32_t>(), d_chart_label.as<uint32_t>(), d_chart_box.as<float4>(), d_dense.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_label.data(), d_chart_label.get(), (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_box.data(), d_chart_box.get(), (size_t)n * 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    info.rects_ms = lm_ms_since(t0);
+
+    // ---- the rectangles and the shelf packer, on the host ----
+    t0 = LmClock::now();
+    std::vector<lupin_pack::Rect> rects(n);
+    for (uint32_t c = 0; c < n; c++)
+    {
+        uint32_t ew = 0, eh = 0;
+        if (!lupin_pack::extent_texels(h_box[c].x, h_box[c].z, desc->texel_size, &ew) || !lupin_pack::extent_texels(h_box[c].y, h_box[c].w, desc->texel_size, &eh))
+            return fail(LUPIN_ERR_INVALID_ARGUMENT, "chart " + std::to_string(c) + " is larger than 16384 texels: choose a larger texel_size");
+        rects[c] = lupin_pack::Rect{ew + 2u * pad, eh + 2u * pad, c, 0u, 0u};   // (dense numbers ascend with the labels)
+    }
+    uint64_t AW = 0, AH = 0;
+    lupin_pack::shelf_pack(rects, &AW, &AH);
+    if (AW > LUPIN_LIGHTMAP_MAX_SIZE || AH > LUPIN_LIGHTMAP_MAX_SIZE)
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, "the mesh's atlas would be " + std::to_string(AW) + " x " + std::to_string(AH) + " texels, above 16384: choose a larger texel_size");
+    std::vector<float2> h_origin(n);
+    for (const lupin_pack::Rect &r : rects) h_origin[r.label] = make_float2((float)(r.x + pad), (float)(r.y + pad));
+    info.pack_ms = lm_ms_since(t0);
+
+    // ---- the UVs ----
+    t0 = LmClock::now();
+    if (n != 0) HIP_TRY(hipMemcpyAsync(d_origin.get(), h_origin.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_uw_uvs, dim3(blocks), dim3(LP_BLOCK), 0, st, tris, T, d_bucket.as<uint32_t>(), d_label.as<uint32_t>(), d_dense.as<uint32_t>(),
+                       d_chart_box.as<float4>(), d_origin.as<float2>(), desc->texel_size, d_uvs.as<float2>(), d_chart.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    // staged, so that a failed copy leaves the outputs untouched
+    std::vector<float> h_uvs((size_t)T * 6);
+    std::vector<uint32_t> h_chart(T);
+    HIP_TRY(hipMemcpyAsync(h_uvs.data(), d_uvs.get(), (size_t)T * 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_chart.data(), d_chart.get(), (size_t)T * 4, hipMemcpyDeviceToHost, st));
+    if (int rc = query_end(ctx, who)) return rc;
+    for (uint32_t t = 0; t < T; t++) info.degenerate_tris += h_chart[t] == LP_UW_NONE ? 1u : 0u;
+    memcpy(out_uvs, h_uvs.data(), (size_t)T * 24);
+    if (out_chart_of_tri) memcpy(out_chart_of_tri, h_chart.data(), (size_t)T * 4);
+    info.num_charts = n;
+    info.width = (uint32_t)AW;
+    info.height = (uint32_t)AH;
+    info.uvs_ms = lm_ms_since(t0);
+    *out_info = info;
     return LUPIN_OK;
 }
 

@@ -28,11 +28,14 @@ constexpr uint32_t LP_LM_NO_OWNER = 0xFFFFFFFFu;
 constexpr uint32_t LP_LM_SMOOTH_NORMALS = 1u;   // LUPIN_LIGHTMAP_SMOOTH_NORMALS
 constexpr uint32_t LP_LM_SCAN_THREADS = 1024;
 
-// one chart on the device: the instance, the key of its first triangle, its place in the atlas
+// one chart on the device: the instance, the key of its first triangle, its place in the atlas, and the lightmap UV set of
+// the instance's mesh (lupin_hip_scene_set_lightmap_uvs: one float2 per triangle corner, the mesh's first corner first), or
+// nullptr: the chart reads the mesh's texcoords
 struct LmChartDev
 {
     uint32_t inst, key_base, tri_count, pad;
     float scale_u, scale_v, offset_u, offset_v;
+    const float2 *lm_uvs;
 };
 
 struct LmTri   // a triangle in texel space
@@ -70,9 +73,9 @@ LP_DEV LmTri lm_triangle(const SceneDev &sc, const LmChartDev &ch, uint32_t tri,
     t.i0 = sc.tri_indices[(size_t)t.gtri * 3 + 0];
     t.i1 = sc.tri_indices[(size_t)t.gtri * 3 + 1];
     t.i2 = sc.tri_indices[(size_t)t.gtri * 3 + 2];
-    const float2 a = sc.texcoords[t.mesh.texcoords_base + t.i0];
-    const float2 b = sc.texcoords[t.mesh.texcoords_base + t.i1];
-    const float2 c = sc.texcoords[t.mesh.texcoords_base + t.i2];
+    const float2 a = ch.lm_uvs ? ch.lm_uvs[(size_t)tri * 3 + 0] : sc.texcoords[t.mesh.texcoords_base + t.i0];
+    const float2 b = ch.lm_uvs ? ch.lm_uvs[(size_t)tri * 3 + 1] : sc.texcoords[t.mesh.texcoords_base + t.i1];
+    const float2 c = ch.lm_uvs ? ch.lm_uvs[(size_t)tri * 3 + 2] : sc.texcoords[t.mesh.texcoords_base + t.i2];
     t.x0 = (a.x * ch.scale_u + ch.offset_u) * Wf; t.y0 = (a.y * ch.scale_v + ch.offset_v) * Hf;
     t.x1 = (b.x * ch.scale_u + ch.offset_u) * Wf; t.y1 = (b.y * ch.scale_v + ch.offset_v) * Hf;
     t.x2 = (c.x * ch.scale_u + ch.offset_u) * Wf; t.y2 = (c.y * ch.scale_v + ch.offset_v) * Hf;

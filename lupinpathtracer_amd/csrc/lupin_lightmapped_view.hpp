@@ -41,15 +41,28 @@ struct LightmappedViewDev   // what of LupinLightmappedViewDesc and the context 
     uint32_t volume;          // sh != NULL: an uncharted hit asks the lookup
 };
 
+// The coordinate a chart places in the atlas: interp_texcoords on the mesh's texcoords, or, where the hit instance's mesh has
+// a lightmap UV set (lm_uvs != nullptr: one float2 per triangle corner, the mesh's first corner first), the same weighted
+// sum over the hit triangle's three corners of that set.
+LP_DEV void lmv_atlas_uv(const SceneDev &sc, const Surface &s, const float2 *__restrict__ lm_uvs, float &tu, float &tv)
+{
+    if (!lm_uvs) { interp_texcoords(sc, s, tu, tv); return; }
+    const size_t corner = (size_t)(s.gtri - s.mesh.tri_offset) * 3;
+    const float2 a = lm_uvs[corner], b = lm_uvs[corner + 1], c = lm_uvs[corner + 2];
+    const float w = 1.0f - s.u - s.v;
+    tu = a.x * w + b.x * s.u + c.x * s.v;
+    tv = a.y * w + b.y * s.u + c.y * s.v;
+}
+
 // `records`, `aux` (2 float4 a slot each), `lm` (1 float4 a slot) and `gbuffer` (nullptr, or 5 float4 a slot) point at the
 // launch's first slot.  chart_of_instance: per instance the lowest chart that names it, or LP_LMV_NO_CHART; charts: per
-// chart (scale_u, scale_v, offset_u, offset_v).
+// chart (scale_u, scale_v, offset_u, offset_v); chart_lm_uvs: per chart the lightmap UV set of its instance's mesh, or nullptr.
 template <bool LDSGEO>
 __global__ void __launch_bounds__(LP_BLOCK) k_lightmapped_gbuffer(SceneDev sc, FrameParams fp, LightmappedViewDev v, unsigned long long first, uint32_t n,
                                                                   float eps, const uint32_t *__restrict__ chart_of_instance,
                                                                   const float4 *__restrict__ charts, float4 *__restrict__ records,
                                                                   float4 *__restrict__ aux, float4 *__restrict__ lm, float4 *__restrict__ gbuffer,
-                                                                  uint32_t stack_words)
+                                                                  uint32_t stack_words, const float2 *const *__restrict__ chart_lm_uvs)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
     const auto geo = make_geo<LDSGEO>(sc, lds_stack, stack_words);
@@ -62,10 +75,10 @@ __global__ void __launch_bounds__(LP_BLOCK) k_lightmapped_gbuffer(SceneDev sc, F
         if (r.hit)
         {
             const uint32_t c = chart_of_instance[r.inst];
-            if (c != LP_LMV_NO_CHART)   // (the host has seen that a charted instance's mesh has texcoords)
+            if (c != LP_LMV_NO_CHART)   // (the host has seen that a charted instance's mesh has texcoords or a lightmap UV set)
             {
                 float tu, tv;
-                interp_texcoords(sc, r.s, tu, tv);
+                lmv_atlas_uv(sc, r.s, chart_lm_uvs[c], tu, tv);
                 const float4 k = charts[c];
                 const float au = tu * k.x + k.z, av = tv * k.y + k.w;
                 const float cx = au * (float)v.width - 0.5f, cy = av * (float)v.height - 0.5f;
@@ -97,7 +110,7 @@ __global__ void __launch_bounds__(LP_BLOCK) k_lightmapped_gbuffer_directional(Sc
                                                                               const float4 *__restrict__ charts, float4 *__restrict__ records,
                                                                               float4 *__restrict__ aux, float4 *__restrict__ lm,
                                                                               float4 *__restrict__ gbuffer, uint32_t stack_words, uint32_t bake_flags,
-                                                                              float4 *__restrict__ dir)
+                                                                              float4 *__restrict__ dir, const float2 *const *__restrict__ chart_lm_uvs)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
     const auto geo = make_geo<LDSGEO>(sc, lds_stack, stack_words);
@@ -113,7 +126,7 @@ __global__ void __launch_bounds__(LP_BLOCK) k_lightmapped_gbuffer_directional(Sc
             if (c != LP_LMV_NO_CHART)
             {
                 float tu, tv;
-                interp_texcoords(sc, r.s, tu, tv);
+                lmv_atlas_uv(sc, r.s, chart_lm_uvs[c], tu, tv);
                 const float4 k = charts[c];
                 const float au = tu * k.x + k.z, av = tv * k.y + k.w;
                 const float cx = au * (float)v.width - 0.5f, cy = av * (float)v.height - 0.5f;
