@@ -1257,6 +1257,106 @@ typedef struct LupinLightmapDenoiseStats {
 } LupinLightmapDenoiseStats;
 void lupin_hip_lightmap_denoise_stats(LupinLightmapDenoiseStats *out);
 
+/* ---- lightmap seam stitching (no reference counterpart) ----
+ * lupin_hip_stitch_lightmap takes a baked (or denoised) atlas and the charts it was baked with, finds the edges along which a
+ * mesh's lightmap UVs are cut, and moves the texels beside them so that what lupin_hip_render_lightmapped fetches on one side
+ * of a cut agrees with what it fetches on the other, while every texel stays near its baked value: a least-squares problem
+ * solved by conjugate gradients on the device.  `rgba` is H x W x 4 floats, alpha != 0 marking an owned texel, exactly what
+ * the view takes.  Every float operation below is one rounded f32 operation in the written order (no contraction, IEEE
+ * division and sqrt); tests/lightmap_stitch_ref.py restates the rule.
+ *
+ * 1. Seam edges.  Every chart on its own.  With T the triangle count of the chart's instance's mesh, half-edge h = 3 t + k
+ *    runs from corner k to corner (k + 1) % 3 of triangle t; its key is (min, max) of its two vertex indices.  A half-edge
+ *    with equal indices is skipped.  A key with one holder is a boundary and ignored; with three or more it is NON-MANIFOLD,
+ *    skipped and counted once; with exactly two, hA < hB, it is an interior edge.  A corner's atlas coordinate is
+ *    ((u * scale_u + offset_u) * (float)W, (v * scale_v + offset_v) * (float)H), (u, v) being the corner's lightmap UV (the
+ *    mesh's lightmap UV set, or its texcoords), as the bake's rasteriser forms it.  Side A is hA from a0 to a1; side B is the
+ *    same two VERTICES (matched by index) in hB's triangle, b0 at the vertex of a0.  The edge is a SEAM when a0 != b0 or
+ *    a1 != b1 in any bit of x or y.  Seams are numbered over all charts in ascending (chart, hA).  Matching is by index only:
+ *    vertices duplicated per face share no edge and give no seam, and no seam joins two instances.
+ *    (Device: a stable radix sort of the keys with h as the value, then of the charts; runs of exactly two.)
+ *
+ * 2. Sample pairs.  len(p, q) = sqrtf(dx * dx + dy * dy), d = q - p.  m = ceilf(max(len(a0, a1), len(b0, b1)) *
+ *    samples_per_texel); n_e = LUPIN_LIGHTMAP_STITCH_MAX_EDGE_SAMPLES if m >= that, (uint32)m if m >= 1, else 1.  Sample j
+ *    of edge e has t = ((float)j + 0.5f) / (float)n_e and the points A = a0 + (a1 - a0) * t, B = b0 + (b1 - b0) * t per
+ *    component.  Pairs are numbered edge by edge, j ascending.  The FOOTPRINT of a point P is the view's fetch (step 7 of
+ *    lupin_hip_render_lightmapped) at (x, y) = (P.x - 0.5f, P.y - 0.5f): the clamp in float, x0 = (uint32)floorf, x1 =
+ *    min(x0 + 1, W - 1), f = xf - floorf(xf), likewise y; the taps 00, 10, 01, 11 with weights (1-fx)(1-fy), fx(1-fy),
+ *    (1-fx)fy, fx fy; cov = the sum, in tap order from 0, of the weights of the taps whose input alpha != 0; an owned tap
+ *    gets weight w / cov, every other tap 0.  A pair one of whose four coordinates x, y is not finite, or with cov == 0 (not
+ *    > 0) on either side, is DROPPED: counted, its eight weights 0.  A pair is a row of eight (texel, weight) entries: the
+ *    four taps of A with their weights, then the four taps of B with their weights negated.
+ *
+ * 3. The problem.  A texel is ACTIVE when an entry with weight != 0 names it; the active texels are numbered in ascending
+ *    texel index.  x0 = the input rgb at the active texels.  Per channel, minimise sum_p (sum_i w_pi x[t_pi])^2 +
+ *    lambda * sum_t (x_t - x0_t)^2 by `iterations` steps of plain conjugate gradients on (A^T A + lambda I) d = -A^T (A x0)
+ *    from d = 0; the three channels are three independent solves with their own scalars:
+ *      s = A x0; E_before = sum(s * s); r = -(A^T s); p = r; d = 0; rr = sum(r * r);
+ *      each step: s = A p; q = A^T s + lambda * p; pq = sum(p * q); a channel whose pq is 0 or not finite STOPS: its alpha
+ *      and beta are 0 from then on; otherwise alpha = rr / pq; d = d + alpha * p; r = r - alpha * q; rr' = sum(r * r);
+ *      beta = rr' / rr; rr = rr'; p = r + beta * p;
+ *      at the end x = x0 + d; s = A x; E_after = sum(s * s).
+ *    (A v)_p adds its eight entries w * v[t] in entry order from 0.0f, an entry with weight 0 adding 0.0f.  (A^T s)_t adds
+ *    w * s_p over the entries that name t, in ascending (pair, entry) order, from 0.0f.
+ *    A sum over n elements: elements are taken in blocks of 256 (zeros past the last); in a block, each run of 64 is summed
+ *    by v[i] = v[i] + v[i ^ m] for m = 32, 16, 8, 4, 2, 1, and the four results are added in ascending order; the block
+ *    sums b_0, b_1, .. are then added lane-strided, lane l = 0..63 adding b_l, b_(l+64), .. in ascending order from 0.0f, and
+ *    the 64 lane sums by the same six steps.  The order depends on n alone: no launch shape, no scheduling, no float atomic.
+ *    The scalars stay on the device; there is no host round trip per step.
+ *
+ * 4. Output.  out_rgba rgb = x at the active texels when iterations > 0; every other texel's rgb, every alpha, and the
+ *    whole atlas when iterations == 0, is the input's bit for bit.  Gutter texels that are not active are NOT re-dilated:
+ *    they keep what the bake's or the denoiser's gutter passes left.  out_rgba may be the same memory as rgba.
+ *    out_info (NULL: not wanted) gets the counts and E_before, E_after per channel, the same with iterations == 0.
+ *
+ * Ordering as lupin_hip_denoise_lightmap and the bakes: recorded calls run first (their error is returned), the call returns
+ * when out_rgba is complete; the scene's hierarchies are not read, so a scene moved by lupin_hip_scene_update_instances
+ * stitches to the same words.  Host arrays are staged in device buffers that live for the call.
+ * LUPIN_ERR_INVALID_ARGUMENT with out_rgba and out_info untouched for: a NULL argument (out_info may be NULL); num_charts ==
+ * 0; width or height 0 or above LUPIN_LIGHTMAP_MAX_SIZE; iterations above LUPIN_LIGHTMAP_STITCH_MAX_ITERATIONS;
+ * samples_per_texel or lambda not finite and positive; an unknown flag; reserved != 0; with
+ * LUPIN_LIGHTMAP_STITCH_DEVICE_POINTERS a pointer that is not 16-byte aligned; a chart whose instance is out of range, whose
+ * mesh has neither a lightmap UV set nor texcoords, or whose scale or offset is not finite; more than 2^32 - 2 half-edges,
+ * sample pairs or incidence entries (8 a pair).  An atlas without a seam: LUPIN_OK, out = in.  Without a HIP device:
+ * LUPIN_ERR_NO_DEVICE.
+ * Known limits and out of scope: seams between instances or meshes; welding by position; re-dilating gutters; stopping by a
+ * tolerance; preconditioning.  A directional plane or an AO plane can be passed as `rgba` one at a time. */
+#define LUPIN_LIGHTMAP_STITCH_MAX_ITERATIONS 1024u
+#define LUPIN_LIGHTMAP_STITCH_MAX_EDGE_SAMPLES 65536u
+enum { LUPIN_LIGHTMAP_STITCH_DEVICE_POINTERS = 1u };                    /* desc.flags: rgba and out_rgba are device memory */
+typedef struct LupinLightmapStitchDesc {
+    uint32_t width;                 /* atlas texels, 1 .. LUPIN_LIGHTMAP_MAX_SIZE */
+    uint32_t height;
+    uint32_t iterations;            /* 0 .. LUPIN_LIGHTMAP_STITCH_MAX_ITERATIONS; 0: out = in, the counts and energies only */
+    float samples_per_texel;        /* seam samples per texel of edge length; finite, > 0 */
+    float lambda;                   /* the weight that keeps a texel near its baked value; finite, > 0 */
+    uint32_t flags;
+    uint32_t reserved;              /* 0 */
+} LupinLightmapStitchDesc;
+typedef struct LupinLightmapStitchInfo {
+    uint32_t seam_edges;
+    uint32_t non_manifold_edges;    /* keys with three or more holders */
+    uint32_t sample_pairs;          /* emitted, the dropped ones among them */
+    uint32_t dropped_pairs;
+    uint32_t active_texels;
+    uint32_t iterations;            /* steps run */
+    float energy_before[3];         /* sum_p (A x0)_p^2 per channel, by the solver's own sum */
+    float energy_after[3];          /* the same of x */
+} LupinLightmapStitchInfo;
+int lupin_hip_stitch_lightmap(LupinContext *ctx, const LupinScene *scene, const LupinLightmapStitchDesc *desc,
+                              const LupinLightmapChart *charts, uint32_t num_charts, const float *rgba /* H*W*4 */,
+                              float *out_rgba /* H*W*4 */, LupinLightmapStitchInfo *out_info /* NULL ok */);
+/* The calling thread's latest successful lupin_hip_stitch_lightmap: host-clock milliseconds per phase (each ends
+ * synchronised) and of the call after its refusals.  LUPIN_ERR_INVALID_ARGUMENT for NULL. */
+typedef struct LupinLightmapStitchStats {
+    float edges_ms;                 /* keys, sorts, runs, the seam edges' count */
+    float samples_ms;               /* edges, counts, scan, pairs */
+    float incidence_ms;             /* the incidence sort, the active texels, the columns */
+    float solve_ms;                 /* all steps, the energies and the output */
+    float call_ms;
+} LupinLightmapStitchStats;
+int lupin_hip_lightmap_stitch_stats(LupinLightmapStitchStats *out);
+
 /* ---- light-probe baking (no reference counterpart) ----
  * The radiance arriving at points in space from every direction, projected onto the nine real spherical harmonics of bands
  * 0..2: what lights everything a lightmap cannot cover.  Every probe is path-traced along `samples` uniformly distributed

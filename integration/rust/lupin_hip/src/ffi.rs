@@ -120,6 +120,20 @@ pub const LUPIN_UNWRAP_NO_CHART: u32 = 0xFFFF_FFFF;
 pub const LUPIN_LIGHTMAP_DENOISE_DEVICE_POINTERS: u32 = 1;
 pub const LUPIN_LIGHTMAP_DENOISE_MAX_PASSES: u32 = 8;
 pub const LUPIN_LIGHTMAP_DENOISE_MAX_SQUARINGS: u32 = 7;
+// lightmap seam stitching (no reference counterpart)
+pub const LUPIN_LIGHTMAP_STITCH_DEVICE_POINTERS: u32 = 1;
+pub const LUPIN_LIGHTMAP_STITCH_MAX_ITERATIONS: u32 = 1024;
+pub const LUPIN_LIGHTMAP_STITCH_MAX_EDGE_SAMPLES: u32 = 65536;
+#[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmapStitchDesc {
+    pub width: u32, pub height: u32, pub iterations: u32, pub samples_per_texel: f32, pub lambda: f32, pub flags: u32, pub reserved: u32,
+}
+#[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinLightmapStitchInfo {
+    pub seam_edges: u32, pub non_manifold_edges: u32, pub sample_pairs: u32, pub dropped_pairs: u32, pub active_texels: u32, pub iterations: u32,
+    pub energy_before: [f32; 3], pub energy_after: [f32; 3],
+}
+#[repr(C)] #[derive(Copy, Clone, Default, Debug)] pub struct LupinLightmapStitchStats {
+    pub edges_ms: f32, pub samples_ms: f32, pub incidence_ms: f32, pub solve_ms: f32, pub call_ms: f32,
+}
 #[repr(C)] #[derive(Copy, Clone)] pub struct LupinLightmapDenoiseDesc {
     pub width: u32, pub height: u32, pub passes: u32, pub normal_squarings: u32, pub dilate: u32, pub flags: u32, pub max_stretch: f32,
 }
@@ -295,6 +309,11 @@ extern "C" {
     pub fn lupin_hip_denoise_lightmap(ctx: *mut LupinContext, desc: *const LupinLightmapDenoiseDesc, rgba: *const f32, records: *const f32,
                                       out_rgba: *mut f32) -> c_int;
     pub fn lupin_hip_lightmap_denoise_stats(out: *mut LupinLightmapDenoiseStats);
+    // lightmap seam stitching: rgba and out_rgba height x width x 4 f32 (they may be the same), out_info null ok
+    pub fn lupin_hip_stitch_lightmap(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinLightmapStitchDesc,
+                                     charts: *const LupinLightmapChart, num_charts: u32, rgba: *const f32, out_rgba: *mut f32,
+                                     out_info: *mut LupinLightmapStitchInfo) -> c_int;
+    pub fn lupin_hip_lightmap_stitch_stats(out: *mut LupinLightmapStitchStats) -> c_int;
     // light-probe baking: probes n x 4 f32 (position | RNG word), out_sh n x 9 x 4 (r, g, b, w per L2 SH coefficient), out_rays null or n * samples x 8
     pub fn lupin_hip_bake_probes(ctx: *mut LupinContext, scene: *const LupinScene, desc: *const LupinProbeDesc, n: u64,
                                  probes: *const f32, out_sh: *mut f32, out_rays: *mut f32) -> c_int;

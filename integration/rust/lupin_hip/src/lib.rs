@@ -447,6 +447,15 @@ pub fn render_lightmapped(device: &Device, scene: &Scene, target: &Texture, came
     gbuffer
 }
 
+/// `lp::stitch_lightmap`: the atlas with its chart borders pulled together, and the call's counts and energies.
+pub fn stitch_lightmap(device: &Device, scene: &Scene, desc: &LupinLightmapStitchDesc, charts: &[LupinLightmapChart], rgba: &[f32]) -> (Vec<f32>, LupinLightmapStitchInfo) {
+    assert!(rgba.len() == desc.width as usize * desc.height as usize * 4);
+    let mut out = vec![0f32; rgba.len()];
+    let mut info = LupinLightmapStitchInfo::default();
+    check(unsafe { lupin_hip_stitch_lightmap(device.raw, scene.raw, desc, charts.as_ptr(), charts.len() as u32, rgba.as_ptr(), out.as_mut_ptr(), &mut info) });
+    (out, info)
+}
+
 // ---- directional lightmaps (no reference counterpart) ----
 /// `lupin_hip_bake_lightmap`'s texels, records and paths, resolved into four L0 / L1 coefficient planes of the cosine-weighted
 /// incident radiance: 4 x `desc.height` x `desc.width` x 4 floats, plane j first, alpha = ownership in every plane.

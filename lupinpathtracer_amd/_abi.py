@@ -198,6 +198,20 @@ class LightmapDenoiseStatsC(C.Structure):   # LupinLightmapDenoiseStats
     _fields_ = [("prep_ms", C.c_float), ("pass_ms", C.c_float * 8), ("dilate_ms", C.c_float), ("call_ms", C.c_float)]
 
 
+class LightmapStitchDescC(C.Structure):   # LupinLightmapStitchDesc ("lambda" is a Python keyword: construct positionally, read with getattr)
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("samples_per_texel", C.c_float),
+                ("lambda", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LightmapStitchInfoC(C.Structure):   # LupinLightmapStitchInfo
+    _fields_ = [("seam_edges", C.c_uint32), ("non_manifold_edges", C.c_uint32), ("sample_pairs", C.c_uint32), ("dropped_pairs", C.c_uint32),
+                ("active_texels", C.c_uint32), ("iterations", C.c_uint32), ("energy_before", C.c_float * 3), ("energy_after", C.c_float * 3)]
+
+
+class LightmapStitchStatsC(C.Structure):   # LupinLightmapStitchStats
+    _fields_ = [("edges_ms", C.c_float), ("samples_ms", C.c_float), ("incidence_ms", C.c_float), ("solve_ms", C.c_float), ("call_ms", C.c_float)]
+
+
 class ProbeDescC(C.Structure):   # LupinProbeDesc
     _fields_ = [("pathtrace_type", C.c_uint32), ("max_bounces", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32),
                 ("max_slots", C.c_uint32), ("advanced", AdvancedParamsC)]
@@ -320,6 +334,9 @@ SYMBOLS = [
     ("lupin_hip_lightmap_stats", None, [C.POINTER(LightmapStatsC)]),
     ("lupin_hip_denoise_lightmap", C.c_int, [_P, C.POINTER(LightmapDenoiseDescC), _P, _P, _P]),
     ("lupin_hip_lightmap_denoise_stats", None, [C.POINTER(LightmapDenoiseStatsC)]),
+    ("lupin_hip_stitch_lightmap", C.c_int,
+     [_P, _P, C.POINTER(LightmapStitchDescC), C.POINTER(LightmapChartC), _U32, _P, _P, C.POINTER(LightmapStitchInfoC)]),
+    ("lupin_hip_lightmap_stitch_stats", C.c_int, [C.POINTER(LightmapStitchStatsC)]),
     ("lupin_hip_bake_probes", C.c_int, [_P, _P, C.POINTER(ProbeDescC), C.c_uint64, _P, _P, _P]),
     ("lupin_hip_occlusion_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),
     ("lupin_hip_transmittance_rays", C.c_int, [_P, _P, C.POINTER(OcclusionDescC), C.c_uint64, _P, _P]),

@@ -1722,6 +1722,64 @@ def lightmap_denoise_stats():
     return {"prep_ms": float(s.prep_ms), "pass_ms": [float(v) for v in s.pass_ms], "dilate_ms": float(s.dilate_ms), "call_ms": float(s.call_ms)}
 
 
+# ---- lightmap seam stitching: lupin_hip_stitch_lightmap (include/lupin_hip.h) ----
+LIGHTMAP_STITCH_DEVICE_POINTERS = 1
+LIGHTMAP_STITCH_MAX_ITERATIONS = 1024
+LIGHTMAP_STITCH_MAX_EDGE_SAMPLES = 65536
+
+
+def stitch_lightmap(ctx, scene, charts, rgba, iterations=32, samples_per_texel=2.0, lam=0.1, want_info=False):
+    """A baked (or denoised) lightmap with its chart borders pulled together: (height, width, 4) float32.  `charts` are the
+    LightmapChart items the atlas was baked with.  Every interior edge of a chart's mesh whose two sides have different
+    lightmap UVs is a seam; it is sampled `samples_per_texel` times per texel of its length, and `iterations` steps of
+    conjugate gradients minimise, per channel, the squared difference of what the lightmapped view fetches on the two sides
+    of every sample plus `lam` times the squared distance of every touched texel from its baked value.  Texels no sample
+    touches, and every alpha, come back bit for bit; iterations == 0 returns the input and reports the counts.
+    want_info: also a dict of the seam edges, non-manifold edges, sample pairs, dropped pairs, active texels, iterations and
+    the seam energy per channel before and after.  numpy arrays, or a contiguous float32 torch tensor on the context's device:
+    then torch's current stream is synchronised, the tensor's memory is read in place and a tensor is returned.  Blocks
+    until the result is complete."""
+    if ctx is None:
+        raise LupinError(_abi_code("LUPIN_ERR_NO_DEVICE"), "stitch_lightmap needs a GPU context; there is no CPU fallback")
+    items = [c if isinstance(c, LightmapChart) else LightmapChart(*c) for c in charts]
+    c_charts = (_abi.LightmapChartC * max(1, len(items)))(*[_abi.LightmapChartC(int(c.instance_idx), c.scale_u, c.scale_v, c.offset_u, c.offset_v)
+                                                           for c in items])
+    info = _abi.LightmapStitchInfoC()
+    if hasattr(rgba, "data_ptr"):   # a torch tensor
+        import torch
+        if not (rgba.is_cuda and rgba.dtype == torch.float32 and rgba.is_contiguous() and rgba.dim() == 3 and rgba.shape[2] == 4):
+            raise ValueError("rgba must be a contiguous (height, width, 4) float32 tensor on the context's device")
+        if rgba.device.index != ctx.device_ordinal:
+            raise ValueError("rgba is on another device than the context")
+        h, w = int(rgba.shape[0]), int(rgba.shape[1])
+        out = torch.zeros((h, w, 4), dtype=torch.float32, device=rgba.device)
+        torch.cuda.current_stream(rgba.device).synchronize()   # the input (and the zero fill) is written
+        d = _abi.LightmapStitchDescC(w, h, int(iterations), float(samples_per_texel), float(lam), LIGHTMAP_STITCH_DEVICE_POINTERS, 0)
+        check(lib().lupin_hip_stitch_lightmap(ctx.handle, scene.handle, C.byref(d), c_charts, len(items), C.c_void_p(rgba.data_ptr()),
+                                              C.c_void_p(out.data_ptr()), C.byref(info)))
+    else:
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        if rgba.ndim != 3 or rgba.shape[2] != 4:
+            raise ValueError("rgba must be (height, width, 4)")
+        h, w = rgba.shape[:2]
+        d = _abi.LightmapStitchDescC(w, h, int(iterations), float(samples_per_texel), float(lam), 0, 0)
+        out = np.zeros((h, w, 4), np.float32)
+        check(lib().lupin_hip_stitch_lightmap(ctx.handle, scene.handle, C.byref(d), c_charts, len(items), ptr(rgba), ptr(out), C.byref(info)))
+    if not want_info:
+        return out
+    return out, {"seam_edges": int(info.seam_edges), "non_manifold_edges": int(info.non_manifold_edges), "sample_pairs": int(info.sample_pairs),
+                 "dropped_pairs": int(info.dropped_pairs), "active_texels": int(info.active_texels), "iterations": int(info.iterations),
+                 "energy_before": np.array(list(info.energy_before), np.float32), "energy_after": np.array(list(info.energy_after), np.float32)}
+
+
+def lightmap_stitch_stats():
+    """The calling thread's latest successful stitch_lightmap: host-clock ms of its phases (seam edges, sample pairs, the
+    incidence lists, the solve with the output) and of the call."""
+    s = _abi.LightmapStitchStatsC()
+    check(lib().lupin_hip_lightmap_stitch_stats(C.byref(s)))
+    return {k: float(getattr(s, k)) for k, _ in _abi.LightmapStitchStatsC._fields_}
+
+
 # ---- light-probe baking: lupin_hip_bake_probes (include/lupin_hip.h, DESIGN.md 15) ----
 PROBE_FLOATS = 4
 PROBE_SH_COEFFS = 9

@@ -43,8 +43,10 @@
 #include "lupin_probe_depth.hpp"
 #include "lupin_baked_view.hpp"
 #include "lupin_lightmapped_view.hpp"
+#include "lupin_lightmap_stitch.hpp"
 #include "lupin_internal.hpp"
 #include "../../include/lupin_pack.hpp"
+#include "../../include/lupin_stitch_rules.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // Host side
@@ -4526,6 +4528,238 @@ int lupin_hip_denoise_lightmap(LupinContext *ctx, const LupinLightmapDenoiseDesc
     stats.call_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_call).count();
     g_lightmap_denoise_stats = stats;
     return LUPIN_OK;
+}
+
+// ---- lightmap seam stitching (no reference counterpart; kernels and rule: lupin_lightmap_stitch.hpp) ----
+
+static_assert(lupin_stitch::MAX_SIZE == LUPIN_LIGHTMAP_MAX_SIZE && lupin_stitch::MAX_ITERATIONS == LUPIN_LIGHTMAP_STITCH_MAX_ITERATIONS &&
+                  lupin_stitch::DEVICE_POINTERS == LUPIN_LIGHTMAP_STITCH_DEVICE_POINTERS && LP_ST_MAX_EDGE_SAMPLES == LUPIN_LIGHTMAP_STITCH_MAX_EDGE_SAMPLES,
+              "lupin_stitch_rules.hpp, lupin_lightmap_stitch.hpp and lupin_hip.h disagree");
+
+static thread_local LupinLightmapStitchStats g_lightmap_stitch_stats = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+int lupin_hip_lightmap_stitch_stats(LupinLightmapStitchStats *out)
+{
+    if (!out) return fail(LUPIN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = g_lightmap_stitch_stats;
+    return LUPIN_OK;
+}
+
+// the number of words of `plane` (n of them) that are not LP_LM_NO_OWNER, and in d_totals what the compaction kernels read
+static int stitch_count(hipStream_t st, const uint32_t *plane, uint32_t n, DeviceBuffer *d_totals, uint32_t *count)
+{
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + LP_BLOCK - 1) / LP_BLOCK);
+    HIP_TRY(DeviceBuffer::make(((size_t)blocks + 1) * 4, d_totals));
+    hipLaunchKernelGGL(k_lm_count, dim3(blocks), dim3(LP_BLOCK), 0, st, plane, n, d_totals->as<uint32_t>());
+    hipLaunchKernelGGL(k_lm_scan, dim3(1), dim3(LP_LM_SCAN_THREADS), 0, st, d_totals->as<uint32_t>(), blocks);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(count, d_totals->as<uint32_t>() + blocks, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LUPIN_OK;
+}
+
+int lupin_hip_stitch_lightmap(LupinContext *ctx, const LupinScene *scene, const LupinLightmapStitchDesc *desc, const LupinLightmapChart *charts,
+                              uint32_t num_charts, const float *rgba, float *out_rgba, LupinLightmapStitchInfo *out_info)
+{
+    const char *who = "lupin_hip_stitch_lightmap";
+    if (int rc = query_refuse(ctx, scene, desc && charts && rgba && out_rgba)) return rc;
+    if (num_charts == 0) return fail(LUPIN_ERR_INVALID_ARGUMENT, "no charts");
+    if (const char *why = lupin_stitch::desc_refusal(desc->width, desc->height, desc->iterations, desc->samples_per_texel, desc->lambda, desc->flags, desc->reserved))
+        return fail(LUPIN_ERR_INVALID_ARGUMENT, why);
+    const bool on_device = (desc->flags & LUPIN_LIGHTMAP_STITCH_DEVICE_POINTERS) != 0;
+    if (on_device && (((uintptr_t)rgba | (uintptr_t)out_rgba) & 15u)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "device pointers must be 16-byte aligned");
+    std::vector<LmChartDev> h_charts;
+    uint64_t total_keys = 0;
+    if (int rc = lightmap_host_charts(scene, charts, num_charts, &h_charts, &total_keys)) return rc;
+    if (!lupin_stitch::half_edges_ok(total_keys)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the charts hold more than 2^32 - 2 half-edges");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = join_primary(ctx)) return rc;   // recorded calls run first
+    hipStream_t st = ctx->stream;                // the primary stream
+    const auto t_call = LmClock::now();
+
+    const uint32_t W = desc->width, H = desc->height, texels = W * H;   // <= 2^28
+    const float Wf = (float)W, Hf = (float)H;
+    const uint32_t N = (uint32_t)(total_keys * 3);   // half-edges
+    LupinLightmapStitchInfo info;
+    memset(&info, 0, sizeof(info));
+    LupinLightmapStitchStats stats = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+
+    // host arrays are staged; the atlas the kernels read (d_in) and the one the result lands in (d_out) may be the same memory
+    DeviceBuffer d_stage;
+    const float4 *d_in = reinterpret_cast<const float4 *>(rgba);
+    float4 *d_out = reinterpret_cast<float4 *>(out_rgba);
+    if (!on_device)
+    {
+        HIP_TRY(DeviceBuffer::make((size_t)texels * 16, &d_stage));
+        HIP_TRY(hipMemcpyAsync(d_stage.get(), rgba, (size_t)texels * 16, hipMemcpyHostToDevice, st));
+        d_in = d_out = d_stage.as<float4>();
+    }
+    // how every path ends: out = in wherever the solver has not written, the call synchronised, the info and the stats out
+    auto finish = [&](bool scattered) -> int {
+        if (on_device) { if (d_out != d_in && !scattered) HIP_TRY(hipMemcpyAsync(d_out, d_in, (size_t)texels * 16, hipMemcpyDeviceToDevice, st)); }
+        else if (scattered) HIP_TRY(hipMemcpyAsync(out_rgba, d_out, (size_t)texels * 16, hipMemcpyDeviceToHost, st));
+        if (int rc = query_end(ctx, who)) return rc;
+        if (!on_device && !scattered && out_rgba != rgba) memmove(out_rgba, rgba, (size_t)texels * 16);
+        if (out_info) *out_info = info;
+        stats.call_ms = lm_ms_since(t_call);
+        g_lightmap_stitch_stats = stats;
+        return LUPIN_OK;
+    };
+    if (N == 0) return finish(false);
+
+    // ---- seam edges: keys, the two sorts, runs of exactly two, the seam test ----
+    auto t0 = LmClock::now();
+    DeviceBuffer d_charts, d_counters, d_partner, d_totals;
+    uint32_t E = 0;
+    uint32_t h_counters[LP_ST_COUNTERS] = {0u, 0u, 0u, 0u};
+    const uint32_t h_blocks = (uint32_t)(((uint64_t)N + LP_BLOCK - 1) / LP_BLOCK);
+    HIP_TRY(DeviceBuffer::make(h_charts.size() * sizeof(LmChartDev), &d_charts));
+    HIP_TRY(DeviceBuffer::make(LP_ST_COUNTERS * 4, &d_counters));
+    HIP_TRY(DeviceBuffer::make((size_t)N * 4, &d_partner));
+    HIP_TRY(hipMemcpyAsync(d_charts.get(), h_charts.data(), h_charts.size() * sizeof(LmChartDev), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_counters.get(), 0, LP_ST_COUNTERS * 4, st));
+    HIP_TRY(hipMemsetAsync(d_partner.get(), 0xFF, (size_t)N * 4, st));
+    {
+        DeviceBuffer d_keys, d_keys2, d_vals, d_vals2, d_ckeys, d_ckeys2;
+        HIP_TRY(DeviceBuffer::make((size_t)N * 8, &d_keys));
+        HIP_TRY(DeviceBuffer::make((size_t)N * 8, &d_keys2));
+        HIP_TRY(DeviceBuffer::make((size_t)N * 4, &d_vals));
+        HIP_TRY(DeviceBuffer::make((size_t)N * 4, &d_vals2));
+        uint32_t max_verts = 1;
+        for (const LupinLightmapChart *c = charts; c != charts + num_charts; c++)
+            max_verts = std::max(max_verts, scene->mesh_vert_count[scene->host_instances[c->instance_idx].mesh_idx]);
+        hipLaunchKernelGGL(k_st_keys, dim3(h_blocks), dim3(LP_BLOCK), 0, st, scene->dev, d_charts.as<LmChartDev>(), num_charts, N,
+                           d_keys.as<unsigned long long>(), d_vals.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        if (int rc = lupin_internal_sort_pairs_u64(st, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(), d_vals.as<uint32_t>(), d_vals2.as<uint32_t>(), N,
+                                 32 + lupin_stitch::bits_for(max_verts - 1u)))
+            return rc;
+        const uint32_t *sorted = d_vals2.as<uint32_t>();
+        if (num_charts > 1)   // equal (min, max) of different charts are apart after a stable sort by chart
+        {
+            HIP_TRY(DeviceBuffer::make((size_t)N * 4, &d_ckeys));
+            HIP_TRY(DeviceBuffer::make((size_t)N * 4, &d_ckeys2));
+            hipLaunchKernelGGL(k_st_chart_keys, dim3(h_blocks), dim3(LP_BLOCK), 0, st, d_charts.as<LmChartDev>(), num_charts, N, d_vals2.as<uint32_t>(),
+                               d_ckeys.as<uint32_t>());
+            HIP_TRY(hipGetLastError());
+            if (int rc = lupin_internal_sort_pairs_u32(st, d_ckeys.as<uint32_t>(), d_ckeys2.as<uint32_t>(), d_vals2.as<uint32_t>(), d_vals.as<uint32_t>(), N,
+                                     lupin_stitch::bits_for(num_charts - 1u)))
+                return rc;
+            sorted = d_vals.as<uint32_t>();
+        }
+        hipLaunchKernelGGL(k_st_runs, dim3(h_blocks), dim3(LP_BLOCK), 0, st, scene->dev, d_charts.as<LmChartDev>(), num_charts, N, sorted, Wf, Hf,
+                           d_partner.as<uint32_t>(), d_counters.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        if (int rc = stitch_count(st, d_partner.as<uint32_t>(), N, &d_totals, &E)) return rc;
+        HIP_TRY(hipMemcpyAsync(h_counters, d_counters.get(), sizeof(h_counters), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (E > N) return fail(LUPIN_ERR_HIP, std::string(who) + ": the compaction counted more seams than there are half-edges");
+    info.seam_edges = E;
+    info.non_manifold_edges = h_counters[LP_ST_NON_MANIFOLD];
+    stats.edges_ms = lm_ms_since(t0);
+    if (E == 0) return finish(false);
+
+    // ---- sample pairs: the edges in ascending hA, their counts, the scan, the rows ----
+    t0 = LmClock::now();
+    DeviceBuffer d_edges, d_counts, d_offsets, d_row_wgt, d_inc_keys, d_inc_vals, d_inc_keys2, d_inc_vals2, d_col;
+    HIP_TRY(DeviceBuffer::make((size_t)E * 32, &d_edges));
+    HIP_TRY(DeviceBuffer::make(((size_t)E + 1) * 8, &d_counts));
+    HIP_TRY(DeviceBuffer::make(((size_t)E + 1) * 8, &d_offsets));
+    HIP_TRY(hipMemsetAsync(d_counts.get(), 0, ((size_t)E + 1) * 8, st));
+    hipLaunchKernelGGL(k_st_edges, dim3(h_blocks), dim3(LP_BLOCK), 0, st, scene->dev, d_charts.as<LmChartDev>(), num_charts, N, d_partner.as<uint32_t>(),
+                       d_totals.as<uint32_t>(), Wf, Hf, desc->samples_per_texel, d_edges.as<float4>(), d_counts.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long pairs64 = 0;
+    if (int rc = lupin_internal_exclusive_sum_u64(st, d_counts.as<unsigned long long>(), d_offsets.as<unsigned long long>(), (size_t)E + 1)) return rc;
+    HIP_TRY(hipMemcpyAsync(&pairs64, d_offsets.as<unsigned long long>() + E, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!lupin_stitch::pairs_ok(pairs64)) return fail(LUPIN_ERR_INVALID_ARGUMENT, "the seams give more than 2^32 - 2 incidence entries (8 a sample pair)");
+    const uint32_t P = (uint32_t)pairs64, n8 = 8u * P;   // P >= E >= 1
+    const uint32_t p_blocks = (P + LP_BLOCK - 1) / LP_BLOCK, e_blocks = (uint32_t)(((uint64_t)n8 + LP_BLOCK - 1) / LP_BLOCK);
+    for (DeviceBuffer *b : {&d_row_wgt, &d_inc_keys, &d_inc_vals, &d_inc_keys2, &d_inc_vals2, &d_col}) HIP_TRY(DeviceBuffer::make((size_t)n8 * 4, b));
+    hipLaunchKernelGGL(k_st_pairs, dim3(p_blocks), dim3(LP_BLOCK), 0, st, d_in, W, H, d_edges.as<float4>(), d_offsets.as<unsigned long long>(), E, P,
+                       d_row_wgt.as<float>(), d_inc_keys.as<uint32_t>(), d_inc_vals.as<uint32_t>(), d_counters.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_counters, d_counters.get(), sizeof(h_counters), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    info.sample_pairs = P;
+    info.dropped_pairs = h_counters[LP_ST_DROPPED];
+    stats.samples_ms = lm_ms_since(t0);
+
+    // ---- incidence: (texel, 8 * pair + entry) sorted by texel, the active texels, the columns ----
+    t0 = LmClock::now();
+    uint32_t A = 0;
+    DeviceBuffer d_totals2, d_act_texel, d_act_start, d_x0;
+    if (int rc = lupin_internal_sort_pairs_u32(st, d_inc_keys.as<uint32_t>(), d_inc_keys2.as<uint32_t>(), d_inc_vals.as<uint32_t>(), d_inc_vals2.as<uint32_t>(), n8,
+                             lupin_stitch::bits_for(texels)))
+        return rc;
+    uint32_t *heads = d_inc_keys.as<uint32_t>();   // (the unsorted keys are done with)
+    hipLaunchKernelGGL(k_st_heads, dim3(e_blocks), dim3(LP_BLOCK), 0, st, d_inc_keys2.as<uint32_t>(), n8, texels, heads, d_counters.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    if (int rc = stitch_count(st, heads, n8, &d_totals2, &A)) return rc;
+    if (A > texels) return fail(LUPIN_ERR_HIP, std::string(who) + ": the compaction counted more active texels than the atlas has");
+    info.active_texels = A;
+    if (A == 0) { stats.incidence_ms = lm_ms_since(t0); return finish(false); }   // every pair was dropped
+    const uint32_t a_blocks = (A + LP_BLOCK - 1) / LP_BLOCK;
+    HIP_TRY(DeviceBuffer::make((size_t)A * 4, &d_act_texel));
+    HIP_TRY(DeviceBuffer::make((size_t)A * 4, &d_act_start));
+    HIP_TRY(DeviceBuffer::make((size_t)A * 16, &d_x0));
+    hipLaunchKernelGGL(k_st_active, dim3(e_blocks), dim3(LP_BLOCK), 0, st, d_inc_keys2.as<uint32_t>(), n8, heads, d_totals2.as<uint32_t>(),
+                       d_act_texel.as<uint32_t>(), d_act_start.as<uint32_t>());
+    HIP_TRY(hipMemsetAsync(d_col.get(), 0, (size_t)n8 * 4, st));
+    hipLaunchKernelGGL(k_st_columns, dim3(a_blocks), dim3(LP_BLOCK), 0, st, d_in, d_act_texel.as<uint32_t>(), d_act_start.as<uint32_t>(), A,
+                       d_counters.as<uint32_t>(), d_inc_vals2.as<uint32_t>(), d_col.as<uint32_t>(), d_x0.as<float4>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    stats.incidence_ms = lm_ms_since(t0);
+
+    // ---- the solve: no host round trip from here to the output ----
+    t0 = LmClock::now();
+    DeviceBuffer d_d, d_r, d_p, d_q, d_s, d_pp, d_ap, d_scalars;
+    for (DeviceBuffer *b : {&d_d, &d_r, &d_p, &d_q}) HIP_TRY(DeviceBuffer::make((size_t)A * 16, b));
+    HIP_TRY(DeviceBuffer::make((size_t)P * 16, &d_s));
+    HIP_TRY(DeviceBuffer::make((size_t)p_blocks * 16, &d_pp));
+    HIP_TRY(DeviceBuffer::make((size_t)a_blocks * 16, &d_ap));
+    HIP_TRY(DeviceBuffer::make(sizeof(StScalars), &d_scalars));
+    HIP_TRY(hipMemsetAsync(d_scalars.get(), 0, sizeof(StScalars), st));
+    const float *wgt = d_row_wgt.as<float>();
+    const uint32_t *col = d_col.as<uint32_t>(), *inc = d_inc_vals2.as<uint32_t>(), *start = d_act_start.as<uint32_t>(), *cnt = d_counters.as<uint32_t>();
+    float4 *dd = d_d.as<float4>(), *r = d_r.as<float4>(), *p = d_p.as<float4>(), *q = d_q.as<float4>(), *s = d_s.as<float4>();
+    float4 *pp = d_pp.as<float4>(), *ap = d_ap.as<float4>();
+    StScalars *scal = d_scalars.as<StScalars>();
+    const float lambda = desc->lambda;
+    auto scalars = [&](uint32_t mode) { hipLaunchKernelGGL(k_st_scalars, dim3(1), dim3(64), 0, st, mode, (const float4 *)pp, p_blocks, (const float4 *)ap, a_blocks, scal); };
+    hipLaunchKernelGGL(k_st_apply<true>, dim3(p_blocks), dim3(LP_BLOCK), 0, st, P, wgt, col, (const float4 *)d_x0.as<float4>(), s, pp);
+    hipLaunchKernelGGL(k_st_adjoint<true>, dim3(a_blocks), dim3(LP_BLOCK), 0, st, A, start, cnt, inc, wgt, (const float4 *)s, lambda, r, p, dd, q, ap);
+    scalars(LP_ST_INIT);
+    for (uint32_t it = 0; it < desc->iterations; it++)
+    {
+        hipLaunchKernelGGL(k_st_apply<false>, dim3(p_blocks), dim3(LP_BLOCK), 0, st, P, wgt, col, (const float4 *)p, s, pp);
+        hipLaunchKernelGGL(k_st_adjoint<false>, dim3(a_blocks), dim3(LP_BLOCK), 0, st, A, start, cnt, inc, wgt, (const float4 *)s, lambda, r, p, dd, q, ap);
+        scalars(LP_ST_ALPHA);
+        hipLaunchKernelGGL(k_st_update, dim3(a_blocks), dim3(LP_BLOCK), 0, st, A, (const StScalars *)scal, (const float4 *)p, (const float4 *)q, dd, r, ap);
+        scalars(LP_ST_BETA);
+        hipLaunchKernelGGL(k_st_direction, dim3(a_blocks), dim3(LP_BLOCK), 0, st, A, (const StScalars *)scal, (const float4 *)r, p);
+    }
+    float4 *x = q;   // (q is done with)
+    hipLaunchKernelGGL(k_st_result, dim3(a_blocks), dim3(LP_BLOCK), 0, st, A, (const float4 *)d_x0.as<float4>(), (const float4 *)dd, x);
+    hipLaunchKernelGGL(k_st_apply<true>, dim3(p_blocks), dim3(LP_BLOCK), 0, st, P, wgt, col, (const float4 *)x, s, pp);
+    scalars(LP_ST_AFTER);
+    const bool scatter = desc->iterations != 0;
+    if (scatter)
+    {
+        if (d_out != d_in) HIP_TRY(hipMemcpyAsync(d_out, d_in, (size_t)texels * 16, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_st_scatter, dim3(a_blocks), dim3(LP_BLOCK), 0, st, A, d_act_texel.as<uint32_t>(), (const float4 *)x, reinterpret_cast<float *>(d_out));
+    }
+    HIP_TRY(hipGetLastError());
+    StScalars h_scal;
+    HIP_TRY(hipMemcpyAsync(&h_scal, d_scalars.get(), sizeof(StScalars), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    info.iterations = desc->iterations;
+    info.energy_before[0] = h_scal.before.x; info.energy_before[1] = h_scal.before.y; info.energy_before[2] = h_scal.before.z;
+    info.energy_after[0] = h_scal.after.x; info.energy_after[1] = h_scal.after.y; info.energy_after[2] = h_scal.after.z;
+    stats.solve_ms = lm_ms_since(t0);
+    return finish(scatter);
 }
 
 static int pack_common(LupinContext *ctx, const LupinTexture *tex, uint32_t tile_size, uint32_t rank, uint32_t world, void *packed, int unpack)

@@ -76,3 +76,9 @@ int lupin_internal_tlas_leaves(const LupinInstance *instances, uint32_t num_inst
                                LupinTlasNode *out_leaves);   // LUPIN_OK | LUPIN_ERR_INVALID_ARGUMENT (mesh_idx out of range)
 bool lupin_internal_tlas_leaves_finite(const LupinInstance *instances, const LupinTlasNode *leaves, uint32_t num_instances);   // transforms and world boxes
 void lupin_internal_tlas_finish(LupinTlasNode *tlas, uint32_t len);   // reversal + child remap
+// lightmap seam stitching's sorts and scan (lupin_stitch_sort.hip): hipCUB's stable radix sort of n (key, value) pairs on bits
+// [0, end_bit) and its exclusive sum, on stream st, in scratch that lives for the call; each returns synchronised
+int lupin_internal_sort_pairs_u64(hipStream_t st, const unsigned long long *keys, unsigned long long *keys_out, const uint32_t *vals, uint32_t *vals_out,
+                                  size_t n, int end_bit);
+int lupin_internal_sort_pairs_u32(hipStream_t st, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out, size_t n, int end_bit);
+int lupin_internal_exclusive_sum_u64(hipStream_t st, const unsigned long long *in, unsigned long long *out, size_t n);
